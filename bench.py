@@ -8,9 +8,14 @@ layer's inverse + log|det J| accumulation + base log-density), inputs resident i
 construction (bit-identical to constructing the reference with the same seed, tests/test_state_dict_compat.py)
 plus the sigma = 0.01 parameter perturbation of SURVEY.md section 8d so that no layer is the identity.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 For N > 1 the driver launches one rank per GPU with torch.distributed.run; the batch is sharded by rows
 (weak scaling: 65 536 rows per rank), the only collective is the 8-byte NLL all-reduce, inside every timed step.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds the untimed extras
+(per-kernel breakdown and roofline, sample direction, bf16x3, CPU baselines, the secondary configurations and batches).
+`--dump-outputs DIR` writes what the last timed step returned as DIR/*.npy (inputs and weights are seeded: two builds
+run with the same arguments can be compared output for output).
 
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field meanings).
 """
@@ -62,6 +67,16 @@ def c2_inputs(batch=BATCH, dim=DIM, seed=1234, rank=0):
 
 def state_to_numpy(model):
     return {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy (float32 stays float32, float64 stays float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        if a.dtype != np.float64:
+            a = a.astype(np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 # ---- algorithmic work per sample of one full pass (SURVEY.md section 8d, DESIGN.md section 4) ------------------
@@ -399,6 +414,9 @@ def train_mode(args, model, x, world, rank, dev):
             "roofline": {"bound": "mfma", "unit": "TFLOP/s", "peak": 157.3, "achieved": flop / dt / 1e12,
                          "frac": flop / dt / 157.3e12, "traffic": None, "flop_per_step_per_gpu": flop,
                          "note": "3 x the forward pass's algorithmic FLOP per rank and step over the whole step's wall time"}}))
+    if args.dump_outputs and rank == 0:
+        # the last timed step's loss and the parameters Adam left (one flat float32 tensor, 21.8 MB at the default model)
+        dump_outputs(args.dump_outputs, {"loss": loss.detach(), "params": flat.param.detach()})
     flat.release()
 
 
@@ -410,15 +428,22 @@ def main():
     ap.add_argument("--batch", type=int, default=BATCH, help="rows per GPU")
     ap.add_argument("--layers", type=int, default=LAYERS)
     ap.add_argument("--no-graph", action="store_true", help="launch kernels eagerly instead of replaying a hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-breakdown", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the untimed extra measurements (other BASELINE configs, "
-                    "training step) that rank 0 appends under \"secondary\" at N = 1")
+    ap.add_argument("--full", action="store_true", help="after the headline measurement also run the untimed extras on rank 0: "
+                    "per-kernel breakdown + roofline, sample direction, bf16x3, CPU baselines, \"secondary\" (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy: log_prob "
+                    "(float32, the rank's rows) + nll (float64); with --train the loss and the flat parameters after the last step")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-breakdown", action="store_true", help="with --full: skip the kernel breakdown, roofline, sample "
+                    "direction and bf16x3 measurements")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the untimed extra measurements (other BASELINE "
+                    "configs, training step) that rank 0 appends under \"secondary\" at N = 1")
     ap.add_argument("--cpu-rows", type=int, default=131072, help="rows of the same workload timed on the host oracle")
     ap.add_argument("--train", action="store_true", help="time the TRAINING step instead (forward_kld + backward + overlapped gradient "
                     "all-reduce + Adam per rank and step; rows/s over all ranks) and print its own JSON line: the second curve of a "
                     "multi-GPU lease (VERDICT r05 #8); the default line (the BASELINE metric) is unchanged")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher ourselves -- one rank per GPU under torch.distributed.run on
@@ -503,6 +528,12 @@ def main():
     nll = float(nll_t.item()) / DIM                  # from the last timed step (the path's 8-byte all-reduce)
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * args.batch * args.steps / elapsed
+    if args.dump_outputs:
+        # what the last timed step returned: every row's log_prob (this rank's shard) and the global NLL
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"log_prob": lp.float(), "nll": nll_t.double()})
+        else:
+            dump_outputs(args.dump_outputs, {"log_prob_rank%d" % rank: lp.float()})
 
     out = {
         "metric": "samples/sec + NLL (nats/dim), 32-layer RQ-NSF d=64 B=65536",
@@ -521,7 +552,7 @@ def main():
         flops = c2_flops_per_sample(layers=args.layers)
         out["end_to_end"] = {"tflops": flops * value / 1e12 / world, "frac_of_fp32_mfma_peak":
                              flops * value / world / 157.3e12, "flop_per_sample": flops}
-        if not args.no_breakdown:
+        if args.full and not args.no_breakdown:
             model.use_graphs(False)
             with torch.no_grad():
                 bd = kernel_breakdown(model, x)
@@ -550,7 +581,7 @@ def main():
                     out["roofline"]["shader_clock_mhz_mfma_probe_5ms"] = _ops.mfma_clock_mhz(dev, 6000)
                 except Exception as exc:   # noqa: BLE001
                     out["roofline"]["shader_clock_mhz_mfma_probe_5ms"] = repr(exc)[:100]
-        if not args.no_breakdown:
+        if args.full and not args.no_breakdown:
             # secondary (SURVEY.md 8d reports both directions): generative pass = every layer's forward + log_q
             g = torch.Generator().manual_seed(4321)
             eps = torch.randn(args.batch, DIM, generator=g).to(dev)
@@ -564,7 +595,7 @@ def main():
                 torch.cuda.synchronize()
                 dt = (time.perf_counter() - t1) / max(args.steps // 2, 3)
             out["sample_direction"] = {"value": args.batch / dt, "unit": "samples/s", "ms_per_step": 1e3 * dt}
-        if not args.no_breakdown:
+        if args.full and not args.no_breakdown:
             # secondary: the same pass with the fused kernel's GEMMs on the bf16 matrix pipe by error-compensated
             # splitting (fp32 = hi + mid + lo bf16, six products, fp32 accumulation; csrc/rqs_fused_x3.hip).  Same
             # parity tests as the exact-fp32 kernel; reported separately, `value` above is the exact-fp32 MFMA path.
@@ -606,7 +637,7 @@ def main():
             nfa.config.set_fused_gemm("f32")
             model.use_graphs(False)
             model.use_graphs(not args.no_graph)
-        if not args.no_cpu_baseline:     # rank 0 only, untimed (at N > 1 the other ranks wait at the closing barrier)
+        if args.full and not args.no_cpu_baseline:     # rank 0 only, untimed (at N > 1 the other ranks wait at the closing barrier)
             out["cpu_baseline"] = cpu_baseline(model, args.cpu_rows, lp.cpu().numpy(),
                                                lp3.cpu().numpy() if not args.no_breakdown else None)
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
@@ -614,7 +645,7 @@ def main():
             if ref_leg is not None:
                 out["cpu_baseline"]["reference"] = ref_leg
                 out["gpu_over_cpu_reference"] = value / ref_leg["value"]
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             out["secondary"] = secondary(model, x)
         print(json.dumps(out))
     if world > 1:

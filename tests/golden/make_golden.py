@@ -1092,7 +1092,149 @@ def gen_image_coupling():
     layer_grads(t, x, "grad_coupling_image")     # reference autograd through both directions of the same layer
 
 
+def _digests(state):
+    """Key order, dtype, shape and the SHA-256 of every tensor's bytes: bit equality of a state_dict without storing its values."""
+    import hashlib
+    keys = list(state.keys())
+    return dict(keys=np.array(keys), dtypes=np.array([str(state[k].dtype) for k in keys]),
+                shapes=np.array([",".join(map(str, state[k].shape)) for k in keys]),
+                sha256=np.array([hashlib.sha256(state[k].detach().contiguous().cpu().numpy().tobytes()).hexdigest() for k in keys]))
+
+
+def gen_seeded_construction():
+    """The reference's seeded constructions the package must reproduce bit for bit (tests/test_host.py): the benchmark model at 3
+    layers (bench.build_c2_model with lib=normflows) and GlowBlock(12, 16, use_lu=True) under seed 3, as digests.  Recorded in a child
+    process in the machine-independent CPU numeric mode of tests/test_host.py (PINNED_CPU_ENV), in which the test rebuilds ours."""
+    if os.environ.get("ATEN_CPU_CAPABILITY") != "default":
+        env = dict(os.environ, ATEN_CPU_CAPABILITY="default", MKL_CBWR="COMPATIBLE", OMP_NUM_THREADS="1", MKL_NUM_THREADS="1",
+                   GLIBC_TUNABLES="glibc.cpu.hwcaps=-AVX2,-FMA,-FMA4")
+        import subprocess
+        subprocess.run([sys.executable, os.path.abspath(__file__), "seeded_construction"], env=env, check=True)
+        return
+    assert torch.backends.cpu.get_cpu_capability() == "DEFAULT"
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    from bench import build_c2_model
+    c2 = _digests(build_c2_model(num_layers=3, lib=nf).state_dict())
+    torch.manual_seed(3)
+    gb = _digests(nf.flows.GlowBlock(12, 16, use_lu=True).state_dict())
+    npz("seeded_construction", **{"c2__" + k: v for k, v in c2.items()}, **{"glow__" + k: v for k, v in gb.items()})
+
+
+def gen_maf_inverse_dpass():
+    """MaskedAffineAutoregressive(9, 28, 2 blocks) in float64 with perturbed weights: x, ld = inverse(z) through the reference's D MADE
+    passes (autoregressive.py:29-38) and torch autograd's gradients of sum(x cx) + sum(ld cl) through that loop."""
+    torch.manual_seed(0)
+    D, H, B = 9, 28, 6
+    layer = nf.flows.MaskedAffineAutoregressive(D, H, num_blocks=2).double()
+    with torch.no_grad():
+        for p in layer.parameters():
+            p.add_(0.3 * torch.randn_like(p))
+    z = torch.randn(B, D, dtype=torch.float64, requires_grad=True)
+    cx, cl = torch.randn(B, D, dtype=torch.float64), torch.randn(B, dtype=torch.float64)
+    x, ld = layer.inverse(z)
+    ((x * cx).sum() + (ld * cl).sum()).backward()
+    npz("maf_inverse_dpass_f64", z=z, cx=cx, cl=cl, x=x, ld=ld, gz=z.grad, **sd(layer, "sd__"),
+        **{"g__" + k.replace(".", "__"): p.grad for k, p in layer.named_parameters()})
+
+
+def gen_ar_inverse_dpass():
+    """The reference's autoregressive layers in float64 (spline, circular spline, affine): inverse(z) through D recorded passes and
+    autograd's gradients for three cotangent choices, plus the first derivatives of the element-wise transform
+    (_elementwise_forward) at the inverse's solution x and theta = net(x): d z / d x (diagonal), d z / d theta, d ld / d x, d ld / d theta."""
+    for kind in ("arnsf", "circular", "maf"):
+        torch.manual_seed(3)
+        D, H, B = 7, 20, 9
+        if kind == "arnsf":
+            ref = nf.flows.AutoregressiveRationalQuadraticSpline(D, 2, H).mprqat
+            z0 = 1.5 * torch.randn(B, D, dtype=torch.float64)
+        elif kind == "circular":
+            ref = nf.flows.CircularAutoregressiveRationalQuadraticSpline(D, 1, H, [1, 4], tail_bound=torch.tensor(
+                [5.0, 3.0, 4.0, 5.0, 3.14159, 5.0, 5.0])).mprqat
+            z0 = torch.randn(B, D, dtype=torch.float64).clamp(-2.9, 2.9)
+        else:
+            ref = nf.flows.MaskedAffineAutoregressive(D, H, num_blocks=2)
+            z0 = torch.randn(B, D, dtype=torch.float64)
+        ref = ref.double()
+        with torch.no_grad():
+            for p in ref.parameters():
+                p.add_(0.2 * torch.randn_like(p))
+        cx, cl = torch.randn(B, D, dtype=torch.float64), torch.randn(B, dtype=torch.float64)
+        out = dict(z=z0, cx=cx, cl=cl, **sd(ref, "sd__"))
+        for tag, use_x, use_l in (("xl", True, True), ("x", True, False), ("l", False, True)):
+            ref.zero_grad(set_to_none=True)
+            z = z0.clone().requires_grad_(True)
+            x, ld = ref.inverse(z)
+            ((x * cx).sum() + (ld * cl).sum() if (use_x and use_l) else ((x * cx).sum() if use_x else (ld * cl).sum())).backward()
+            out.update({tag + "__x": x, tag + "__ld": ld, tag + "__gz": z.grad})
+            out.update({tag + "__g__" + k.replace(".", "__"): p.grad for k, p in ref.named_parameters()})
+        x = out["xl__x"].detach()
+        with torch.no_grad():
+            theta = ref.autoregressive_net(x)
+        P = theta.shape[1]
+        dzdx, dldx = torch.zeros(B, D, dtype=torch.float64), torch.zeros(B, D, dtype=torch.float64)
+        dzdt, dldt = torch.zeros(B, D, P, dtype=torch.float64), torch.zeros(B, P, dtype=torch.float64)
+        for b in range(B):
+            jx, jt = torch.autograd.functional.jacobian(lambda xa, th: ref._elementwise_forward(xa[None], th[None]), (x[b], theta[b]))
+            dzdx[b], dzdt[b] = jx[0][0].diagonal(), jx[1][0]
+            dldx[b], dldt[b] = jt[0][0], jt[1][0]
+        zf, lf = ref._elementwise_forward(x, theta)
+        npz("ar_inverse_dpass_%s_f64" % kind, **out, theta=theta, zf=zf, lf=lf, dzdx=dzdx, dzdt=dzdt, dldx=dldx, dldt=dldt)
+
+
+def gen_containers():
+    """The reference's containers (core.py) over its own layers, float32: NormalizingFlow over 3 x [CoupledRQS(8, 1, 32),
+    LULinearPermute(8)] + ActNorm(8) (log_prob -- which initialises ActNorm --, inverse_and_log_det, forward_and_log_det from given
+    noise, forward_kld) and a reduced Glow MultiscaleFlow (examples/glow.ipynb cell 2: L = 2, K = 2, 3 channels, hidden 16, 8x8
+    images; log_prob, forward_and_log_det from given noise).  The state_dicts are stored after ActNorm's initialisation."""
+    torch.manual_seed(0)
+    flows = []
+    for _ in range(3):
+        flows += [nf.flows.CoupledRationalQuadraticSpline(8, 1, 32), nf.flows.LULinearPermute(8)]
+    flows += [nf.flows.ActNorm(8)]
+    with torch.no_grad():
+        for f in flows:
+            for p_ in f.parameters():
+                p_.add_(0.05 * torch.randn_like(p_))
+    x = torch.randn(130, 8)
+    m = nf.NormalizingFlow(nf.distributions.DiagGaussian(8, trainable=False), flows)
+    with torch.no_grad():
+        lp = m.log_prob(x)
+        z, ld = m.inverse_and_log_det(x)
+        eps = torch.randn(64, 8)
+        xs, lds = m.forward_and_log_det(eps)
+    kld = m.forward_kld(x)
+    torch.manual_seed(1)
+    L_, K_, C, hidden = 2, 2, 3, 16
+    q0, merges, gflows = [], [], []
+    for i in range(L_):
+        gflows += [[nf.flows.GlowBlock(C * 2 ** (L_ + 1 - i), hidden, split_mode="channel", scale=True) for _ in range(K_)]
+                   + [nf.flows.Squeeze()]]
+        if i > 0:
+            merges += [nf.flows.Merge()]
+            shape = (C * 2 ** (L_ - i), 8 // 2 ** (L_ - i), 8 // 2 ** (L_ - i))
+        else:
+            shape = (C * 2 ** (L_ + 1), 8 // 2 ** L_, 8 // 2 ** L_)
+        q0 += [nf.distributions.DiagGaussian(shape, trainable=False)]
+    img = torch.rand(16, C, 8, 8)
+    ms = nf.MultiscaleFlow(q0, gflows, merges)
+    with torch.no_grad():
+        lp_ms = ms.log_prob(img)
+        zs = [torch.randn(8, *q.shape) for q in q0]
+        xs_ms, ld_ms = ms.forward_and_log_det(zs)
+    npz("containers_f32", x=x, lp=lp, z=z, ld=ld, eps=eps, xs=xs, lds=lds, kld=kld, **sd(m, "sd__"),
+        img=img, ms_lp=lp_ms, **{"ms_z%d" % i: t for i, t in enumerate(zs)}, ms_xs=xs_ms, ms_ld=ld_ms, **sd(ms, "ms__"))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "seeded_construction":
+        gen_seeded_construction()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "reference_only":
+        gen_seeded_construction()
+        gen_maf_inverse_dpass()
+        gen_ar_inverse_dpass()
+        gen_containers()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "image_coupling":
         gen_image_coupling()
         sys.exit(0)

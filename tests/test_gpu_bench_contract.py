@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -11,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_emits_one_contract_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full",
                           "--cpu-rows", "2048"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
@@ -57,6 +58,31 @@ def test_bench_emits_one_contract_line():
     assert all(0.5 < ob["rows_%d" % B_]["log_prob_ms"] < 4.5 for B_ in (4096, 16384, 32768)), ob
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) prints the headline fields and none of the extras; --dump-outputs writes the last timed step's
+    log_prob of every row (float32) and the NLL (float64), and the seeded inputs make a second run return the same outputs."""
+    lines, dumps = [], []
+    for i in range(2):
+        d_ = tmp_path / ("run%d" % i)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                              "--dump-outputs", str(d_)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        ls = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
+        assert len(ls) == 1
+        lines.append(json.loads(ls[0]))
+        dumps.append({n: np.load(d_ / (n + ".npy")) for n in ("log_prob", "nll")})
+    d = lines[0]
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] - 65536 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    for k in ("roofline", "kernel_ms", "sample_direction", "bf16x3_split_gemm", "cpu_baseline", "secondary"):
+        assert k not in d, k
+    lp, nll = dumps[0]["log_prob"], dumps[0]["nll"]
+    assert lp.dtype == np.float32 and lp.shape == (65536,) and np.isfinite(lp).all()
+    assert nll.dtype == np.float64 and abs(float(nll) / 64 - d["nll_nats_per_dim"]) < 1e-12
+    assert abs(-float(lp.astype(np.float64).mean()) - float(nll)) < 1e-4 * abs(float(nll))
+    assert np.array_equal(lp, dumps[1]["log_prob"]) and float(nll) == float(dumps[1]["nll"])
+
+
 def test_bench_two_ranks_on_one_device():
     """The N > 1 code path of bench.py (rank-seeded shards, barrier + max-over-ranks timing, the NLL all-reduce, rank 0
     printing) with two ranks sharing cuda:0 over gloo (NF_BENCH_ONE_DEVICE=1; the real run is one rank per GPU over
@@ -64,8 +90,8 @@ def test_bench_two_ranks_on_one_device():
     env = dict(os.environ, NF_BENCH_ONE_DEVICE="1", MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="4")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                           "--master-addr", "127.0.0.1", "--master-port", "29683", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8192", "--no-breakdown", "--cpu-rows", "2048"],
-                         capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8192", "--full", "--no-breakdown",
+                          "--cpu-rows", "2048"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-2500:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -83,7 +109,7 @@ def test_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(NF_BENCH_ONE_DEVICE="1", OMP_NUM_THREADS="4")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--batch", "8192", "--no-breakdown", "--cpu-rows", "2048"],
+                          "--batch", "8192", "--full", "--no-breakdown", "--cpu-rows", "2048"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-2500:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]

@@ -837,69 +837,44 @@ def test_drop_in_under_reference_style_container(nfa):
 
 
 def test_drop_in_under_the_reference_own_containers(nfa):
-    """The reference's REAL containers around our layers (runs wherever /root/reference and a GPU exist together; skipped on a
-    box without the reference): `nf.NormalizingFlow(q0, [ours...])` log_prob / sample / forward_kld (core.py:9-60, 87-102,
-    167-197) and `nf.MultiscaleFlow` (core.py:455-616) with our GlowBlock / Squeeze / Merge layers give bit-for-bit what our own
-    containers give on the same layers, and our layers load the reference's state_dict unchanged."""
-    import sys
-    # the build container has /root/reference; on the GPU box the package arrives staged (tools/stage_reference.py -> .refstage/,
-    # git-ignored, NF_REFERENCE_PATH) -- round 5 ran it there: profiles/r05_reference_containers_gpubox.log
-    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cands = [os.environ.get("NF_REFERENCE_PATH"), os.path.join(here, ".refstage"), "/root/reference"]
-    ref = next((os.path.abspath(c) for c in cands if c and os.path.isdir(os.path.join(c, "normflows"))), None)
-    if ref is None:
-        pytest.skip("the reference is not on this box (stage it with tools/stage_reference.py)")
-    sys.path.insert(0, ref)
-    nf = pytest.importorskip("normflows")
-    assert os.path.abspath(nf.__file__).startswith(ref), nf.__file__
-    torch.manual_seed(0)
+    """Our layers and containers against the reference's REAL containers (core.py:9-60, 87-102, 167-197: NormalizingFlow;
+    core.py:455-616: MultiscaleFlow) over the reference's own layers, recorded in tests/golden/containers_f32.npz (make_golden.py
+    reference_only; float32 on the CPU, state_dicts after ActNorm's data-dependent initialisation).  Our layers load the reference's
+    state_dicts unchanged (strict); the reference's loops written out over our layers one by one, and our containers (layer pairs
+    fused into one persistent launch: another summation order), give its log_prob, inverse, forward from given noise and forward_kld."""
+    g = load_golden("containers_f32")
+    T = lambda k: torch.from_numpy(np.asarray(g[k])).to(DEV)
     flows = []
     for _ in range(3):
         flows += [nfa.flows.CoupledRationalQuadraticSpline(8, 1, 32), nfa.flows.LULinearPermute(8)]
     flows += [nfa.flows.ActNorm(8)]
-    for f in flows:
-        f.to(DEV)
+    ours = nfa.NormalizingFlow(nfa.distributions.DiagGaussian(8, trainable=False), flows)
+    ours.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in golden_state(g).items()}, strict=True)
+    ours = ours.to(DEV)
+    x, lp_t, eps = T("x"), g["lp"], T("eps")
     with torch.no_grad():
-        for f in flows:
-            for p_ in f.parameters():
-                p_.add_(0.05 * torch.randn_like(p_))
-    x = torch.randn(130, 8, device=DEV)
-    ours = nfa.NormalizingFlow(nfa.distributions.DiagGaussian(8, trainable=False), flows).to(DEV)
-    with torch.no_grad():
-        ours.log_prob(x)                                   # ActNorm's data-dependent init happens once, here
-    theirs = nf.NormalizingFlow(nf.distributions.DiagGaussian(8, trainable=False), flows).to(DEV)
-    with torch.no_grad():
-        # (1) the reference's loops (core.py:36-38, 193-195) call our layers one by one: BIT-identical to the same calls written out
-        # here.  (First run on the GPU box in round 5: the original version of this test expected bit equality against our own
-        # container, whose fused chain sums in another order, and failed by one unit in the fifth digit.)
-        q0 = theirs.q0                                      # (the reference's own base distribution: torch ops)
-        lp_t = theirs.log_prob(x)
+        # (1) the reference's loops (core.py:36-38, 193-195) written out over our layers one by one
         z_, lq_ = x, torch.zeros(len(x), device=DEV)
         for f in reversed(flows):
             z_, ld_ = f.inverse(z_)
             lq_ = lq_ + ld_
-        assert torch.equal(lp_t, lq_ + q0.log_prob(z_))
-        z_t, ld_t = theirs.inverse_and_log_det(x)
-        assert torch.equal(z_t, z_)
-        torch.manual_seed(5)
-        xs_t, lq_t = theirs.sample(64)
-        torch.manual_seed(5)
-        zs, lqs = q0(64)
+        assert _rel(lp_t, N(lq_ + ours.q0.log_prob(z_))) < 1e-5
+        assert np.allclose(N(z_), g["z"], atol=2e-5) and _rel(g["ld"], N(lq_)) < 1e-5
+        zs, lds = eps, torch.zeros(len(eps), device=DEV)
         for f in flows:
             zs, ld_ = f(zs)
-            lqs = lqs - ld_
-        assert torch.equal(xs_t, zs) and torch.equal(lq_t, lqs)
-        # (2) against our default (layer pairs fused into one persistent launch): another summation order, 1e-5
-        lp_f = ours.log_prob(x)
-        assert _rel(N(lp_t), N(lp_f)) < 1e-5, _rel(N(lp_t), N(lp_f))
-        torch.manual_seed(5)
-        xs_f, lq_f = ours.sample(64)
-        assert torch.allclose(xs_t, xs_f, atol=2e-5) and _rel(N(lq_t), N(lq_f)) < 1e-5
-    lt = theirs.forward_kld(x)
+            lds = lds + ld_
+        assert np.allclose(N(zs), g["xs"], atol=2e-5) and _rel(g["lds"], N(lds)) < 1e-5
+        # (2) our containers (the fused chain: another summation order): log_prob, and log_q of samples from the given noise
+        assert _rel(lp_t, N(ours.log_prob(x))) < 1e-5
+        z_f, ld_f = ours.inverse_and_log_det(x)
+        assert np.allclose(N(z_f), g["z"], atol=2e-5) and _rel(lp_t, N(ld_f + ours.q0.log_prob(z_f))) < 1e-5
+        xs_f, lds_f = ours.forward_and_log_det(eps)
+        lq0 = N(ours.q0.log_prob(eps))
+        assert np.allclose(N(xs_f), g["xs"], atol=2e-5) and _rel(lq0 - g["lds"], lq0 - N(lds_f)) < 1e-5
     lo = ours.forward_kld(x)
-    assert abs(float(lt) - float(lo)) < 2e-6 * abs(float(lo))
-    # MultiscaleFlow (Glow, examples/glow.ipynb cell 2, reduced): the reference's container over our blocks
-    torch.manual_seed(1)
+    assert abs(float(g["kld"]) - float(lo)) < 2e-6 * abs(float(lo))
+    # MultiscaleFlow (Glow, examples/glow.ipynb cell 2, reduced) over our GlowBlock / Squeeze / Merge layers
     L_, K_, C, hidden = 2, 2, 3, 16
     q0, merges, gflows = [], [], []
     for i in range(L_):
@@ -911,28 +886,18 @@ def test_drop_in_under_the_reference_own_containers(nfa):
         else:
             shape = (C * 2 ** (L_ + 1), 8 // 2 ** L_, 8 // 2 ** L_)
         q0 += [nfa.distributions.DiagGaussian(shape, trainable=False)]
-    img = torch.rand(16, C, 8, 8, device=DEV)
-    ours_ms = nfa.MultiscaleFlow(q0, gflows, merges).to(DEV)
+    ours_ms = nfa.MultiscaleFlow(q0, gflows, merges)
+    ours_ms.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in golden_state(g, "ms__").items()}, strict=True)
+    ours_ms = ours_ms.to(DEV)
     with torch.no_grad():
-        lp_o = ours_ms.log_prob(img)                       # initialises every ActNorm
-    theirs_ms = nf.MultiscaleFlow(q0, gflows, merges).to(DEV)
-    with torch.no_grad():
-        lp_t = theirs_ms.log_prob(img)
-        assert _rel(N(lp_t), N(lp_o)) < 1e-5               # (ours runs whole levels as one launch: another summation order)
-        torch.manual_seed(9)
-        xs_t, lq_t = theirs_ms.sample(8)
-        torch.manual_seed(9)
-        xs_o, lq_o = ours_ms.sample(8)
-        assert torch.allclose(xs_t, xs_o, atol=1e-4) and _rel(N(lq_t), N(lq_o)) < 1e-5
-    # and the other way round: our layers take the reference layers' state_dict unchanged
-    torch.manual_seed(2)
-    ref_layer = nf.flows.CoupledRationalQuadraticSpline(8, 1, 32)
+        assert _rel(g["ms_lp"], N(ours_ms.log_prob(T("img")))) < 1e-5      # (ours runs whole levels as one launch: another summation order)
+        zs_ms = [T("ms_z%d" % i) for i in range(L_)]
+        xs_o, ld_o = ours_ms.forward_and_log_det(zs_ms)
+        lq0 = N(sum(q.log_prob(z) for q, z in zip(ours_ms.q0, zs_ms)))
+        assert np.allclose(N(xs_o), g["ms_xs"], atol=1e-4) and _rel(lq0 - g["ms_ld"], lq0 - N(ld_o)) < 1e-5
+    # and a layer built apart from any container takes the reference layer's state_dict unchanged
     mine = nfa.flows.CoupledRationalQuadraticSpline(8, 1, 32)
-    mine.load_state_dict(ref_layer.state_dict(), strict=True)
-    with torch.no_grad():
-        a, la = ref_layer.inverse(x.cpu())
-        b, lb = mine.to(DEV).inverse(x)
-    assert torch.allclose(a, b.cpu(), atol=1e-5) and torch.allclose(la, lb.cpu(), atol=1e-5)
+    mine.load_state_dict({k[len("flows.0."):]: v for k, v in ours.state_dict().items() if k.startswith("flows.0.")}, strict=True)
 
 
 def test_cpu_tensor_is_rejected(nfa):

@@ -12,8 +12,6 @@ import torch
 
 from conftest import ROOT, golden_state, load_golden
 
-REF = "/root/reference"
-
 
 @pytest.fixture(scope="module")
 def nfa():
@@ -352,27 +350,49 @@ def test_golden_state_dicts_load_strict(nfa):
     blk.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in golden_state(g, "sd0__").items()}, strict=True)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout only exists in the build container")
+# A CPU numeric mode whose results do not depend on the machine: ATen's scalar kernels (its vectorised RNG and init kernels give other
+# bits per instruction set), MKL's reproducible code path, glibc's libm without its FMA variants, one thread.  The reference's digests
+# in tests/golden/seeded_construction.npz were recorded in the same mode (make_golden.py gen_seeded_construction).
+PINNED_CPU_ENV = {"ATEN_CPU_CAPABILITY": "default", "MKL_CBWR": "COMPATIBLE", "OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1",
+                  "GLIBC_TUNABLES": "glibc.cpu.hwcaps=-AVX2,-FMA,-FMA4"}
+
+_SEEDED_DIGESTS = r"""
+import hashlib, json, sys
+import torch
+sys.path.insert(0, sys.argv[1])
+import normflows_amd as nfa
+from bench import build_c2_model
+dig = lambda sd: [[k, str(v.dtype), ",".join(map(str, v.shape)), hashlib.sha256(v.detach().contiguous().numpy().tobytes()).hexdigest()]
+                  for k, v in sd.items()]
+c2 = dig(build_c2_model(num_layers=3, lib=nfa).state_dict())
+torch.manual_seed(3)
+glow = dig(nfa.flows.GlowBlock(12, 16, use_lu=True).state_dict())
+print(json.dumps({"capability": torch.backends.cpu.get_cpu_capability(), "c2": c2, "glow": glow}))
+"""
+
+
 def test_seeded_construction_is_bit_identical_to_reference(nfa):
     """Same constructor calls under the same seed give bit-identical parameters, permutations and masks
-    (the bench model is reproduced on the GPU box without shipping 21.8 MB of weights)."""
-    sys.path.insert(0, REF)
-    import normflows as nf
-    from bench import build_c2_model
-    a = build_c2_model(num_layers=3, lib=nf).state_dict()
-    b = build_c2_model(num_layers=3, lib=nfa).state_dict()
-    assert list(a.keys()) == list(b.keys())
-    for k in a:
-        assert a[k].dtype == b[k].dtype and torch.equal(a[k], b[k]), k
-    torch.manual_seed(3)
-    ga = nf.flows.GlowBlock(12, 16, use_lu=True)
+    (the bench model is reproduced on the GPU box without shipping 21.8 MB of weights).  The reference's state_dicts are
+    pinned by tests/golden/seeded_construction.npz (make_golden.py reference_only): key order, dtype, shape and the SHA-256
+    of every tensor's bytes, recorded in PINNED_CPU_ENV; our constructions run in a child process in the same mode."""
+    import json
+    g = load_golden("seeded_construction")
+    out = subprocess.run([sys.executable, "-c", _SEEDED_DIGESTS, ROOT], capture_output=True, text=True, timeout=600,
+                         env=dict(os.environ, **PINNED_CPU_ENV))
+    assert out.returncode == 0, out.stderr[-2000:]
+    mine = json.loads(out.stdout.strip().splitlines()[-1])
+    assert mine["capability"] == "DEFAULT", mine["capability"]          # the pinned mode took effect
+    for tag in ("c2", "glow"):
+        want = [[str(a) for a in row] for row in zip(*(g[tag + "__" + f] for f in ("keys", "dtypes", "shapes", "sha256")))]
+        assert [r[0] for r in mine[tag]] == [r[0] for r in want], tag
+        for got_row, want_row in zip(mine[tag], want):
+            assert got_row == want_row, (tag, got_row, want_row)
+    # strict loading of a state_dict with the reference's keys and shapes
     torch.manual_seed(3)
     gb = nfa.flows.GlowBlock(12, 16, use_lu=True)
-    sa, sb = ga.state_dict(), gb.state_dict()
-    assert list(sa.keys()) == list(sb.keys()) and all(torch.equal(sa[k], sb[k]) for k in sa)
-    # both directions of strict loading
-    gb.load_state_dict(sa, strict=True)
-    ga.load_state_dict(sb, strict=True)
+    assert list(gb.state_dict().keys()) == [str(k) for k in g["glow__keys"]]
+    gb.load_state_dict({str(k): v.clone() for k, v in gb.state_dict().items()}, strict=True)
 
 
 def test_pair_scheduler_orders(nfa, monkeypatch):
@@ -1381,28 +1401,23 @@ def test_conv_conditioner_training_path_declines_other_structures():
     assert made_pack.convnet_train_structure(14, 300, 12) is not None
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout only exists in the build container")
-def test_implicit_differentiation_of_the_maf_inverse_vs_reference_d_pass_autograd():
-    """The formula behind autograd.MafInverseFn, with the REFERENCE's own modules in float64 and no kernel involved: for x = T^-1(z)
-    (affine/autoregressive.py:29-38, D MADE passes) and cotangents (c_x, c_ld), the sweep v <- (c_x - J^T g_p(v, c_ld)) / s reaches a
-    bit-stable v in at most D sweeps, g_z = v and the parameter gradient = the VJP of ONE MADE pass with g_p(-v, -c_ld) -- equal to
-    torch autograd through the reference's D-pass loop to 1e-11 of scale."""
-    sys.path.insert(0, REF)
-    nf = pytest.importorskip("normflows")
-    torch.manual_seed(0)
+def test_implicit_differentiation_of_the_maf_inverse_vs_reference_d_pass_autograd(nfa):
+    """The formula behind autograd.MafInverseFn, in float64 with no kernel involved: for x = T^-1(z) (affine/autoregressive.py:29-38,
+    D MADE passes) and cotangents (c_x, c_ld), the sweep v <- (c_x - J^T g_p(v, c_ld)) / s reaches a bit-stable v in at most D
+    sweeps, g_z = v and the parameter gradient = the VJP of ONE MADE pass with g_p(-v, -c_ld) -- equal to torch autograd through the
+    reference's D-pass loop to 1e-11 of scale.  The reference's weights, x and gradients come from
+    tests/golden/maf_inverse_dpass_f64.npz (make_golden.py reference_only); the MADE is this package's, on the CPU."""
+    g = load_golden("maf_inverse_dpass_f64")
     D, H, B = 9, 28, 6
-    layer = nf.flows.MaskedAffineAutoregressive(D, H, num_blocks=2).double()
-    with torch.no_grad():
-        for p in layer.parameters():
-            p.add_(0.3 * torch.randn_like(p))
-    z = torch.randn(B, D, dtype=torch.float64, requires_grad=True)
-    cx, cl = torch.randn(B, D, dtype=torch.float64), torch.randn(B, dtype=torch.float64)
-    x, ld = layer.inverse(z)
-    ((x * cx).sum() + (ld * cl).sum()).backward()
-    ref = [z.grad.clone()] + [p.grad.clone() for p in layer.parameters()]
-    layer.zero_grad()
-    with torch.no_grad():
-        xs, _ = layer.inverse(z.detach())
+    layer = nfa.flows.MaskedAffineAutoregressive(D, H, num_blocks=2).double()
+    layer.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in golden_state(g).items()}, strict=True)
+    cx, cl = torch.from_numpy(g["cx"]), torch.from_numpy(g["cl"])
+    ref = [torch.from_numpy(g["gz"])] + [torch.from_numpy(g["g__" + k.replace(".", "__")]) for k, _ in layer.named_parameters()]
+    xs = torch.from_numpy(g["x"])
+    with torch.no_grad():         # x solves z = s(x) x + t(x) with THIS MADE: the recorded solution belongs to these weights
+        pr0 = layer.autoregressive_net(xs).view(B, D, 2)
+        z_back = (torch.sigmoid(pr0[..., 0] + 2.0) + 1e-3) * xs + pr0[..., 1]
+    assert float((z_back - torch.from_numpy(g["z"])).abs().max()) < 1e-12
     xq = xs.clone().requires_grad_(True)
     prm = layer.autoregressive_net(xq)
     pr = prm.view(B, D, 2)
@@ -1425,49 +1440,61 @@ def test_implicit_differentiation_of_the_maf_inverse_vs_reference_d_pass_autogra
 
 
 @pytest.mark.parametrize("kind", ["arnsf", "circular", "maf"])
-def test_generic_implicit_inverse_function_on_the_reference_own_layers(kind):
-    """autograd.ArInverseImplicitFn -- the Function itself, on the CPU, in float64 -- driving the REFERENCE's own autoregressive layers
+def test_generic_implicit_inverse_function_on_the_reference_own_layers(nfa, kind):
+    """autograd.ArInverseImplicitFn -- the Function itself, on the CPU, in float64 -- driving the reference's autoregressive layers
     through a three-method adapter (inverse / forward / the element-wise transform at given parameters): the autoregressive spline
     layer (neural_spline/autoregressive.py:11-134), its circular variant, the affine layer.  Gradients of x = T^-1(z) and its
     log-determinant for random cotangents against torch autograd through the reference's D recorded passes
-    (autoregressive.py:29-40): 1e-10 of scale, at most D + 1 sweeps; each cotangent alone as well."""
-    sys.path.insert(0, REF)
-    nf = pytest.importorskip("normflows")
+    (autoregressive.py:29-40): 1e-10 of scale, at most D + 1 sweeps; each cotangent alone as well.
+
+    The reference's side is recorded in tests/golden/ar_inverse_dpass_<kind>_f64.npz (make_golden.py reference_only): its weights,
+    x = T^-1(z), the D-pass gradients, and the first derivatives of its element-wise transform at (x, theta = net(x)).  The
+    autoregressive net is this package's MADE (CPU, float64) loaded with those weights; the element-wise transform enters as its
+    first-order expansion at that point, which is exactly what the implicit backward evaluates (the transform's value and its first
+    derivatives at the solution)."""
     from normflows_amd.autograd import ArInverseImplicitFn
-    torch.manual_seed(3)
+    g = load_golden("ar_inverse_dpass_%s_f64" % kind)
+    T = lambda k: torch.from_numpy(np.asarray(g[k]))
     D, H, B = 7, 20, 9
     if kind == "arnsf":
-        ref = nf.flows.AutoregressiveRationalQuadraticSpline(D, 2, H).mprqat
-        z0 = 1.5 * torch.randn(B, D, dtype=torch.float64)
+        mine = nfa.flows.AutoregressiveRationalQuadraticSpline(D, 2, H).mprqat
     elif kind == "circular":
-        ref = nf.flows.CircularAutoregressiveRationalQuadraticSpline(D, 1, H, [1, 4], tail_bound=torch.tensor([5.0, 3.0, 4.0, 5.0, 3.14159, 5.0, 5.0])).mprqat
-        z0 = torch.randn(B, D, dtype=torch.float64).clamp(-2.9, 2.9)
+        mine = nfa.flows.CircularAutoregressiveRationalQuadraticSpline(D, 1, H, [1, 4], tail_bound=torch.tensor(
+            [5.0, 3.0, 4.0, 5.0, 3.14159, 5.0, 5.0])).mprqat
     else:
-        ref = nf.flows.MaskedAffineAutoregressive(D, H, num_blocks=2)
-        z0 = torch.randn(B, D, dtype=torch.float64)
-    ref = ref.double()
+        mine = nfa.flows.MaskedAffineAutoregressive(D, H, num_blocks=2)
+    mine = mine.double()
+    mine.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in golden_state(g).items()}, strict=True)
+    net = mine.autoregressive_net
+    x0, theta0 = T("xl__x"), T("theta")
     with torch.no_grad():
-        for p in ref.parameters():
-            p.add_(0.2 * torch.randn_like(p))
+        assert float((net(x0) - theta0).abs().max()) < 1e-12 * max(1.0, float(theta0.abs().max()))   # the same net as the reference's
+    zf0, lf0, dzdx, dzdt, dldx, dldt = T("zf"), T("lf"), T("dzdx"), T("dzdt"), T("dldx"), T("dldt")
+    assert float((zf0 - T("z")).abs().max()) < 1e-12 * max(1.0, float(zf0.abs().max()))     # x solves the recorded z
+
+    def elementwise(x, theta):
+        dx, dt = x - x0, theta - theta0
+        return zf0 + dzdx * dx + torch.einsum("bdp,bp->bd", dzdt, dt), lf0 + (dldx * dx).sum(1) + (dldt * dt).sum(1)
 
     class Adapter:
-        autoregressive_net = ref.autoregressive_net
-        inverse = staticmethod(lambda z: ref.inverse(z))
-        forward = staticmethod(lambda x: ref.forward(x))
-        _elementwise = staticmethod(lambda x, theta, direction: ref._elementwise_forward(x, theta))
-    params = tuple(ref.parameters())
-    cx, cl = torch.randn(B, D, dtype=torch.float64), torch.randn(B, dtype=torch.float64)
-    for use_x, use_l in ((True, True), (True, False), (False, True)):
-        out = []
-        for implicit in (False, True):
-            ref.zero_grad(set_to_none=True)
-            z = z0.clone().requires_grad_(True)
-            x, ld = ArInverseImplicitFn.apply(Adapter, z, *params) if implicit else ref.inverse(z)
-            ((x * cx).sum() * float(use_x) + (ld * cl).sum() * float(use_l) if (use_x and use_l) else
-             ((x * cx).sum() if use_x else (ld * cl).sum())).backward()
-            out.append([x.detach(), ld.detach(), z.grad] + [p.grad.clone() for p in params])
+        autoregressive_net = net
+        inverse = staticmethod(lambda z: (x0.clone(), -lf0.clone()))
+        forward = staticmethod(lambda x: elementwise(x, net(x)))
+        _elementwise = staticmethod(lambda x, theta, direction: elementwise(x, theta))
+    names = [k for k, _ in mine.named_parameters()]
+    params = tuple(p for _, p in mine.named_parameters())
+    cx, cl, z0 = T("cx"), T("cl"), T("z")
+    for tag, use_x, use_l in (("xl", True, True), ("x", True, False), ("l", False, True)):
+        mine.zero_grad(set_to_none=True)
+        z = z0.clone().requires_grad_(True)
+        x, ld = ArInverseImplicitFn.apply(Adapter, z, *params)
+        ((x * cx).sum() * float(use_x) + (ld * cl).sum() * float(use_l) if (use_x and use_l) else
+         ((x * cx).sum() if use_x else (ld * cl).sum())).backward()
+        got = [x.detach(), ld.detach(), z.grad] + [p.grad for p in params]
+        want = [T(tag + "__x"), T(tag + "__ld"), T(tag + "__gz")] + [T(tag + "__g__" + n.replace(".", "__")) for n in names]
         assert 1 <= ArInverseImplicitFn.last_sweeps <= D + 1
-        for k, (a, b) in enumerate(zip(out[1], out[0])):
+        for k, (a, b) in enumerate(zip(got, want)):
+            a = torch.zeros_like(b) if a is None else a
             assert float((a - b).abs().max()) <= 1e-10 * max(1.0, float(b.abs().max())), (kind, use_x, use_l, k, float((a - b).abs().max()))
 
 
