@@ -623,6 +623,20 @@ int nf_nsf_wide(const void *x, void *y, void *logdet, const void *blob, const in
 int nf_nsf_wide_k(const void *x, void *y, void *logdet, const void *blob, const int32_t *table, const void *tabs,
                   const void *lu_logdet, int64_t B, int D, int hidden_padded, int K, int direction, int acc, double tail_bound,
                   double min_bin_width, double min_bin_height, double min_derivative, nf_stream_t stream);
+/* The CONDITIONAL layer (num_context_channels = C) in one launch, inference only: nf_nsf_wide_k's layer whose ResidualNet reads a
+ * context.  Replaces in addition nets/resnet.py:37-50 (ResidualBlock with context_layer: temps = glu(cat(t2, Wc ctx + bc)) =
+ * t2 * sigmoid(Wc ctx + bc)), :92-104 (initial_layer on cat(identity features, context)) and the per-call context of
+ * core.py:216-366 (ConditionalNormalizingFlow.log_prob / sample).
+ *   context     : (B, C) float32 rows with row stride ldc (floats, inner stride 1); ldc = 0: one context row for every row
+ *                 (context.expand(B, C) without a copy).
+ *   blob, table : normalizing-flows_amd/flows/nsf_ctx_pack.py (table[25] = C, table[26] = PC = C rounded up to 32; the caller
+ *                 packs for the same C: normflows_amd.ops.nsf_wide_ctx checks the host copy); tabs: nf_nsf_wide_tables.
+ *   -EINVAL for B < 0, C < 1, ldc < 0 and nf_nsf_wide_k's cases; -ENOTSUP where the x tile's positions overflow
+ *   (identity and transform features each rounded up to 32, + PC > 128: D <= 64 with C <= 64, D <= 96 with C <= 32), for
+ *   hidden_padded 512 (not built: it spills registers) and for K outside 4 | 8 | 16; -EFAULT for a NULL pointer; B == 0: NF_OK. */
+int nf_nsf_wide_ctx(const void *x, const void *context, void *y, void *logdet, const void *blob, const int32_t *table,
+                    const void *tabs, int64_t B, int64_t ldc, int D, int C, int hidden_padded, int K, int direction, int acc,
+                    double tail_bound, double min_bin_width, double min_bin_height, double min_derivative, nf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * MADE in ONE launch -- the single-pass direction of the autoregressive flows.  Replaces

@@ -315,6 +315,16 @@ def set_nsf_wide(mode=True):
     nsf_wide = bool(mode)
 
 
+# Conditional CoupledRationalQuadraticSpline (num_context_channels, ResidualNet with a GLU context gate) at inference as ONE launch
+# (nf_nsf_wide_ctx, csrc/nsf_ctx.hip); False = the conditioner as eager modules + nf_rqs_coupling (A/B runs, differential tests).
+nsf_context = True
+
+
+def set_nsf_context(mode=True):
+    global nsf_context
+    nsf_context = bool(mode)
+
+
 # Debug mode of the element-wise spline API (utils.splines): after every call a check launch (nf_rqs_spline_check)
 # sets device-side flags and the shim reads them back -- a host synchronisation per call, which is why it is off by default -- and
 # raises what the reference raises: AssertionError for a negative discriminant in the inverse direction (utils/splines.py:181),

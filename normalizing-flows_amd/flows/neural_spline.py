@@ -287,6 +287,10 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
             return self._image(inputs, context, False, ld, acc)
         if needs_grad(inputs, context, self):
             return self._autograd(inputs, context, False, ld, acc)
+        if context is not None:
+            ctx_pack = self._ctx_pack(inputs, context)
+            if ctx_pack is not None:
+                return self._wide_ctx(inputs, context, ctx_pack, 0, ld, acc)
         if self.use_fused and self._fused_eligible(inputs, context):
             return self._fused(inputs, 0, ld, acc)
         wide = self._wide_pack(inputs, context)
@@ -304,6 +308,10 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
             return self._image(inputs, context, True, ld, acc)
         if needs_grad(inputs, context, self):
             return self._autograd(inputs, context, True, ld, acc)
+        if context is not None:
+            ctx_pack = self._ctx_pack(inputs, context)
+            if ctx_pack is not None:
+                return self._wide_ctx(inputs, context, ctx_pack, 1, ld, acc)
         if self.use_fused and self._fused_eligible(inputs, context):
             return self._fused(inputs, 1, ld, acc)
         wide = self._wide_pack(inputs, context)
@@ -363,6 +371,39 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         blob, table, tabs, hp, lad = packed
         return ops.nsf_wide(inputs, blob, table, tabs, hp, direction, self.tail_bound, self.min_bin_width, self.min_bin_height,
                             self.min_derivative, logdet=ld, acc=acc, lu_logdet=lad, K=self.num_bins)
+
+    # -- the conditional layer (ResidualNet with context_features) at inference as one launch (csrc/nsf_ctx.hip) ---------------
+    def _ctx_pack(self, inputs, context):
+        """Device copies of flows/nsf_ctx_pack.py's streams + the batch-shared spline's knot tables, rebuilt when a parameter
+        changes (the context_layer parameters are part of the net's); None when the layer or the call is outside nf_nsf_wide_ctx's
+        structure (then: the conditioner as eager modules + nf_rqs_coupling)."""
+        if not (self.use_fused and _config.nsf_context and inputs.dim() == 2 and inputs.dtype == torch.float32 and inputs.is_cuda
+                and torch.is_tensor(context) and context.dim() == 2 and context.dtype == torch.float32 and context.is_cuda
+                and context.shape[0] == inputs.shape[0]):
+            return None
+        net, u = self.transform_net, self.unconditional_transform
+        if u is None or not isinstance(net, ResidualNet) or net.context_features is None or context.shape[1] != net.context_features:
+            return None
+        tensors = list(net.parameters()) + [u.unnormalized_widths, u.unnormalized_heights, u.unnormalized_derivatives]
+        key = _keys.pkey(tensors) + (str(inputs.device), net.training)
+        cache = self.__dict__.get("_ctx_cache")
+        if cache is None or cache[0] != key:
+            from . import nsf_ctx_pack
+            packed = nsf_ctx_pack.pack_nsf_ctx(self)
+            if packed is not None:
+                blob, table = packed
+                tabs = ops.nsf_wide_tables(u.unnormalized_widths.detach(), u.unnormalized_heights.detach(),
+                                           u.unnormalized_derivatives.detach(), self.num_bins, self.tail_bound, self.min_bin_width,
+                                           self.min_bin_height, self.min_derivative)
+                packed = (torch.from_numpy(blob).to(inputs.device), torch.from_numpy(table).to(inputs.device), tabs, int(table[3]),
+                          table)
+            cache = self.__dict__["_ctx_cache"] = (key, packed)
+        return cache[1]
+
+    def _wide_ctx(self, inputs, context, packed, direction, ld, acc):
+        blob, table, tabs, hp, table_host = packed
+        return ops.nsf_wide_ctx(inputs, context, blob, table, tabs, hp, direction, self.tail_bound, self.min_bin_width,
+                                self.min_bin_height, self.min_derivative, logdet=ld, acc=acc, K=self.num_bins, table_host=table_host)
 
     # -- images (nsf/coupling.py:150-160): every pixel is a row of C channel features for the 2-D coupling kernel ----
     def _image(self, inputs, context, sample, ld, acc):

@@ -1176,6 +1176,38 @@ def nsf_wide(x, blob, table, tabs, hidden_padded, direction, tail_bound, min_bin
     return y, logdet
 
 
+def nsf_wide_ctx(x, context, blob, table, tabs, hidden_padded, direction, tail_bound, min_bin_width=1e-3, min_bin_height=1e-3,
+                 min_derivative=1e-3, logdet=None, acc=None, K=8, table_host=None):
+    """The conditional CoupledRationalQuadraticSpline as one launch (nf_nsf_wide_ctx); blob / table from
+    flows/nsf_ctx_pack.pack_nsf_ctx (table_host: its host copy, checked against the context's width), tabs from nsf_wide_tables.
+    context (B, C) float32: a row stride is passed as it is when the inner stride is 1 (0 for context.expand(B, C)), otherwise the
+    context is made contiguous."""
+    L.require_device(x, context, blob, table, tabs)
+    if x.dtype != torch.float32:
+        raise NotImplementedError("nsf_wide_ctx: float32 only")
+    B, D = x.shape
+    if context.dim() != 2 or context.shape[0] != B or context.dtype != torch.float32:
+        raise ValueError("nsf_wide_ctx: context must be (%d, C) float32, got %s %s" % (B, tuple(context.shape), context.dtype))
+    C_ = context.shape[1]
+    if table_host is not None and (int(table_host[25]) != C_ or int(table_host[26]) != (C_ + 31) // 32 * 32):
+        raise ValueError("nsf_wide_ctx: the pack is for %d context features, the context has %d" % (int(table_host[25]), C_))
+    if context.stride(1) != 1 and C_ > 1:
+        context = context.contiguous()
+    ldc = context.stride(0) if B > 1 else C_
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    if logdet is None:
+        logdet = torch.empty(B, dtype=x.dtype, device=x.device)
+        acc = L.LD_WRITE
+    elif acc is None:
+        acc = L.LD_ADD
+    rc = L.lib().nf_nsf_wide_ctx(ptr(x), ptr_any(context), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(tabs), i64(B), i64(ldc),
+                                 i32(D), i32(C_), i32(hidden_padded), i32(int(K)), i32(direction), i32(acc), f64(float(tail_bound)),
+                                 f64(min_bin_width), f64(min_bin_height), f64(min_derivative), L.stream())
+    L.check(rc, "nf_nsf_wide_ctx")
+    return y, logdet
+
+
 def made_forward_affine(x, blob, table, hidden_padded, logdet=None, acc=None):
     """MaskedAffineAutoregressive.forward (autoregressive.py:24-27, :101-110 over nets/made.py:296-304) as one launch
     (nf_made_forward_affine); blob / table from flows/made_pack.pack_made_forward."""
