@@ -13,8 +13,9 @@ Who joins.  Nothing may read such a gradient on another stream before `join()`:
     `loss.backward()` / `torch.autograd.grad()` on the current stream (optimizer step, clipping, all-reduce, .grad reads) is ordered
     behind the side stream's work; under hipGraph capture the same callback closes the fork inside the capture;
   * dp.OverlappedGradientAverager calls `join()` before it starts a bucket's all-reduce during backward.
-PairTrainFn takes the side stream only when no other reader can exist before that: every parameter of the pair writes into a registered
-gradient buffer whose .grad is unset (autograd adopts the returned view: no accumulation kernel on the current stream) and has no
+PairTrainFn takes the side stream only when no other reader can exist before that: every parameter of the pair writes into its registered
+gradient buffer, handed to this call while .grad is unset (autograd adopts the returned view: no accumulation kernel on the current
+stream), the parameter had one training forward since zero_grad (no second contribution of the same graph to add), and has no
 tensor hooks (post-accumulate hooks declared join-aware excepted: hook_is_aware).  
 """
 import torch

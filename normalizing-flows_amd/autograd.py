@@ -216,6 +216,7 @@ class LULinearPermuteFn(torch.autograd.Function):
     def forward(ctx, x, perm, lower_entries, upper_entries, udiag_raw, bias, eps, direction, ld_acc=None, acc=1, factors_out=None,
                 holder=None):
         D = x.shape[1]
+        _gradbuf.use((lower_entries, upper_entries, udiag_raw, bias))     # (a second use before zero_grad: see _pair_side_ok)
         ctx.acc, ctx.has_acc = acc, ld_acc is not None
         if ld_acc is not None:
             ctx.mark_dirty(ld_acc)      # the caller's running log-density, updated in place (inside the launch where possible)
@@ -423,6 +424,7 @@ class CouplingTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w0, b0, wf, bf, uw, uh, ud, iidx, tidx, blob, parity, kw, wfull, wpad, ld_acc, acc, *blk):
         nb = len(blk) // 4
+        _gradbuf.use((w0, b0, wf, bf, uw, uh, ud) + blk)
         wb = [blk[4 * i + j].detach() for i in range(nb) for j in (0, 2)]
         bb = [blk[4 * i + j].detach() for i in range(nb) for j in (1, 3)]
         fk = dict(tail_bound=kw["tail_bound"], min_bin_width=kw["min_bin_width"], min_bin_height=kw["min_bin_height"],
@@ -508,6 +510,14 @@ class CouplingTrainFn(torch.autograd.Function):
                 (gld if ctx.has_acc else None), None, *gblk)
 
 
+def _pair_side_ok(params, dests):
+    """May gradient writes into `dests` move to the side stream?  Only when nothing reads them on the current stream before the join:
+    every destination is the parameter's registered slice, handed out to this call (autograd adopts it as .grad without a kernel:
+    no existing .grad to accumulate into), the parameter had ONE training-Function forward since zero_grad (no second contribution
+    of the same graph for autograd to add to it), and no tensor hook looks at it on the way."""
+    return all(_gradbuf.is_slice(p_, d_) and _gradbuf.sole_use(p_) and _sidestream.nobody_reads_early(p_) for p_, d_ in zip(params, dests))
+
+
 class PairTrainFn(torch.autograd.Function):
     """A benchmark-shaped [CoupledRationalQuadraticSpline, LULinearPermute] pair in the density direction under autograd (round 6):
     ONE forward launch for LULinearPermute.inverse + the whole coupling layer (nf_rqs_fused_train_pair_fwd: the inference kernel's
@@ -521,6 +531,7 @@ class PairTrainFn(torch.autograd.Function):
     def forward(ctx, x, perm, lower, upper, udiag, lbias, lu_eps, lu_fbuf, lu_wd, w0, b0, wf, bf, uw, uh, ud, iidx, tidx, blob, parity, kw,
                 wfull, wpad, ld_acc, acc, *blk):
         nb = len(blk) // 4
+        _gradbuf.use((w0, b0, wf, bf, uw, uh, ud, lower, upper, udiag, lbias) + blk)
         fk = dict(tail_bound=kw["tail_bound"], min_bin_width=kw["min_bin_width"], min_bin_height=kw["min_bin_height"],
                   min_derivative=kw["min_derivative"])
         xlu, y, ld, cond24, acts = ops.rqs_fused_train_pair_fwd(x, blob, parity, nb, logdet=ld_acc,
@@ -556,12 +567,13 @@ class PairTrainFn(torch.autograd.Function):
         D = x.shape[1]
         Lm, Um = lu_fbuf[:D * D].view(D, D), lu_fbuf[D * D:2 * D * D].view(D, D)
         # The last two of the seven launches only produce parameter gradients: on the side stream when nobody can read them before the
-        # join at the end of this backward pass (_sidestream.py) -- every gradient goes into a registered buffer that autograd will
-        # adopt as .grad without a kernel (no existing .grad to accumulate into) and no tensor hook looks at it on the way.
+        # join at the end of this backward pass (_sidestream.py, _pair_side_ok).
         side = None
         if _config.train_reduce_async:
             params = (w0, b0, wf, bf, uw, uh, ud, lower, upper, udiag, lbias) + tuple(blk)
-            if all(_gradbuf.target(p_) is not None and _sidestream.nobody_reads_early(p_) for p_ in params):
+            dests = (dest["w0"], dest["b0"], dest["wf"], dest["bf"], dest["uw"], dest["uh"], dest["ud"], dest["lower"], dest["upper"],
+                     dest["udiag"], dest["lbias"]) + tuple(dest["blocks"])
+            if _pair_side_ok(params, dests):
                 side = _sidestream.stream(x.device)
         # ONE C-ABI call, seven launches: the coupling's four passes, the composed LU's pass, one reduction for both, the LU's factors
         # (two calls when the last two launches go to the side stream)

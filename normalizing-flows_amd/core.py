@@ -189,6 +189,19 @@ class _frozen_parameters:
         return False
 
 
+def _row_wise(f):
+    """True when flow `f` provably maps every row of a batch on its own, so that zero rows appended to the batch change nothing it
+    computes for the others.  Exact types only (a subclass may reduce over the batch); ActNorm only once initialised (its first call
+    takes (s, t) from the batch statistics).  BatchNorm and any other flow: False."""
+    from .flows.affine import AffineConstFlow
+    from .flows.mixing import Permute
+    from .flows.normalization import ActNorm
+    t = type(f)
+    if t in (CoupledRationalQuadraticSpline, LULinearPermute, Permute, AffineConstFlow):
+        return True
+    return t is ActNorm and f.initialised()
+
+
 def run_chain(flows, z, inverse, ld, acc):
     """_run_chain_impl behind the training step's one-launch weight packing (_prepack.py): a differentiable density pass first
     packs every eligible layer's weights / LU factors with one launch per kind; the layers then skip their own pack launches."""
@@ -393,7 +406,8 @@ class NormalizingFlow(nn.Module):
 
     def _train_pad_rows(self, x):
         """Rows of zero padding that put a differentiable density pass on the 64-row-tile training kernels (config.train_pad_batch):
-        > 0 only for a ragged batch of >= 1024 rows through a model with a benchmark-shaped [CoupledRQS, LULinearPermute] pair."""
+        > 0 only for a ragged batch of >= 1024 rows through a model with a benchmark-shaped [CoupledRQS, LULinearPermute] pair, and
+        only when every flow of the chain is row-wise (_row_wise): the padding rows must not change what the real rows see."""
         B = x.shape[0] if x.dim() == 2 else 0
         if (B < 1024 or B % 64 == 0 or not _config.train_pad_batch or not x.is_cuda or x.dtype != torch.float32 or x.shape[1] != 64
                 or not torch.is_grad_enabled() or not (_config.train_pair and _config.train_bwd_onecall)):
@@ -403,7 +417,7 @@ class NormalizingFlow(nn.Module):
             if (isinstance(a, CoupledRationalQuadraticSpline) and isinstance(b, LULinearPermute) and b.linear.features == 64
                     and a.prqct._train_full_ok(x, None, False) and all(p.requires_grad for p in a.parameters())
                     and all(p.requires_grad for p in b.parameters())):
-                return (-B) % 64
+                return (-B) % 64 if all(_row_wise(f) for f in fl) else 0
         return 0
 
     def _log_prob_impl(self, x):

@@ -211,7 +211,11 @@ extern "C" int nf_coupling_train_bwd(const void *x, const void *grad_y, const vo
 // ---- a [CoupledRQS, LULinearPermute] pair: the coupling's backward, then the composed LU's (autograd.PairTrainFn) -------------------
 // floats of `scratch` for nf_pair_train_bwd: nf_coupling_train_bwd's + the coupling's input gradient (B x 64), the LU pass's
 // partial tiles and the reduced dW_d (64 x 64)
+// The pair appends ONE reduction job (the LU's) to the coupling's 2 * num_blocks + 2: one block fewer than the single layer allows.
+static inline bool pair_blocks_ok(int num_blocks) { return num_blocks >= 1 && 2 * num_blocks + 3 <= RJ_MAX; }
+
 extern "C" int64_t nf_pair_train_bwd_scratch_floats(int64_t B, int num_blocks) {
+    if (!pair_blocks_ok(num_blocks)) return NF_ENOTSUP;
     const int64_t n = nf_coupling_train_bwd_scratch_floats(B, num_blocks);
     if (n < 0) return n;
     const int g = nf_lu_bwd_composed_grid(B);
@@ -259,6 +263,7 @@ static int pair_train_bwd_head(const void *x_in, const void *xlu, const void *gr
                                int num_blocks, int K, double tail_bound, double min_bin_width, double min_bin_height,
                                double min_derivative, nf_stream_t stream, nf::PairTail &T) {
     using namespace nf;
+    if (!pair_blocks_ok(num_blocks)) return NF_ENOTSUP;       // before any launch: J.j[] has room for 2 * num_blocks + 3 jobs
     if (!x_in || !Wd || !Lm || !Um || !perm || !unconstrained_upper_diag || !grad_x_in || !g_lower || !g_upper || !g_udiag || !g_lbias ||
         !scratch)
         return NF_EFAULT;

@@ -162,14 +162,19 @@ class FlatParameters:
         return [self.param]
 
     def zero_grad(self):
-        """Host only: the next backward writes every slice (sync() zero-fills what it did not)."""
+        """Host only: the next backward writes every slice (sync() zero-fills what it did not).  Each slice is handed to a backward
+        kernel at most once until the next zero_grad() / sync(): a second gradient of the same parameter (another micro-batch, a
+        second loss of the same graph, torch.autograd.grad) goes to a fresh tensor that autograd adds the ordinary way (_gradbuf.py)."""
+        from . import _gradbuf
         for p in self.params:
             p.grad = None
+            _gradbuf.reset(p)
         self.param.grad = self.grad
 
     def sync(self):
         """Make `self.param.grad` the gradient of the last backward: slices the kernels wrote are already there (their `.grad` IS
         the slice); other gradients are copied in, missing ones zero-filled.  Returns the number of slices that needed a launch."""
+        from . import _gradbuf
         n = 0
         with torch.no_grad():
             for p, v in self.views:
@@ -180,6 +185,7 @@ class FlatParameters:
                 elif g.data_ptr() != v.data_ptr() or g.stride() != v.stride():
                     v.copy_(g)
                     n += 1
+                _gradbuf.reset(p, uses=False)   # the slice holds .grad now: handed out again only once .grad is None
         self.param.grad = self.grad
         return n
 

@@ -24,10 +24,14 @@ class ActNorm(AffineConstFlow):
         self._init_known = None
         return super()._load_from_state_dict(*args, **kwargs)
 
-    def _maybe_init(self, z, inverse):
+    def initialised(self):
+        """True once (s, t) hold their data-dependent values: from then on the flow treats every row on its own."""
         if self._init_known is None:
             self._init_known = bool(self.data_dep_init_done.item() > 0.0)
-        if self._init_known:
+        return self._init_known
+
+    def _maybe_init(self, z, inverse):
+        if self.initialised():
             return
         assert self.s is not None and self.t is not None
         if not (self._per_channel or self._elementwise):

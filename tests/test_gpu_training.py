@@ -1237,10 +1237,19 @@ def test_pair_backward_tail_on_the_side_stream(nfa):
             l1, g1 = step()
             assert l1 == l0 and torch.equal(g1, g0)
         assert len(sides) == 12 and all(isinstance(s_, torch.cuda.Stream) for s_ in sides)
-        # an existing .grad (no zero_grad): autograd would ACCUMULATE on the current stream -> one stream
+        # an existing .grad (no zero_grad): autograd would ACCUMULATE on the current stream -> one stream; a second, DIFFERENT batch
+        # adds its gradient to the slice .grad already is (with the same batch, a slice written over would still give g0 + g0)
+        x2 = torch.randn(4096, 64, device=DEV)
+        flat.zero_grad()
+        m.forward_kld(x2).backward()
+        assert flat.sync() == 0
+        g2 = flat.grad.clone()
+        step()
         del sides[:]
-        m.forward_kld(x).backward()
+        m.forward_kld(x2).backward()
         assert len(sides) == 4 and all(s_ is None for s_ in sides)
+        flat.sync()
+        assert torch.equal(flat.grad, g0 + g2)
         # a tensor hook on one parameter of the second pair: that pair stays on one stream, the others do not
         del sides[:]
         flat.zero_grad()
@@ -1271,6 +1280,98 @@ def test_pair_backward_tail_on_the_side_stream(nfa):
         ops.pair_train_bwd = orig
         nfa.config.set_train_reduce_async(False)          # (the default: measured, no gain -- config.py)
         flat.release()
+
+
+@pytest.mark.parametrize("path", ["pair", "onecall", "async"])
+def test_flat_parameters_accumulate_two_batches_on_the_benchmark_kernels(nfa, path):
+    """Two DIFFERENT 1024-row batches through the benchmark-shaped model on dp.FlatParameters: gradient accumulation over micro-batches,
+    two losses in one graph, backward() then torch.autograd.grad, and torch.autograd.grad twice.  A registered gradient slice goes
+    to a backward kernel at most once per zero_grad() (_gradbuf.py): every accumulated gradient equals g1 + g2 of the same kernels
+    run without FlatParameters BIT FOR BIT (deterministic kernels, one float32 add), also in the flat buffer after sync(), and the
+    float64 model's g1 + g2 to 2e-3 of each parameter's scale (a slice written over gives an O(1) error: 2 g2 instead of g1 + g2).
+    path: the pair Functions (default), config.set_train_pair(False) (the one-call CouplingTrainFn + LULinearPermuteFn's fused
+    backward), config.set_train_reduce_async(True) (the pair backward's tail on the side stream only where no second contribution can
+    read the slice early: never when the parameters are used twice in one graph)."""
+    import copy
+    from bench import build_c2_model
+    from normflows_amd import ops
+    torch.manual_seed(21)
+    m = build_c2_model(num_layers=4, sigma=0.05).to(DEV)
+    plain, m64 = copy.deepcopy(m), copy.deepcopy(m).double()
+    x1, x2 = torch.randn(1024, 64, device=DEV), torch.randn(1024, 64, device=DEV)
+    sides = []
+    orig = ops.pair_train_bwd
+
+    def spy(*a, **k):
+        sides.append(k.get("side"))
+        return orig(*a, **k)
+    ops.pair_train_bwd = spy
+    flat = None
+    try:
+        nfa.config.set_train_pair(path != "onecall")
+        nfa.config.set_train_reduce_async(path == "async")
+
+        def grads(model, x):
+            model.zero_grad(set_to_none=True)
+            model.forward_kld(x).backward()
+            return [p_.grad.clone() for p_ in model.parameters()]
+        g1, g2 = grads(plain, x1), grads(plain, x2)
+        assert all(torch.equal(a_, b_) for a_, b_ in zip(g1, grads(plain, x1))), "deterministic"
+        g12 = [a_ + b_ for a_, b_ in zip(g1, g2)]
+        r1, r2 = grads(m64, x1.double()), grads(m64, x2.double())
+        r12 = [a_ + b_ for a_, b_ in zip(r1, r2)]
+        names = [n for n, _ in m.named_parameters()]
+        flat = nfa.dp.FlatParameters(m)
+        params = list(m.parameters())
+
+        def check(what, got, want, want64):
+            for n, a_, b_, c_ in zip(names, got, want, want64):
+                assert torch.equal(a_, b_), (path, what, n, float((a_ - b_).abs().max()))
+                scale = float(c_.abs().max())
+                assert float((a_.double() - c_).abs().max()) <= 2e-3 * scale, (path, what, n, float((a_.double() - c_).abs().max()), scale)
+
+        def check_flat(what, want):
+            flat.sync()
+            for n, (lo, hi), b_ in zip(names, flat.offsets, want):
+                assert torch.equal(flat.grad[lo:hi], b_.reshape(-1)), (path, what, "flat", n)
+        n_pair = 4 if path != "onecall" else 0
+        # micro-batch accumulation
+        flat.zero_grad()
+        del sides[:]
+        m.forward_kld(x1).backward()
+        m.forward_kld(x2).backward()
+        check("micro-batches", [p_.grad for p_ in params], g12, r12)
+        check_flat("micro-batches", g12)
+        assert len(sides) == 2 * n_pair
+        if path == "async":          # the first backward writes unclaimed slices; the second accumulates on the current stream
+            assert all(isinstance(s_, torch.cuda.Stream) for s_ in sides[:4]) and all(s_ is None for s_ in sides[4:]), sides
+        # one graph, two losses: every parameter is used twice in the graph -> never the side stream
+        flat.zero_grad()
+        del sides[:]
+        (m.forward_kld(x1) + m.forward_kld(x2)).backward()
+        check("one graph", [p_.grad for p_ in params], g12, r12)
+        check_flat("one graph", g12)
+        assert len(sides) == 2 * n_pair and all(s_ is None for s_ in sides), sides
+        # backward(), then torch.autograd.grad: .grad keeps g1, the returned gradients are g2
+        flat.zero_grad()
+        m.forward_kld(x1).backward()
+        got2 = torch.autograd.grad(m.forward_kld(x2), params)
+        check("autograd.grad after backward", got2, g2, r2)
+        check("backward before autograd.grad", [p_.grad for p_ in params], g1, r1)
+        check_flat("backward before autograd.grad", g1)
+        # torch.autograd.grad twice: the second call does not write over the first one's result
+        flat.zero_grad()
+        got1 = torch.autograd.grad(m.forward_kld(x1), params)
+        got2 = torch.autograd.grad(m.forward_kld(x2), params)
+        check("second autograd.grad", got2, g2, r2)
+        check("first autograd.grad", got1, g1, r1)
+        assert all(p_.grad is None for p_ in params)
+    finally:
+        ops.pair_train_bwd = orig
+        nfa.config.set_train_pair(True)
+        nfa.config.set_train_reduce_async(False)
+        if flat is not None:
+            flat.release()
 
 
 @pytest.fixture(params=["wg128", "wg256"])
@@ -1363,6 +1464,109 @@ def test_ragged_training_batch_runs_padded_on_the_tile_kernels(nfa):
     for n in g0:
         err = float((g1[n] - g0[n]).abs().max()) / max(float(g0[n].abs().max()), 1e-12)
         assert err < 2e-3, (n, err)
+
+
+class _CenterRows(torch.nn.Module):
+    """A user flow that reduces over the batch: subtracts the batch mean (log-det 0)."""
+
+    def forward(self, z):
+        return z - z.mean(0, keepdim=True), torch.zeros(z.shape[0], dtype=z.dtype, device=z.device)
+
+    def inverse(self, z):
+        return self.forward(z)
+
+
+def _ragged_pad_run(nfa, extra, where, steps=1):
+    """The benchmark pairs with `extra` put in front of (`where` = "first") or behind ("last") them in the flow list, on a ragged
+    batch of 1024 + 77 rows: for each of `steps` steps, the pair kernels' batch sizes (spy), log_prob, the input gradient and every
+    parameter gradient, once with config.train_pad_batch on and once on a deep copy with it off.  Between steps the parameters of
+    `extra` move by +0.1 (an ActNorm fresh from its data-dependent initialisation sits where its own gradients vanish: only rounding
+    noise would be left to compare)."""
+    import copy
+    from bench import build_c2_model
+    from normflows_amd import ops
+    base = build_c2_model(num_layers=4, sigma=0.05)
+    fl = [extra] + list(base.flows) if where == "first" else list(base.flows) + [extra]
+    m = nfa.NormalizingFlow(base.q0, fl).to(DEV)
+    m_off = copy.deepcopy(m)
+    torch.manual_seed(5)
+    x = torch.randn(1024 + 77, 64, device=DEV) * 1.5 + 0.3
+    calls = []
+    orig = ops.pair_train_bwd
+
+    def spy(*a, **k):
+        calls.append(a[0].shape[0])
+        return orig(*a, **k)
+    ops.pair_train_bwd = spy
+    out = {True: [], False: []}
+    try:
+        for pad, model in ((True, m), (False, m_off)):
+            nfa.config.set_train_pad_batch(pad)
+            for step in range(steps):
+                if step:
+                    with torch.no_grad():
+                        for p_ in (model.flows[0] if where == "first" else model.flows[-1]).parameters():
+                            p_.add_(0.1)
+                del calls[:]
+                model.zero_grad(set_to_none=True)
+                xa = x.clone().requires_grad_(True)
+                lp = model.log_prob(xa)
+                assert lp.shape == (x.shape[0],)
+                (-lp.mean()).backward()
+                out[pad].append((list(calls), lp.detach().clone(), None if xa.grad is None else xa.grad.clone(),
+                                 {n: p_.grad.clone() for n, p_ in model.named_parameters()}))
+    finally:
+        ops.pair_train_bwd = orig
+        nfa.config.set_train_pad_batch(True)
+    return x, m, m_off, out
+
+
+def _assert_ragged_runs_agree(on, off, what):
+    """The ragged test's tolerances (test_ragged_training_batch_runs_padded_on_the_tile_kernels)."""
+    _, lp1, gx1, g1 = on
+    _, lp0, gx0, g0 = off
+    assert_close(N(lp1), N(lp0), what="%s log_prob" % what, rtol=1e-5, atol=2e-4)
+    assert (gx1 is None) == (gx0 is None), what
+    if gx0 is not None:
+        bad = ((gx1 - gx0).abs() > 1e-4 * float(gx0.abs().max())).any(dim=1)
+        assert int(bad.sum()) <= 2, (what, int(bad.sum()))
+    for n in g0:
+        err = float((g1[n] - g0[n]).abs().max()) / max(float(g0[n].abs().max()), 1e-12)
+        assert err < 2e-3, (what, n, err)
+
+
+@pytest.mark.parametrize("where", ["first", "last"])
+def test_ragged_batch_pads_only_a_row_wise_chain_actnorm(nfa, where):
+    """config.train_pad_batch pads a ragged batch only when every flow of the chain is row-wise (core._row_wise): an ActNorm that is
+    not initialised yet would take its data-dependent (s, t) from statistics that include the zero rows.  First step: no padding
+    (the pair kernels do not run: the general kernels on 1101 rows), s and t are the float64 statistics of the 1101 real rows where
+    ActNorm sees the data first (last in the list: log(std_unbiased + 1e-6), mean), and s, t, log_prob and every gradient agree with a
+    run with padding off.  Second step, ActNorm initialised: the chain pads again (the pair kernels on 1152 rows) and still agrees."""
+    x, m, m_off, out = _ragged_pad_run(nfa, nfa.flows.ActNorm(64), where, steps=2)
+    an, an_off = (m.flows[0], m_off.flows[0]) if where == "first" else (m.flows[-1], m_off.flows[-1])
+    if where == "last":           # (s, t as the first step initialised them: + 0.1 since)
+        xd = x.double()
+        s_ref, t_ref = torch.log(xd.std(0, unbiased=True) + 1e-6), xd.mean(0)
+        s_err = float((an.s.detach().double().view(-1) - 0.1 - s_ref).abs().max())
+        t_err = float((an.t.detach().double().view(-1) - 0.1 - t_ref).abs().max())
+        assert s_err < 1e-5 and t_err < 1e-5 * max(1.0, float(t_ref.abs().max())), (s_err, t_err)
+    for step in range(2):
+        _assert_ragged_runs_agree(out[True][step], out[False][step], "ActNorm %s, step %d" % (where, step))
+    assert torch.equal(an.s, an_off.s) and torch.equal(an.t, an_off.t)
+    assert out[True][0][0] == [] and out[False][0][0] == [] and out[False][1][0] == [], (out[True][0][0], out[False][1][0])
+    assert out[True][1][0] == [1152] * 4, out[True][1][0]        # initialised: the chain is row-wise, padded onto whole tiles
+
+
+@pytest.mark.parametrize("kind", ["batchnorm", "center"])
+def test_ragged_batch_is_not_padded_through_batch_statistics(nfa, kind):
+    """A flow that reduces over the batch -- BatchNorm (its density direction through Reverse), or a user flow that subtracts the batch
+    mean -- in a chain with benchmark-shaped pairs: zero padding rows would change the real rows' output, so the ragged batch is not
+    padded (the pair kernels do not run) and log_prob and every gradient agree with a run with padding off."""
+    extra = nfa.flows.Reverse(nfa.flows.BatchNorm()) if kind == "batchnorm" else _CenterRows()
+    where = "last" if kind == "batchnorm" else "first"       # (BatchNorm passes no gradient to its input: put it where x enters)
+    _, _, _, out = _ragged_pad_run(nfa, extra, where)
+    _assert_ragged_runs_agree(out[True][0], out[False][0], kind)
+    assert out[True][0][0] == [] and out[False][0][0] == [], out[True][0][0]
 
 
 def test_backward_after_reforward_with_other_weights_raises(nfa):

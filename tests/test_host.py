@@ -293,6 +293,9 @@ def test_c_abi_argument_validation_training_entry_points(nfa):
                                      one, f64(1e-3), one, gl, one, one, one, one, one, one, one, one, one, one, four, one, i32(0),
                                      i64(B), i32(64), i32(128), i32(nb), i32(8), f64(3.0), f64(1e-3), f64(1e-3), f64(1e-3), null)
     assert pb(x_in=null) == -14 and pb(Wd=null) == -14 and pb(gl=null) == -14 and pb(B=100) == -95 and pb(nb=0) == -95
+    # the pair appends the LU's reduction job to the coupling's 2 nb + 2: 6 blocks would overrun the job list (the single layer takes 6)
+    assert pb(nb=6) == -95 and lib.nf_pair_train_bwd_scratch_floats(i64(65536), i32(6)) == -95
+    assert lib.nf_pair_train_bwd_scratch_floats(i64(65536), i32(5)) > 0 and lib.nf_coupling_train_bwd_scratch_floats(i64(65536), i32(6)) > 0
 
     def pf(B=128, D=64, H=128, nb=2, K=8, x=one, xlu=one, acc=1, parity=0):
         return lib.nf_rqs_fused_train_pair_fwd(x, xlu, one, one, one, one, one, i32(parity), i64(B), i32(D), i32(H), i32(nb), i32(K),
@@ -529,6 +532,43 @@ avg3.remove()
 net.zero_grad(set_to_none=True)                                                   # a dropped view is re-attached
 fg.zero()
 assert all(p.grad is v for p, v in fg.views)
+# micro-batch accumulation on dp.FlatParameters under no_sync(): the backward of the first micro-batch writes the registered slice,
+# the second one's gradient is ADDED to it (not written over it) before the in-place all-reduce of the flat buffer
+from normflows_amd import _gradbuf
+
+
+class WritesDestination(torch.autograd.Function):      # a training Function whose kernels take gradient destinations
+    @staticmethod
+    def forward(ctx, x, w):
+        ctx.save_for_backward(x, w)
+        return x @ w
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        gw = _gradbuf.out(w)
+        torch.mv(x.t(), g, out=gw)
+        return None, gw
+
+
+mf = torch.nn.Module()
+mf.w = torch.nn.Parameter(torch.tensor([0.5, -1.0, 2.0]))
+mf.b = torch.nn.Parameter(torch.tensor(0.25))
+flat = nfa.dp.FlatParameters(mf)
+avg4 = nfa.dp.OverlappedGradientAverager(flat.params, bucket_bytes=8, flat=flat)
+mb = lambda v: (WritesDestination.apply(torch.full((1, 3), float(v)), mf.w) + mf.b).sum()
+for step in range(2):
+    flat.zero_grad()
+    with avg4.no_sync():
+        mb(rank + 1).backward()                         # per-element gradient rank + 1 ...
+    mb(10 * (rank + 1)).backward()                      # ... then 10 (rank + 1): 11 (rank + 1) on this rank
+    assert avg4.finish() == len(avg4.buckets)
+    flat.sync()
+    want = 11.0 * (1 + world) / 2.0
+    assert torch.equal(mf.w.grad, torch.full((3,), want)) and torch.equal(flat.grad[:3], torch.full((3,), want)), (mf.w.grad, flat.grad)
+    assert float(flat.grad[3]) == 2.0
+avg4.remove()
+flat.release()
 # ActNorm data-dependent init under DP: global per-channel mean / unbiased std from the ranks' local moments
 xa = torch.randn(23, 5, 3, generator=g) * 2.0 + 0.7            # (rows, channels, pixels), same on every rank
 lo, hi = nfa.dp.shard_bounds(23, world, rank)
@@ -611,7 +651,7 @@ sum((p * n_).sum() for p, n_ in zip(params, noise)).backward()
 assert len(avg2._pending) == len(avg2.buckets) and avg2.finish() == len(avg2.buckets)
 torch.cat = real_cat
 assert not cat_calls, "the flat path must not gather buckets"
-assert flat.sync() == 0 or True
+assert flat.sync() == len(params)        # plain autograd gradients: every slice is copied in once more (the averages, already in place)
 off = 0
 for p, r_ in zip(params, ref):
     assert torch.allclose(p.grad, r_, rtol=2e-6, atol=1e-6), "in-place flat averaging must equal the gather / scatter path"
@@ -1767,6 +1807,103 @@ def test_flat_parameters_and_gradient_destinations(nfa):
         assert all(torch.allclose(p, q, atol=1e-6) for p, q in zip(net.parameters(), ref.parameters()))
     flat.release()
     assert _gradbuf.target(net[0].weight) is None
+
+
+class _WritesDestination(torch.autograd.Function):
+    """Stands in for a training Function whose kernels take gradient destinations (autograd.PairTrainFn / CouplingTrainFn /
+    LULinearPermuteFn): y_b = x_b . w, the forward counts the use, the backward writes dL/dw into _gradbuf.out(w) and records whether
+    PairTrainFn's rule would have let a side stream write it."""
+    side_ok = []
+
+    @staticmethod
+    def forward(ctx, x, w):
+        from normflows_amd import _gradbuf
+        _gradbuf.use((w,))
+        ctx.save_for_backward(x, w)
+        return x @ w
+
+    @staticmethod
+    def backward(ctx, g):
+        from normflows_amd import _gradbuf, autograd as nfa_autograd
+        x, w = ctx.saved_tensors
+        gw = _gradbuf.out(w)
+        torch.mv(x.t(), g, out=gw)
+        _WritesDestination.side_ok.append(nfa_autograd._pair_side_ok([w], [gw]))
+        return g[:, None] * w, gw
+
+
+def test_flat_parameters_accumulate_gradients_of_several_backward_passes(nfa):
+    """A registered gradient slice goes to a backward kernel at most once per zero_grad() and only while .grad is None: a second
+    gradient of the same parameter must ADD to the first, never overwrite it before autograd adds the two.  Per-element gradient
+    1 from x1, 10 from x2 (exact in float32): every scenario below expects 11 where the slice reused on every call gave 20 (two
+    micro-batches), 2 (two losses of one graph) or a .grad clobbered by torch.autograd.grad."""
+    from normflows_amd import _gradbuf
+    side = _WritesDestination.side_ok
+    m = torch.nn.Module()
+    m.w = torch.nn.Parameter(torch.tensor([0.5, -1.0, 2.0]))
+    m.b = torch.nn.Parameter(torch.tensor(0.25))                # plain autograd: sync() copies its gradient in
+    flat = nfa.dp.FlatParameters(m)
+    sl = dict((id(p), v) for p, v in flat.views)[id(m.w)]
+    x1, x2 = torch.ones(1, 3), torch.full((1, 3), 10.0)
+
+    def loss(x):
+        return (_WritesDestination.apply(x, m.w) + m.b).sum()
+
+    def full(v):
+        return torch.full((3,), float(v))
+    # the ordinary step keeps its zero-copy property: the kernel writes the slice, autograd adopts it, sync() copies nothing for w
+    flat.zero_grad()
+    loss(x1).backward()
+    assert m.w.grad.data_ptr() == sl.data_ptr() and torch.equal(m.w.grad, full(1))
+    assert side == [True]
+    assert flat.sync() == 1 and torch.equal(flat.grad[:3], full(1)) and float(flat.grad[3]) == 1.0     # (1 = the copy of b's gradient)
+    # two different micro-batches, no zero_grad between them
+    flat.zero_grad()
+    del side[:]
+    loss(x1).backward()
+    loss(x2).backward()
+    assert torch.equal(m.w.grad, full(11)), m.w.grad
+    assert side == [True, False]                                # the second writes a fresh tensor: never on the side stream
+    flat.sync()
+    assert torch.equal(flat.grad[:3], full(11)) and float(flat.grad[3]) == 2.0
+    # two losses in ONE graph: both contributions meet in autograd's input buffer
+    flat.zero_grad()
+    del side[:]
+    (loss(x1) + loss(x2)).backward()
+    assert torch.equal(m.w.grad, full(11)), m.w.grad
+    assert side == [False, False]                               # two uses in the graph: the one that got the slice may not go either
+    flat.sync()
+    assert torch.equal(flat.grad[:3], full(11))
+    # backward(), then torch.autograd.grad: .grad stays the first gradient, the returned tensor is the second
+    flat.zero_grad()
+    loss(x1).backward()
+    gw, = torch.autograd.grad(loss(x2), m.w)
+    assert torch.equal(m.w.grad, full(1)) and torch.equal(gw, full(10)), (m.w.grad, gw)
+    assert gw.data_ptr() != sl.data_ptr()
+    flat.sync()
+    assert torch.equal(flat.grad[:3], full(1))
+    # torch.autograd.grad twice: the second result does not overwrite the first
+    flat.zero_grad()
+    ga, = torch.autograd.grad(loss(x1), m.w)
+    gb, = torch.autograd.grad(loss(x2), m.w)
+    assert torch.equal(ga, full(1)) and torch.equal(gb, full(10)), (ga, gb)
+    assert m.w.grad is None
+    # a hand-set .grad is accumulated into, not overwritten
+    flat.zero_grad()
+    m.w.grad = full(5)
+    loss(x1).backward()
+    assert torch.equal(m.w.grad, full(6)), m.w.grad
+    flat.sync()
+    assert torch.equal(flat.grad[:3], full(6))
+    # sync() leaves .grad = the slice and makes it available again once .grad is dropped (model.zero_grad(set_to_none=True))
+    flat.zero_grad()
+    loss(x1).backward()
+    flat.sync()
+    m.zero_grad(set_to_none=True)
+    loss(x2).backward()
+    assert m.w.grad.data_ptr() == sl.data_ptr() and torch.equal(m.w.grad, full(10))
+    flat.release()
+    assert _gradbuf.target(m.w) is None and not _gradbuf.sole_use(m.w)
 
 
 def test_pack_keys_follow_flat_and_master_weight_optimizers(nfa):
