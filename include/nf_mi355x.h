@@ -638,6 +638,34 @@ int nf_nsf_wide_ctx(const void *x, const void *context, void *y, void *logdet, c
                     const void *tabs, int64_t B, int64_t ldc, int D, int C, int hidden_padded, int K, int direction, int acc,
                     double tail_bound, double min_bin_width, double min_bin_height, double min_derivative, nf_stream_t stream);
 
+/* The GLU-gated ResidualNet conditioner (nets/resnet.py:7-104 with context_features: the conditioner of a conditional
+ * CoupledRationalQuadraticSpline) under autograd, float32 (csrc/resnet_ctx_train.hip):
+ *   h0 = W0 [x; c] + b0;  per block t = W1 relu(h) + b1, u = W2 relu(t) + b2, h += u * sigmoid(Wc c + bc);  out = Wf h + bf.
+ *   nf_resnet_ctx_forward_train : x (B, nI) with row stride ldx >= nI, context (B, C) with row stride ldc (0: one row shared by all),
+ *                                 -> out (B, out_features) and save (nf_resnet_ctx_save_floats floats).
+ *   nf_resnet_ctx_backward      : g_out (B, out_features) contiguous + save -> g_x (B, nI), g_context (B, C) and G
+ *                                 (nf_resnet_ctx_grad_floats floats: every layer's output gradient).
+ *   nf_resnet_ctx_wgrad         : every weight / bias gradient into grads (parameter order W0, b0, per block W1, b1, W2, b2, Wc, bc,
+ *                                 then Wf, bf), one launch over the njobs tiles of `jobs` and the nf_resnet_ctx_wgrad_chunks(B, njobs)
+ *                                 row chunks into part (nf_resnet_ctx_scratch_floats floats: at most 2^25 unless a single chunk's
+ *                                 njobs x 4160 is more) + a fixed-order reduction: deterministic.  B == 0 writes nothing.
+ *   blob, table, jobs: normalizing-flows_amd/flows/ctx_train_pack.py.
+ * Coverage: 1 <= num_blocks <= 4, hidden <= 256, round32(nI) + round32(C) <= 128, any out_features <= 65536 and B >= 0; NF_ENOTSUP
+ * outside it (hidden > 256 is not built: it would spill registers), NF_EINVAL for a malformed call, NF_EFAULT for a NULL pointer
+ * when B > 0.  Nothing is launched unless every check passes. */
+int64_t nf_resnet_ctx_save_floats(int64_t B, int nI, int C, int hidden, int num_blocks);
+int64_t nf_resnet_ctx_grad_floats(int64_t B, int hidden, int num_blocks);
+int nf_resnet_ctx_wgrad_chunks(int64_t B, int njobs);
+int64_t nf_resnet_ctx_scratch_floats(int64_t B, int njobs);
+int nf_resnet_ctx_forward_train(const void *x, int64_t ldx, const void *context, int64_t ldc, void *out, void *save, const void *blob,
+                                const int32_t *table, int64_t B, int nI, int C, int hidden, int out_features, int num_blocks,
+                                nf_stream_t stream);
+int nf_resnet_ctx_backward(const void *g_out, const void *save, void *G, void *g_x, void *g_context, const void *blob,
+                           const int32_t *table, int64_t B, int nI, int C, int hidden, int out_features, int num_blocks,
+                           nf_stream_t stream);
+int nf_resnet_ctx_wgrad(const void *g_out, const void *save, const void *G, void *grads, void *part, const int32_t *jobs, int njobs,
+                        const int32_t *table, int64_t B, int hidden, int num_blocks, nf_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * MADE in ONE launch -- the single-pass direction of the autoregressive flows.  Replaces
  * normflows/nets/made.py:296-304 (MADE.forward: initial MaskedLinear, MaskedResidualBlocks :196-214, final MaskedLinear; every

@@ -991,6 +991,42 @@ class MadeFn(torch.autograd.Function):
         return (None, None, gx if ctx.needs_input_grad[2] else None) + tuple(grads)
 
 
+class ResNetCtxFn(torch.autograd.Function):
+    """ResidualNet.forward with a context (nets/resnet.py:7-104: initial layer on cat(x, context), per block the GLU gate
+    glu(cat(t2, context_layer(context))) = t2 * sigmoid(Wc context + bc)) under autograd: forward = nf_resnet_ctx_forward_train (saves
+    the pre-activations, u and the gate), backward = nf_resnet_ctx_backward (g_x, g_context and every layer's output gradient) +
+    nf_resnet_ctx_wgrad (all weight / bias gradients, one launch + a fixed-order reduction).  `pack` = (blob, table, jobs, st) as
+    built at forward time (nets.ResidualNet._ctx_train_pack); params in flows/ctx_train_pack.params_of order."""
+
+    @staticmethod
+    def forward(ctx, pack, x, context, *params):
+        blob, table, jobs, st = pack
+        out, save = ops.resnet_ctx_forward_train(x, context, blob, table, st)
+        ctx.save_for_backward(save)
+        ctx.pack = pack
+        ctx.B = x.shape[0]
+        return out
+
+    @staticmethod
+    @once_differentiable          # (the backward is a set of kernels, not a differentiable graph: double backward raises)
+    def backward(ctx, gout):
+        save, = ctx.saved_tensors
+        blob, table, jobs, st = ctx.pack
+        gout = gout.contiguous()
+        need = ctx.needs_input_grad
+        gx, gc, G = ops.resnet_ctx_backward(gout, save, blob, table, st)
+        grads = [None] * len(st["shapes"])
+        if any(need[3:]):
+            flat = ops.resnet_ctx_wgrad(gout, save, G, table, jobs, st)
+            for k, (off, shape) in enumerate(zip(st["poff"], st["shapes"])):
+                if need[3 + k]:
+                    n = 1
+                    for d in shape:
+                        n *= d
+                    grads[k] = flat[off:off + n].view(shape)
+        return (None, gx if need[1] else None, gc if need[2] else None) + tuple(grads)
+
+
 class ConvNetFn(torch.autograd.Function):
     """GlowBlock's conditioner ConvNet2d([Cin, hidden, hidden, Cout], kernels (3, 1, 3), LeakyReLU(0); nets/cnn.py:5-63) under
     autograd (flows/affine/glow.py:10-100 inside core.py:87-102) without the convolution library: pixels are rows, the 3x3

@@ -325,6 +325,17 @@ def set_nsf_context(mode=True):
     nsf_context = bool(mode)
 
 
+# The GLU-gated conditioner of a conditional CoupledRationalQuadraticSpline (ResidualNet with context_features) under autograd on
+# HIP kernels (autograd.ResNetCtxFn, csrc/resnet_ctx_train.hip); False = the conditioner as eager torch modules.  The route also
+# follows made_train, so inside higher_order_gradients() the torch modules run and double backward keeps working.
+nsf_context_train = True
+
+
+def set_nsf_context_train(mode=True):
+    global nsf_context_train
+    nsf_context_train = bool(mode)
+
+
 # Debug mode of the element-wise spline API (utils.splines): after every call a check launch (nf_rqs_spline_check)
 # sets device-side flags and the shim reads them back -- a host synchronisation per call, which is why it is off by default -- and
 # raises what the reference raises: AssertionError for a negative discriminant in the inverse direction (utils/splines.py:181),

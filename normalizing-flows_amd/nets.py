@@ -172,6 +172,12 @@ class ResidualNet(nn.Module):
                 from . import autograd
                 lins = [self.initial_layer] + [l for b in self.blocks for l in b.linear_layers] + [self.final_layer]
                 return autograd.MadeFn.apply(packs[0], packs[1], inputs, *[t for l in lins for t in (l.weight, l.bias)])
+        if context is not None and torch.is_grad_enabled():
+            pack = self._ctx_train_pack(inputs, context)
+            if pack is not None:
+                from . import autograd
+                from .flows import ctx_train_pack
+                return autograd.ResNetCtxFn.apply(pack, inputs, context, *ctx_train_pack.params_of(self))
         temps = inputs if self.preprocessing is None else self.preprocessing(inputs)
         if context is None:
             temps = self.initial_layer(temps)
@@ -180,6 +186,39 @@ class ResidualNet(nn.Module):
         for block in self.blocks:
             temps = block(temps, context=context)
         return self.final_layer(temps)
+
+    def _ctx_train_pack(self, inputs, context):
+        """(blob, table, jobs, structure) for autograd.ResNetCtxFn, or None outside its coverage (the eager modules run then).  The
+        structure (gather indices, offsets, weight-gradient jobs) is built once per module and device; the blob is gathered from the
+        parameters as they are in THIS call."""
+        from . import config
+        if not (config.nsf_context_train and config.made_train):
+            return None
+        if not (inputs.dim() == 2 and inputs.is_cuda and inputs.dtype == torch.float32 and torch.is_tensor(context)
+                and context.dim() == 2 and context.is_cuda and context.dtype == torch.float32 and context.device == inputs.device
+                and context.shape[0] == inputs.shape[0] and context.shape[1] == self.context_features):
+            return None
+        if not (inputs.requires_grad or context.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return None
+        from .flows import ctx_train_pack
+        if inputs.shape[0] > ctx_train_pack.MAX_ROWS or ctx_train_pack.supported(self) is not None:
+            return None
+        params = ctx_train_pack.params_of(self)
+        if inputs.shape[1] != params[0].shape[1] - self.context_features:
+            return None
+        if not all(p.is_cuda and p.device == inputs.device and p.is_contiguous() for p in params):
+            return None
+        key = (str(inputs.device),) + tuple(tuple(p.shape) for p in params)
+        cached = self.__dict__.get("_ctx_train_struct")
+        if cached is None or cached[0] != key:
+            st = ctx_train_pack.structure_for(self)
+            dev = inputs.device
+            cached = self.__dict__["_ctx_train_struct"] = (key, st, torch.from_numpy(st["src"]).to(dev),
+                                                           torch.from_numpy(st["table"]).to(dev), torch.from_numpy(st["jobs"]).to(dev))
+        _, st, src, table, jobs = cached
+        from . import ops
+        blob = ops.pack_gather([p.detach() for p in params], src)
+        return blob, table, jobs, st
 
     def is_plain_relu(self):
         """True when the net is the plain ReLU MLP the fused HIP kernel implements."""

@@ -1208,6 +1208,70 @@ def nsf_wide_ctx(x, context, blob, table, tabs, hidden_padded, direction, tail_b
     return y, logdet
 
 
+def resnet_ctx_forward_train(x, context, blob, table, st):
+    """The GLU-gated ResidualNet under autograd (nf_resnet_ctx_forward_train): (out (B, O), save) -- save holds what
+    resnet_ctx_backward / resnet_ctx_wgrad read.  st: flows/ctx_train_pack.structure; context (B, C) float32 with unit inner stride
+    is passed with its row stride (0 for context.expand(B, C))."""
+    L.require_device(x, context, blob, table)
+    if x.dtype != torch.float32 or context.dtype != torch.float32:
+        raise NotImplementedError("resnet_ctx_forward_train: float32 only")
+    B = x.shape[0]
+    if x.dim() != 2 or x.shape[1] != st["nI"] or context.dim() != 2 or tuple(context.shape) != (B, st["C"]):
+        raise ValueError("resnet_ctx_forward_train: x (%d, %d) and context (%d, %d) expected, got %s %s"
+                         % (B, st["nI"], B, st["C"], tuple(x.shape), tuple(context.shape)))
+    if context.stride(1) != 1 and st["C"] > 1:
+        context = context.contiguous()
+    ldc = context.stride(0) if B > 1 else st["C"]
+    x = x.contiguous()
+    out = torch.empty(B, st["O"], dtype=x.dtype, device=x.device)
+    lib = L.lib()
+    n = lib.nf_resnet_ctx_save_floats(i64(B), i32(st["nI"]), i32(st["C"]), i32(st["H"]), i32(st["NB"]))
+    L.check(n if n < 0 else 0, "nf_resnet_ctx_save_floats")
+    save = torch.empty(max(int(n), 1), dtype=x.dtype, device=x.device)
+    rc = lib.nf_resnet_ctx_forward_train(ptr(x), i64(st["nI"]), ptr_any(context), i64(ldc), ptr(out), ptr(save), ptr(blob), ptr(table),
+                                         i64(B), i32(st["nI"]), i32(st["C"]), i32(st["H"]), i32(st["O"]), i32(st["NB"]), L.stream())
+    L.check(rc, "nf_resnet_ctx_forward_train")
+    return out, save
+
+
+def resnet_ctx_backward(g_out, save, blob, table, st):
+    """Input-gradient chain of the gated ResidualNet (nf_resnet_ctx_backward): (g_x (B, nI), g_context (B, C), G) -- G holds every
+    layer's output gradient for resnet_ctx_wgrad."""
+    L.require_device(g_out, save, blob, table)
+    B = g_out.shape[0]
+    g_out = g_out.contiguous()
+    lib = L.lib()
+    n = lib.nf_resnet_ctx_grad_floats(i64(B), i32(st["H"]), i32(st["NB"]))
+    L.check(n if n < 0 else 0, "nf_resnet_ctx_grad_floats")
+    G = torch.empty(max(int(n), 1), dtype=g_out.dtype, device=g_out.device)
+    gx = torch.empty(B, st["nI"], dtype=g_out.dtype, device=g_out.device)
+    gc = torch.empty(B, st["C"], dtype=g_out.dtype, device=g_out.device)
+    rc = lib.nf_resnet_ctx_backward(ptr(g_out), ptr(save), ptr(G), ptr(gx), ptr(gc), ptr(blob), ptr(table), i64(B), i32(st["nI"]),
+                                    i32(st["C"]), i32(st["H"]), i32(st["O"]), i32(st["NB"]), L.stream())
+    L.check(rc, "nf_resnet_ctx_backward")
+    return gx, gc, G
+
+
+def resnet_ctx_wgrad(g_out, save, G, table, jobs, st):
+    """Every weight / bias gradient of the gated ResidualNet (nf_resnet_ctx_wgrad: one launch over 64 x 64 tiles and row chunks + a
+    fixed-order reduction): the flat buffer in the parameter order of flows/ctx_train_pack.params_of."""
+    L.require_device(g_out, save, G, table, jobs)
+    B = g_out.shape[0]
+    g_out = g_out.contiguous()
+    if B == 0:                  # (nothing to reduce: the kernels launch nothing, the gradients are zero)
+        return torch.zeros(st["nflat"], dtype=g_out.dtype, device=g_out.device)
+    lib = L.lib()
+    njobs = int(jobs.shape[0])
+    n = lib.nf_resnet_ctx_scratch_floats(i64(B), i32(njobs))
+    L.check(n if n < 0 else 0, "nf_resnet_ctx_scratch_floats")
+    part = torch.empty(max(int(n), 1), dtype=g_out.dtype, device=g_out.device)
+    grads = torch.empty(st["nflat"], dtype=g_out.dtype, device=g_out.device)
+    rc = lib.nf_resnet_ctx_wgrad(ptr(g_out), ptr(save), ptr(G), ptr(grads), ptr(part), ptr(jobs), i32(njobs), ptr(table), i64(B),
+                                 i32(st["H"]), i32(st["NB"]), L.stream())
+    L.check(rc, "nf_resnet_ctx_wgrad")
+    return grads
+
+
 def made_forward_affine(x, blob, table, hidden_padded, logdet=None, acc=None):
     """MaskedAffineAutoregressive.forward (autoregressive.py:24-27, :101-110 over nets/made.py:296-304) as one launch
     (nf_made_forward_affine); blob / table from flows/made_pack.pack_made_forward."""
