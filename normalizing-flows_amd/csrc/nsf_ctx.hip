@@ -3,7 +3,8 @@
 // Until now every layer that received a context ran its conditioner as eager modules (cat -> Linear -> per block relu / Linear / relu /
 // Linear / context_layer / cat / glu / add -> Linear) and handed a materialised (B, (3K - 1) nT) output to nf_rqs_coupling.
 //
-// The engine and the layer are nsf_wide.hip's (mlp_tile.hpp; read its header first); the context changes the network in two places:
+// The engine and the layer are nsf_wide.hip's (mlp_tile.hpp; read its header first), the tile's load, final stage and store are the
+// fragments both kernels include (nsf_tile.hpp); the context changes the network in two places:
 //   * the initial layer reads cat(identity features, context): the row's C context values sit in the x tile at positions
 //     [Dp, Dp + PC) (PC = C rounded up to 32, the padding zero; Dp + PC <= 128, so the LDS size does not change), and the layer is two
 //     items: the identity positions [0, PI) as in nsf_wide, then an ADD item over the context positions (zero bias group);
@@ -14,30 +15,9 @@
 // The context is read with a row stride `ldc` (0: one observation for every row, context.expand(B, C) without a copy).  A context row
 // only reaches its own tile column (B operand = row), so a NaN in one row's context stays in that row; the transform columns still never
 // reach the conditioner.  Extra work: (1 + NB) C H MACs per row.
-#include "mlp_tile.hpp"
+#include "nsf_tile.hpp"
 
 namespace nf {
-
-constexpr int nc_tabw(int KB) { return 3 * (KB + 1); }          // (= nsf_wide.hip: floats per identity feature of the knot tables)
-constexpr int nc_tab_floats(int KB) { return KB == 16 ? 3328 : 2048; }
-
-template <int TR>
-__device__ __forceinline__ int nc_xidx(int pos, int row) { return ((pos >> 2) * TR + row) * 4 + (pos & 3); }
-
-template <bool INV, int TR, int KB>
-__device__ __forceinline__ float nc_identity(float *xreg, const float *tabs, const RqsParams<float> &p, int nI, int tid) {
-    const int n = tid % TR;
-    float ld = 0.0f;
-#pragma unroll 1
-    for (int i = tid / TR; i < nI; i += 64 * MF_NW / TR) {
-        float *xp = xreg + nc_xidx<TR>(i, n);
-        float y, lad;
-        rqs_table_fast<INV, KB>(p, *xp, tabs + i * nc_tabw(KB), y, lad);
-        *xp = y;
-        ld += lad;
-    }
-    return ld;
-}
 
 // Instantiated as nsf_wide_kernel's first two shapes without the LU: (NHI, NS, TR) = (1, 2, 128) Hp 128, (1, 2, 64) Hp 256.  Hp 512
 // ((2, 2, 64)) compiles but spills 26-31 registers (108-120 bytes of scratch) even with gate and W2 alternating: not built.
@@ -54,13 +34,15 @@ nsf_ctx_kernel(const float *__restrict__ x, const float *__restrict__ ctx, float
     const int D = table[0], Hp = table[3], NB = table[4], nI = table[5], nT = table[6], par_i = table[7], G = table[9], nfi = table[10],
               PI = table[15];
     constexpr int KGS = 8 * TR, NIG = 64 * MF_NW / TR;
-    constexpr int MP = 3 * KB, FPL = 16 / KB, FPG = 2 * FPL, NC_TABW = nc_tabw(KB);
-    constexpr int NFI = KB == 16 ? 8 : 4;
+    constexpr int MP = 3 * KB, FPL = 16 / KB, FPG = 2 * FPL;
+    constexpr int NFI = nsf_nfi(KB);
     float *acts = lds;                                       // [Hp / 8 k-groups][2][TR][4]
     float *xreg = lds + (size_t)(Hp / 8) * KGS;              // [128 / 8][2][TR][4]: identity | transform | context positions
-    float *ldp = acts + nc_tab_floats(KB);
+    float *ldp = acts + nsf_tab_floats(KB);
     const int nitems = (2 + 3 * NB) * NHI + nfi;
     const int *items = table + MF_HDR + w * nitems * 3;
+    const int fin0 = (2 + 3 * NB) * NHI;
+    const float ld_const = 0.0f;
     const float *stream = blob + table[16 + w];
     const int lane_b = (TR * hh + n) * 4;
     const float *xctx = xreg + (size_t)(Dp / 8) * KGS;       // B operand of the context positions (Dp is a multiple of 32)
@@ -74,38 +56,15 @@ nsf_ctx_kernel(const float *__restrict__ x, const float *__restrict__ ctx, float
         ring.ap = stream + lane * 4;
         int tq = tid;
         asm volatile("" : "+v"(tq));
-        {   // x tile -> LDS (columns sorted into positions), then the context row at [Dp, Dp + PC)
-            const int r = tq % TR, cg = tq / TR;
-            const float *xr = x + (row0 + r) * D;
-#pragma unroll 1
-            for (int c = cg; 4 * c < D; c += NIG) {
-                f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (r < nrows) {
-                    if ((D & 3) == 0) v = *reinterpret_cast<const f32x4 *>(xr + 4 * c);
-                    else
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) if (4 * c + i < D) v[i] = xr[4 * c + i];
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int col = 4 * c + i;
-                    if (col < D) xreg[nc_xidx<TR>(((col ^ par_i) & 1) ? PI + (col >> 1) : (col >> 1), r)] = v[i];
-                }
-            }
-#pragma unroll 1
-            for (int ps = nI + cg; ps < PI; ps += NIG) xreg[nc_xidx<TR>(ps, r)] = 0.0f;
-#pragma unroll 1
-            for (int ps = PI + nT + cg; ps < Dp; ps += NIG) xreg[nc_xidx<TR>(ps, r)] = 0.0f;
-            const float *cr = ctx + (row0 + r) * ldc;         // (ldc = 0: every row reads row 0)
-#pragma unroll 1
-            for (int ps = cg; ps < PC; ps += NIG) xreg[nc_xidx<TR>(Dp + ps, r)] = (r < nrows && ps < C) ? cr[ps] : 0.0f;
-        }
+#define NSF_TILE_CONTEXT                                     // the fragment also loads the context row
+#include "nsf_tile_load.hpp"
+#undef NSF_TILE_CONTEXT
         float ld_ident = 0.0f;
         if constexpr (DIR == 1) {                            // sampling: the identity half's inverse spline first (nsf/coupling.py:112-114)
 #pragma unroll 1
-            for (int i = tq; i < nI * NC_TABW; i += 64 * MF_NW) acts[i] = tabs[i];
+            for (int i = tq; i < nI * nsf_tabw(KB); i += 64 * MF_NW) acts[i] = tabs[i];
             MF_BARRIER();
-            ld_ident = nc_identity<true, TR, KB>(xreg, acts, p, nI, tq);
+            ld_ident = nsf_identity<true, TR, KB>(xreg, acts, p, nI, tq);
         }
         f32x16 h[NHI][NS], t[NHI][NS], u[NS];
         MF_BARRIER();
@@ -149,93 +108,8 @@ nsf_ctx_kernel(const float *__restrict__ x, const float *__restrict__ ctx, float
             }
         }
         // ---- final layer on the raw block output in groups of transform features + the spline (= nsf_wide.hip) ----------------------
-        MF_BARRIER();
-#pragma unroll
-        for (int s = 0; s < NHI; ++s) mf_publish<NS, false, TR>(acts, items[3 * s + 1], items[3 * s + 2], hh, n, h[s]);
-        MF_BARRIER();
-        float ldt[NFI][2];
-#pragma unroll
-        for (int q = 0; q < NFI; ++q) ldt[q][0] = ldt[q][1] = 0.0f;
-#pragma nounroll
-        for (int j = 0; j < nfi; ++j) {
-            const int *it = items + 3 * ((2 + 3 * NB) * NHI + j);
-            const int g = it[1], sbo = it[2];
-            if (g < 0) continue;
-            f32x16 o[3][2];
-            mf_final_item<TR>(ring, it[0], acts + lane_b + 128 * sbo, o);
-            float lsum[2] = {0.0f, 0.0f};
-#pragma unroll
-            for (int sb = 0; sb < 2; ++sb)
-#pragma unroll
-                for (int f = 0; f < FPL; ++f) {
-                    float prm[MP];
-#pragma unroll
-                    for (int v = 0; v < MP; ++v) prm[v] = o[(MP * f + v) >> 4][sb][(MP * f + v) & 15];
-                    const int tf = FPG * g + FPL * hh + f;
-                    const bool valid = tf < nT;
-                    float *xp = xreg + nc_xidx<TR>(PI + (valid ? tf : 0), 32 * (sbo + sb) + n);
-                    float yv, lad;
-                    rqs_regs_h<DIR == 1, KB>(p, *xp, prm, yv, lad);
-                    if (valid) {
-                        *xp = yv;
-                        lsum[sb] += lad;
-                    }
-                }
-#pragma unroll
-            for (int q = 0; q < NFI; ++q) {
-                ldt[q][0] = j == q ? lsum[0] : ldt[q][0];
-                ldt[q][1] = j == q ? lsum[1] : ldt[q][1];
-            }
-        }
-        MF_BARRIER();
-        if constexpr (DIR == 0) {
-#pragma unroll 1
-            for (int i = tq; i < nI * NC_TABW; i += 64 * MF_NW) acts[i] = tabs[i];
-        }
-#pragma unroll
-        for (int j = 0; j < NFI; ++j) {
-            if (j >= nfi) break;
-            const int *it = items + 3 * ((2 + 3 * NB) * NHI + j);
-            const int g = it[1], sbo = it[2];
-            if (g >= 0) {
-#pragma unroll
-                for (int sb = 0; sb < 2; ++sb) {
-                    const float v = ldt[j][sb] + __shfl_xor(ldt[j][sb], 32);
-                    if (hh == 0) ldp[g * TR + 32 * (sbo + sb) + n] = v;
-                }
-            }
-        }
-        if constexpr (DIR == 0) {                            // density: the identity half's spline after the conditioner (:88-92)
-            MF_BARRIER();
-            ld_ident = nc_identity<false, TR, KB>(xreg, acts, p, nI, tq);
-        }
-        ldp[(G + tq / TR) * TR + tq % TR] = ld_ident;
-        MF_BARRIER();
-        if (tq < nrows) {
-            float v = 0.0f;
-#pragma unroll 1
-            for (int s = 0; s < G + NIG; ++s) v += ldp[s * TR + tq];      // fixed order: deterministic
-            ld_store(logdet + row0 + tq, v, acc_mode);
-        }
-        {
-            const int r = tq % TR, cg = tq / TR;
-            float *yr = y + (row0 + r) * D;
-            if (r < nrows) {
-#pragma unroll 1
-                for (int c = cg; 4 * c < D; c += NIG) {
-                    f32x4 v;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int col = 4 * c + i < D ? 4 * c + i : D - 1;
-                        v[i] = xreg[nc_xidx<TR>(((col ^ par_i) & 1) ? PI + (col >> 1) : (col >> 1), r)];
-                    }
-                    if ((D & 3) == 0) *reinterpret_cast<f32x4 *>(yr + 4 * c) = v;
-                    else
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) if (4 * c + i < D) yr[4 * c + i] = v[i];
-                }
-            }
-        }
+#include "nsf_tile_final.hpp"
+#include "nsf_tile_store.hpp"
         MF_BARRIER();
     }
 }

@@ -5,7 +5,8 @@
 //
 // The engine is mlp_tile.hpp's (made_fwd.hip describes it): 8 waves own 64 rows for the whole layer, pre-activations in accumulator
 // registers, the next layer's B operand in LDS in MFMA order, one contiguous weight stream per wave through a register ring,
-// persistent over the tiles.  What is specific here (host packer: flows/nsf_wide_pack.py):
+// persistent over the tiles.  What is specific here (host packer: flows/nsf_wide_pack.py; the stages the conditional layer's kernel
+// nsf_ctx.hip runs as they are live in nsf_tile.hpp and the nsf_tile_*.hpp fragments it describes):
 //   * the x tile is held with its columns SORTED (B-operand order over POSITIONS: identity feature i at position i < PI, transform
 //     feature j at PI + j; PI = the identity count rounded up to 32, zeros at the padding positions): the initial layer contracts
 //     over the first PI positions only -- the conditioner sees the identity features alone (nsf/coupling.py:83-84), so a NaN / inf in
@@ -21,12 +22,9 @@
 //   * per-row log-det: the lane-halves' sums, the groups' and the identity columns' partials through LDS in a fixed order.
 // Bound: fp32 MFMA.  FLOP per row: 2 (nI H + 4 H^2 + 23 nT H) algorithmic (executed: full-width initial layer, padded hidden
 // units, 24 rows per feature); HBM: 8 D + 4 bytes per row.
-#include "mlp_tile.hpp"
+#include "nsf_tile.hpp"
 
 namespace nf {
-
-constexpr int nw_tabw(int KB) { return 3 * (KB + 1); }          // floats per identity feature: cumw[K + 1] | cumh[K + 1] | deriv[K + 1]
-constexpr int nw_tab_floats(int KB) { return KB == 16 ? 3328 : 2048; }   // table region at the start of the activation region (64 features)
 
 // knot tables of the batch-shared spline, once per parameter version (same arithmetic as rqs_fused.hip's pack_tables_kernel)
 __global__ void nsf_wide_tables_kernel(const float *__restrict__ uw, const float *__restrict__ uh, const float *__restrict__ ud,
@@ -39,26 +37,6 @@ __global__ void nsf_wide_tables_kernel(const float *__restrict__ uw, const float
     auto hacc = [=](int k) { return hj[k]; };
     auto dacc = [=](int k) { return dj[k]; };
     rqs_build_table<float>(p, wacc, hacc, dacc, tab + j * 3 * (K + 1));
-}
-
-// float index of POSITION `pos` of row `row` (0 .. TR - 1) of the tile in B-operand order [pos / 4][row][4]
-template <int TR>
-__device__ __forceinline__ int nw_xidx(int pos, int row) { return ((pos >> 2) * TR + row) * 4 + (pos & 3); }
-
-// batch-shared spline on the identity columns of the tile, in place; thread = (row n = tid % TR, feature residue tid / TR)
-template <bool INV, int TR, int KB>
-__device__ __forceinline__ float nw_identity(float *xreg, const float *tabs, const RqsParams<float> &p, int nI, int tid) {
-    const int n = tid % TR;
-    float ld = 0.0f;
-#pragma unroll 1
-    for (int i = tid / TR; i < nI; i += 64 * MF_NW / TR) {
-        float *xp = xreg + nw_xidx<TR>(i, n);                 // identity feature i sits at position i
-        float y, lad;
-        rqs_table_fast<INV, KB>(p, *xp, tabs + i * nw_tabw(KB), y, lad);
-        *xp = y;
-        ld += lad;
-    }
-    return ld;
 }
 
 // The adjacent LULinearPermute (mixing.py:535-563) as one dense product on the tile, in place: every wave computes its 32 output
@@ -94,15 +72,16 @@ nsf_wide_kernel(const float *__restrict__ x, float *__restrict__ y, float *__res
     const int D = table[0], Dp = table[1], Hp = table[3], NB = table[4], nI = table[5], nT = table[6], par_i = table[7],
               par_t = table[8], G = table[9], nfi = table[10], PI = table[15];
     constexpr int KGS = 8 * TR, NIG = 64 * MF_NW / TR;       // floats per k-group of activations; identity-feature residues
-    constexpr int MP = 3 * KB, FPL = 16 / KB, FPG = 2 * FPL, NW_TABW = nw_tabw(KB);
-    constexpr int NFI = KB == 16 ? 8 : 4;                    // final items a wave may own (flows/nsf_wide_pack.bins_geometry)
+    constexpr int MP = 3 * KB, FPL = 16 / KB, FPG = 2 * FPL;
+    constexpr int NFI = nsf_nfi(KB);
     float *acts = lds;                                       // [Hp / 8 k-groups][2][TR][4]
     float *xreg = lds + (size_t)(Hp / 8) * KGS;              // [Dp / 8][2][TR][4]
-    float *ldp = acts + nw_tab_floats(KB);                   // log-det partials [G + NIG][TR], behind the staged tables
+    float *ldp = acts + nsf_tab_floats(KB);                   // log-det partials [G + NIG][TR], behind the staged tables
     const int nitems = (1 + 2 * NB) * NHI + nfi + (LU ? 1 : 0);
     const int *items_all = table + MF_HDR + w * nitems * 3;  // [nitems][nkg, rb | g, sb0]
     const int *items = items_all + ((LU && DIR == 0) ? 3 : 0);   // the network's items (the density direction's LU entry comes first)
-    const float lu_ld = LU ? (DIR == 0 ? lu_lad[0] : -lu_lad[0]) : 0.0f;
+    const int fin0 = (1 + 2 * NB) * NHI;                     // index of the wave's first final entry
+    const float ld_const = LU ? (DIR == 0 ? lu_lad[0] : -lu_lad[0]) : 0.0f;
     const float *stream = blob + table[16 + w];
     const int lane_b = (TR * hh + n) * 4;
     const int64_t ntiles = (B + TR - 1) / TR;
@@ -117,29 +96,7 @@ nsf_wide_kernel(const float *__restrict__ x, float *__restrict__ y, float *__res
         // invariants those values stayed live across the products (the last 1-4 spilled registers of the 64-row instantiations)
         int tq = tid;
         asm volatile("" : "+v"(tq));
-        {   // x tile -> LDS, columns sorted into positions (rows beyond the batch and the padding positions are zero)
-            const int r = tq % TR, cg = tq / TR;
-            const float *xr = x + (row0 + r) * D;
-#pragma unroll 1        // (runtime trip counts: the unroller's remainder bookkeeping stayed live across the whole tile -- 1-8 spilled registers)
-            for (int c = cg; 4 * c < D; c += NIG) {
-                f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (r < nrows) {
-                    if ((D & 3) == 0) v = *reinterpret_cast<const f32x4 *>(xr + 4 * c);
-                    else
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) if (4 * c + i < D) v[i] = xr[4 * c + i];
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int col = 4 * c + i;
-                    if (col < D) xreg[nw_xidx<TR>(((col ^ par_i) & 1) ? PI + (col >> 1) : (col >> 1), r)] = v[i];
-                }
-            }
-#pragma unroll 1
-            for (int ps = nI + cg; ps < PI; ps += NIG) xreg[nw_xidx<TR>(ps, r)] = 0.0f;
-#pragma unroll 1
-            for (int ps = PI + nT + cg; ps < Dp; ps += NIG) xreg[nw_xidx<TR>(ps, r)] = 0.0f;
-        }
+#include "nsf_tile_load.hpp"
         float ld_ident = 0.0f;
         if constexpr (LU && DIR == 0) {
             MF_BARRIER();
@@ -147,9 +104,9 @@ nsf_wide_kernel(const float *__restrict__ x, float *__restrict__ y, float *__res
         }
         if constexpr (DIR == 1) {                            // sampling: the identity half's inverse spline comes first (:112-114)
 #pragma unroll 1
-            for (int i = tq; i < nI * NW_TABW; i += 64 * MF_NW) acts[i] = tabs[i];
+            for (int i = tq; i < nI * nsf_tabw(KB); i += 64 * MF_NW) acts[i] = tabs[i];
             MF_BARRIER();
-            ld_ident = nw_identity<true, TR, KB>(xreg, acts, p, nI, tq);
+            ld_ident = nsf_identity<true, TR, KB>(xreg, acts, p, nI, tq);
         }
         f32x16 h[NHI][NS], t[NHI][NS];
         MF_BARRIER();
@@ -178,101 +135,9 @@ nsf_wide_kernel(const float *__restrict__ x, float *__restrict__ y, float *__res
             }
         }
         // ---- final layer on the raw block output (:104) in groups of four transform features + the spline ----------------------------
-        MF_BARRIER();
-#pragma unroll
-        for (int s = 0; s < NHI; ++s) mf_publish<NS, false, TR>(acts, items[3 * s + 1], items[3 * s + 2], hh, n, h[s]);
-        MF_BARRIER();
-        float ldt[NFI][2];                                   // [final item][sample block] (nfi <= NFI)
-#pragma unroll
-        for (int q = 0; q < NFI; ++q) ldt[q][0] = ldt[q][1] = 0.0f;
-#pragma nounroll
-        for (int j = 0; j < nfi; ++j) {                       // (rolled: one copy of the item's code; the sums go to their slot by selects)
-            const int *it = items + 3 * ((1 + 2 * NB) * NHI + j);
-            const int g = it[1], sbo = it[2];                 // group of four transform features, first of its two sample blocks
-            if (g < 0) continue;
-            f32x16 o[3][2];
-            mf_final_item<TR>(ring, it[0], acts + lane_b + 128 * sbo, o);
-            float lsum[2] = {0.0f, 0.0f};
-#pragma unroll
-            for (int sb = 0; sb < 2; ++sb)
-#pragma unroll
-                for (int f = 0; f < FPL; ++f) {
-                    float prm[MP];
-#pragma unroll
-                    for (int v = 0; v < MP; ++v) prm[v] = o[(MP * f + v) >> 4][sb][(MP * f + v) & 15];
-                    const int tf = FPG * g + FPL * hh + f;
-                    const bool valid = tf < nT;
-                    float *xp = xreg + nw_xidx<TR>(PI + (valid ? tf : 0), 32 * (sbo + sb) + n);
-                    float yv, lad;
-                    // round 5: binary bin descent (rqs_regs_t; the packed PAIR version of the benchmark kernel spilled 11-23 registers here)
-#ifdef NF_EPI_SCALAR
-                    rqs_regs<DIR == 1, KB>(p, *xp, prm, yv, lad);
-#elif defined(NF_EPI_FULL_KNOTS)
-                    rqs_regs_t<DIR == 1, KB>(p, *xp, prm, yv, lad);
-#else           // round 6: first descent level before the knots exist (fused_common.hpp rqs_regs_h): half the live arrays
-                    rqs_regs_h<DIR == 1, KB>(p, *xp, prm, yv, lad);
-#endif
-                    if (valid) {
-                        *xp = yv;
-                        lsum[sb] += lad;
-                    }
-                }
-#pragma unroll
-            for (int q = 0; q < NFI; ++q) {
-                ldt[q][0] = j == q ? lsum[0] : ldt[q][0];
-                ldt[q][1] = j == q ? lsum[1] : ldt[q][1];
-            }
-        }
-        MF_BARRIER();                                        // every wave is done with the activations
-        if constexpr (DIR == 0) {
-#pragma unroll 1
-            for (int i = tq; i < nI * NW_TABW; i += 64 * MF_NW) acts[i] = tabs[i];
-        }
-#pragma unroll
-        for (int j = 0; j < NFI; ++j) {
-            if (j >= nfi) break;
-            const int *it = items + 3 * ((1 + 2 * NB) * NHI + j);
-            const int g = it[1], sbo = it[2];
-            if (g >= 0) {
-#pragma unroll
-                for (int sb = 0; sb < 2; ++sb) {
-                    const float v = ldt[j][sb] + __shfl_xor(ldt[j][sb], 32);
-                    if (hh == 0) ldp[g * TR + 32 * (sbo + sb) + n] = v;
-                }
-            }
-        }
-        if constexpr (DIR == 0) {                            // density: the identity half's spline after the conditioner (:88-92)
-            MF_BARRIER();
-            ld_ident = nw_identity<false, TR, KB>(xreg, acts, p, nI, tq);
-        }
-        ldp[(G + tq / TR) * TR + tq % TR] = ld_ident;
-        MF_BARRIER();
+#include "nsf_tile_final.hpp"
         if constexpr (LU && DIR == 1) nw_lu_stage<TR>(ring, items_all + 3 * (nitems - 1), xreg, lane_b, hh, n);
-        if (tq < nrows) {
-            float v = lu_ld;
-#pragma unroll 1
-            for (int s = 0; s < G + NIG; ++s) v += ldp[s * TR + tq];      // fixed order: deterministic
-            ld_store(logdet + row0 + tq, v, acc_mode);
-        }
-        {
-            const int r = tq % TR, cg = tq / TR;
-            float *yr = y + (row0 + r) * D;
-            if (r < nrows) {
-#pragma unroll 1
-                for (int c = cg; 4 * c < D; c += NIG) {
-                    f32x4 v;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int col = 4 * c + i < D ? 4 * c + i : D - 1;
-                        v[i] = xreg[nw_xidx<TR>(((col ^ par_i) & 1) ? PI + (col >> 1) : (col >> 1), r)];
-                    }
-                    if ((D & 3) == 0) *reinterpret_cast<f32x4 *>(yr + 4 * c) = v;
-                    else
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) if (4 * c + i < D) yr[4 * c + i] = v[i];
-                }
-            }
-        }
+#include "nsf_tile_store.hpp"
         MF_BARRIER();                                        // the next tile overwrites the x tile and the activations
     }
 }

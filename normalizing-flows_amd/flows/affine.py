@@ -11,7 +11,7 @@ from torch import nn
 
 from .. import ops
 from ..autograd import ActNormFn, AffineCouplingFn, MaskedAffineFn, needs_grad
-from .base import Flow, run_flow
+from .base import Flow, fold_logdet, run_flow
 from .reshape import Merge, Split
 
 
@@ -53,16 +53,10 @@ class lazy_ld:
 
 def _fold_ld(ld, acc, log_det):
     """Accumulate protocol under autograd: the kernels' in-place accumulation is not differentiable."""
-    if ld is None:
-        return log_det
-    if _LAZY and _LAZY[-1][0] is ld and log_det.shape == ld.shape and log_det.dtype == ld.dtype:
+    if ld is not None and _LAZY and _LAZY[-1][0] is ld and log_det.shape == ld.shape and log_det.dtype == ld.dtype:
         _LAZY[-1][1].append((not (acc is None or acc > 0), log_det))
         return ld
-    if acc is None or acc > 0:
-        ld += log_det
-    else:
-        ld -= log_det
-    return ld
+    return fold_logdet(ld, acc, log_det)
 
 
 class AffineConstFlow(Flow):

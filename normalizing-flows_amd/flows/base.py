@@ -15,6 +15,20 @@ from torch import nn
 from .. import _prof
 
 
+def ld_sign(acc):
+    """+1 | -1: the sign with which a layer's log-det enters the caller's accumulator (acc None: the layer returns it, +)."""
+    return 1 if (acc is None or acc > 0) else -1
+
+
+def fold_logdet(ld, acc, log_det):
+    """Accumulate protocol outside a kernel: log_det when there is no accumulator, else `ld` updated in place (one elementwise launch)."""
+    if ld is None:
+        return log_det
+    if acc is None or acc > 0:
+        ld += log_det
+    else:
+        ld -= log_det
+    return ld
 
 
 class Flow(nn.Module):

@@ -24,7 +24,8 @@ from .. import ops
 from ..autograd import CouplingDensityFn, CouplingTrainFn, FinalSplineDensityFn, IdentLinearFn, SplineFn, needs_grad
 from ..nets import PeriodicFeaturesElementwise, ResidualNet
 from ..utils.masks import create_alternating_binary_mask
-from .base import Flow
+from . import nsf_ctx_pack, nsf_wide_pack
+from .base import Flow, fold_logdet, ld_sign
 
 DEFAULT_MIN_BIN_WIDTH = 1e-3
 DEFAULT_MIN_BIN_HEIGHT = 1e-3
@@ -67,6 +68,12 @@ def _tails_kwargs(tails, tail_bound, role, device=None, cache=None):
     else:
         kw["tail_bound"] = tail_bound
     return kw
+
+
+def _image_rows(shape):
+    """(B, n*M, H, W) conditioner output -> (B*HW, n*M) rows with the M numbers of a feature contiguous."""
+    B, _, H, W = shape
+    return lambda p, n: p.reshape(B, n, -1, H, W).permute(0, 3, 4, 1, 2).reshape(B * H * W, -1).contiguous()
 
 
 FUSED_D, FUSED_H = 64, 128     # the shape of csrc/rqs_fused.hip (narrower layers are zero-padded into it)
@@ -127,14 +134,7 @@ class PiecewiseRationalQuadraticCDF(Flow):
                   min_derivative=self.min_derivative, **_tails_kwargs(tails, bound, "i", inputs.device, cache))
         if needs_grad(inputs, self):   # standalone use in a trained model: forward kernel + backward kernel
             y, log_det = SplineFn.apply(x2.contiguous(), None, uw, uh, ud, self.num_bins, inverse, kw)
-            y = y.reshape(inputs.shape)
-            if ld is None:
-                return y, log_det
-            if acc is None or acc > 0:
-                ld += log_det
-            else:
-                ld -= log_det
-            return y, ld
+            return y.reshape(inputs.shape), fold_logdet(ld, acc, log_det)
         idx = torch.arange(x2.shape[1], device=inputs.device)
         none = idx[:0]
         y, ld = ops.rqs_coupling(x2, None, uw.detach(), uh.detach(), ud.detach(), idx, none, self.num_bins,
@@ -280,43 +280,40 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         out = self.transform_net(ident, context)
         return out.contiguous()
 
-    def _density(self, inputs, context=None, ld=None, acc=None):
-        """prqct.forward (nsf/coupling.py:71-98): conditioner on the raw identity features."""
+    def _route(self, inputs, context, direction, ld, acc):
+        """One coupling layer in `direction` (0 density = prqct.forward, 1 sampling = prqct.inverse): images, autograd, then the
+        one-launch kernels in the order conditional -> benchmark shape -> wide, else layer-wise."""
         self._check(inputs)
         if inputs.dim() == 4:
-            return self._image(inputs, context, False, ld, acc)
+            return self._image(inputs, context, bool(direction), ld, acc)
         if needs_grad(inputs, context, self):
-            return self._autograd(inputs, context, False, ld, acc)
+            return self._autograd(inputs, context, bool(direction), ld, acc)
         if context is not None:
             ctx_pack = self._ctx_pack(inputs, context)
             if ctx_pack is not None:
-                return self._wide_ctx(inputs, context, ctx_pack, 0, ld, acc)
+                return self._wide_ctx(inputs, context, ctx_pack, direction, ld, acc)
         if self.use_fused and self._fused_eligible(inputs, context):
-            return self._fused(inputs, 0, ld, acc)
+            return self._fused(inputs, direction, ld, acc)
         wide = self._wide_pack(inputs, context)
         if wide is not None:
-            return self._wide(inputs, wide, 0, ld, acc)
+            return self._wide(inputs, wide, direction, ld, acc)
+        return (self._sample_layerwise if direction else self._density_layerwise)(inputs, context, ld, acc)
+
+    def _density(self, inputs, context=None, ld=None, acc=None):
+        """prqct.forward (nsf/coupling.py:71-98): conditioner on the raw identity features."""
+        return self._route(inputs, context, 0, ld, acc)
+
+    def _sample(self, inputs, context=None, ld=None, acc=None):
+        """prqct.inverse (nsf/coupling.py:100-128): CDF^-1 on the identity half first, conditioner on ITS output."""
+        return self._route(inputs, context, 1, ld, acc)
+
+    def _density_layerwise(self, inputs, context, ld, acc):
         cond = self._conditioner(inputs, context)
         uw, uh, ud = self._uncond()
         return ops.rqs_coupling(inputs, cond, uw, uh, ud, self.identity_features, self.transform_features,
                                 self.num_bins, L.RQS_DENSITY, logdet=ld, acc=acc, **self._kernel_kwargs())
 
-    def _sample(self, inputs, context=None, ld=None, acc=None):
-        """prqct.inverse (nsf/coupling.py:100-128): CDF^-1 on the identity half first, conditioner on ITS output."""
-        self._check(inputs)
-        if inputs.dim() == 4:
-            return self._image(inputs, context, True, ld, acc)
-        if needs_grad(inputs, context, self):
-            return self._autograd(inputs, context, True, ld, acc)
-        if context is not None:
-            ctx_pack = self._ctx_pack(inputs, context)
-            if ctx_pack is not None:
-                return self._wide_ctx(inputs, context, ctx_pack, 1, ld, acc)
-        if self.use_fused and self._fused_eligible(inputs, context):
-            return self._fused(inputs, 1, ld, acc)
-        wide = self._wide_pack(inputs, context)
-        if wide is not None:
-            return self._wide(inputs, wide, 1, ld, acc)
+    def _sample_layerwise(self, inputs, context, ld, acc):
         uw, uh, ud = self._uncond()
         kw = self._kernel_kwargs()
         y, ld = ops.rqs_coupling(inputs, None, uw, uh, ud, self.identity_features, self.transform_features,
@@ -352,20 +349,23 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         slot = (id(lu), direction) if lu is not None else None
         cache = caches.get(slot)
         if cache is None or cache[0] != key:
-            from . import nsf_wide_pack
             lu_np = lad = None
             if lu is not None:
                 Wd, Ws, bd, bs, lad = lu._dense_matrices()
                 lu_np = (Wd.cpu().numpy(), bd.cpu().numpy()) if direction == 0 else (Ws.cpu().numpy(), bs.cpu().numpy())
             packed = nsf_wide_pack.pack_nsf_wide(self, lu=lu_np, direction=direction)
-            if packed is not None:
-                blob, table = packed
-                tabs = ops.nsf_wide_tables(u.unnormalized_widths.detach(), u.unnormalized_heights.detach(),
-                                           u.unnormalized_derivatives.detach(), self.num_bins, self.tail_bound, self.min_bin_width,
-                                           self.min_bin_height, self.min_derivative)
-                packed = (torch.from_numpy(blob).to(inputs.device), torch.from_numpy(table).to(inputs.device), tabs, int(table[3]), lad)
-            cache = caches[slot] = (key, packed)
+            cache = caches[slot] = (key, self._upload_pack(packed, inputs.device, lad))
         return cache[1]
+
+    def _upload_pack(self, packed, device, last):
+        """(blob, table) of a packer -> (device blob, device table, knot tables of the batch-shared spline, Hp, last); None stays."""
+        if packed is None:
+            return None
+        blob, table = packed
+        u = self.unconditional_transform
+        tabs = ops.nsf_wide_tables(u.unnormalized_widths.detach(), u.unnormalized_heights.detach(), u.unnormalized_derivatives.detach(),
+                                   self.num_bins, self.tail_bound, self.min_bin_width, self.min_bin_height, self.min_derivative)
+        return torch.from_numpy(blob).to(device), torch.from_numpy(table).to(device), tabs, int(table[3]), last
 
     def _wide(self, inputs, packed, direction, ld, acc):
         blob, table, tabs, hp, lad = packed
@@ -388,16 +388,8 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         key = _keys.pkey(tensors) + (str(inputs.device), net.training)
         cache = self.__dict__.get("_ctx_cache")
         if cache is None or cache[0] != key:
-            from . import nsf_ctx_pack
             packed = nsf_ctx_pack.pack_nsf_ctx(self)
-            if packed is not None:
-                blob, table = packed
-                tabs = ops.nsf_wide_tables(u.unnormalized_widths.detach(), u.unnormalized_heights.detach(),
-                                           u.unnormalized_derivatives.detach(), self.num_bins, self.tail_bound, self.min_bin_width,
-                                           self.min_bin_height, self.min_derivative)
-                packed = (torch.from_numpy(blob).to(inputs.device), torch.from_numpy(table).to(inputs.device), tabs, int(table[3]),
-                          table)
-            cache = self.__dict__["_ctx_cache"] = (key, packed)
+            cache = self.__dict__["_ctx_cache"] = (key, self._upload_pack(packed, inputs.device, None if packed is None else packed[1]))
         return cache[1]
 
     def _wide_ctx(self, inputs, context, packed, direction, ld, acc):
@@ -422,18 +414,10 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         u = self.unconditional_transform
         ld_rows = torch.zeros(B * HW, dtype=inputs.dtype, device=inputs.device)
 
-        def to_rows(p, n):   # (B, n*M, H, W) -> (B*HW, n*M) with the M numbers of a feature contiguous
-            return p.reshape(B, n, -1, H, W).permute(0, 3, 4, 1, 2).reshape(B * HW, -1).contiguous()
+        to_rows = _image_rows(inputs.shape)
 
         def uncond_call(x_rows, mode, y=None):
-            prm = torch.cat([u.unnormalized_widths.detach(), u.unnormalized_heights.detach(),
-                             u.unnormalized_derivatives.detach()], -1)          # (nI, H, W, M_i)
-            if prm.dim() != 4:
-                raise NotImplementedError("image coupling needs an unconditional transform built with img_shape")
-            prm = prm.permute(1, 2, 0, 3).reshape(1, HW, -1).expand(B, HW, -1).reshape(B * HW, -1).contiguous()
-            ukw = dict(min_bin_width=u.min_bin_width, min_bin_height=u.min_bin_height,
-                       min_derivative=u.min_derivative, wh_div=1.0)
-            ukw.update(_tails_kwargs(u.tails, u.tail_bound, "t", inputs.device, self.__dict__.setdefault("_tcache_u", {})))
+            prm, ukw = self._image_uncond(inputs, True)
             return ops.rqs_coupling(x_rows, prm, None, None, None, Tf, I, self.num_bins, mode, y=y, logdet=ld_rows,
                                     acc=L.LD_ADD, **ukw)   # roles swapped: the identity half is the 'transform' set here
 
@@ -454,13 +438,21 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
                              logdet=ld_rows, acc=L.LD_ADD, **kw)
         out = y_rows.view(B, H, W, C).permute(0, 3, 1, 2).contiguous()
         log_det = ld_rows.view(B, HW).sum(1)
-        if ld is not None:
-            if acc is None or acc > 0:
-                ld += log_det
-            else:
-                ld -= log_det
-            return out, ld
-        return out, log_det
+        return out, fold_logdet(ld, acc, log_det)
+
+    def _image_uncond(self, inputs, detach):
+        """The per-pixel unconditional parameters (nI, H, W, M_i) expanded over the batch as rows (B HW, nI M_i) + the kernel
+        arguments of the unconditional transform; detached at inference, attached under autograd (torch sums their gradient)."""
+        u = self.unconditional_transform
+        B, HW = inputs.shape[0], inputs.shape[2] * inputs.shape[3]
+        prm = torch.cat([u.unnormalized_widths, u.unnormalized_heights, u.unnormalized_derivatives], -1)
+        if prm.dim() != 4:
+            raise NotImplementedError("image coupling needs an unconditional transform built with img_shape")
+        prm = prm.detach() if detach else prm
+        prm = prm.permute(1, 2, 0, 3).reshape(1, HW, -1).expand(B, HW, -1).reshape(B * HW, -1).contiguous()
+        ukw = dict(min_bin_width=u.min_bin_width, min_bin_height=u.min_bin_height, min_derivative=u.min_derivative, wh_div=1.0)
+        ukw.update(_tails_kwargs(u.tails, u.tail_bound, "t", inputs.device, self.__dict__.setdefault("_tcache_u", {})))
+        return prm, ukw
 
     def _image_autograd(self, inputs, context, sample, ld, acc):
         """Training path of _image: the same pixel-row view, each half through SplineFn (forward + backward kernel); the
@@ -476,17 +468,10 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         kw.pop("bound_i", None)
         u = self.unconditional_transform
 
-        def to_rows(p, n):
-            return p.reshape(B, n, -1, H, W).permute(0, 3, 4, 1, 2).reshape(B * HW, -1).contiguous()
+        to_rows = _image_rows(inputs.shape)
 
         def uncond(x_rows, inverse):
-            prm = torch.cat([u.unnormalized_widths, u.unnormalized_heights, u.unnormalized_derivatives], -1)
-            if prm.dim() != 4:
-                raise NotImplementedError("image coupling needs an unconditional transform built with img_shape")
-            prm = prm.permute(1, 2, 0, 3).reshape(1, HW, -1).expand(B, HW, -1).reshape(B * HW, -1).contiguous()
-            ukw = dict(min_bin_width=u.min_bin_width, min_bin_height=u.min_bin_height,
-                       min_derivative=u.min_derivative, wh_div=1.0)
-            ukw.update(_tails_kwargs(u.tails, u.tail_bound, "t", inputs.device, self.__dict__.setdefault("_tcache_u", {})))
+            prm, ukw = self._image_uncond(inputs, False)
             return SplineFn.apply(x_rows.contiguous(), prm, None, None, None, K, inverse, ukw)
 
         ld_i = None
@@ -506,13 +491,7 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         y_rows = y_rows.index_copy(1, I, ident).index_copy(1, Tf, trans)
         out = y_rows.view(B, H, W, C).permute(0, 3, 1, 2).contiguous()
         log_det = ld_rows.view(B, HW).sum(1)
-        if ld is not None:
-            if acc is None or acc > 0:
-                ld += log_det
-            else:
-                ld -= log_det
-            return out, ld
-        return out, log_det
+        return out, fold_logdet(ld, acc, log_det)
 
     def _train_buffers(self, inputs):
         """Zero-padded images of the initial (H, D) and final (nT, 24, H) weights used by the fused training path: owned by
@@ -541,6 +520,11 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         return (self._train_fused_ok(inputs, context, sample) and _config.train_full and inputs.shape[1] == 64
                 and self.transform_net.initial_layer.weight.shape[0] == 128)
 
+    def _train_kwargs(self, **more):
+        """Keyword dict of the fused training Functions (autograd.py): the spline's constants + the caller's entries."""
+        return dict(tail_bound=float(self.tail_bound), min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
+                    min_derivative=self.min_derivative, wh_div=self._wh_div(), **more)
+
     def _train_blob_for(self, inputs):
         blob = self.__dict__.get("_train_blob")
         if blob is None or blob.device != inputs.device:
@@ -557,8 +541,7 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
             net = self.transform_net
             inputs = inputs.contiguous()
             wfull, wpad, col_map, wfull_t = self._train_buffers(inputs)
-            fkw = dict(tail_bound=float(self.tail_bound), min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
-                       min_derivative=self.min_derivative, wh_div=self._wh_div(), col_map=col_map)
+            fkw = self._train_kwargs(col_map=col_map)
             if self._train_full_ok(inputs, context, sample):
                 blob = self._train_blob_for(inputs)
                 fkw["prepacked"] = _prepack.take(self)      # packed by run_chain's one launch for the whole model
@@ -567,22 +550,18 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
                 return CouplingTrainFn.apply(inputs, net.initial_layer.weight, net.initial_layer.bias, net.final_layer.weight,
                                              net.final_layer.bias, u.unnormalized_widths, u.unnormalized_heights,
                                              u.unnormalized_derivatives, self.identity_features, self.transform_features, blob,
-                                             self._fused_parity, fkw, wfull_t, wpad, ld, 1 if (acc is None or acc > 0) else -1,
+                                             self._fused_parity, fkw, wfull_t, wpad, ld, ld_sign(acc),
                                              *blk)
             h2 = IdentLinearFn.apply(inputs, net.initial_layer.weight, net.initial_layer.bias, self.identity_features, wfull)
             for block in net.blocks:
                 h2 = block(h2)
-            blob = self.__dict__.get("_train_blob")
-            if blob is None or blob.device != inputs.device:
-                blob = self._train_blob = ops.rqs_fused_train_blob(len(net.blocks), inputs.device)
-            fkw = dict(tail_bound=float(self.tail_bound), min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
-                       min_derivative=self.min_derivative, wh_div=self._wh_div(),
-                       holder=self.__dict__.setdefault("_img_holder", {}))
+            blob = self._train_blob_for(inputs)
+            fkw = self._train_kwargs(holder=self.__dict__.setdefault("_img_holder", {}))
             outputs, log_det = FinalSplineDensityFn.apply(inputs.contiguous(), h2, net.final_layer.weight, net.final_layer.bias,
                                                           u.unnormalized_widths, u.unnormalized_heights,
                                                           u.unnormalized_derivatives, self.identity_features,
                                                           self.transform_features, blob, self._fused_parity, len(net.blocks), fkw,
-                                                          wpad, ld, 1 if (acc is None or acc > 0) else -1)
+                                                          wpad, ld, ld_sign(acc))
             return outputs, log_det      # log_det IS ld (updated inside the launch) when the caller passed its accumulator
         ident = inputs.index_select(1, self.identity_features)
         if not sample:   # nsf/coupling.py:71-98 as one forward + one backward kernel on full rows
@@ -591,13 +570,7 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
                 else (None, None, None)
             outputs, log_det = CouplingDensityFn.apply(inputs.contiguous(), cond, uw, uh, ud, self.identity_features,
                                                        self.transform_features, self.num_bins, kw)
-            if ld is not None:
-                if acc is None or acc > 0:
-                    ld += log_det
-                else:
-                    ld -= log_det
-                return outputs, ld
-            return outputs, log_det
+            return outputs, fold_logdet(ld, acc, log_det)
         trans = inputs.index_select(1, self.transform_features)
         ld_i = None
         if not sample:
@@ -615,13 +588,7 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         log_det = ld_t if ld_i is None else ld_t + ld_i
         outputs = torch.empty_like(inputs)
         outputs = outputs.index_copy(1, self.identity_features, ident).index_copy(1, self.transform_features, trans)
-        if ld is not None:
-            if acc is None or acc > 0:
-                ld += log_det
-            else:
-                ld -= log_det
-            return outputs, ld
-        return outputs, log_det
+        return outputs, fold_logdet(ld, acc, log_det)
 
     # -- fused path: conditioner on MFMA + spline epilogue in one kernel (csrc/rqs_fused.hip) -----------------
     def _fused_eligible(self, inputs, context):
@@ -633,18 +600,13 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         if self.tails != "linear" or self._per_feature or self.unconditional_transform is None:
             return False
         if self._fused_ok is None:
-            ii = self.identity_features.cpu()
-            ti = self.transform_features.cpu()
-            n = self.features
-            alt0 = torch.equal(ii, torch.arange(0, n, 2)) and torch.equal(ti, torch.arange(1, n, 2))
-            alt1 = torch.equal(ii, torch.arange(1, n, 2)) and torch.equal(ti, torch.arange(0, n, 2))
+            parity = nsf_wide_pack.layer_conditions(self, weights_f32=False)   # (this route never asked for float32 weights)
             # the kernel's shape is (64 features, 128 hidden units; 4, 8 or 16 bins); narrower layers run on it zero-padded
             # (_fused_blob / _pad_rows below): 2 <= features <= 64, hidden <= 128, any number of blocks
-            ok = ((alt0 or alt1) and 2 <= n <= FUSED_D and net.hidden_features <= FUSED_H and self.num_bins in (4, 8, 16)
-                  and self.min_bin_width * self.num_bins <= 1.0 and self.min_bin_height * self.num_bins <= 1.0
+            ok = (parity is not None and 2 <= self.features <= FUSED_D and net.hidden_features <= FUSED_H
                   and ops.rqs_fused_supported(FUSED_D // 2, FUSED_D // 2, FUSED_H, len(net.blocks), self.num_bins))
             self._fused_ok = bool(ok)
-            self._fused_parity = 0 if alt0 else 1
+            self._fused_parity = parity or 0             # (only read when eligible)
         return self._fused_ok
 
     def _fused_hidden(self):
@@ -839,15 +801,13 @@ class CoupledRationalQuadraticSpline(Flow):
         net, u, lin = p.transform_net, p.unconditional_transform, lu.linear
         z = z.contiguous()
         wfull, wpad, col_map, wfull_t = p._train_buffers(z)
-        fkw = dict(tail_bound=float(p.tail_bound), min_bin_width=p.min_bin_width, min_bin_height=p.min_bin_height,
-                   min_derivative=p.min_derivative, wh_div=p._wh_div(), col_map=col_map, prepacked=True,
-                   holder=p.__dict__.setdefault("_img_holder", {}))
+        fkw = p._train_kwargs(col_map=col_map, prepacked=True, holder=p.__dict__.setdefault("_img_holder", {}))
         blk = [q for b in net.blocks for l in b.linear_layers for q in (l.weight, l.bias)]
         y, _ = PairTrainFn.apply(z, lu.permutation._permutation, lin.lower_entries, lin.upper_entries, lin.unconstrained_upper_diag,
                                  lin.bias, lin.eps, lu._factors_buffer(z.device), lu._wd_buffer(z.device), net.initial_layer.weight,
                                  net.initial_layer.bias, net.final_layer.weight, net.final_layer.bias, u.unnormalized_widths,
                                  u.unnormalized_heights, u.unnormalized_derivatives, p.identity_features, p.transform_features,
-                                 p._train_blob_for(z), p._fused_parity, fkw, wfull_t, wpad, ld, 1 if (acc is None or acc > 0) else -1,
+                                 p._train_blob_for(z), p._fused_parity, fkw, wfull_t, wpad, ld, ld_sign(acc),
                                  *blk)
         return y
 

@@ -4,7 +4,8 @@ CoupledRationalQuadraticSpline(..., num_context_channels=C) (wrapper.py:20-35) w
 temps = t2 * sigmoid(context_layer(context)).
 
 Geometry as flows/nsf_wide_pack.py (read its docstring first: row-blocks, k-groups, bias groups, A fragments, final-layer groups, the
-per-wave streams with the wrapped copy of their first 8 entries), with these differences:
+per-wave streams with the wrapped copy of their first 8 entries; its layer_conditions, final_groups and write_streams do the work here),
+with these differences:
   * the x tile holds the context at positions [Dp, Dp + PC): PC = C rounded up to 32, the padding positions zero; Dp + PC <= 128;
   * the initial layer is TWO items per hidden item: the identity columns W0[:, :nI] over positions [0, PI) with the bias b0, then
     the context columns W0[:, nI:] over the PC context positions with a zero bias group (the kernel adds it to the accumulator);
@@ -21,8 +22,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from .made_pack import ROWS, KG, RING, a_stream, bias_group
-from .nsf_wide_pack import HDR, SUPPORTED_BINS, bins_geometry, final_row, geometry, hidden_item
+from .nsf_wide_pack import final_groups, geometry, hidden_item, layer_conditions, padded_linear, positions, write_streams
 
 MAX_HIDDEN = 256        # Hp 512 spills registers with the gate next to the block's accumulators (csrc/nsf_ctx.hip)
 
@@ -46,22 +46,12 @@ def supported(prqct):
         return False
     if not all(isinstance(b.activation, nn.ReLU) or b.activation is torch.nn.functional.relu for b in net.blocks):
         return False
-    if prqct.tails != "linear" or getattr(prqct, "_per_feature", False) or prqct.unconditional_transform is None:
-        return False
-    K = prqct.num_bins
-    if K not in SUPPORTED_BINS or prqct.min_bin_width * K > 1.0 or prqct.min_bin_height * K > 1.0:
-        return False
     D, C = prqct.features, int(net.context_features)
     if not (2 <= D <= 128 and C >= 1 and 1 <= net.hidden_features <= MAX_HIDDEN and 1 <= len(net.blocks) <= 7):
         return False
     if x_positions(D) + padded_context(C) > 128:
         return False
-    if net.initial_layer.weight.dtype != torch.float32:
-        return False
-    ii, ti = prqct.identity_features.cpu(), prqct.transform_features.cpu()
-    alt0 = torch.equal(ii, torch.arange(0, D, 2)) and torch.equal(ti, torch.arange(1, D, 2))
-    alt1 = torch.equal(ii, torch.arange(1, D, 2)) and torch.equal(ti, torch.arange(0, D, 2))
-    return alt0 or alt1
+    return layer_conditions(prqct) is not None
 
 
 def pack_nsf_ctx(prqct):
@@ -69,110 +59,31 @@ def pack_nsf_ctx(prqct):
     if not supported(prqct):
         return None
     net = prqct.transform_net
-    D, H, NB, C = prqct.features, net.hidden_features, len(net.blocks), int(net.context_features)
-    ident = prqct.identity_features.cpu().numpy()
-    trans = prqct.transform_features.cpu().numpy()
-    nI, nT = len(ident), len(trans)
-    par_i, par_t = int(ident[0]), int(trans[0])
+    D, H, NB, C, K = prqct.features, net.hidden_features, len(net.blocks), int(net.context_features), prqct.num_bins
+    nI, nT, par_i, par_t, PI, Dp, _ = positions(prqct)
     Hp = 128 if H <= 128 else 256
-    PI, PT, PC = (nI + 31) // 32 * 32, (nT + 31) // 32 * 32, padded_context(C)
-    Dp = PI + PT
+    PC = padded_context(C)
     assert Dp == x_positions(D) and Dp + PC <= 128
     nhi, NS, TR = geometry(Hp)
-    K = prqct.num_bins
-    M_, MP_, FPL, FPG, nfi_max = bins_geometry(K)
-    G = (nT + FPG - 1) // FPG
-    nsp = TR // 64
-    nfi = (G * nsp + 7) // 8
-    if nfi > nfi_max:
+    finals = final_groups(net.final_layer, nT, K, H, TR)
+    w0 = net.initial_layer.weight.detach().cpu().numpy().astype(np.float32)      # (H, nI + C): cat(identity features, context)
+    if finals is None or w0.shape[1] != nI + C:
         return None
-    f32 = lambda t: t.detach().cpu().numpy().astype(np.float32)
-
-    w0 = f32(net.initial_layer.weight)                       # (H, nI + C): cat(identity features, context)
-    if w0.shape[1] != nI + C:
-        return None
-    W0i = np.zeros((Hp, PI), dtype=np.float32)
-    W0i[:H, :nI] = w0[:, :nI]
+    Kh = (H + 31) // 32 * 32
+    # the initial layer as two items: the identity columns with the bias, the context columns with a zero bias group (the kernel adds)
     W0c = np.zeros((Hp, PC), dtype=np.float32)
     W0c[:H, :C] = w0[:, nI:]
-    b0 = np.zeros(Hp, dtype=np.float32)
-    b0[:H] = f32(net.initial_layer.bias)
-    zero = np.zeros(Hp, dtype=np.float32)
-    Kh = (H + 31) // 32 * 32
+    head = [padded_linear(net.initial_layer, Hp, PI, w0[:, :nI]), (W0c, np.zeros(Hp, dtype=np.float32))]
+    blocks = [(padded_linear(blk.linear_layers[0], Hp, Kh), padded_linear(blk.context_layer, Hp, PC),
+               padded_linear(blk.linear_layers[1], Hp, Kh)) for blk in net.blocks]
 
-    def hidden(lin, cols, ncols):
-        W = np.zeros((Hp, cols), dtype=np.float32)
-        W[:H, :ncols] = f32(lin.weight)
-        b = np.zeros(Hp, dtype=np.float32)
-        b[:H] = f32(lin.bias)
-        return W, b
+    def items(w):    # the wave's hidden items in consumption order (nsf_ctx.hip): per block the W1 items, then per hidden item gate and W2
+        at = lambda i: hidden_item(Hp, w, i)
+        out = [l + at(i) for l in head for i in range(nhi)]
+        for l1, gate, l2 in blocks:
+            out += [l1 + at(i) for i in range(nhi)]
+            out += [l + at(i) for i in range(nhi) for l in (gate, l2)]
+        return out
 
-    # the stream's layers in consumption order, per hidden item of a wave (nsf_ctx.hip): [(W, b), ...] groups of "all items" or "per item"
-    head = [(W0i, b0), (W0c, zero)]
-    blocks = []
-    for blk in net.blocks:
-        l1, l2 = blk.linear_layers
-        blocks.append((hidden(l1, Kh, H), hidden(blk.context_layer, PC, C), hidden(l2, Kh, H)))
-
-    wf, bf = f32(net.final_layer.weight), f32(net.final_layer.bias)
-    if wf.shape[0] != M_ * nT:
-        return None
-    wh_scale = np.float32(1.4426950408889634 / np.sqrt(float(H)))          # log2(e) / sqrt(hidden): rqs_regs takes exp2
-    WF = np.zeros((G, 3, ROWS, Kh), dtype=np.float32)
-    BF = np.zeros((G, 3, ROWS), dtype=np.float32)
-    for g in range(G):
-        for r3 in range(3):
-            for rho in range(ROWS):
-                row = final_row(g, r3, rho, nT, K)
-                if row >= 0:
-                    sc = wh_scale if (row % M_) < 2 * K else np.float32(1.0)
-                    WF[g, r3, rho, :H] = wf[row] * sc
-                    BF[g, r3, rho] = bf[row] * sc
-
-    nh = (2 + 3 * NB) * nhi
-    nitems = nh + nfi
-    hdr = np.zeros(HDR, dtype=np.int32)
-    tab = np.zeros((8, nitems, 3), dtype=np.int32)
-    chunks, off = [], 0
-    for w in range(8):
-        hdr[16 + w] = off
-        stream, idx = [], 0
-
-        def item(Wl, bl, i):
-            nonlocal idx
-            rb, sb0 = hidden_item(Hp, w, i)
-            tab[w, idx] = (Wl.shape[1] // KG, rb, sb0)
-            idx += 1
-            stream.append(bias_group(bl[rb * ROWS:(rb + 1) * ROWS]))
-            stream.append(a_stream(Wl[rb * ROWS:(rb + 1) * ROWS]))
-
-        for Wl, bl in head:
-            for i in range(nhi):
-                item(Wl, bl, i)
-        for (l1, gate, l2) in blocks:
-            for i in range(nhi):
-                item(*l1, i)
-            for i in range(nhi):
-                item(*gate, i)
-                item(*l2, i)
-        assert idx == nh
-        for j in range(nfi):
-            g, sp = divmod(w + 8 * j, nsp)
-            if g >= G:
-                tab[w, nh + j] = (0, -1, 0)
-                continue
-            nkg = Kh // KG
-            tab[w, nh + j] = (nkg, g, 2 * sp)
-            for r3 in range(3):
-                stream.append(bias_group(BF[g, r3]))
-            frag = np.stack([a_stream(WF[g, r3]).reshape(nkg, 256) for r3 in range(3)], axis=1)   # [nkg][3][256]
-            stream.append(frag.reshape(-1))
-        stream = np.concatenate(stream)
-        stream = np.concatenate([stream, np.resize(stream, RING * 256)])
-        chunks.append(stream)
-        off += stream.size
-    hdr[:16] = [D, Dp, H, Hp, NB, nI, nT, par_i, par_t, G, nfi, off, nhi, 0, TR, PI]
-    hdr[24], hdr[25], hdr[26] = K, C, PC
-    blob = np.concatenate(chunks).astype(np.float32)
-    assert blob.size == off and off < 2 ** 31
-    return blob, np.concatenate([hdr, tab.reshape(-1)]).astype(np.int32)
+    hdr = [D, Dp, H, Hp, NB, nI, nT, par_i, par_t, 0, 0, 0, nhi, 0, TR, PI]
+    return write_streams(hdr, {24: K, 25: C, 26: PC}, items, finals)

@@ -24,6 +24,9 @@ rows, nsf/coupling.py:334-339).  Geometry (csrc/mlp_tile.hpp, nsf_wide.hip):
     sample block w >> 2, FIRST in the stream in the density direction (core.py:193-195 visits the LU layer before its coupling
     layer), LAST in the sampling direction -- so a pack is per direction.
 
+This module owns what the conditional pack (flows/nsf_ctx_pack.py) does in the same way: layer_conditions (also the benchmark kernel's
+eligibility test, neural_spline._fused_eligible), positions, padded_linear, final_groups and the per-wave stream writer write_streams.
+
 int32 table : hdr[32] = [D, Dp, H, Hp, NB, nI, nT, par_i, par_t, G, nfi, total floats, nhi, has_lu, TR, PI], hdr[16 + w] = offset (floats)
               of wave w's stream, hdr[24] = bins; then per wave: [LU entry (density)] | (1 + 2 NB) nhi hidden entries [nkg, rb, sb0] | nfi final
               entries [nkg, g, sb0] (g = -1: none; a group's item covers sample blocks sb0, sb0 + 1) | [LU entry (sampling)]; LU entry =
@@ -75,74 +78,64 @@ def final_row(g, r3, rho, nT, K=K_BINS):
     return tf * m + prm
 
 
+def layer_conditions(prqct, weights_f32=True):
+    """What nf_nsf_wide, nf_nsf_wide_ctx and the benchmark kernel (csrc/rqs_fused.hip) ask of the coupling transform alike: linear
+    tails shared by all features, the batch-shared spline on the identity half, 4 / 8 / 16 bins whose minimum widths / heights leave
+    room, float32 weights (weights_f32), an alternating mask.  Returns the mask's parity (the first identity feature: 0 | 1), or None."""
+    if prqct.tails != "linear" or getattr(prqct, "_per_feature", False) or prqct.unconditional_transform is None:
+        return None
+    K = prqct.num_bins
+    if K not in SUPPORTED_BINS or prqct.min_bin_width * K > 1.0 or prqct.min_bin_height * K > 1.0:
+        return None
+    if weights_f32 and prqct.transform_net.initial_layer.weight.dtype != torch.float32:
+        return None
+    D = prqct.features
+    ii, ti = prqct.identity_features.cpu(), prqct.transform_features.cpu()
+    for par in (0, 1):
+        if torch.equal(ii, torch.arange(par, D, 2)) and torch.equal(ti, torch.arange(1 - par, D, 2)):
+            return par
+    return None
+
+
 def supported(prqct):
     from .. import nets
     net = prqct.transform_net
     if not (isinstance(net, nets.ResidualNet) and net.is_plain_relu()):
         return False
-    if prqct.tails != "linear" or getattr(prqct, "_per_feature", False) or prqct.unconditional_transform is None:
+    if not (2 <= prqct.features <= 128 and 1 <= net.hidden_features <= 512 and 1 <= len(net.blocks) <= 7):
         return False
-    K = prqct.num_bins
-    if K not in SUPPORTED_BINS or prqct.min_bin_width * K > 1.0 or prqct.min_bin_height * K > 1.0:
-        return False
-    D = prqct.features
-    if not (2 <= D <= 128 and 1 <= net.hidden_features <= 512 and len(net.blocks) >= 1 and len(net.blocks) <= 7):
-        return False
-    if net.initial_layer.weight.dtype != torch.float32:
-        return False
-    ii, ti = prqct.identity_features.cpu(), prqct.transform_features.cpu()
-    alt0 = torch.equal(ii, torch.arange(0, D, 2)) and torch.equal(ti, torch.arange(1, D, 2))
-    alt1 = torch.equal(ii, torch.arange(1, D, 2)) and torch.equal(ti, torch.arange(0, D, 2))
-    return alt0 or alt1
+    return layer_conditions(prqct) is not None
 
 
-def pack_nsf_wide(prqct, lu=None, direction=0):
-    """(blob float32 ndarray, table int32 ndarray) or None (the caller keeps the layer-wise path).  lu = (W (D, D), b (D,)) numpy
-    arrays of the adjacent LULinearPermute in `direction` (0 density, 1 sampling), or None."""
-    if not supported(prqct):
-        return None
-    net = prqct.transform_net
-    D, H, NB = prqct.features, net.hidden_features, len(net.blocks)
-    ident = prqct.identity_features.cpu().numpy()
-    trans = prqct.transform_features.cpu().numpy()
-    nI, nT = len(ident), len(trans)
-    par_i, par_t = int(ident[0]), int(trans[0])
-    Hp = 128 if H <= 128 else (256 if H <= 256 else 512)
-    PI, PT = (nI + 31) // 32 * 32, (nT + 31) // 32 * 32
-    Dp = PI + PT
-    col_of = -np.ones(Dp, dtype=np.int64)          # position -> column of the row (or -1: padding)
-    col_of[:nI] = ident
-    col_of[PI:PI + nT] = trans
-    nhi, NS, TR = geometry(Hp)
-    K = prqct.num_bins
-    M_, MP_, FPL, FPG, nfi_max = bins_geometry(K)
+def _f32(t):
+    return t.detach().cpu().numpy().astype(np.float32)
+
+
+def padded_linear(lin, Hp, cols, w=None):
+    """(W (Hp, cols), b (Hp,)): a Linear's weight (or the columns `w` of it) and bias, zero-padded to the tile's row-blocks and k-groups."""
+    w = _f32(lin.weight) if w is None else w
+    W = np.zeros((Hp, cols), dtype=np.float32)
+    W[:w.shape[0], :w.shape[1]] = w
+    b = np.zeros(Hp, dtype=np.float32)
+    b[:w.shape[0]] = _f32(lin.bias)
+    return W, b
+
+
+def final_groups(lin, nT, K, H, TR):
+    """(WF (G, 3, 32, Kh), BF (G, 3, 32), G, nfi): the final Linear cut into groups of 3 row-blocks in final_row's order, log2(e) /
+    sqrt(hidden) folded into the width / height rows (rqs_regs takes exp2); a wave owns nfi final items = (group, pair of sample
+    blocks).  None when a wave would own more than the kernel keeps log-det sums for, or the Linear is not the (3 K - 1) nT rows."""
+    M_, _, _, FPG, nfi_max = bins_geometry(K)
     G = (nT + FPG - 1) // FPG
-    nsp = TR // 64                      # pairs of sample blocks per tile: a final item = (group, pair)
-    nfi = (G * nsp + 7) // 8
-    if nfi > nfi_max:                   # (the kernel keeps a wave's log-det sums per final item in registers)
+    nfi = (G * (TR // 64) + 7) // 8
+    wf, bf = _f32(lin.weight), _f32(lin.bias)
+    if nfi > nfi_max or wf.shape[0] != M_ * nT:
         return None
-    f32 = lambda t: t.detach().cpu().numpy().astype(np.float32)
-
-    W0 = np.zeros((Hp, PI), dtype=np.float32)
-    W0[:H, :nI] = f32(net.initial_layer.weight)
-    b0 = np.zeros(Hp, dtype=np.float32)
-    b0[:H] = f32(net.initial_layer.bias)
     # round 5: the CONTRACTION extent of the hidden -> hidden and final products is the hidden width rounded up to 32 (a k-loop runs
     # in steps of four k-groups), not Hp: a 192-wide network keeps Hp = 256 for its row-blocks (8 waves x 32 units) but its k-loops
     # run over 24 k-groups instead of 32 -- the padding is no longer paid for in K (D 96 / hidden 192: 675 -> see profiles/r05_*)
     Kh = (H + 31) // 32 * 32
-    layers = [(W0, b0)]
-    for blk in net.blocks:
-        for lin in blk.linear_layers:
-            W = np.zeros((Hp, Kh), dtype=np.float32)
-            W[:H, :H] = f32(lin.weight)
-            b = np.zeros(Hp, dtype=np.float32)
-            b[:H] = f32(lin.bias)
-            layers.append((W, b))
-    wf, bf = f32(net.final_layer.weight), f32(net.final_layer.bias)        # (23 nT, H)
-    if wf.shape[0] != M_ * nT:
-        return None
-    wh_scale = np.float32(1.4426950408889634 / np.sqrt(float(H)))          # log2(e) / sqrt(hidden): rqs_regs takes exp2
+    wh_scale = np.float32(1.4426950408889634 / np.sqrt(float(H)))
     WF = np.zeros((G, 3, ROWS, Kh), dtype=np.float32)
     BF = np.zeros((G, 3, ROWS), dtype=np.float32)
     for g in range(G):
@@ -153,62 +146,102 @@ def pack_nsf_wide(prqct, lu=None, direction=0):
                     sc = wh_scale if (row % M_) < 2 * K else np.float32(1.0)
                     WF[g, r3, rho, :H] = wf[row] * sc
                     BF[g, r3, rho] = bf[row] * sc
+    return WF, BF, G, nfi
 
-    nhl = 1 + 2 * NB
-    has_lu = lu is not None
-    nitems = nhl * nhi + nfi + (1 if has_lu else 0)
-    base = 1 if (has_lu and direction == 0) else 0
-    if has_lu:
+
+def write_streams(head, extra, wave_items, finals, tail_items=lambda w: ()):
+    """(blob, table) from head = the 16 leading header fields (G, nfi and the total are filled in here), extra = {index: value} of
+    later ones, the waves' hidden items in consumption
+    order -- wave_items(w) / tail_items(w) (behind the finals): [(W, b, rb, sb0), ...], rb = -1: an entry without work -- and
+    final_groups' result.  Per item a table entry and its bias group(s) + A fragments; per wave the ring wrap (a copy of its first 8
+    stream entries); the header's stream offsets, G, nfi and total."""
+    WF, BF, G, nfi = finals
+    nsp, nkg_f = head[14] // 64, WF.shape[3] // KG        # pairs of sample blocks per tile: a final item = (group, pair)
+    hdr = np.zeros(HDR, dtype=np.int32)
+    tab, chunks, off = [], [], 0
+    for w in range(8):
+        hdr[16 + w] = off
+        stream = []
+
+        def emit(items):
+            for W, b, rb, sb0 in items:
+                if rb < 0:
+                    tab.append((0, -1, 0))
+                    continue
+                tab.append((W.shape[1] // KG, rb, sb0))
+                stream.append(bias_group(b[rb * ROWS:(rb + 1) * ROWS]))
+                stream.append(a_stream(W[rb * ROWS:(rb + 1) * ROWS]))
+
+        emit(wave_items(w))
+        for j in range(nfi):
+            g, sp = divmod(w + 8 * j, nsp)
+            if g >= G:
+                tab.append((0, -1, 0))
+                continue
+            tab.append((nkg_f, g, 2 * sp))
+            for r3 in range(3):
+                stream.append(bias_group(BF[g, r3]))
+            frag = np.stack([a_stream(WF[g, r3]).reshape(nkg_f, 256) for r3 in range(3)], axis=1)   # [nkg][3][256]
+            stream.append(frag.reshape(-1))
+        emit(tail_items(w))
+        stream = np.concatenate(stream)
+        stream = np.concatenate([stream, np.resize(stream, RING * 256)])
+        chunks.append(stream)
+        off += stream.size
+    hdr[:16] = head
+    hdr[9], hdr[10], hdr[11] = G, nfi, off
+    for i, v in extra.items():
+        hdr[i] = v
+    blob = np.concatenate(chunks).astype(np.float32)
+    assert blob.size == off and off < 2 ** 31
+    return blob, np.concatenate([hdr, np.asarray(tab, dtype=np.int32).reshape(-1)]).astype(np.int32)
+
+
+def positions(prqct):
+    """(nI, nT, par_i, par_t, PI, Dp, position -> column of the row or -1) of the sorted x tile."""
+    ident = prqct.identity_features.cpu().numpy()
+    trans = prqct.transform_features.cpu().numpy()
+    nI, nT = len(ident), len(trans)
+    PI, PT = (nI + 31) // 32 * 32, (nT + 31) // 32 * 32
+    col_of = -np.ones(PI + PT, dtype=np.int64)
+    col_of[:nI] = ident
+    col_of[PI:PI + nT] = trans
+    return nI, nT, int(ident[0]), int(trans[0]), PI, PI + PT, col_of
+
+
+def pack_nsf_wide(prqct, lu=None, direction=0):
+    """(blob float32 ndarray, table int32 ndarray) or None (the caller keeps the layer-wise path).  lu = (W (D, D), b (D,)) numpy
+    arrays of the adjacent LULinearPermute in `direction` (0 density, 1 sampling), or None."""
+    if not supported(prqct):
+        return None
+    net = prqct.transform_net
+    D, H, NB, K = prqct.features, net.hidden_features, len(net.blocks), prqct.num_bins
+    nI, nT, par_i, par_t, PI, Dp, col_of = positions(prqct)
+    Hp = 128 if H <= 128 else (256 if H <= 256 else 512)
+    nhi, NS, TR = geometry(Hp)
+    finals = final_groups(net.final_layer, nT, K, H, TR)
+    if finals is None:
+        return None
+    Kh = (H + 31) // 32 * 32
+    layers = [padded_linear(net.initial_layer, Hp, PI)] + [padded_linear(lin, Hp, Kh) for blk in net.blocks for lin in blk.linear_layers]
+
+    def hidden(w):
+        return [(Wl, bl) + hidden_item(Hp, w, i) for Wl, bl in layers for i in range(nhi)]
+
+    first, last = hidden, lambda w: ()
+    if lu is not None:
         valid = col_of >= 0
         WL = np.zeros((Dp, Dp), dtype=np.float32)
         WL[np.ix_(valid, valid)] = np.asarray(lu[0], dtype=np.float32)[np.ix_(col_of[valid], col_of[valid])]
         bL = np.zeros(Dp, dtype=np.float32)
         bL[valid] = np.asarray(lu[1], dtype=np.float32)[col_of[valid]]
-    hdr = np.zeros(HDR, dtype=np.int32)
-    tab = np.zeros((8, nitems, 3), dtype=np.int32)
-    chunks, off = [], 0
 
-    def lu_item(w, stream, idx):
-        rb, sb0 = w & 3, (w >> 2) * (TR // 64)          # TR = 128: both sample blocks of the wave's half of the tile
-        if rb >= Dp // ROWS:
-            tab[w, idx] = (0, -1, 0)
-            return
-        tab[w, idx] = (Dp // KG, rb, sb0)
-        stream.append(bias_group(bL[rb * ROWS:(rb + 1) * ROWS]))
-        stream.append(a_stream(WL[rb * ROWS:(rb + 1) * ROWS]))
+        def lu_item(w):      # row-block w & 3; TR = 128: both sample blocks of the wave's half of the tile
+            return [(WL, bL, (w & 3) if (w & 3) < Dp // ROWS else -1, (w >> 2) * (TR // 64))]
 
-    for w in range(8):
-        hdr[16 + w] = off
-        stream = []
-        if has_lu and direction == 0:
-            lu_item(w, stream, 0)
-        for l in range(nhl):
-            Wl, bl = layers[l]
-            nkg = Wl.shape[1] // KG
-            for i in range(nhi):
-                rb, sb0 = hidden_item(Hp, w, i)
-                tab[w, base + l * nhi + i] = (nkg, rb, sb0)
-                stream.append(bias_group(bl[rb * ROWS:(rb + 1) * ROWS]))
-                stream.append(a_stream(Wl[rb * ROWS:(rb + 1) * ROWS]))
-        for j in range(nfi):
-            g, sp = divmod(w + 8 * j, nsp)
-            if g >= G:
-                tab[w, base + nhl * nhi + j] = (0, -1, 0)
-                continue
-            nkg = Kh // KG
-            tab[w, base + nhl * nhi + j] = (nkg, g, 2 * sp)
-            for r3 in range(3):
-                stream.append(bias_group(BF[g, r3]))
-            frag = np.stack([a_stream(WF[g, r3]).reshape(nkg, 256) for r3 in range(3)], axis=1)   # [nkg][3][256]
-            stream.append(frag.reshape(-1))
-        if has_lu and direction == 1:
-            lu_item(w, stream, nitems - 1)
-        stream = np.concatenate(stream)
-        stream = np.concatenate([stream, np.resize(stream, RING * 256)])
-        chunks.append(stream)
-        off += stream.size
-    hdr[:16] = [D, Dp, H, Hp, NB, nI, nT, par_i, par_t, G, nfi, off, nhi, int(has_lu), TR, PI]
-    hdr[24] = K
-    blob = np.concatenate(chunks).astype(np.float32)
-    assert blob.size == off and off < 2 ** 31
-    return blob, np.concatenate([hdr, tab.reshape(-1)]).astype(np.int32)
+        if direction == 0:
+            first = lambda w: lu_item(w) + hidden(w)
+        else:
+            last = lu_item
+    head = [D, Dp, H, Hp, NB, nI, nT, par_i, par_t, 0, 0, 0, nhi, int(lu is not None), TR, PI]
+    return write_streams(head, {24: K}, first, finals, last)

@@ -112,21 +112,56 @@ def test_nsf_ctx_pack_boundary_widths(nfa):
                 assert packed[1][1] == nsf_ctx_pack.x_positions(D)
 
 
-def test_context_free_wide_pack_unchanged(nfa):
-    """pack_nsf_wide's output for a context-free layer is byte-identical with the conditional pack present (digest of the pack of a
-    layer with value-set parameters, recorded before nsf_ctx_pack.py existed)."""
-    from normflows_amd.flows import nsf_wide_pack
-    layer = nfa.flows.CoupledRationalQuadraticSpline(10, 2, 160, num_bins=8, init_identity=False)
+def _by_value(n, i):
+    return torch.sin(torch.arange(n, dtype=torch.float64) * 0.37 + i)
+
+
+def _pack_digest(nfa, D, C, H, NB, K, rev, lu_direction=None):
+    """sha256 of blob + table of the layer whose parameters (and LU matrix / bias, when asked for) are set by value."""
+    from normflows_amd.flows import nsf_ctx_pack, nsf_wide_pack
+    layer = nfa.flows.CoupledRationalQuadraticSpline(D, NB, H, num_context_channels=C, num_bins=K, init_identity=False,
+                                                     reverse_mask=rev).eval()
     with torch.no_grad():
         for i, p in enumerate(layer.parameters()):
-            p.copy_(torch.sin(torch.arange(p.numel(), dtype=torch.float64) * 0.37 + i).reshape(p.shape).float())
-    blob, table = nsf_wide_pack.pack_nsf_wide(layer.prqct)
-    digest = hashlib.sha256(blob.tobytes() + table.tobytes()).hexdigest()
-    assert digest == WIDE_PACK_DIGEST, digest
+            p.copy_(_by_value(p.numel(), i).reshape(p.shape).float())
+    if C is not None:
+        blob, table = nsf_ctx_pack.pack_nsf_ctx(layer.prqct)
+    elif lu_direction is None:
+        blob, table = nsf_wide_pack.pack_nsf_wide(layer.prqct)
+    else:
+        lu = (_by_value(D * D, 0).reshape(D, D).numpy(), _by_value(D, 1).numpy())
+        blob, table = nsf_wide_pack.pack_nsf_wide(layer.prqct, lu=lu, direction=lu_direction)
     assert not hasattr(layer.prqct, "_ctx_cache")
+    return hashlib.sha256(blob.tobytes() + table.tobytes()).hexdigest()
+
+
+def test_context_free_wide_pack_unchanged(nfa):
+    """pack_nsf_wide's output for a context-free layer is byte-identical with the conditional pack present (digest of the pack of a
+    layer with value-set parameters, recorded before nsf_ctx_pack.py existed); and every pack of PACK_DIGESTS -- plain, with the LU
+    item in either position, conditional -- is byte-identical with what the two separate packers produced (recorded at commit
+    767411e, the last one in which nsf_ctx_pack.py carried its own copy of the stream writer)."""
+    digest = _pack_digest(nfa, 10, None, 160, 2, 8, False)
+    assert digest == WIDE_PACK_DIGEST, digest
+    for case, want in PACK_DIGESTS.items():
+        got = _pack_digest(nfa, *case)
+        assert got == want, (case, got)
 
 
 WIDE_PACK_DIGEST = "d8e1479aec5bb4c9a7da9ea344b78ce190b222731460d5135e77721ce1ed4ceb"
+# (D, C, hidden, blocks, bins, reverse_mask, LU direction): Hp 512, 4 and 16 bins, the LU item first / last, every conditional shape class
+PACK_DIGESTS = {
+    (128, None, 512, 2, 16, False, None): "853f8c4adabe3be6cc4b5fd8f101a41b3776147af1ef6e7739b8ed5a11b22735",
+    (128, None, 512, 2, 16, False, 0): "2085ffd05b114256545b4da881bc634da2069339137eae6326c0f3f5bea37801",
+    (128, None, 512, 2, 16, False, 1): "b492e69d62bed6c308ba2e3a5d392305839208769b2ef5626b940b3cf745cfe3",
+    (7, None, 300, 2, 8, True, None): "9400f1cbb2811b5641680abf366507f51e10ee6efb728e9dd3ffa86e03f0267d",
+    (7, None, 300, 2, 8, True, 0): "09be73ab68553d1bd65d4f8b822a8c4fb6d555fb0698cccb420acbab00393850",
+    (7, None, 300, 2, 8, True, 1): "0d6fd4a98a28496ce2594dc1a15cb9fdb1eb86a904827d4698956cdc25f8cde1",
+    (64, None, 256, 2, 4, False, None): "a68bd8bacdd6e120e7bc39898c6e12bc249ce1792e4cb183a12820d34b34a945",
+    (6, 3, 40, 2, 8, False, None): "16b58683dac993cecaa9e7f3e3170b4b303fa5e4b822621557e5235d0238346d",
+    (17, 33, 200, 1, 16, True, None): "1d786121a01c6eb4c37ab5b30b09bec2590532d0450a7fb7da7a8c549bc127f4",
+    (64, 64, 256, 2, 8, False, None): "543d7cc6027f850e9766bba7d87a92d978c018eb79960d1f0347c2aa9d17a1f3",
+    (65, 32, 128, 1, 4, True, None): "34c3ec37649460ac191a6100143f383e9f8390c7556ce4df23c03c2b19269d3c",
+}
 
 
 def test_nsf_wide_ctx_argument_validation_without_gpu(nfa):
