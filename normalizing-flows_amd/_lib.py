@@ -106,12 +106,16 @@ def build_safe_waits(force=False):
     return SAFE_WAITS_LIB
 
 
+def _header_text():
+    import re
+    txt = open(os.path.join(INCLUDE, "nf_mi355x.h")).read()
+    return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+
+
 def exported_symbols_declared():
     """Names of every function declared in include/nf_mi355x.h (used by the symbol-export test)."""
     import re
-    txt = open(os.path.join(INCLUDE, "nf_mi355x.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(nf_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(nf_[a-z0-9_]+)\s*\(", _header_text())))
 
 
 def int64_functions_declared():
@@ -120,34 +124,74 @@ def int64_functions_declared():
     had its return type set only on the ablation-build path -- the density-direction backward of config 5's layer failed above
     ~720 000 rows per call with a scratch buffer a fraction of the size the kernel addressed.)"""
     import re
-    txt = open(os.path.join(INCLUDE, "nf_mi355x.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"^\s*int64_t\s+(nf_[a-z0-9_]+)\s*\(", txt, flags=re.M)))
+    return sorted(set(re.findall(r"^\s*int64_t\s+(nf_[a-z0-9_]+)\s*\(", _header_text(), flags=re.M)))
 
 
-def _declare_return_types(handle):
-    handle.nf_version.restype = C.c_char_p
-    handle.nf_strerror.restype = C.c_char_p
-    for fn in int64_functions_declared():
+_SCALARS = {"int": C.c_int, "int64_t": C.c_int64, "double": C.c_double, "float": C.c_float, "nf_stream_t": C.c_void_p}
+
+
+def _ctype(decl, fn):
+    """The ctypes type of one C declarator (a return type, or a parameter with or without its name) of function `fn`: any pointer is
+    c_void_p (which accepts None, ints, ctypes arrays and string buffers), scalars by _SCALARS; anything else is an error, never skipped."""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    if "*" in words:
+        return C.c_char_p if words[0] == "char" else C.c_void_p
+    if len(words) > 2 or not words or words[0] not in _SCALARS:
+        raise NativeLibraryError("include/nf_mi355x.h: %s has a type this binding does not know: %r" % (fn, decl))
+    return _SCALARS[words[0]]
+
+
+def prototypes_declared():
+    """{name: (restype, [argtypes])} of every function include/nf_mi355x.h declares, parsed like the two lists above."""
+    import re
+    out = {}
+    for ret, fn, params in re.findall(r"([A-Za-z_][\w \*]*?)\b(nf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _header_text()):
+        params = [p.strip() for p in params.split(",")]
+        out[fn] = (_ctype(ret, fn), [] if params == ["void"] else [_ctype(p, fn) for p in params])
+    return out
+
+
+def _declare_prototypes(handle):
+    """restype and argtypes of every entry point from the header: a bare Python number is then converted to the width the C side reads
+    (not passed as a 32-bit int), and a wrong count or kind of argument raises instead of reaching the kernel launch."""
+    for fn, (restype, argtypes) in prototypes_declared().items():
         if hasattr(handle, fn):
-            getattr(handle, fn).restype = C.c_int64
+            f = getattr(handle, fn)
+            f.restype, f.argtypes = restype, argtypes
 
 
 def lib():
     global _lib
     if _lib is None:
-        override = os.environ.get("NF_MI355X_LIB")   # ablation builds (tools/*_ablate.py): another build of the SAME sources
-        if override:
-            _lib = C.CDLL(override)
-            _declare_return_types(_lib)
-            return _lib
-        if not os.path.exists(LIBPATH):
-            raise NativeLibraryError(
-                "libnf_mi355x.so is missing (%s). Build it with `python -c 'import __graft_entry__ as g; g.build()'`."
-                " There is no CPU or eager fallback." % LIBPATH)
-        _lib = C.CDLL(LIBPATH)
-        _declare_return_types(_lib)       # (every int64_t function of the header, not a hand-kept list)
+        path = os.environ.get("NF_MI355X_LIB")   # ablation builds (tools/*_ablate.py): another build of the SAME sources
+        if not path:
+            path = LIBPATH
+            if not os.path.exists(LIBPATH):
+                raise NativeLibraryError(
+                    "libnf_mi355x.so is missing (%s). Build it with `python -c 'import __graft_entry__ as g; g.build()'`."
+                    " There is no CPU or eager fallback." % LIBPATH)
+        handle = C.CDLL(path)
+        _declare_prototypes(handle)       # (every function of the header, not a hand-kept list)
+        _lib = handle
     return _lib
+
+
+def call(name, *args):
+    """Call the entry point `name` (returns an errno-style code) and raise on failure under that same name."""
+    check(getattr(lib(), name)(*args), name)
+
+
+def query(name, *args):
+    """The value of a size / scratch / layout query `name` (*_pack_size, *_scratch_floats, *_partials, ...) as a Python int."""
+    return int(getattr(lib(), name)(*args))
+
+
+def size(name, *args):
+    """query() for the size functions whose negative values are error codes: those raise under the function's name."""
+    n = query(name, *args)
+    if n < 0:
+        check(n, name)
+    return n
 
 
 def check(rc, what):
@@ -191,6 +235,11 @@ def ptr(t):
     if not t.is_contiguous():
         raise ValueError("tensor handed to the C ABI must be contiguous")
     return C.c_void_p(t.data_ptr())
+
+
+def ptr_any(t):
+    """Device pointer of a tensor whose rows may be strided (last dim unit stride)."""
+    return C.c_void_p(0 if t is None else t.data_ptr())
 
 
 def stream():

@@ -9,13 +9,20 @@ import math
 import torch
 
 from . import _lib as L
-from ._lib import f64, i32, i64, ptr
+from ._lib import ptr, ptr_any
 
 
-def _ld_buffer(logdet, B, like):
-    if logdet is None:
+def _ld_buffer(logdet, acc, B, like, want=True):
+    """The log-det convention of the wrappers, (tensor, acc): no `logdet` given -> a new (B) tensor that the kernel overwrites
+    (LD_WRITE); given without `acc` -> the kernel adds to it (LD_ADD).  want=False: nothing is allocated for a missing `logdet`."""
+    if logdet is None and want:
         return torch.empty(B, dtype=like.dtype, device=like.device), L.LD_WRITE
-    return logdet, None
+    return logdet, L.LD_ADD if acc is None else acc
+
+
+def _ld_acc(logdet, acc):
+    """actnorm / inv1x1_conv: the per-sample `logdet` is optional and never allocated; LD_ADD when it is given without `acc`."""
+    return (L.LD_ADD if logdet is not None and acc is None else acc) or 0
 
 
 def rqs_spline(x, w, h, d, inverse=False, tails="linear", tail_bound=1.0, left=0.0, right=1.0, bottom=0.0, top=1.0,
@@ -36,18 +43,14 @@ def rqs_spline(x, w, h, d, inverse=False, tails="linear", tail_bound=1.0, left=0
     w2, h2, d2 = rows(w), rows(h), rows(d)
     y = torch.empty_like(xs)
     lad = torch.empty_like(xs)
-    rc = L.lib().nf_rqs_spline(ptr_any(xs), ptr_any(w2), i64(w2.stride(0) if N else K), ptr_any(h2),
-                               i64(h2.stride(0) if N else K), ptr_any(d2), i64(d2.stride(0) if N else 1), ptr_any(y),
-                               ptr_any(lad), i64(N), i32(K), i32(L.TAILS[tails]), f64(tail_bound), f64(left), f64(right),
-                               f64(bottom), f64(top), f64(min_bin_width), f64(min_bin_height), f64(min_derivative),
-                               f64(wh_div), i32(int(inverse)), i32(L.dtype_code(x)), L.stream())
-    L.check(rc, "nf_rqs_spline")
+    L.call("nf_rqs_spline", ptr_any(xs), ptr_any(w2), w2.stride(0) if N else K, ptr_any(h2), h2.stride(0) if N else K,
+           ptr_any(d2), d2.stride(0) if N else 1, ptr_any(y), ptr_any(lad), N, K, L.TAILS[tails], tail_bound, left, right, bottom,
+           top, min_bin_width, min_bin_height, min_derivative, wh_div, int(inverse), L.dtype_code(x), L.stream())
     from . import config
     if config.debug_checks and N > 0:      # device-side flags, read back only in debug mode (config.set_debug_checks)
         flags = torch.zeros(1, dtype=torch.int32, device=x.device)
-        rc = L.lib().nf_rqs_spline_check(ptr_any(xs), ptr_any(y), i64(N), i32(L.TAILS[tails]), f64(tail_bound), f64(left), f64(right),
-                                         f64(bottom), f64(top), i32(int(inverse)), i32(L.dtype_code(x)), ptr_any(flags), L.stream())
-        L.check(rc, "nf_rqs_spline_check")
+        L.call("nf_rqs_spline_check", ptr_any(xs), ptr_any(y), N, L.TAILS[tails], tail_bound, left, right, bottom, top,
+               int(inverse), L.dtype_code(x), ptr_any(flags), L.stream())
         f = int(flags.item())
         if f & 1:
             raise RuntimeError("rational_quadratic_spline: input outside the domain with tails=None (the reference's gather fails on "
@@ -57,10 +60,15 @@ def rqs_spline(x, w, h, d, inverse=False, tails="linear", tail_bound=1.0, left=0
     return y.view(x.shape), lad.view(x.shape)
 
 
-def ptr_any(t):
-    """Device pointer of a tensor whose rows may be strided (last dim unit stride)."""
-    import ctypes
-    return ctypes.c_void_p(0 if t is None else t.data_ptr())
+def _tails_args(x, tails, tail_bound, tails_t, bound_t, tails_i, bound_i):
+    """What tells nf_rqs_coupling[_bwd] from its per-feature variant: (name suffix, tails code, scalar bound, the variant's trailing
+    tensors [tails_t, bound_t, tails_i, bound_i] as int32 / x.dtype on x's device)."""
+    if not (tails == "feature" or bound_t is not None or bound_i is not None):
+        return "", L.TAILS[tails], tail_bound, []
+    fix = lambda t, dtype: None if t is None else t.to(device=x.device, dtype=dtype).contiguous()   # noqa: E731
+    code = 3 if tails == "feature" else L.TAILS[tails]
+    scalar_bound = float(tail_bound) if not torch.is_tensor(tail_bound) else 1.0
+    return "_ft", code, scalar_bound, [fix(tails_t, torch.int32), fix(bound_t, x.dtype), fix(tails_i, torch.int32), fix(bound_i, x.dtype)]
 
 
 def rqs_coupling(x, cond, uw, uh, ud, identity_idx, transform_idx, K, mode, y=None, logdet=None, acc=None,
@@ -74,32 +82,11 @@ def rqs_coupling(x, cond, uw, uh, ud, identity_idx, transform_idx, K, mode, y=No
     x = x.contiguous()
     if y is None:
         y = torch.empty_like(x)
-    if logdet is None:
-        logdet = torch.empty(B, dtype=x.dtype, device=x.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    per_feature = tails == "feature" or bound_t is not None or bound_i is not None
-    if not per_feature:
-        rc = L.lib().nf_rqs_coupling(ptr(x), ptr(y), ptr(logdet), ptr(cond), ptr(uw), ptr(uh), ptr(ud),
-                                     ptr(identity_idx), i32(identity_idx.numel()), ptr(transform_idx),
-                                     i32(transform_idx.numel()), i64(B), i32(D), i32(K), i32(L.TAILS[tails]),
-                                     f64(tail_bound), f64(min_bin_width), f64(min_bin_height), f64(min_derivative),
-                                     f64(wh_div), i32(mode), i32(acc), i32(L.dtype_code(x)), L.stream())
-        L.check(rc, "nf_rqs_coupling")
-        return y, logdet
-    fix_b = lambda t: None if t is None else t.to(device=x.device, dtype=x.dtype).contiguous()
-    fix_t = lambda t: None if t is None else t.to(device=x.device, dtype=torch.int32).contiguous()
-    bt, bi, tt, ti = fix_b(bound_t), fix_b(bound_i), fix_t(tails_t), fix_t(tails_i)
-    code = 3 if tails == "feature" else L.TAILS[tails]
-    scalar_bound = float(tail_bound) if not torch.is_tensor(tail_bound) else 1.0
-    rc = L.lib().nf_rqs_coupling_ft(ptr(x), ptr(y), ptr(logdet), ptr(cond), ptr(uw), ptr(uh), ptr(ud),
-                                    ptr(identity_idx), i32(identity_idx.numel()), ptr(transform_idx),
-                                    i32(transform_idx.numel()), i64(B), i32(D), i32(K), i32(code), f64(scalar_bound),
-                                    f64(min_bin_width), f64(min_bin_height), f64(min_derivative), f64(wh_div),
-                                    i32(mode), i32(acc), i32(L.dtype_code(x)), ptr(tt), ptr(bt), ptr(ti), ptr(bi),
-                                    L.stream())
-    L.check(rc, "nf_rqs_coupling_ft")
+    logdet, acc = _ld_buffer(logdet, acc, B, x)
+    ft, code, bound, feat = _tails_args(x, tails, tail_bound, tails_t, bound_t, tails_i, bound_i)
+    L.call("nf_rqs_coupling" + ft, ptr(x), ptr(y), ptr(logdet), ptr(cond), ptr(uw), ptr(uh), ptr(ud), ptr(identity_idx),
+           identity_idx.numel(), ptr(transform_idx), transform_idx.numel(), B, D, K, code, bound, min_bin_width, min_bin_height,
+           min_derivative, wh_div, mode, acc, L.dtype_code(x), *map(ptr, feat), L.stream())
     return y, logdet
 
 
@@ -110,39 +97,33 @@ def lu_linear_permute(x, perm, lower_entries, upper_entries, unconstrained_upper
     B, D = x.shape
     x = x.contiguous()
     y = torch.empty_like(x)
-    if logdet is None:
-        logdet = torch.empty(B, dtype=x.dtype, device=x.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_lu_linear_permute(ptr(x), ptr(y), ptr(logdet), ptr(perm), ptr(lower_entries), ptr(upper_entries),
-                                      ptr(unconstrained_upper_diag), ptr(bias), i64(B), i32(D), f64(eps),
-                                      i32(direction), i32(acc), i32(L.dtype_code(x)), L.stream())
-    L.check(rc, "nf_lu_linear_permute")
+    logdet, acc = _ld_buffer(logdet, acc, B, x)
+    L.call("nf_lu_linear_permute", ptr(x), ptr(y), ptr(logdet), ptr(perm), ptr(lower_entries), ptr(upper_entries),
+           ptr(unconstrained_upper_diag), ptr(bias), B, D, eps, direction, acc, L.dtype_code(x), L.stream())
     return y, logdet
+
+
+def _mask_rows(z, b):
+    """(B, elements per sample, the mask b broadcast to one sample's shape and flattened) of masked_affine[_bwd]."""
+    B = z.shape[0]
+    inner = z[0].numel() if B else int(math.prod(z.shape[1:]))
+    bb = b.to(z.dtype)
+    if bb.numel() != inner:
+        bb = bb.expand((1,) + tuple(z.shape[1:]))
+    return B, inner, bb.contiguous().view(-1)
 
 
 def masked_affine(z, b, s, t, direction, logdet=None, acc=None):
     """affine/coupling.py:209-229.  b broadcastable to z.shape[1:]; s, t same shape as z or None."""
     L.require_device(z, b, s, t)
     z = z.contiguous()
-    B = z.shape[0]
-    inner = z[0].numel() if B else int(math.prod(z.shape[1:]))
-    bb = b.to(z.dtype)
-    if bb.numel() != inner:
-        bb = bb.expand((1,) + tuple(z.shape[1:]))
-    bb = bb.contiguous().view(-1)
+    B, inner, bb = _mask_rows(z, b)
     y = torch.empty_like(z)
-    if logdet is None:
-        logdet = torch.empty(B, dtype=z.dtype, device=z.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
+    logdet, acc = _ld_buffer(logdet, acc, B, z)
     s = None if s is None else s.contiguous()
     t = None if t is None else t.contiguous()
-    rc = L.lib().nf_masked_affine(ptr(z), ptr(bb), ptr(s), ptr(t), ptr(y), ptr(logdet), i64(B), i64(inner),
-                                  i32(direction), i32(acc), i32(L.dtype_code(z)), L.stream())
-    L.check(rc, "nf_masked_affine")
+    L.call("nf_masked_affine", ptr(z), ptr(bb), ptr(s), ptr(t), ptr(y), ptr(logdet), B, inner, direction, acc, L.dtype_code(z),
+           L.stream())
     return y, logdet
 
 
@@ -155,15 +136,9 @@ def affine_coupling(z, param, c1, flip, scale_map, direction, logdet=None, acc=N
     B, Cc = z.shape[:2]
     HW = int(math.prod(z.shape[2:])) if z.dim() > 2 else 1
     y = torch.empty_like(z)
-    if logdet is None:
-        logdet = torch.empty(B, dtype=z.dtype, device=z.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_affine_coupling_pb(ptr(z), ptr(param), ptr(None if param_bias is None else param_bias.contiguous()),
-                                       ptr(y), ptr(logdet), i64(B), i32(Cc), i32(c1), i32(int(flip)), i64(HW),
-                                       i32(L.SCALE[scale_map]), i32(direction), i32(acc), i32(L.dtype_code(z)), L.stream())
-    L.check(rc, "nf_affine_coupling_pb")
+    logdet, acc = _ld_buffer(logdet, acc, B, z)
+    L.call("nf_affine_coupling_pb", ptr(z), ptr(param), _cptr(param_bias), ptr(y), ptr(logdet), B, Cc, c1, int(flip), HW,
+           L.SCALE[scale_map], direction, acc, L.dtype_code(z), L.stream())
     return y, logdet
 
 
@@ -175,12 +150,8 @@ def actnorm(z, s, t, direction, logdet=None, acc=None, want_scalar=True):
     HW = int(math.prod(z.shape[2:])) if z.dim() > 2 else 1
     y = torch.empty_like(z)
     lds = torch.empty((), dtype=z.dtype, device=z.device) if want_scalar else None
-    if logdet is not None and acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_actnorm(ptr(z), ptr(s.contiguous().view(-1)), ptr(t.contiguous().view(-1)), ptr(y), ptr(lds),
-                            ptr(logdet), i64(B), i32(Cc), i64(HW), i32(direction), i32(acc or 0), i32(L.dtype_code(z)),
-                            L.stream())
-    L.check(rc, "nf_actnorm")
+    L.call("nf_actnorm", ptr(z), ptr(s.contiguous().view(-1)), ptr(t.contiguous().view(-1)), ptr(y), ptr(lds), ptr(logdet), B, Cc,
+           HW, direction, _ld_acc(logdet, acc), L.dtype_code(z), L.stream())
     return y, lds
 
 
@@ -191,17 +162,14 @@ def actnorm_stats(z):
     HW = int(math.prod(z.shape[2:])) if z.dim() > 2 else 1
     mean = torch.empty(Cc, dtype=z.dtype, device=z.device)
     std = torch.empty(Cc, dtype=z.dtype, device=z.device)
-    rc = L.lib().nf_actnorm_stats(ptr(z), ptr(mean), ptr(std), i64(B), i32(Cc), i64(HW), i32(L.dtype_code(z)),
-                                  L.stream())
-    L.check(rc, "nf_actnorm_stats")
+    L.call("nf_actnorm_stats", ptr(z), ptr(mean), ptr(std), B, Cc, HW, L.dtype_code(z), L.stream())
     return mean, std
 
 
 def actnorm_init(mean, std, s_out, t_out, direction):
     L.require_device(mean, std, s_out, t_out)
-    rc = L.lib().nf_actnorm_init(ptr(mean), ptr(std), ptr(s_out), ptr(t_out), i32(mean.numel()), i32(direction),
-                                 i32(L.dtype_code(mean)), L.stream())
-    L.check(rc, "nf_actnorm_init")
+    L.call("nf_actnorm_init", ptr(mean), ptr(std), ptr(s_out), ptr(t_out), mean.numel(), direction, L.dtype_code(mean),
+           L.stream())
 
 
 def inv1x1_assemble(P, Lm, U, sign_S, log_S, inverse):
@@ -209,10 +177,8 @@ def inv1x1_assemble(P, Lm, U, sign_S, log_S, inverse):
     Cc = Lm.shape[0]
     W = torch.empty((Cc, Cc), dtype=Lm.dtype, device=Lm.device)
     ldu = torch.empty((), dtype=Lm.dtype, device=Lm.device)
-    rc = L.lib().nf_inv1x1_assemble(ptr(P.contiguous()), ptr(Lm.contiguous()), ptr(U.contiguous()),
-                                    ptr(sign_S.contiguous()), ptr(log_S.contiguous()), ptr(W), ptr(ldu), i32(Cc),
-                                    i32(int(inverse)), i32(L.dtype_code(Lm)), L.stream())
-    L.check(rc, "nf_inv1x1_assemble")
+    L.call("nf_inv1x1_assemble", ptr(P.contiguous()), ptr(Lm.contiguous()), ptr(U.contiguous()), ptr(sign_S.contiguous()),
+           ptr(log_S.contiguous()), ptr(W), ptr(ldu), Cc, int(inverse), L.dtype_code(Lm), L.stream())
     return W, ldu
 
 
@@ -221,11 +187,19 @@ def inv1x1_lu_grads(P, Lm, U, sign_S, log_S, gW, gl):
     L.require_device(P, Lm, U, sign_S, log_S, gW, gl)
     Cc = Lm.shape[0]
     gL, gU, gs = torch.empty_like(Lm), torch.empty_like(U), torch.empty_like(log_S)
-    rc = L.lib().nf_inv1x1_lu_grads(ptr(P.contiguous()), ptr(Lm.contiguous()), ptr(U.contiguous()), ptr(sign_S.contiguous()),
-                                    ptr(log_S.contiguous()), ptr(gW.contiguous()), ptr(None if gl is None else gl.contiguous()),
-                                    ptr(gL), ptr(gU), ptr(gs), i32(Cc), i32(L.dtype_code(Lm)), L.stream())
-    L.check(rc, "nf_inv1x1_lu_grads")
+    L.call("nf_inv1x1_lu_grads", ptr(P.contiguous()), ptr(Lm.contiguous()), ptr(U.contiguous()), ptr(sign_S.contiguous()),
+           ptr(log_S.contiguous()), ptr(gW.contiguous()), _cptr(gl), ptr(gL), ptr(gU), ptr(gs), Cc, L.dtype_code(Lm), L.stream())
     return gL, gU, gs
+
+
+def _scratch(name, device, *args):
+    """A float32 scratch buffer of the size the query `name` gives for `args` (at least one element)."""
+    return torch.empty(max(L.query(name, *args), 1), dtype=torch.float32, device=device)
+
+
+def _cptr(t):
+    """Device pointer of an optional tensor, made contiguous first (NULL for None)."""
+    return ptr(None if t is None else t.contiguous())
 
 
 def _ptr_array(tensors):
@@ -243,8 +217,7 @@ def ld_fold_multi(ld, terms, negate):
         raise NotImplementedError("ld_fold_multi: contiguous float32 vectors of one length")
     terms = [t.contiguous() for t in terms]
     neg = (C.c_int * len(terms))(*[1 if x else 0 for x in negate])
-    rc = L.lib().nf_ld_fold_multi(ptr(ld), _ptr_array(terms), neg, i32(len(terms)), i64(ld.numel()), L.stream())
-    L.check(rc, "nf_ld_fold_multi")
+    L.call("nf_ld_fold_multi", ptr(ld), _ptr_array(terms), neg, len(terms), ld.numel(), L.stream())
     return ld
 
 
@@ -263,8 +236,7 @@ def inv1x1_assemble_multi(layers):
     ld = torch.empty(n, dtype=torch.float32, device=dev)
     Ws, lds = list(W.unbind(0)), list(ld.unbind(0))
     arrs = [_ptr_array([c[k] for c in cols]) for k in range(5)]
-    rc = L.lib().nf_inv1x1_assemble_multi(*arrs, _ptr_array(Ws), _ptr_array(lds), i32(n), i32(Cc), L.stream())
-    L.check(rc, "nf_inv1x1_assemble_multi")
+    L.call("nf_inv1x1_assemble_multi", *arrs, _ptr_array(Ws), _ptr_array(lds), n, Cc, L.stream())
     return list(zip(Ws, lds))
 
 
@@ -283,9 +255,8 @@ def inv1x1_lu_grads_multi(layers, gWs, gls):
     gs = torch.empty(n, Cc, dtype=torch.float32, device=dev)
     gLs, gUs, gss = list(gL.unbind(0)), list(gU.unbind(0)), list(gs.unbind(0))
     arrs = [_ptr_array([c[k] for c in cols]) for k in range(5)]
-    rc = L.lib().nf_inv1x1_lu_grads_multi(*arrs, _ptr_array(gWs), _ptr_array(gls), _ptr_array(gLs), _ptr_array(gUs), _ptr_array(gss),
-                                          i32(n), i32(Cc), L.stream())
-    L.check(rc, "nf_inv1x1_lu_grads_multi")
+    L.call("nf_inv1x1_lu_grads_multi", *arrs, _ptr_array(gWs), _ptr_array(gls), _ptr_array(gLs), _ptr_array(gUs), _ptr_array(gss),
+           n, Cc, L.stream())
     return list(zip(gLs, gUs, gss))
 
 
@@ -296,12 +267,8 @@ def inv1x1_conv(z, W, logdet_unit, logdet=None, acc=None, want_scalar=True, bias
     HW = int(math.prod(z.shape[2:]))
     y = torch.empty_like(z)
     lds = torch.empty((), dtype=z.dtype, device=z.device) if want_scalar else None
-    if logdet is not None and acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_inv1x1_conv_affine(ptr(z), ptr(W.contiguous()), ptr(None if bias is None else bias.contiguous()),
-                                       ptr(logdet_unit), ptr(y), ptr(lds), ptr(logdet), i64(B), i32(Cc), i64(HW),
-                                       i32(acc or 0), i32(L.dtype_code(z)), L.stream())
-    L.check(rc, "nf_inv1x1_conv_affine")
+    L.call("nf_inv1x1_conv_affine", ptr(z), ptr(W.contiguous()), _cptr(bias), ptr(logdet_unit), ptr(y), ptr(lds), ptr(logdet), B,
+           Cc, HW, _ld_acc(logdet, acc), L.dtype_code(z), L.stream())
     return y, lds
 
 
@@ -312,8 +279,7 @@ def inv1x1_conv_t(z, W):
     B, Cc = z.shape[:2]
     HW = int(math.prod(z.shape[2:]))
     y = torch.empty_like(z)
-    L.check(L.lib().nf_inv1x1_conv_t(ptr(z), ptr(W.contiguous()), ptr(y), i64(B), i32(Cc), i64(HW), i32(L.dtype_code(z)), L.stream()),
-            "nf_inv1x1_conv_t")
+    L.call("nf_inv1x1_conv_t", ptr(z), ptr(W.contiguous()), ptr(y), B, Cc, HW, L.dtype_code(z), L.stream())
     return y
 
 
@@ -322,20 +288,12 @@ def masked_affine_bwd(z, b, s, t, gy, gld, direction):
     """(gz, gs, gt) of nf_masked_affine for cotangents gy (like z) and gld (B) -- coupling.py:209-229 under autograd."""
     L.require_device(z, b, s, t, gy, gld)
     z, gy = z.contiguous(), gy.contiguous()
-    B = z.shape[0]
-    inner = z[0].numel() if B else int(math.prod(z.shape[1:]))
-    bb = b.to(z.dtype)
-    if bb.numel() != inner:
-        bb = bb.expand((1,) + tuple(z.shape[1:]))
-    bb = bb.contiguous().view(-1)
+    B, inner, bb = _mask_rows(z, b)
     gz = torch.empty_like(z)
     gs = None if s is None else torch.empty_like(z)
     gt = None if t is None else torch.empty_like(z)
-    rc = L.lib().nf_masked_affine_bwd(ptr(z), ptr(bb), ptr(None if s is None else s.contiguous()),
-                                      ptr(None if t is None else t.contiguous()), ptr(gy),
-                                      ptr(None if gld is None else gld.contiguous()), ptr(gz), ptr(gs), ptr(gt), i64(B),
-                                      i64(inner), i32(direction), i32(L.dtype_code(z)), L.stream())
-    L.check(rc, "nf_masked_affine_bwd")
+    L.call("nf_masked_affine_bwd", ptr(z), ptr(bb), _cptr(s), _cptr(t), ptr(gy), _cptr(gld), ptr(gz), ptr(gs), ptr(gt), B, inner,
+           direction, L.dtype_code(z), L.stream())
     return gz, gs, gt
 
 
@@ -346,10 +304,8 @@ def affine_coupling_bwd(z, param, gy, gld, c1, flip, scale_map, direction):
     B, Cc = z.shape[:2]
     HW = int(math.prod(z.shape[2:])) if z.dim() > 2 else 1
     gz, gp = torch.empty_like(z), torch.empty_like(param)
-    rc = L.lib().nf_affine_coupling_bwd(ptr(z), ptr(param), ptr(gy), ptr(None if gld is None else gld.contiguous()), ptr(gz),
-                                        ptr(gp), i64(B), i32(Cc), i32(c1), i32(int(flip)), i64(HW), i32(L.SCALE[scale_map]),
-                                        i32(direction), i32(L.dtype_code(z)), L.stream())
-    L.check(rc, "nf_affine_coupling_bwd")
+    L.call("nf_affine_coupling_bwd", ptr(z), ptr(param), ptr(gy), _cptr(gld), ptr(gz), ptr(gp), B, Cc, c1, int(flip), HW,
+           L.SCALE[scale_map], direction, L.dtype_code(z), L.stream())
     return gz, gp
 
 
@@ -364,14 +320,9 @@ def actnorm_bwd(z, s, t, gy, gld, direction):
     gt = torch.empty(Cc, dtype=z.dtype, device=z.device)
     if B == 0:
         return gz, gs.zero_(), gt.zero_()
-    import ctypes
-    lib = L.lib()
-    lib.nf_actnorm_bwd_scratch_doubles.restype = ctypes.c_int64
-    scratch = torch.empty(int(lib.nf_actnorm_bwd_scratch_doubles(i64(B), i32(Cc))), dtype=torch.float64, device=z.device)
-    rc = lib.nf_actnorm_bwd(ptr(z), ptr(s.contiguous().view(-1)), ptr(t.contiguous().view(-1)), ptr(gy),
-                            ptr(None if gld is None else gld.contiguous()), ptr(gz), ptr(gs), ptr(gt), ptr(scratch), i64(B),
-                            i32(Cc), i64(HW), i32(direction), i32(L.dtype_code(z)), L.stream())
-    L.check(rc, "nf_actnorm_bwd")
+    scratch = torch.empty(L.query("nf_actnorm_bwd_scratch_doubles", B, Cc), dtype=torch.float64, device=z.device)
+    L.call("nf_actnorm_bwd", ptr(z), ptr(s.contiguous().view(-1)), ptr(t.contiguous().view(-1)), ptr(gy), _cptr(gld), ptr(gz),
+           ptr(gs), ptr(gt), ptr(scratch), B, Cc, HW, direction, L.dtype_code(z), L.stream())
     return gz, gs, gt
 
 
@@ -382,8 +333,7 @@ def rows_matvec(x, W):
         raise NotImplementedError("rows_matvec: (B, D <= 128) float32")
     x = x.contiguous()
     y = torch.empty_like(x)
-    rc = L.lib().nf_rows_matvec(ptr(x), ptr(W.to(torch.float32).contiguous()), ptr(y), i64(x.shape[0]), i32(x.shape[1]), L.stream())
-    L.check(rc, "nf_rows_matvec")
+    L.call("nf_rows_matvec", ptr(x), ptr(W.to(torch.float32).contiguous()), ptr(y), x.shape[0], x.shape[1], L.stream())
     return y
 
 
@@ -399,10 +349,8 @@ def rows_block(x, M1, c1, M2, c2, trans=False, mask1=None, mask2=None, relu=True
     assert tuple(M1.shape) == (H, H) and tuple(M2.shape) == (H, H)
     out1, out2 = torch.empty_like(x), torch.empty_like(x)
     c = lambda t: None if t is None else t.contiguous()   # noqa: E731
-    rc = L.lib().nf_rows_block(ptr(x), i64(H), ptr(M1), i64(H), i32(int(trans)), ptr(c(c1)), ptr(c(mask1)), i64(H), ptr(out1),
-                               i64(H), ptr(M2), i64(H), i32(int(trans)), ptr(c(c2)), ptr(c(mask2)), i64(H), ptr(out2), i64(H),
-                               i64(B), i32(H), i32(int(relu)), i32(int(relu)), L.stream())
-    L.check(rc, "nf_rows_block")
+    L.call("nf_rows_block", ptr(x), H, ptr(M1), H, int(trans), ptr(c(c1)), ptr(c(mask1)), H, ptr(out1), H, ptr(M2), H, int(trans),
+           ptr(c(c2)), ptr(c(mask2)), H, ptr(out2), H, B, H, int(relu), int(relu), L.stream())
     return out1, out2
 
 
@@ -412,10 +360,8 @@ def lu_compose(perm, lower_entries, upper_entries, unconstrained_upper_diag, bia
     L.require_device(perm, lower_entries, upper_entries, unconstrained_upper_diag, bias)
     D = bias.numel()
     out = torch.empty(2 * D * D + 2 * D + 1, dtype=torch.float32, device=bias.device)
-    rc = L.lib().nf_lu_compose(ptr(perm), ptr(lower_entries.contiguous()), ptr(upper_entries.contiguous()),
-                               ptr(unconstrained_upper_diag.contiguous()), ptr(bias.contiguous()), f64(eps), ptr(out), i32(D),
-                               L.stream())
-    L.check(rc, "nf_lu_compose")
+    L.call("nf_lu_compose", ptr(perm), ptr(lower_entries.contiguous()), ptr(upper_entries.contiguous()),
+           ptr(unconstrained_upper_diag.contiguous()), ptr(bias.contiguous()), eps, ptr(out), D, L.stream())
     N = D * D
     return out[:N].view(D, D), out[N:2 * N].view(D, D), out[2 * N:2 * N + D], out[2 * N + D:2 * N + 2 * D], out[2 * N + 2 * D:]
 
@@ -425,9 +371,8 @@ def lu_factors(perm, lower_entries, upper_entries, unconstrained_upper_diag, eps
     L.require_device(perm, lower_entries, upper_entries, unconstrained_upper_diag)
     D = unconstrained_upper_diag.numel()
     out = torch.empty(5 * D * D + D + 1, dtype=torch.float32, device=unconstrained_upper_diag.device)
-    rc = L.lib().nf_lu_factors(ptr(perm), ptr(lower_entries.contiguous()), ptr(upper_entries.contiguous()),
-                               ptr(unconstrained_upper_diag.contiguous()), f64(eps), ptr(out), i32(D), L.stream())
-    L.check(rc, "nf_lu_factors")
+    L.call("nf_lu_factors", ptr(perm), ptr(lower_entries.contiguous()), ptr(upper_entries.contiguous()),
+           ptr(unconstrained_upper_diag.contiguous()), eps, ptr(out), D, L.stream())
     return lu_factors_views(out, D)
 
 
@@ -442,16 +387,15 @@ def lu_factors_views(out, D):
 def lu_factors_multi(table, n_layers, eps, D):
     """nf_lu_factors for n_layers layers in one launch; table: (n_layers x 5) int64 device pointers (perm, lower, upper, udiag, out)."""
     L.require_device(table)
-    L.check(L.lib().nf_lu_factors_multi(ptr(table), i32(n_layers), f64(eps), i32(D), L.stream()), "nf_lu_factors_multi")
+    L.call("nf_lu_factors_multi", ptr(table), n_layers, eps, D, L.stream())
 
 
 def rqs_fused_pack_all_multi(table, n_layers, num_blocks, tail_bound=3.0, min_bin_width=1e-3, min_bin_height=1e-3,
                              min_derivative=1e-3):
     """nf_rqs_fused_pack_all for n_layers layers in one launch; table: (n_layers x (11 + 4 num_blocks)) int64 device pointers."""
     L.require_device(table)
-    rc = L.lib().nf_rqs_fused_pack_all_multi(ptr(table), i32(n_layers), i32(128), i32(num_blocks), i32(8), f64(tail_bound),
-                                             f64(min_bin_width), f64(min_bin_height), f64(min_derivative), L.stream())
-    L.check(rc, "nf_rqs_fused_pack_all_multi")
+    L.call("nf_rqs_fused_pack_all_multi", ptr(table), n_layers, 128, num_blocks, 8, tail_bound, min_bin_width, min_bin_height,
+           min_derivative, L.stream())
 
 
 def lu_param_grads(gL, gU, gld, unconstrained_upper_diag, n_tri, eps=1e-3, sign=1.0, perm=None, out=None):
@@ -472,10 +416,9 @@ def lu_param_grads(gL, gU, gld, unconstrained_upper_diag, n_tri, eps=1e-3, sign=
         g_lower = torch.empty(n_tri, dtype=torch.float32, device=dev)
         g_upper = torch.empty(n_tri, dtype=torch.float32, device=dev)
         g_udiag = torch.empty(D, dtype=torch.float32, device=dev)
-    rc = L.lib().nf_lu_param_grads(ptr(gL.contiguous()), ptr(gU.contiguous()), ptr(perm), ptr(gld),
-                                   i64(0 if gld is None else gld.numel()), ptr(unconstrained_upper_diag.contiguous()),
-                                   f64(eps), f64(sign), ptr(g_lower), ptr(g_upper), ptr(g_udiag), i32(D), L.stream())
-    L.check(rc, "nf_lu_param_grads")
+    L.call("nf_lu_param_grads", ptr(gL.contiguous()), ptr(gU.contiguous()), ptr(perm), ptr(gld),
+           0 if gld is None else gld.numel(), ptr(unconstrained_upper_diag.contiguous()), eps, sign, ptr(g_lower), ptr(g_upper),
+           ptr(g_udiag), D, L.stream())
     return g_lower, g_upper, g_udiag
 
 
@@ -485,14 +428,9 @@ def rows_matvec_affine(x, W, bias, ld_const=None, ld_sign=1.0, logdet=None, acc=
     x = x.contiguous()
     B, D = x.shape
     y = torch.empty_like(x)
-    if ld_const is not None and logdet is None:
-        logdet = torch.empty(B, dtype=x.dtype, device=x.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_rows_matvec_affine(ptr(x), ptr(W), ptr(bias), ptr(y), ptr(logdet if ld_const is not None else None),
-                                       ptr(ld_const), f64(ld_sign), i32(acc), i64(B), i32(D), L.stream())
-    L.check(rc, "nf_rows_matvec_affine")
+    logdet, acc = _ld_buffer(logdet, acc, B, x, want=ld_const is not None)
+    L.call("nf_rows_matvec_affine", ptr(x), ptr(W), ptr(bias), ptr(y), ptr(logdet if ld_const is not None else None),
+           ptr(ld_const), ld_sign, acc, B, D, L.stream())
     return y, logdet
 
 
@@ -503,37 +441,26 @@ def rows_matvec2(x, W1, W2, bias=None, ld_const=None, ld_sign=1.0, logdet=None, 
     B, D = x.shape
     u = torch.empty_like(x) if want_u else None
     y = torch.empty_like(x)
-    if ld_const is not None and logdet is None:
-        logdet = torch.empty(B, dtype=x.dtype, device=x.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_rows_matvec2(ptr(x), ptr(W1.contiguous()), ptr(W2.contiguous()), ptr(bias), ptr(u), ptr(y),
-                                 ptr(logdet if ld_const is not None else None), ptr(ld_const), f64(ld_sign), i32(acc), i64(B),
-                                 i32(D), L.stream())
-    L.check(rc, "nf_rows_matvec2")
+    logdet, acc = _ld_buffer(logdet, acc, B, x, want=ld_const is not None)
+    L.call("nf_rows_matvec2", ptr(x), ptr(W1.contiguous()), ptr(W2.contiguous()), ptr(bias), ptr(u), ptr(y),
+           ptr(logdet if ld_const is not None else None), ptr(ld_const), ld_sign, acc, B, D, L.stream())
     return u, y, logdet
 
 
 def inv1x1_wgrad(z, gy, gld):
     """(gW (C, C), g log|det|-per-pixel (0-dim)) of the per-pixel product y = W z (mixing.py:106-133): gW = sum over
     pixels of gy z^T, partial sums per group of images added in a fixed order."""
-    import ctypes
     L.require_device(z, gy, gld)
     z, gy = z.contiguous(), gy.contiguous()
     B, Cc = z.shape[:2]
     HW = int(math.prod(z.shape[2:])) if z.dim() > 2 else 1
-    lib = L.lib()
-    lib.nf_inv1x1_wgrad_scratch_elems.restype = ctypes.c_int64
-    n = lib.nf_inv1x1_wgrad_scratch_elems(i64(B), i32(Cc))
+    n = L.query("nf_inv1x1_wgrad_scratch_elems", B, Cc)
     if n < 0:
         raise NotImplementedError("inv1x1_wgrad: C <= 64")
-    scratch = torch.empty(int(n), dtype=z.dtype, device=z.device)
+    scratch = torch.empty(n, dtype=z.dtype, device=z.device)
     gW = torch.empty(Cc, Cc, dtype=z.dtype, device=z.device)
     gl = torch.empty((), dtype=z.dtype, device=z.device)
-    rc = lib.nf_inv1x1_wgrad(ptr(z), ptr(gy), ptr(None if gld is None else gld.contiguous()), ptr(gW), ptr(gl), ptr(scratch),
-                             i64(B), i32(Cc), i64(HW), i32(L.dtype_code(z)), L.stream())
-    L.check(rc, "nf_inv1x1_wgrad")
+    L.call("nf_inv1x1_wgrad", ptr(z), ptr(gy), _cptr(gld), ptr(gW), ptr(gl), ptr(scratch), B, Cc, HW, L.dtype_code(z), L.stream())
     return gW, gl
 
 
@@ -543,15 +470,9 @@ def diag_gaussian_log_prob(z, loc, log_scale, log_scale_shift=0.0, out=None, acc
     z = z.contiguous()
     B = z.shape[0]
     d = int(math.prod(z.shape[1:]))
-    if out is None:
-        out = torch.empty(B, dtype=z.dtype, device=z.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_diag_gaussian_log_prob(ptr(z), ptr(loc.contiguous().view(-1)), ptr(log_scale.contiguous().view(-1)),
-                                           f64(log_scale_shift), ptr(out), i64(B), i64(d), i32(acc),
-                                           i32(L.dtype_code(z)), L.stream())
-    L.check(rc, "nf_diag_gaussian_log_prob")
+    out, acc = _ld_buffer(out, acc, B, z)
+    L.call("nf_diag_gaussian_log_prob", ptr(z), ptr(loc.contiguous().view(-1)), ptr(log_scale.contiguous().view(-1)),
+           log_scale_shift, ptr(out), B, d, acc, L.dtype_code(z), L.stream())
     return out
 
 
@@ -562,40 +483,33 @@ def squeeze(z, direction):
     B, Cc, H, W = z.shape
     shape = (B, Cc // 4, 2 * H, 2 * W) if direction == 0 else (B, 4 * Cc, H // 2, W // 2)
     y = torch.empty(shape, dtype=z.dtype, device=z.device)
-    rc = L.lib().nf_squeeze(ptr(z), ptr(y), i64(B), i32(Cc), i32(H), i32(W), i32(direction), i32(L.dtype_code(z)),
-                            L.stream())
-    L.check(rc, "nf_squeeze")
+    L.call("nf_squeeze", ptr(z), ptr(y), B, Cc, H, W, direction, L.dtype_code(z), L.stream())
     return y
 
 
 # ---- fused NSF coupling layer (conditioner on MFMA + spline epilogue) ------------------------------------------
 def rqs_fused_supported(nI, nT, hidden, num_blocks, K):
-    return L.lib().nf_rqs_fused_pack_size(i32(nI), i32(nT), i32(hidden), i32(num_blocks), i32(K)) > 0
+    return L.query("nf_rqs_fused_pack_size", nI, nT, hidden, num_blocks, K) > 0
 
 
 def rqs_fused_pack(w_init, b_init, w_blocks, b_blocks, w_final, b_final, uw, uh, ud, K, tail_bound, min_bin_width,
                    min_bin_height, min_derivative):
     """Re-lay-out one layer's weights in MFMA operand order (nf_rqs_fused_pack).  Returns the packed device blob."""
-    import ctypes
     L.require_device(w_init, b_init, w_final, b_final, uw, uh, ud, *w_blocks, *b_blocks)
     hidden, nI = w_init.shape
     nT = uw.shape[0]
     nb = len(w_blocks) // 2
-    lib = L.lib()
-    lib.nf_rqs_fused_pack_size.restype = ctypes.c_int64
-    size = lib.nf_rqs_fused_pack_size(i32(nI), i32(nT), i32(hidden), i32(nb), i32(K))
+    size = L.query("nf_rqs_fused_pack_size", nI, nT, hidden, nb, K)
     if size <= 0:
         raise NotImplementedError("nf_rqs_fused: shape not supported")
     blob = torch.empty(size // 4, dtype=torch.float32, device=w_init.device)
     keep = [t.contiguous() for t in (w_init, b_init, w_final, b_final, uw, uh, ud)]
     wb = [t.contiguous() for t in w_blocks]
     bb = [t.contiguous() for t in b_blocks]
-    wp = (ctypes.c_void_p * max(len(wb), 1))(*[t.data_ptr() for t in wb])
-    bp = (ctypes.c_void_p * max(len(bb), 1))(*[t.data_ptr() for t in bb])
-    rc = lib.nf_rqs_fused_pack(ptr(blob), ptr(keep[0]), ptr(keep[1]), wp, bp, ptr(keep[2]), ptr(keep[3]), ptr(keep[4]),
-                               ptr(keep[5]), ptr(keep[6]), i32(nI), i32(nT), i32(hidden), i32(nb), i32(K),
-                               f64(tail_bound), f64(min_bin_width), f64(min_bin_height), f64(min_derivative), L.stream())
-    L.check(rc, "nf_rqs_fused_pack")
+    wp, bp = _ptr_array(wb), _ptr_array(bb)
+    L.call("nf_rqs_fused_pack", ptr(blob), ptr(keep[0]), ptr(keep[1]), wp, bp, ptr(keep[2]), ptr(keep[3]), ptr(keep[4]),
+           ptr(keep[5]), ptr(keep[6]), nI, nT, hidden, nb, K, tail_bound, min_bin_width, min_bin_height, min_derivative,
+           L.stream())
     return blob
 
 
@@ -603,36 +517,41 @@ def rqs_fused_pack_lu(blob, num_blocks, perm, lower_entries, upper_entries, unco
     """Add the layer's LULinearPermute (composed dense 64 x 64 matrices, both directions) to a packed blob of K bins."""
     L.require_device(blob, perm, lower_entries, upper_entries, unconstrained_upper_diag, bias)
     D = bias.numel()
-    rc = L.lib().nf_rqs_fused_pack_lu(ptr(blob), i32(num_blocks), ptr(perm), ptr(lower_entries.contiguous()),
-                                      ptr(upper_entries.contiguous()), ptr(unconstrained_upper_diag.contiguous()),
-                                      ptr(bias.contiguous()), i32(D), f64(eps), i32(K), L.stream())
-    L.check(rc, "nf_rqs_fused_pack_lu")
+    L.call("nf_rqs_fused_pack_lu", ptr(blob), num_blocks, ptr(perm), ptr(lower_entries.contiguous()),
+           ptr(upper_entries.contiguous()), ptr(unconstrained_upper_diag.contiguous()), ptr(bias.contiguous()), D, eps, K,
+           L.stream())
     return blob
+
+
+def _rqs_fused_launch(name, x, blobs, parities, hidden, num_blocks, K, direction, logdet, acc, limits, fuse_lu, live_d=None,
+                      padded_rows=False):
+    """The shared body of rqs_fused[_x3][_chain], `name` the entry point: one layer (blobs a tensor, parities its mask parity) or a chain
+    (lists of both, in processing order); padded_rows: rows must have 64 columns, of which live_d are in use."""
+    chain = not torch.is_tensor(blobs)
+    L.require_device(x, *(blobs if chain else [blobs]))
+    if x.dtype != torch.float32:
+        raise TypeError("%s is fp32 only" % name)
+    x = x.contiguous()
+    B, D = x.shape
+    y = torch.empty_like(x)
+    logdet, acc = _ld_buffer(logdet, acc, B, x)
+    if padded_rows and D != 64:
+        raise ValueError("%s: rows of 64 columns (narrower layers: padded by the caller, live_d = columns in use)" % name)
+    if chain:
+        layers = (_ptr_array(blobs), (C.c_int * len(blobs))(*[int(v) for v in parities]), len(blobs))
+    else:
+        layers = (ptr(blobs), parities)
+    L.call(name, ptr(x), ptr(y), ptr(logdet), *layers, int(fuse_lu), B, D if live_d is None else live_d, hidden, num_blocks, K,
+           *limits, direction, acc, L.stream())
+    return y, logdet
 
 
 def rqs_fused(x, blob, mask_parity, hidden, num_blocks, K, direction, logdet=None, acc=None, tail_bound=3.0,
               min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3, fuse_lu=False, live_d=None):
     """One launch for a whole CoupledRationalQuadraticSpline layer (+ its LULinearPermute when fuse_lu).
     direction 0 = density, 1 = sample."""
-    L.require_device(x, blob)
-    if x.dtype != torch.float32:
-        raise TypeError("nf_rqs_fused is fp32 only")
-    x = x.contiguous()
-    B, D = x.shape
-    y = torch.empty_like(x)
-    if logdet is None:
-        logdet = torch.empty(B, dtype=x.dtype, device=x.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    if D != 64:
-        raise ValueError("nf_rqs_fused: rows of 64 columns (narrower layers: padded by the caller, live_d = columns in use)")
-    rc = L.lib().nf_rqs_fused(ptr(x), ptr(y), ptr(logdet), ptr(blob), i32(mask_parity), i32(int(fuse_lu)), i64(B),
-                              i32(D if live_d is None else live_d), i32(hidden),
-                              i32(num_blocks), i32(K), f64(tail_bound), f64(min_bin_width), f64(min_bin_height),
-                              f64(min_derivative), i32(direction), i32(acc), L.stream())
-    L.check(rc, "nf_rqs_fused")
-    return y, logdet
+    return _rqs_fused_launch("nf_rqs_fused", x, blob, mask_parity, hidden, num_blocks, K, direction, logdet, acc,
+                             (tail_bound, min_bin_width, min_bin_height, min_derivative), fuse_lu, live_d, padded_rows=True)
 
 
 def rqs_coupling_bwd(x, grad_y, grad_logdet, cond, uw, uh, ud, identity_idx, transform_idx, K, mode, tails="linear",
@@ -649,38 +568,18 @@ def rqs_coupling_bwd(x, grad_y, grad_logdet, cond, uw, uh, ud, identity_idx, tra
     guw = torch.zeros_like(uw) if uw is not None else None
     guh = torch.zeros_like(uh) if uh is not None else None
     gud = torch.zeros_like(ud) if ud is not None else None
-    if tails == "feature" or bound_t is not None or bound_i is not None:
-        fix_b = lambda t: None if t is None else t.to(device=x.device, dtype=x.dtype).contiguous()
-        fix_t = lambda t: None if t is None else t.to(device=x.device, dtype=torch.int32).contiguous()
-        bt, bi, tt, ti = fix_b(bound_t), fix_b(bound_i), fix_t(tails_t), fix_t(tails_i)
-        code = 3 if tails == "feature" else L.TAILS[tails]
-        scalar_bound = float(tail_bound) if not torch.is_tensor(tail_bound) else 1.0
-        rc = L.lib().nf_rqs_coupling_bwd_ft(ptr(x), ptr(grad_y), ptr(grad_logdet), ptr(cond), ptr(uw), ptr(uh), ptr(ud),
-                                            ptr(identity_idx), i32(identity_idx.numel()), ptr(transform_idx),
-                                            i32(transform_idx.numel()), i64(B), i32(D), i32(K), i32(code),
-                                            f64(scalar_bound), f64(min_bin_width), f64(min_bin_height),
-                                            f64(min_derivative), f64(wh_div), i32(mode), ptr(gx), ptr(gcond), ptr(guw),
-                                            ptr(guh), ptr(gud), i32(L.dtype_code(x)), ptr(tt), ptr(bt), ptr(ti), ptr(bi),
-                                            L.stream())
-        L.check(rc, "nf_rqs_coupling_bwd_ft")
-        return gx, gcond, guw, guh, gud
-    rc = L.lib().nf_rqs_coupling_bwd(ptr(x), ptr(grad_y), ptr(grad_logdet), ptr(cond), ptr(uw), ptr(uh), ptr(ud),
-                                     ptr(identity_idx), i32(identity_idx.numel()), ptr(transform_idx),
-                                     i32(transform_idx.numel()), i64(B), i32(D), i32(K), i32(L.TAILS[tails]),
-                                     f64(tail_bound), f64(min_bin_width), f64(min_bin_height), f64(min_derivative),
-                                     f64(wh_div), i32(mode), ptr(gx), ptr(gcond), ptr(guw), ptr(guh), ptr(gud),
-                                     i32(L.dtype_code(x)), L.stream())
-    L.check(rc, "nf_rqs_coupling_bwd")
+    ft, code, bound, feat = _tails_args(x, tails, tail_bound, tails_t, bound_t, tails_i, bound_i)
+    L.call("nf_rqs_coupling_bwd" + ft, ptr(x), ptr(grad_y), ptr(grad_logdet), ptr(cond), ptr(uw), ptr(uh), ptr(ud),
+           ptr(identity_idx), identity_idx.numel(), ptr(transform_idx), transform_idx.numel(), B, D, K, code, bound,
+           min_bin_width, min_bin_height, min_derivative, wh_div, mode, ptr(gx), ptr(gcond), ptr(guw), ptr(guh), ptr(gud),
+           L.dtype_code(x), *map(ptr, feat), L.stream())
     return gx, gcond, guw, guh, gud
 
 
 # ---- training forward of the fused layer's last stage (csrc/rqs_fused.hip, TRAIN variant) ------------------------------
 def rqs_fused_train_blob(num_blocks, device):
     """Empty packed-blob buffer of the fused layer (filled by rqs_fused_pack_final)."""
-    import ctypes
-    lib = L.lib()
-    lib.nf_rqs_fused_pack_size.restype = ctypes.c_int64
-    size = lib.nf_rqs_fused_pack_size(i32(32), i32(32), i32(128), i32(num_blocks), i32(8))
+    size = L.query("nf_rqs_fused_pack_size", 32, 32, 128, num_blocks, 8)
     if size <= 0:
         raise NotImplementedError("nf_rqs_fused: shape not supported")
     return torch.zeros(size // 4, dtype=torch.float32, device=device)
@@ -689,11 +588,24 @@ def rqs_fused_train_blob(num_blocks, device):
 def rqs_fused_pack_final(blob, w_final, b_final, uw, uh, ud, num_blocks, tail_bound=3.0, min_bin_width=1e-3,
                          min_bin_height=1e-3, min_derivative=1e-3):
     L.require_device(blob, w_final, b_final, uw, uh, ud)
-    rc = L.lib().nf_rqs_fused_pack_final(ptr(blob), ptr(w_final.contiguous()), ptr(b_final.contiguous()), ptr(uw.contiguous()),
-                                         ptr(uh.contiguous()), ptr(ud.contiguous()), i32(128), i32(num_blocks), i32(8),
-                                         f64(tail_bound), f64(min_bin_width), f64(min_bin_height), f64(min_derivative), L.stream())
-    L.check(rc, "nf_rqs_fused_pack_final")
+    L.call("nf_rqs_fused_pack_final", ptr(blob), ptr(w_final.contiguous()), ptr(b_final.contiguous()), ptr(uw.contiguous()),
+           ptr(uh.contiguous()), ptr(ud.contiguous()), 128, num_blocks, 8, tail_bound, min_bin_width, min_bin_height,
+           min_derivative, L.stream())
     return blob
+
+
+def _train_fwd(name, x, second, blob, mask_parity, num_blocks, limits, logdet, acc, with_acts=True):
+    """The shared body of the three training forwards: allocates y, logdet (by the wrappers' convention), cond24 and, with_acts, the
+    (2 num_blocks + 1, B, 128) activations; `second`: the tensor the entry point takes after x (h2 / xlu), if any.
+    Returns (y, logdet, cond24, acts)."""
+    B = x.shape[0]
+    y = torch.empty_like(x)
+    ld, acc = _ld_buffer(logdet, acc, B, x)
+    cond = torch.empty(B, 32, 24, dtype=x.dtype, device=x.device)
+    acts = torch.empty(2 * num_blocks + 1, B, 128, dtype=x.dtype, device=x.device) if with_acts else None
+    L.call(name, ptr(x), *([] if second is None else [ptr(second)]), ptr(y), ptr(ld), ptr(cond),
+           *([ptr(acts)] if with_acts else []), ptr(blob), mask_parity, B, 64, 128, num_blocks, 8, *limits, acc, L.stream())
+    return y, ld, cond, acts
 
 
 def rqs_fused_train_fwd(x, h2, blob, mask_parity, num_blocks, tail_bound=3.0, min_bin_width=1e-3, min_bin_height=1e-3,
@@ -701,34 +613,19 @@ def rqs_fused_train_fwd(x, h2, blob, mask_parity, num_blocks, tail_bound=3.0, mi
     """(y, logdet, cond24) of nf_rqs_fused_train_fwd: final Linear + density-direction coupling transform in one launch;
     cond24 (B, 32, 24) is the conditioner output kept for rqs_coupling_bwd_p24.  logdet given: folded into it per acc."""
     L.require_device(x, h2, blob)
-    x, h2 = x.contiguous(), h2.contiguous()
-    B = x.shape[0]
-    y = torch.empty_like(x)
-    if logdet is None:
-        ld, acc = torch.empty(B, dtype=x.dtype, device=x.device), L.LD_WRITE
-    else:
-        ld, acc = logdet, (L.LD_ADD if acc is None else acc)
-    cond = torch.empty(B, 32, 24, dtype=x.dtype, device=x.device)
-    rc = L.lib().nf_rqs_fused_train_fwd(ptr(x), ptr(h2), ptr(y), ptr(ld), ptr(cond), ptr(blob), i32(mask_parity), i64(B), i32(64),
-                                        i32(128), i32(num_blocks), i32(8), f64(tail_bound), f64(min_bin_width),
-                                        f64(min_bin_height), f64(min_derivative), i32(acc), L.stream())
-    L.check(rc, "nf_rqs_fused_train_fwd")
-    return y, ld, cond
+    return _train_fwd("nf_rqs_fused_train_fwd", x.contiguous(), h2.contiguous(), blob, mask_parity, num_blocks,
+                      (tail_bound, min_bin_width, min_bin_height, min_derivative), logdet, acc, with_acts=False)[:3]
 
 
 def rqs_fused_pack_all(blob, w_init, b_init, w_blocks, b_blocks, w_final, b_final, uw, uh, ud, tail_bound=3.0, min_bin_width=1e-3,
                        min_bin_height=1e-3, min_derivative=1e-3, wfull=None, wpad=None, identity_idx=None):
     """The whole layer's blob (no LU) in one launch (nf_rqs_fused_pack_all); hidden 128, 8 bins."""
-    import ctypes
     L.require_device(blob, w_init, b_init, w_final, b_final, uw, uh, ud, wfull, wpad, identity_idx, *w_blocks, *b_blocks)
     n = len(w_blocks)
-    wp = (ctypes.c_void_p * max(n, 1))(*[w.data_ptr() for w in w_blocks])
-    bp = (ctypes.c_void_p * max(n, 1))(*[b.data_ptr() for b in b_blocks])
-    rc = L.lib().nf_rqs_fused_pack_all(ptr(blob), ptr(w_init), ptr(b_init), wp, bp, ptr(w_final), ptr(b_final), ptr(uw), ptr(uh),
-                                       ptr(ud), i32(128), i32(n // 2), i32(8), f64(tail_bound), f64(min_bin_width),
-                                       f64(min_bin_height), f64(min_derivative), ptr(wfull), ptr(wpad), ptr(identity_idx),
-                                       L.stream())
-    L.check(rc, "nf_rqs_fused_pack_all")
+    wp, bp = _ptr_array(w_blocks), _ptr_array(b_blocks)
+    L.call("nf_rqs_fused_pack_all", ptr(blob), ptr(w_init), ptr(b_init), wp, bp, ptr(w_final), ptr(b_final), ptr(uw), ptr(uh),
+           ptr(ud), 128, n // 2, 8, tail_bound, min_bin_width, min_bin_height, min_derivative, ptr(wfull), ptr(wpad),
+           ptr(identity_idx), L.stream())
     return blob
 
 
@@ -737,20 +634,15 @@ def rqs_fused_train_full_fwd(x, blob, mask_parity, num_blocks, tail_bound=3.0, m
     """(y, logdet, cond24, acts) of nf_rqs_fused_train_full_fwd: the whole conditioner + coupling transform in one launch;
     acts (2 num_blocks + 1, B, 128) = h0, then (t, h) per residual block."""
     L.require_device(x, blob)
-    x = x.contiguous()
-    B = x.shape[0]
-    y = torch.empty_like(x)
-    if logdet is None:
-        ld, acc = torch.empty(B, dtype=x.dtype, device=x.device), L.LD_WRITE
-    else:
-        ld, acc = logdet, (L.LD_ADD if acc is None else acc)
-    cond = torch.empty(B, 32, 24, dtype=x.dtype, device=x.device)
-    acts = torch.empty(2 * num_blocks + 1, B, 128, dtype=x.dtype, device=x.device)
-    rc = L.lib().nf_rqs_fused_train_full_fwd(ptr(x), ptr(y), ptr(ld), ptr(cond), ptr(acts), ptr(blob), i32(mask_parity), i64(B),
-                                             i32(64), i32(128), i32(num_blocks), i32(8), f64(tail_bound), f64(min_bin_width),
-                                             f64(min_bin_height), f64(min_derivative), i32(acc), L.stream())
-    L.check(rc, "nf_rqs_fused_train_full_fwd")
-    return y, ld, cond, acts
+    return _train_fwd("nf_rqs_fused_train_full_fwd", x.contiguous(), None, blob, mask_parity, num_blocks,
+                      (tail_bound, min_bin_width, min_bin_height, min_derivative), logdet, acc)
+
+
+def _spline_grad_views(alloc, uw, uh, ud):
+    """(guw, guh, gud) shaped like the batch-shared spline parameters, as views of ONE buffer from `alloc` (torch.zeros / torch.empty)."""
+    nw, nh = uw.numel(), uh.numel()
+    gz = alloc(nw + nh + ud.numel(), dtype=uw.dtype, device=uw.device)
+    return gz[:nw].view_as(uw), gz[nw:nw + nh].view_as(uh), gz[nw + nh:].view_as(ud)
 
 
 def rqs_coupling_bwd_p24(x, grad_y, grad_logdet, cond24, uw, uh, ud, identity_idx, transform_idx, tail_bound=3.0,
@@ -761,15 +653,10 @@ def rqs_coupling_bwd_p24(x, grad_y, grad_logdet, cond24, uw, uh, ud, identity_id
     x, grad_y, grad_logdet = x.contiguous(), grad_y.contiguous(), grad_logdet.contiguous()
     gx = torch.empty_like(x)
     gcond = torch.empty_like(cond24)
-    nw, nh = uw.numel(), uh.numel()                        # one zero fill for the three atomically-accumulated outputs
-    gz = torch.zeros(nw + nh + ud.numel(), dtype=uw.dtype, device=uw.device)
-    guw, guh, gud = gz[:nw].view_as(uw), gz[nw:nw + nh].view_as(uh), gz[nw + nh:].view_as(ud)
-    rc = L.lib().nf_rqs_coupling_bwd_p24(ptr(x), ptr(grad_y), ptr(grad_logdet), ptr(cond24), ptr(uw), ptr(uh), ptr(ud),
-                                         ptr(identity_idx), i32(identity_idx.numel()), ptr(transform_idx),
-                                         i32(transform_idx.numel()), i64(B), i32(D), f64(tail_bound), f64(min_bin_width),
-                                         f64(min_bin_height), f64(min_derivative), f64(wh_div), ptr(gx), ptr(gcond), ptr(guw),
-                                         ptr(guh), ptr(gud), L.stream())
-    L.check(rc, "nf_rqs_coupling_bwd_p24")
+    guw, guh, gud = _spline_grad_views(torch.zeros, uw, uh, ud)     # one zero fill for the three atomically-accumulated outputs
+    L.call("nf_rqs_coupling_bwd_p24", ptr(x), ptr(grad_y), ptr(grad_logdet), ptr(cond24), ptr(uw), ptr(uh), ptr(ud),
+           ptr(identity_idx), identity_idx.numel(), ptr(transform_idx), transform_idx.numel(), B, D, tail_bound, min_bin_width,
+           min_bin_height, min_derivative, wh_div, ptr(gx), ptr(gcond), ptr(guw), ptr(guh), ptr(gud), L.stream())
     return gx, gcond, guw, guh, gud
 
 
@@ -783,20 +670,33 @@ def final_bwd(x, grad_y, grad_logdet, cond24, w_t, blob, uw, uh, ud, mask_parity
     gx = torch.empty_like(x)
     gcond = torch.empty_like(cond24)
     gh = torch.empty(B, 128, dtype=x.dtype, device=x.device)
-    lib = L.lib()
-    nparts = lib.nf_final_bwd_partials(i64(B))
+    nparts = L.query("nf_final_bwd_partials", B)
     part = torch.empty(max(nparts, 1) * 768, dtype=x.dtype, device=x.device)
-    gz = torch.empty(uw.numel() + uh.numel() + ud.numel(), dtype=uw.dtype, device=uw.device)
-    nw, nh = uw.numel(), uh.numel()
-    guw, guh, gud = gz[:nw].view_as(uw), gz[nw:nw + nh].view_as(uh), gz[nw + nh:].view_as(ud)
-    kw = (f64(tail_bound), f64(min_bin_width), f64(min_bin_height), f64(min_derivative))
-    rc = lib.nf_final_bwd(ptr(x), ptr(grad_y), ptr(grad_logdet), ptr(cond24), ptr(w_t), ptr(blob), ptr(gx), ptr(gcond), ptr(gh),
-                          ptr(part), i32(mask_parity), i64(B), i32(64), i32(128), i32(num_blocks), i32(8), *kw, L.stream())
-    L.check(rc, "nf_final_bwd")
-    rc = lib.nf_final_bwd_reduce(ptr(part), i32(nparts), ptr(uw.contiguous()), ptr(uh.contiguous()), ptr(ud.contiguous()), ptr(guw),
-                                 ptr(guh), ptr(gud), i32(8), *kw, L.stream())
-    L.check(rc, "nf_final_bwd_reduce")
+    guw, guh, gud = _spline_grad_views(torch.empty, uw, uh, ud)
+    kw = (tail_bound, min_bin_width, min_bin_height, min_derivative)
+    L.call("nf_final_bwd", ptr(x), ptr(grad_y), ptr(grad_logdet), ptr(cond24), ptr(w_t), ptr(blob), ptr(gx), ptr(gcond), ptr(gh),
+           ptr(part), mask_parity, B, 64, 128, num_blocks, 8, *kw, L.stream())
+    L.call("nf_final_bwd_reduce", ptr(part), nparts, ptr(uw.contiguous()), ptr(uh.contiguous()), ptr(ud.contiguous()), ptr(guw),
+           ptr(guh), ptr(gud), 8, *kw, L.stream())
     return gx, gcond, gh, guw, guh, gud
+
+
+def _train_bwd_operands(who, B, num_blocks, w_blocks, dest, more_keys, device):
+    """What coupling_train_bwd and pair_train_bwd (`who`) prepare alike: the gradient destinations `dest` validated (more_keys: the
+    pair's LU destinations), then (scratch, the contiguous block weights -- to be kept alive through the call --, their pointer array,
+    the pointer array of dest["blocks"])."""
+    n = L.query("nf_%s_scratch_floats" % who, B, num_blocks)
+    if n <= 0:
+        raise NotImplementedError("%s: batch a multiple of 64, 1 <= num_blocks <= 5" % who)
+    tensors = [dest[k] for k in ("w0", "b0", "wf", "bf", "uw", "uh", "ud") + tuple(more_keys)] + list(dest["blocks"])
+    if len(w_blocks) != 2 * num_blocks or len(dest["blocks"]) != 4 * num_blocks:
+        raise ValueError("%s: 2 weights and 4 gradient destinations per residual block" % who)
+    L.require_device(*tensors)
+    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
+        raise ValueError("%s: gradient destinations must be contiguous float32" % who)
+    scratch = torch.empty(n, dtype=torch.float32, device=device)
+    wb = [w.contiguous() for w in w_blocks]
+    return scratch, wb, _ptr_array(wb), _ptr_array(dest["blocks"])
 
 
 def pair_train_bwd(x_in, xlu, grad_y, grad_logdet, cond24, acts, w_t, blob, wfull_t, w_blocks, uw, uh, ud, col_map, n_cols, mask_parity,
@@ -812,39 +712,23 @@ def pair_train_bwd(x_in, xlu, grad_y, grad_logdet, cond24, acts, w_t, blob, wful
                      *w_blocks)
     B = x_in.shape[0]
     x_in, xlu, grad_y, grad_logdet = x_in.contiguous(), xlu.contiguous(), grad_y.contiguous(), grad_logdet.contiguous()
-    lib = L.lib()
-    lib.nf_pair_train_bwd_scratch_floats.restype = C.c_int64
-    n = int(lib.nf_pair_train_bwd_scratch_floats(i64(B), i32(num_blocks)))
-    if n <= 0:
-        raise NotImplementedError("pair_train_bwd: batch a multiple of 64, 1 <= num_blocks <= 5")
-    keys = ("w0", "b0", "wf", "bf", "uw", "uh", "ud", "lower", "upper", "udiag", "lbias")
-    tensors = [dest[k] for k in keys] + list(dest["blocks"])
-    if len(w_blocks) != 2 * num_blocks or len(dest["blocks"]) != 4 * num_blocks:
-        raise ValueError("pair_train_bwd: 2 weights and 4 gradient destinations per residual block")
-    L.require_device(*tensors)
-    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
-        raise ValueError("pair_train_bwd: gradient destinations must be contiguous float32")
-    scratch = torch.empty(n, dtype=torch.float32, device=x_in.device)
+    scratch, wb, wp, gp = _train_bwd_operands("pair_train_bwd", B, num_blocks, w_blocks, dest, ("lower", "upper", "udiag", "lbias"),
+                                              x_in.device)
     gx = torch.empty_like(x_in)
-    wb = [w.contiguous() for w in w_blocks]
-    wp = (C.c_void_p * len(wb))(*[w.data_ptr() for w in wb])
-    gp = (C.c_void_p * len(dest["blocks"]))(*[t.data_ptr() for t in dest["blocks"]])
     uw_, uh_, ud_, Lm_, Um_, udiag_ = uw.contiguous(), uh.contiguous(), ud.contiguous(), Lm.contiguous(), Um.contiguous(), udiag.contiguous()
-    args = (ptr(x_in), ptr(xlu), ptr(grad_y), ptr(grad_logdet), ptr(cond24), ptr(acts), ptr(w_t), ptr(blob),
-            ptr(wfull_t), wp, ptr(uw_), ptr(uh_), ptr(ud_), ptr(col_map),
-            i32(int(n_cols)), ptr(Wd), ptr(Lm_), ptr(Um_), ptr(perm), ptr(udiag_),
-            f64(lu_eps), ptr(gx), ptr(dest["lower"]), ptr(dest["upper"]), ptr(dest["udiag"]), ptr(dest["lbias"]),
-            ptr(dest["w0"]), ptr(dest["b0"]), ptr(dest["wf"]), ptr(dest["bf"]), ptr(dest["uw"]), ptr(dest["uh"]),
-            ptr(dest["ud"]), gp, ptr(scratch), i32(mask_parity), i64(B), i32(64), i32(128), i32(num_blocks), i32(8),
-            f64(tail_bound), f64(min_bin_width), f64(min_bin_height), f64(min_derivative))
+    args = (ptr(x_in), ptr(xlu), ptr(grad_y), ptr(grad_logdet), ptr(cond24), ptr(acts), ptr(w_t), ptr(blob), ptr(wfull_t), wp, ptr(uw_),
+            ptr(uh_), ptr(ud_), ptr(col_map), int(n_cols), ptr(Wd), ptr(Lm_), ptr(Um_), ptr(perm), ptr(udiag_), lu_eps, ptr(gx),
+            ptr(dest["lower"]), ptr(dest["upper"]), ptr(dest["udiag"]), ptr(dest["lbias"]), ptr(dest["w0"]), ptr(dest["b0"]),
+            ptr(dest["wf"]), ptr(dest["bf"]), ptr(dest["uw"]), ptr(dest["uh"]), ptr(dest["ud"]), gp, ptr(scratch), mask_parity, B, 64, 128,
+            num_blocks, 8, tail_bound, min_bin_width, min_bin_height, min_derivative)
     if side is None:
-        L.check(lib.nf_pair_train_bwd(*args, L.stream()), "nf_pair_train_bwd")
+        L.call("nf_pair_train_bwd", *args, L.stream())
         return gx
     tail = C.create_string_buffer(2048)                       # NF_PAIR_TAIL_BYTES
-    L.check(lib.nf_pair_train_bwd_head(*args, tail, L.stream()), "nf_pair_train_bwd_head")
+    L.call("nf_pair_train_bwd_head", *args, tail, L.stream())
     cur = torch.cuda.current_stream()
     side.wait_stream(cur)                                     # fork: an event recorded here, behind the five launches
-    L.check(lib.nf_pair_train_bwd_tail(tail, C.c_void_p(side.cuda_stream)), "nf_pair_train_bwd_tail")
+    L.call("nf_pair_train_bwd_tail", tail, C.c_void_p(side.cuda_stream))
     # what the side stream reads or writes must not go back to the allocator (or be rewritten on the current stream) before it is done
     # (parameters, the prepacked factors and the flat gradient buffer outlive the step; the caller's join comes before they change)
     for t in (scratch, grad_logdet):
@@ -854,8 +738,7 @@ def pair_train_bwd(x_in, xlu, grad_y, grad_logdet, cond24, acts, w_t, blob, wful
 
 def lu_pack_train_multi(table, n_layers, num_blocks, eps, D=64):
     """The LU stage of n training blobs + the composed matrices for the backward in one launch (nf_lu_pack_train_multi)."""
-    L.check(L.lib().nf_lu_pack_train_multi(ptr(table), i32(n_layers), i32(num_blocks), i32(D), f64(eps), L.stream()),
-            "nf_lu_pack_train_multi")
+    L.call("nf_lu_pack_train_multi", ptr(table), n_layers, num_blocks, D, eps, L.stream())
 
 
 def rqs_fused_train_pair_fwd(x, blob, mask_parity, num_blocks, tail_bound=3.0, min_bin_width=1e-3, min_bin_height=1e-3,
@@ -864,19 +747,9 @@ def rqs_fused_train_pair_fwd(x, blob, mask_parity, num_blocks, tail_bound=3.0, m
     launch; xlu (B, 64) = the LU's output (the coupling's input), the rest as rqs_fused_train_full_fwd."""
     L.require_device(x, blob)
     x = x.contiguous()
-    B = x.shape[0]
-    y, xlu = torch.empty_like(x), torch.empty_like(x)
-    if logdet is None:
-        ld, acc = torch.empty(B, dtype=x.dtype, device=x.device), L.LD_WRITE
-    else:
-        ld, acc = logdet, (L.LD_ADD if acc is None else acc)
-    cond = torch.empty(B, 32, 24, dtype=x.dtype, device=x.device)
-    acts = torch.empty(2 * num_blocks + 1, B, 128, dtype=x.dtype, device=x.device)
-    rc = L.lib().nf_rqs_fused_train_pair_fwd(ptr(x), ptr(xlu), ptr(y), ptr(ld), ptr(cond), ptr(acts), ptr(blob), i32(mask_parity),
-                                             i64(B), i32(64), i32(128), i32(num_blocks), i32(8), f64(tail_bound), f64(min_bin_width),
-                                             f64(min_bin_height), f64(min_derivative), i32(acc), L.stream())
-    L.check(rc, "nf_rqs_fused_train_pair_fwd")
-    return xlu, y, ld, cond, acts
+    xlu = torch.empty_like(x)
+    return (xlu,) + _train_fwd("nf_rqs_fused_train_pair_fwd", x, xlu, blob, mask_parity, num_blocks,
+                               (tail_bound, min_bin_width, min_bin_height, min_derivative), logdet, acc)
 
 
 def lu_bwd_composed(g, x, Wd, db_out=None):
@@ -884,9 +757,7 @@ def lu_bwd_composed(g, x, Wd, db_out=None):
     L.require_device(g, x, Wd, db_out)
     g, x, Wd = g.contiguous(), x.contiguous(), Wd.contiguous()
     B, D = g.shape
-    lib = L.lib()
-    lib.nf_lu_bwd_composed_scratch_floats.restype = C.c_int64
-    n = int(lib.nf_lu_bwd_composed_scratch_floats(i64(B)))
+    n = L.query("nf_lu_bwd_composed_scratch_floats", B)
     if n <= 0 or D != 64 or g.dtype != torch.float32:
         raise NotImplementedError("lu_bwd_composed: float32, D = 64, batch a multiple of 64")
     scratch = torch.empty(n, dtype=torch.float32, device=g.device)
@@ -896,8 +767,7 @@ def lu_bwd_composed(g, x, Wd, db_out=None):
     elif db_out.numel() != D or db_out.dtype != torch.float32 or not db_out.is_contiguous():
         raise ValueError("lu_bwd_composed: db_out = a contiguous float32 (D) tensor")
     gx = torch.empty_like(g)
-    rc = lib.nf_lu_bwd_composed(ptr(g), ptr(x), ptr(Wd), ptr(gx), ptr(dWd), ptr(db_out), ptr(scratch), i64(B), i32(D), L.stream())
-    L.check(rc, "nf_lu_bwd_composed")
+    L.call("nf_lu_bwd_composed", ptr(g), ptr(x), ptr(Wd), ptr(gx), ptr(dWd), ptr(db_out), ptr(scratch), B, D, L.stream())
     return gx, dWd, db_out
 
 
@@ -917,10 +787,9 @@ def lu_param_grads_composed(dWd, Lm, Um, perm, gld, unconstrained_upper_diag, n_
         g_lower = torch.empty(n_tri, dtype=torch.float32, device=dev)
         g_upper = torch.empty(n_tri, dtype=torch.float32, device=dev)
         g_udiag = torch.empty(D, dtype=torch.float32, device=dev)
-    rc = L.lib().nf_lu_param_grads_composed(ptr(dWd.contiguous()), ptr(Lm.contiguous()), ptr(Um.contiguous()), ptr(perm), ptr(gld),
-                                            i64(0 if gld is None else gld.numel()), ptr(unconstrained_upper_diag.contiguous()),
-                                            f64(eps), ptr(g_lower), ptr(g_upper), ptr(g_udiag), i32(D), L.stream())
-    L.check(rc, "nf_lu_param_grads_composed")
+    L.call("nf_lu_param_grads_composed", ptr(dWd.contiguous()), ptr(Lm.contiguous()), ptr(Um.contiguous()), ptr(perm), ptr(gld),
+           0 if gld is None else gld.numel(), ptr(unconstrained_upper_diag.contiguous()), eps, ptr(g_lower), ptr(g_upper),
+           ptr(g_udiag), D, L.stream())
     return g_lower, g_upper, g_udiag
 
 
@@ -933,66 +802,32 @@ def coupling_train_bwd(x, grad_y, grad_logdet, cond24, acts, w_t, blob, wfull_t,
     L.require_device(x, grad_y, grad_logdet, cond24, acts, w_t, blob, wfull_t, uw, uh, ud, col_map, *w_blocks)
     B = x.shape[0]
     x, grad_y, grad_logdet = x.contiguous(), grad_y.contiguous(), grad_logdet.contiguous()
-    lib = L.lib()
-    lib.nf_coupling_train_bwd_scratch_floats.restype = C.c_int64
-    n = int(lib.nf_coupling_train_bwd_scratch_floats(i64(B), i32(num_blocks)))
-    if n <= 0:
-        raise NotImplementedError("coupling_train_bwd: batch a multiple of 64, 1 <= num_blocks <= 5")
-    tensors = [dest[k] for k in ("w0", "b0", "wf", "bf", "uw", "uh", "ud")] + list(dest["blocks"])
-    if len(w_blocks) != 2 * num_blocks or len(dest["blocks"]) != 4 * num_blocks:
-        raise ValueError("coupling_train_bwd: 2 weights and 4 gradient destinations per residual block")
-    L.require_device(*tensors)
-    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
-        raise ValueError("coupling_train_bwd: gradient destinations must be contiguous float32")
-    scratch = torch.empty(n, dtype=torch.float32, device=x.device)
+    scratch, wb, wp, gp = _train_bwd_operands("coupling_train_bwd", B, num_blocks, w_blocks, dest, (), x.device)
     gx = torch.empty_like(x)
-    wb = [w.contiguous() for w in w_blocks]
-    wp = (C.c_void_p * len(wb))(*[w.data_ptr() for w in wb])
-    gp = (C.c_void_p * len(dest["blocks"]))(*[t.data_ptr() for t in dest["blocks"]])
-    rc = lib.nf_coupling_train_bwd(ptr(x), ptr(grad_y), ptr(grad_logdet), ptr(cond24), ptr(acts), ptr(w_t), ptr(blob), ptr(wfull_t), wp,
-                                   ptr(uw.contiguous()), ptr(uh.contiguous()), ptr(ud.contiguous()), ptr(col_map), i32(int(n_cols)),
-                                   ptr(gx), ptr(dest["w0"]), ptr(dest["b0"]), ptr(dest["wf"]), ptr(dest["bf"]), ptr(dest["uw"]),
-                                   ptr(dest["uh"]), ptr(dest["ud"]), gp, ptr(scratch), i32(mask_parity), i64(B), i32(64), i32(128),
-                                   i32(num_blocks), i32(8), f64(tail_bound), f64(min_bin_width), f64(min_bin_height),
-                                   f64(min_derivative), L.stream())
-    L.check(rc, "nf_coupling_train_bwd")
+    L.call("nf_coupling_train_bwd", ptr(x), ptr(grad_y), ptr(grad_logdet), ptr(cond24), ptr(acts), ptr(w_t), ptr(blob),
+           ptr(wfull_t), wp, ptr(uw.contiguous()), ptr(uh.contiguous()), ptr(ud.contiguous()), ptr(col_map), int(n_cols), ptr(gx),
+           ptr(dest["w0"]), ptr(dest["b0"]), ptr(dest["wf"]), ptr(dest["bf"]), ptr(dest["uw"]), ptr(dest["uh"]), ptr(dest["ud"]),
+           gp, ptr(scratch), mask_parity, B, 64, 128, num_blocks, 8, tail_bound, min_bin_width, min_bin_height, min_derivative,
+           L.stream())
     return gx
 
 
 # ---- bf16x3 (error-compensated split-bf16 MFMA) variant of the fused layer ----------------------------------------
 def rqs_fused_x3_pack(f32_blob, num_blocks, has_lu, nI=32, nT=32, hidden=128, K=8):
     """Derive the split-bf16 weight blob from an rqs_fused_pack blob of the same layer (nf_rqs_fused_x3_pack)."""
-    import ctypes
     L.require_device(f32_blob)
-    lib = L.lib()
-    lib.nf_rqs_fused_x3_pack_size.restype = ctypes.c_int64
-    size = lib.nf_rqs_fused_x3_pack_size(i32(nI), i32(nT), i32(hidden), i32(num_blocks), i32(K))
+    size = L.query("nf_rqs_fused_x3_pack_size", nI, nT, hidden, num_blocks, K)
     if size <= 0:
         raise NotImplementedError("nf_rqs_fused_x3: shape not supported")
     blob = torch.zeros((size + 3) // 4, dtype=torch.float32, device=f32_blob.device)
-    rc = lib.nf_rqs_fused_x3_pack(ptr(blob), ptr(f32_blob), i32(num_blocks), i32(int(has_lu)), L.stream())
-    L.check(rc, "nf_rqs_fused_x3_pack")
+    L.call("nf_rqs_fused_x3_pack", ptr(blob), ptr(f32_blob), num_blocks, int(has_lu), L.stream())
     return blob
 
 
 def rqs_fused_x3(x, blob, mask_parity, hidden, num_blocks, K, direction, logdet=None, acc=None, tail_bound=3.0,
                  min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3, fuse_lu=False):
-    L.require_device(x, blob)
-    if x.dtype != torch.float32:
-        raise TypeError("nf_rqs_fused_x3 is fp32 only")
-    x = x.contiguous()
-    B, D = x.shape
-    y = torch.empty_like(x)
-    if logdet is None:
-        logdet = torch.empty(B, dtype=x.dtype, device=x.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_rqs_fused_x3(ptr(x), ptr(y), ptr(logdet), ptr(blob), i32(mask_parity), i32(int(fuse_lu)), i64(B),
-                                 i32(D), i32(hidden), i32(num_blocks), i32(K), f64(tail_bound), f64(min_bin_width),
-                                 f64(min_bin_height), f64(min_derivative), i32(direction), i32(acc), L.stream())
-    L.check(rc, "nf_rqs_fused_x3")
-    return y, logdet
+    return _rqs_fused_launch("nf_rqs_fused_x3", x, blob, mask_parity, hidden, num_blocks, K, direction, logdet, acc,
+                             (tail_bound, min_bin_width, min_bin_height, min_derivative), fuse_lu)
 
 
 def maf_affine(x, params, direction, logdet=None, acc=None, want_logdet=True):
@@ -1002,14 +837,8 @@ def maf_affine(x, params, direction, logdet=None, acc=None, want_logdet=True):
     params = params.contiguous()
     B, D = x.shape
     y = torch.empty_like(x)
-    if logdet is None and want_logdet:
-        logdet = torch.empty(B, dtype=x.dtype, device=x.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_maf_affine(ptr(x), ptr(params), ptr(y), ptr(logdet), i64(B), i32(D), i32(direction), i32(acc or 0),
-                               i32(L.dtype_code(x)), L.stream())
-    L.check(rc, "nf_maf_affine")
+    logdet, acc = _ld_buffer(logdet, acc, B, x, want=want_logdet)
+    L.call("nf_maf_affine", ptr(x), ptr(params), ptr(y), ptr(logdet), B, D, direction, acc or 0, L.dtype_code(x), L.stream())
     return y, logdet
 
 
@@ -1029,9 +858,8 @@ def conv3x3_gather(x, flip=False, ld=None):
     else:
         Rp = (R + 63) // 64 * 64
         col = (torch.empty if Rp == R else torch.zeros)(Rp, ld, dtype=x.dtype, device=x.device)
-    rc = L.lib().nf_conv3x3_gather(ptr_any(x), ptr(col), i64(B), i32(C), i32(H), i32(W), i32(col.shape[1]), i32(1 if flip else 0),
-                                   i64(x.stride(0) if B > 1 else C * H * W), L.stream())
-    L.check(rc, "nf_conv3x3_gather")
+    L.call("nf_conv3x3_gather", ptr_any(x), ptr(col), B, C, H, W, col.shape[1], 1 if flip else 0,
+           x.stride(0) if B > 1 else C * H * W, L.stream())
     return col
 
 
@@ -1044,9 +872,7 @@ def conv3x3_gather_sum(P, bias, shape, flip=False):
     if P.dtype != torch.float32 or P.dim() != 2 or P.shape[0] < B * H * W or P.shape[1] < 9 * C:
         raise ValueError("conv3x3_gather_sum: P must be (>= B H W, >= 9 C) float32")
     out = torch.empty(B, C, H, W, dtype=P.dtype, device=P.device)
-    rc = L.lib().nf_conv3x3_gather_sum(ptr(P), ptr(None if bias is None else bias.contiguous()), ptr(out), i64(B), i32(C), i32(H),
-                                       i32(W), i32(P.shape[1]), i32(1 if flip else 0), L.stream())
-    L.check(rc, "nf_conv3x3_gather_sum")
+    L.call("nf_conv3x3_gather_sum", ptr(P), _cptr(bias), ptr(out), B, C, H, W, P.shape[1], 1 if flip else 0, L.stream())
     return out
 
 
@@ -1058,7 +884,7 @@ def channel_sum(g):
         raise ValueError("channel_sum: a float32 (B, C, H, W) tensor")
     B, C, H, W = g.shape
     out = torch.empty(C, dtype=g.dtype, device=g.device)
-    L.check(L.lib().nf_channel_sum(ptr(g), ptr(out), i64(B), i32(C), i64(H * W), L.stream()), "nf_channel_sum")
+    L.call("nf_channel_sum", ptr(g), ptr(out), B, C, H * W, L.stream())
     return out
 
 
@@ -1072,9 +898,8 @@ def maf_affine_bwd(x, params, gy, gld, direction):
     gparams = torch.empty_like(params)
     gy = None if gy is None else gy.contiguous()
     gld = None if gld is None else gld.contiguous()
-    rc = L.lib().nf_maf_affine_bwd(ptr(x), ptr(params), ptr(gy), ptr(gld), ptr(gx), ptr(gparams), i64(B), i32(D), i32(direction),
-                                   i32(L.dtype_code(x)), L.stream())
-    L.check(rc, "nf_maf_affine_bwd")
+    L.call("nf_maf_affine_bwd", ptr(x), ptr(params), ptr(gy), ptr(gld), ptr(gx), ptr(gparams), B, D, direction, L.dtype_code(x),
+           L.stream())
     return gx, gparams
 
 
@@ -1082,74 +907,32 @@ def maf_implicit_sweep(x, params, gx, gld, gxm, v, gp, changed):
     """nf_maf_implicit_sweep: v, gp updated in place; `changed` (int32 scalar tensor) set when v moved."""
     L.require_device(x, params, gx, gld, gxm, v, gp, changed)
     B, D = x.shape
-    rc = L.lib().nf_maf_implicit_sweep(ptr(x), ptr(params), ptr(gx), ptr(gld), ptr(gxm), ptr(v), ptr(gp), ptr(changed), i64(B), i32(D),
-                                       i32(L.dtype_code(x)), L.stream())
-    L.check(rc, "nf_maf_implicit_sweep")
+    L.call("nf_maf_implicit_sweep", ptr(x), ptr(params), ptr(gx), ptr(gld), ptr(gxm), ptr(v), ptr(gp), ptr(changed), B, D,
+           L.dtype_code(x), L.stream())
 
 
 def rqs_fused_chain(x, blobs, parities, hidden, num_blocks, K, direction, logdet=None, acc=None, tail_bound=3.0,
                     min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3, fuse_lu=True, live_d=None):
     """Up to 64 fused layers of identical shape in ONE persistent launch (nf_rqs_fused_chain).  `blobs` / `parities`
     are in processing order."""
-    import ctypes
-    L.require_device(x, *blobs)
-    if x.dtype != torch.float32:
-        raise TypeError("nf_rqs_fused_chain is fp32 only")
-    x = x.contiguous()
-    B, D = x.shape
-    y = torch.empty_like(x)
-    if logdet is None:
-        logdet = torch.empty(B, dtype=x.dtype, device=x.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    n = len(blobs)
-    bp = (ctypes.c_void_p * n)(*[b.data_ptr() for b in blobs])
-    pp = (ctypes.c_int * n)(*[int(v) for v in parities])
-    if D != 64:
-        raise ValueError("nf_rqs_fused_chain: rows of 64 columns (narrower layers: padded by the caller, live_d = columns in use)")
-    rc = L.lib().nf_rqs_fused_chain(ptr(x), ptr(y), ptr(logdet), bp, pp, i32(n), i32(int(fuse_lu)), i64(B),
-                                    i32(D if live_d is None else live_d),
-                                    i32(hidden), i32(num_blocks), i32(K), f64(tail_bound), f64(min_bin_width),
-                                    f64(min_bin_height), f64(min_derivative), i32(direction), i32(acc), L.stream())
-    L.check(rc, "nf_rqs_fused_chain")
-    return y, logdet
+    return _rqs_fused_launch("nf_rqs_fused_chain", x, blobs, parities, hidden, num_blocks, K, direction, logdet,
+                             acc, (tail_bound, min_bin_width, min_bin_height, min_derivative), fuse_lu, live_d, padded_rows=True)
 
 
 def rqs_fused_x3_chain(x, blobs, parities, hidden, num_blocks, K, direction, logdet=None, acc=None, tail_bound=3.0,
                        min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3, fuse_lu=True, live_d=None):
     """Up to 64 fused layers of identical shape on the split-bf16 matrix path in ONE persistent launch
     (nf_rqs_fused_x3_chain).  `blobs` (rqs_fused_x3_pack) / `parities` are in processing order."""
-    import ctypes
-    L.require_device(x, *blobs)
-    if x.dtype != torch.float32:
-        raise TypeError("nf_rqs_fused_x3_chain is fp32 only")
-    x = x.contiguous()
-    B, D = x.shape
-    y = torch.empty_like(x)
-    if logdet is None:
-        logdet = torch.empty(B, dtype=x.dtype, device=x.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    n = len(blobs)
-    bp = (ctypes.c_void_p * n)(*[b.data_ptr() for b in blobs])
-    pp = (ctypes.c_int * n)(*[int(v) for v in parities])
-    rc = L.lib().nf_rqs_fused_x3_chain(ptr(x), ptr(y), ptr(logdet), bp, pp, i32(n), i32(int(fuse_lu)), i64(B), i32(D),
-                                       i32(hidden), i32(num_blocks), i32(K), f64(tail_bound), f64(min_bin_width),
-                                       f64(min_bin_height), f64(min_derivative), i32(direction), i32(acc), L.stream())
-    L.check(rc, "nf_rqs_fused_x3_chain")
-    return y, logdet
+    return _rqs_fused_launch("nf_rqs_fused_x3_chain", x, blobs, parities, hidden, num_blocks, K, direction,
+                             logdet, acc, (tail_bound, min_bin_width, min_bin_height, min_derivative), fuse_lu)
 
 
 def nsf_wide_tables(uw, uh, ud, K, tail_bound, min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3):
     """Knot tables (n_identity, 3 (K + 1)) of the batch-shared spline for nf_nsf_wide (nsf/coupling.py:170-259)."""
     L.require_device(uw, uh, ud)
     tabs = torch.empty(uw.shape[0], 3 * (K + 1), dtype=torch.float32, device=uw.device)
-    rc = L.lib().nf_nsf_wide_tables(ptr(uw.contiguous()), ptr(uh.contiguous()), ptr(ud.contiguous()), ptr(tabs), i32(uw.shape[0]),
-                                    i32(K), f64(float(tail_bound)), f64(min_bin_width), f64(min_bin_height), f64(min_derivative),
-                                    L.stream())
-    L.check(rc, "nf_nsf_wide_tables")
+    L.call("nf_nsf_wide_tables", ptr(uw.contiguous()), ptr(uh.contiguous()), ptr(ud.contiguous()), ptr(tabs), uw.shape[0], K,
+           float(tail_bound), min_bin_width, min_bin_height, min_derivative, L.stream())
     return tabs
 
 
@@ -1164,16 +947,19 @@ def nsf_wide(x, blob, table, tabs, hidden_padded, direction, tail_bound, min_bin
     B, D = x.shape
     x = x.contiguous()
     y = torch.empty_like(x)
-    if logdet is None:
-        logdet = torch.empty(B, dtype=x.dtype, device=x.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_nsf_wide_k(ptr(x), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(tabs), ptr(lu_logdet), i64(B), i32(D), i32(hidden_padded),
-                               i32(int(K)), i32(direction), i32(acc), f64(float(tail_bound)), f64(min_bin_width), f64(min_bin_height),
-                               f64(min_derivative), L.stream())
-    L.check(rc, "nf_nsf_wide_k")
+    logdet, acc = _ld_buffer(logdet, acc, B, x)
+    L.call("nf_nsf_wide_k", ptr(x), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(tabs), ptr(lu_logdet), B, D, hidden_padded,
+           int(K), direction, acc, float(tail_bound), min_bin_width, min_bin_height, min_derivative, L.stream())
     return y, logdet
+
+
+def _context_rows(context):
+    """(context, its row stride) as the conditional kernels read a (B, C) context: the row stride is passed as it is when the inner
+    stride is 1 (0 for context.expand(B, C)), otherwise the context is made contiguous."""
+    B, C_ = context.shape
+    if context.stride(1) != 1 and C_ > 1:
+        context = context.contiguous()
+    return context, context.stride(0) if B > 1 else C_
 
 
 def nsf_wide_ctx(x, context, blob, table, tabs, hidden_padded, direction, tail_bound, min_bin_width=1e-3, min_bin_height=1e-3,
@@ -1191,20 +977,12 @@ def nsf_wide_ctx(x, context, blob, table, tabs, hidden_padded, direction, tail_b
     C_ = context.shape[1]
     if table_host is not None and (int(table_host[25]) != C_ or int(table_host[26]) != (C_ + 31) // 32 * 32):
         raise ValueError("nsf_wide_ctx: the pack is for %d context features, the context has %d" % (int(table_host[25]), C_))
-    if context.stride(1) != 1 and C_ > 1:
-        context = context.contiguous()
-    ldc = context.stride(0) if B > 1 else C_
+    context, ldc = _context_rows(context)
     x = x.contiguous()
     y = torch.empty_like(x)
-    if logdet is None:
-        logdet = torch.empty(B, dtype=x.dtype, device=x.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_nsf_wide_ctx(ptr(x), ptr_any(context), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(tabs), i64(B), i64(ldc),
-                                 i32(D), i32(C_), i32(hidden_padded), i32(int(K)), i32(direction), i32(acc), f64(float(tail_bound)),
-                                 f64(min_bin_width), f64(min_bin_height), f64(min_derivative), L.stream())
-    L.check(rc, "nf_nsf_wide_ctx")
+    logdet, acc = _ld_buffer(logdet, acc, B, x)
+    L.call("nf_nsf_wide_ctx", ptr(x), ptr_any(context), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(tabs), B, ldc, D, C_,
+           hidden_padded, int(K), direction, acc, float(tail_bound), min_bin_width, min_bin_height, min_derivative, L.stream())
     return y, logdet
 
 
@@ -1219,18 +997,13 @@ def resnet_ctx_forward_train(x, context, blob, table, st):
     if x.dim() != 2 or x.shape[1] != st["nI"] or context.dim() != 2 or tuple(context.shape) != (B, st["C"]):
         raise ValueError("resnet_ctx_forward_train: x (%d, %d) and context (%d, %d) expected, got %s %s"
                          % (B, st["nI"], B, st["C"], tuple(x.shape), tuple(context.shape)))
-    if context.stride(1) != 1 and st["C"] > 1:
-        context = context.contiguous()
-    ldc = context.stride(0) if B > 1 else st["C"]
+    context, ldc = _context_rows(context)
     x = x.contiguous()
     out = torch.empty(B, st["O"], dtype=x.dtype, device=x.device)
-    lib = L.lib()
-    n = lib.nf_resnet_ctx_save_floats(i64(B), i32(st["nI"]), i32(st["C"]), i32(st["H"]), i32(st["NB"]))
-    L.check(n if n < 0 else 0, "nf_resnet_ctx_save_floats")
-    save = torch.empty(max(int(n), 1), dtype=x.dtype, device=x.device)
-    rc = lib.nf_resnet_ctx_forward_train(ptr(x), i64(st["nI"]), ptr_any(context), i64(ldc), ptr(out), ptr(save), ptr(blob), ptr(table),
-                                         i64(B), i32(st["nI"]), i32(st["C"]), i32(st["H"]), i32(st["O"]), i32(st["NB"]), L.stream())
-    L.check(rc, "nf_resnet_ctx_forward_train")
+    n = L.size("nf_resnet_ctx_save_floats", B, st["nI"], st["C"], st["H"], st["NB"])
+    save = torch.empty(max(n, 1), dtype=x.dtype, device=x.device)
+    L.call("nf_resnet_ctx_forward_train", ptr(x), st["nI"], ptr_any(context), ldc, ptr(out), ptr(save), ptr(blob), ptr(table), B,
+           st["nI"], st["C"], st["H"], st["O"], st["NB"], L.stream())
     return out, save
 
 
@@ -1240,15 +1013,12 @@ def resnet_ctx_backward(g_out, save, blob, table, st):
     L.require_device(g_out, save, blob, table)
     B = g_out.shape[0]
     g_out = g_out.contiguous()
-    lib = L.lib()
-    n = lib.nf_resnet_ctx_grad_floats(i64(B), i32(st["H"]), i32(st["NB"]))
-    L.check(n if n < 0 else 0, "nf_resnet_ctx_grad_floats")
-    G = torch.empty(max(int(n), 1), dtype=g_out.dtype, device=g_out.device)
+    n = L.size("nf_resnet_ctx_grad_floats", B, st["H"], st["NB"])
+    G = torch.empty(max(n, 1), dtype=g_out.dtype, device=g_out.device)
     gx = torch.empty(B, st["nI"], dtype=g_out.dtype, device=g_out.device)
     gc = torch.empty(B, st["C"], dtype=g_out.dtype, device=g_out.device)
-    rc = lib.nf_resnet_ctx_backward(ptr(g_out), ptr(save), ptr(G), ptr(gx), ptr(gc), ptr(blob), ptr(table), i64(B), i32(st["nI"]),
-                                    i32(st["C"]), i32(st["H"]), i32(st["O"]), i32(st["NB"]), L.stream())
-    L.check(rc, "nf_resnet_ctx_backward")
+    L.call("nf_resnet_ctx_backward", ptr(g_out), ptr(save), ptr(G), ptr(gx), ptr(gc), ptr(blob), ptr(table), B, st["nI"], st["C"],
+           st["H"], st["O"], st["NB"], L.stream())
     return gx, gc, G
 
 
@@ -1260,15 +1030,12 @@ def resnet_ctx_wgrad(g_out, save, G, table, jobs, st):
     g_out = g_out.contiguous()
     if B == 0:                  # (nothing to reduce: the kernels launch nothing, the gradients are zero)
         return torch.zeros(st["nflat"], dtype=g_out.dtype, device=g_out.device)
-    lib = L.lib()
     njobs = int(jobs.shape[0])
-    n = lib.nf_resnet_ctx_scratch_floats(i64(B), i32(njobs))
-    L.check(n if n < 0 else 0, "nf_resnet_ctx_scratch_floats")
-    part = torch.empty(max(int(n), 1), dtype=g_out.dtype, device=g_out.device)
+    n = L.size("nf_resnet_ctx_scratch_floats", B, njobs)
+    part = torch.empty(max(n, 1), dtype=g_out.dtype, device=g_out.device)
     grads = torch.empty(st["nflat"], dtype=g_out.dtype, device=g_out.device)
-    rc = lib.nf_resnet_ctx_wgrad(ptr(g_out), ptr(save), ptr(G), ptr(grads), ptr(part), ptr(jobs), i32(njobs), ptr(table), i64(B),
-                                 i32(st["H"]), i32(st["NB"]), L.stream())
-    L.check(rc, "nf_resnet_ctx_wgrad")
+    L.call("nf_resnet_ctx_wgrad", ptr(g_out), ptr(save), ptr(G), ptr(grads), ptr(part), ptr(jobs), njobs, ptr(table), B, st["H"],
+           st["NB"], L.stream())
     return grads
 
 
@@ -1281,14 +1048,8 @@ def made_forward_affine(x, blob, table, hidden_padded, logdet=None, acc=None):
     B, D = x.shape
     x = x.contiguous()
     y = torch.empty_like(x)
-    if logdet is None:
-        logdet = torch.empty(B, dtype=x.dtype, device=x.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_made_forward_affine(ptr(x), ptr(y), ptr(logdet), ptr(blob), ptr(table), i64(B), i32(D), i32(hidden_padded),
-                                        i32(acc), L.stream())
-    L.check(rc, "nf_made_forward_affine")
+    logdet, acc = _ld_buffer(logdet, acc, B, x)
+    L.call("nf_made_forward_affine", ptr(x), ptr(y), ptr(logdet), ptr(blob), ptr(table), B, D, hidden_padded, acc, L.stream())
     return y, logdet
 
 
@@ -1302,15 +1063,9 @@ def made_forward_spline(x, blob, table, hidden_padded, tail_bound, min_bin_width
     B, D = x.shape
     x = x.contiguous()
     y = torch.empty_like(x)
-    if logdet is None:
-        logdet = torch.empty(B, dtype=x.dtype, device=x.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_made_forward_spline(ptr(x), ptr(y), ptr(logdet), ptr(blob), ptr(table), i64(B), i32(D), i32(hidden_padded),
-                                        i32(acc), f64(float(tail_bound)), f64(min_bin_width), f64(min_bin_height),
-                                        f64(min_derivative), L.stream())
-    L.check(rc, "nf_made_forward_spline")
+    logdet, acc = _ld_buffer(logdet, acc, B, x)
+    L.call("nf_made_forward_spline", ptr(x), ptr(y), ptr(logdet), ptr(blob), ptr(table), B, D, hidden_padded, acc,
+           float(tail_bound), min_bin_width, min_bin_height, min_derivative, L.stream())
     return y, logdet
 
 
@@ -1322,9 +1077,7 @@ def made_forward(x, blob, table, hidden_padded, mult):
     B, D = x.shape
     x = x.contiguous()
     params = torch.empty(B, mult * D, dtype=x.dtype, device=x.device)
-    rc = L.lib().nf_made_forward(ptr(x), ptr(params), ptr(blob), ptr(table), i64(B), i32(D), i32(hidden_padded), i32(mult),
-                                 L.stream())
-    L.check(rc, "nf_made_forward")
+    L.call("nf_made_forward", ptr(x), ptr(params), ptr(blob), ptr(table), B, D, hidden_padded, mult, L.stream())
     return params
 
 
@@ -1340,14 +1093,12 @@ def pack_gather(params, src):
     out = torch.empty(src.numel(), dtype=torch.float32, device=src.device)
     if len(params) <= 16 and all(p.dtype == torch.float32 and p.is_contiguous() for p in params):
         # round 6: straight from the parameter tensors (no torch.cat per module and step)
-        pp = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
+        pp = _ptr_array(params)
         nn_ = (C.c_int64 * len(params))(*[p.numel() for p in params])
-        rc = L.lib().nf_pack_gather_multi(pp, nn_, i32(len(params)), ptr(src), ptr(out), i64(src.numel()), L.stream())
-        L.check(rc, "nf_pack_gather_multi")
+        L.call("nf_pack_gather_multi", pp, nn_, len(params), ptr(src), ptr(out), src.numel(), L.stream())
         return out
     flat = torch.cat([zero] + [p.detach().reshape(-1) for p in params])
-    rc = L.lib().nf_pack_gather(ptr(flat), ptr(src), ptr(out), i64(src.numel()), L.stream())
-    L.check(rc, "nf_pack_gather")
+    L.call("nf_pack_gather", ptr(flat), ptr(src), ptr(out), src.numel(), L.stream())
     return out
 
 
@@ -1366,8 +1117,7 @@ def pack_gather_batch(param_lists, src):
     outs = list(out.unbind(0))
     pp = _ptr_array([p for pl in param_lists for p in pl])
     nn_ = (C.c_int64 * n_par)(*[p.numel() for p in param_lists[0]])
-    rc = L.lib().nf_pack_gather_batch(pp, nn_, i32(n_par), ptr(src), _ptr_array(outs), i64(src.numel()), i32(n_mod), L.stream())
-    L.check(rc, "nf_pack_gather_batch")
+    L.call("nf_pack_gather_batch", pp, nn_, n_par, ptr(src), _ptr_array(outs), src.numel(), n_mod, L.stream())
     return outs
 
 
@@ -1386,9 +1136,8 @@ def made_forward_train(x, blob, table, hidden_padded, out_features, num_blocks, 
     params = torch.empty(B, out_features, dtype=x.dtype, device=x.device)
     save = torch.empty(2 * num_blocks + 1, Bp, hidden_padded, dtype=x.dtype, device=x.device)
     bits = torch.empty(max(Bp // 64, 1), 2 * num_blocks, 2, 512, dtype=torch.int32, device=x.device)
-    rc = L.lib().nf_made_forward_train(ptr(x), ptr(params), ptr(save), ptr(bits), ptr(blob), ptr(table), i64(B), i32(D),
-                                       i32(hidden_padded), i32(max(1, out_features // D)), L.stream())
-    L.check(rc, "nf_made_forward_train")
+    L.call("nf_made_forward_train", ptr(x), ptr(params), ptr(save), ptr(bits), ptr(blob), ptr(table), B, D, hidden_padded,
+           max(1, out_features // D), L.stream())
     return params, save, bits
 
 
@@ -1403,9 +1152,8 @@ def made_backward(g_params, bits, blob, table, D, hidden_padded, num_blocks, row
     Bp = (B + 63) // 64 * 64
     gx = torch.empty(B, D if ld_out is None else ld_out, dtype=g_params.dtype, device=g_params.device)
     G = torch.empty(2 * num_blocks + 1, Bp, hidden_padded, dtype=g_params.dtype, device=g_params.device) if want_G else None
-    rc = L.lib().nf_made_backward(ptr(g_params), ptr(bits), ptr(gx), ptr(G), ptr(blob), ptr(table), i64(B), i32(D),
-                                  i32(hidden_padded), i32(max(1, md // D)), L.stream())
-    L.check(rc, "nf_made_backward")
+    L.call("nf_made_backward", ptr(g_params), ptr(bits), ptr(gx), ptr(G), ptr(blob), ptr(table), B, D, hidden_padded,
+           max(1, md // D), L.stream())
     return gx, G
 
 
@@ -1415,23 +1163,22 @@ def _pad_rows_cols(t, rows, cols):
     return torch.nn.functional.pad(t, (0, cols - t.shape[1], 0, rows - t.shape[0])).contiguous()
 
 
+def _made_wgrad_operands(g_params, x, Bp, Mp, Dx, nflat, B, ntiles):
+    """(g_params padded to (Bp, Mp), x padded to (Bp, Dx), the zeroed flat gradient, the partial-sum scratch) of nf_made_wgrad[_pos]."""
+    grads = torch.zeros(nflat, dtype=torch.float32, device=x.device)
+    part = torch.empty(max(L.size("nf_made_wgrad_scratch_floats", B, ntiles), 1), dtype=torch.float32, device=x.device)
+    return _pad_rows_cols(g_params, Bp, Mp), _pad_rows_cols(x, Bp, Dx), grads, part
+
+
 def made_wgrad(g_params, x, G, save, wtable, stable, mask, ntiles, nflat, Mp, Dx, rows=None):
     """Every weight / bias gradient of the MADE (nf_made_wgrad): the flat vector in flows/made_pack.pack_made_backward's layout,
     masked entries zero."""
     L.require_device(g_params, x, G, save, wtable, stable, mask)
     B = g_params.shape[0] if rows is None else rows          # (rows: the operands are already padded buffers)
     Bp = G.shape[1]
-    gp_pad = _pad_rows_cols(g_params, Bp, Mp)
-    x_pad = _pad_rows_cols(x, Bp, Dx)
-    grads = torch.zeros(nflat, dtype=torch.float32, device=x.device)
-    lib = L.lib()
-    n = int(lib.nf_made_wgrad_scratch_floats(i64(B), i32(ntiles)))
-    if n < 0:
-        L.check(n, "nf_made_wgrad_scratch_floats")
-    part = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
-    rc = lib.nf_made_wgrad(ptr(gp_pad), ptr(x_pad), ptr(G), ptr(save), ptr(grads), ptr(mask), ptr(part), ptr(wtable), ptr(stable),
-                           i32(ntiles), i64(B), L.stream())
-    L.check(rc, "nf_made_wgrad")
+    gp_pad, x_pad, grads, part = _made_wgrad_operands(g_params, x, Bp, Mp, Dx, nflat, B, ntiles)
+    L.call("nf_made_wgrad", ptr(gp_pad), ptr(x_pad), ptr(G), ptr(save), ptr(grads), ptr(mask), ptr(part), ptr(wtable),
+           ptr(stable), ntiles, B, L.stream())
     return grads
 
 
@@ -1444,18 +1191,16 @@ def made_wgrad_pos(g_params, x, gscratch, fscratch, wtable, stable, mask, ntiles
     B = g_params.shape[0]
     if B % 64:
         raise NotImplementedError("made_wgrad_pos: a multiple of 64 rows")
-    gp_pad = _pad_rows_cols(g_params, B, Mp)
-    x_pad = _pad_rows_cols(x, B, Dx)
-    grads = torch.zeros(nflat, dtype=torch.float32, device=x.device)
-    lib = L.lib()
-    n = int(lib.nf_made_wgrad_scratch_floats(i64(B), i32(ntiles)))
-    if n < 0:
-        L.check(n, "nf_made_wgrad_scratch_floats")
-    part = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
-    rc = lib.nf_made_wgrad_pos(ptr(gp_pad), ptr(x_pad), ptr(gscratch), ptr(fscratch), ptr(grads), ptr(mask), ptr(part), ptr(wtable),
-                               ptr(stable), i32(ntiles), i64(B), i32(num_layers), i32(positions), L.stream())
-    L.check(rc, "nf_made_wgrad_pos")
+    gp_pad, x_pad, grads, part = _made_wgrad_operands(g_params, x, B, Mp, Dx, nflat, B, ntiles)
+    L.call("nf_made_wgrad_pos", ptr(gp_pad), ptr(x_pad), ptr(gscratch), ptr(fscratch), ptr(grads), ptr(mask), ptr(part),
+           ptr(wtable), ptr(stable), ntiles, B, num_layers, positions, L.stream())
     return grads
+
+
+def _host_table(table_host):
+    """The host copy of a format-1 table as the contiguous int32 array the *_tri entry points read (keep it alive through the call)."""
+    import numpy as np
+    return np.ascontiguousarray(table_host, dtype=np.int32)
 
 
 def maf_inverse(z, blob, table, hidden_padded, logdet=None, acc=None, num_blocks=2, table_host=None):
@@ -1470,35 +1215,23 @@ def maf_inverse(z, blob, table, hidden_padded, logdet=None, acc=None, num_blocks
     B, D = z.shape
     z = z.contiguous()
     y = torch.empty_like(z)
-    if logdet is None:
-        logdet = torch.empty(B, dtype=z.dtype, device=z.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    lib = L.lib()
+    logdet, acc = _ld_buffer(logdet, acc, B, z)
     if table_host is not None:
-        import numpy as np
-        th = np.ascontiguousarray(table_host, dtype=np.int32)
+        th = _host_table(table_host)
         if int(th[7]) != 1:
             raise ValueError("maf_inverse: table_host is given for format-1 packs only")
-        n = lib.nf_maf_inverse_h_scratch_floats(i64(B), i32(D), i32(hidden_padded), i32(num_blocks))
-        scratch = torch.empty(max(int(n), 1), dtype=torch.float32, device=z.device)
-        rc = lib.nf_maf_inverse_h_tri(ptr(z), ptr(y), ptr(logdet), ptr(blob), ptr(table), C.c_void_p(th.ctypes.data), ptr(scratch),
-                                      i64(B), i32(D), i32(hidden_padded), i32(num_blocks), i32(acc), L.stream())
-        L.check(rc, "nf_maf_inverse_h_tri")
+        scratch = _scratch("nf_maf_inverse_h_scratch_floats", z.device, B, D, hidden_padded, num_blocks)
+        L.call("nf_maf_inverse_h_tri", ptr(z), ptr(y), ptr(logdet), ptr(blob), ptr(table), th.ctypes.data, ptr(scratch), B, D,
+               hidden_padded, num_blocks, acc, L.stream())
         return y, logdet
     if config.maf_halves or num_blocks != 2:
-        n = lib.nf_maf_inverse_h_scratch_floats(i64(B), i32(D), i32(hidden_padded), i32(num_blocks))
-        scratch = torch.empty(max(int(n), 1), dtype=torch.float32, device=z.device)
-        rc = lib.nf_maf_inverse_h(ptr(z), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(scratch), i64(B), i32(D),
-                                  i32(hidden_padded), i32(num_blocks), i32(acc), L.stream())
-        L.check(rc, "nf_maf_inverse_h")
+        scratch = _scratch("nf_maf_inverse_h_scratch_floats", z.device, B, D, hidden_padded, num_blocks)
+        L.call("nf_maf_inverse_h", ptr(z), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(scratch), B, D, hidden_padded,
+               num_blocks, acc, L.stream())
         return y, logdet
-    n = lib.nf_maf_inverse_scratch_floats(i64(B), i32(D), i32(hidden_padded))
-    scratch = torch.empty(max(int(n), 1), dtype=torch.float32, device=z.device)
-    rc = lib.nf_maf_inverse(ptr(z), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(scratch), i64(B), i32(D),
-                            i32(hidden_padded), i32(acc), L.stream())
-    L.check(rc, "nf_maf_inverse")
+    scratch = _scratch("nf_maf_inverse_scratch_floats", z.device, B, D, hidden_padded)
+    L.call("nf_maf_inverse", ptr(z), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(scratch), B, D, hidden_padded, acc,
+           L.stream())
     return y, logdet
 
 
@@ -1514,29 +1247,22 @@ def maf_inverse_bits(z, blob, table, hidden_padded, num_blocks, tiles, table_hos
     z = z.contiguous()
     y = torch.empty_like(z)
     logdet = torch.empty(B, dtype=z.dtype, device=z.device)
-    lib = L.lib()
-    n = lib.nf_maf_inverse_h_scratch_floats(i64(B), i32(D), i32(hidden_padded), i32(num_blocks))
-    scratch = torch.empty(max(int(n), 1), dtype=torch.float32, device=z.device)
+    scratch = _scratch("nf_maf_inverse_h_scratch_floats", z.device, B, D, hidden_padded, num_blocks)
     bits = torch.empty(max((B + 31) // 32 * tiles * 64 * num_blocks, 1), dtype=torch.int32, device=z.device)
     if want_params:
-        import numpy as np
         prm = torch.empty(B, 2 * D, dtype=torch.float32, device=z.device)
-        th = None if table_host is None else np.ascontiguousarray(table_host, dtype=np.int32)
-        rc = lib.nf_maf_inverse_h_train(ptr(z), ptr(y), ptr(logdet), ptr(blob), ptr(table), C.c_void_p(None if th is None else th.ctypes.data),
-                                        ptr(scratch), ptr(bits), ptr(prm), i64(B), i32(D), i32(hidden_padded), i32(num_blocks),
-                                        i32(L.LD_WRITE), L.stream())
-        L.check(rc, "nf_maf_inverse_h_train")
+        th = None if table_host is None else _host_table(table_host)
+        L.call("nf_maf_inverse_h_train", ptr(z), ptr(y), ptr(logdet), ptr(blob), ptr(table),
+               None if th is None else th.ctypes.data, ptr(scratch), ptr(bits), ptr(prm), B, D, hidden_padded, num_blocks,
+               L.LD_WRITE, L.stream())
         return (y, logdet, bits, scratch, prm) if return_scratch else (y, logdet, bits, prm)
     if table_host is not None:
-        import numpy as np
-        th = np.ascontiguousarray(table_host, dtype=np.int32)
-        rc = lib.nf_maf_inverse_h_tri_bits(ptr(z), ptr(y), ptr(logdet), ptr(blob), ptr(table), C.c_void_p(th.ctypes.data), ptr(scratch),
-                                           ptr(bits), i64(B), i32(D), i32(hidden_padded), i32(num_blocks), i32(L.LD_WRITE), L.stream())
-        L.check(rc, "nf_maf_inverse_h_tri_bits")
+        th = _host_table(table_host)
+        L.call("nf_maf_inverse_h_tri_bits", ptr(z), ptr(y), ptr(logdet), ptr(blob), ptr(table), th.ctypes.data, ptr(scratch),
+               ptr(bits), B, D, hidden_padded, num_blocks, L.LD_WRITE, L.stream())
         return (y, logdet, bits, scratch) if return_scratch else (y, logdet, bits)
-    rc = lib.nf_maf_inverse_h_bits(ptr(z), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(scratch), ptr(bits), i64(B), i32(D),
-                                   i32(hidden_padded), i32(num_blocks), i32(L.LD_WRITE), L.stream())
-    L.check(rc, "nf_maf_inverse_h_bits")
+    L.call("nf_maf_inverse_h_bits", ptr(z), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(scratch), ptr(bits), B, D,
+           hidden_padded, num_blocks, L.LD_WRITE, L.stream())
     return (y, logdet, bits, scratch) if return_scratch else (y, logdet, bits)
 
 
@@ -1550,21 +1276,15 @@ def maf_solve_t(x, params, gx, gld, bits, blob, table, hidden_padded, num_blocks
     B, D = x.shape
     x, params, gx = x.contiguous(), params.contiguous(), gx.contiguous()
     v = torch.empty_like(x)
-    lib = L.lib()
-    n = lib.nf_maf_solve_t_scratch_floats(i64(B), i32(D), i32(hidden_padded), i32(num_blocks))
-    scratch = torch.empty(max(int(n), 1), dtype=torch.float32, device=x.device)
+    scratch = _scratch("nf_maf_solve_t_scratch_floats", x.device, B, D, hidden_padded, num_blocks)
     from . import config
     if table_host is not None and config.maf_solve_fast:      # round 6: the regular-8 tiles on the statically unrolled sequential part
-        import numpy as np
-        th = np.ascontiguousarray(table_host, dtype=np.int32)
-        rc = lib.nf_maf_solve_t_tri(ptr(x), ptr(params), ptr(gx), ptr(None if gld is None else gld.contiguous()), ptr(bits), ptr(v),
-                                    ptr(blob), ptr(table), C.c_void_p(th.ctypes.data), ptr(scratch), i64(B), i32(D), i32(hidden_padded),
-                                    i32(num_blocks), L.stream())
-        L.check(rc, "nf_maf_solve_t_tri")
+        th = _host_table(table_host)
+        L.call("nf_maf_solve_t_tri", ptr(x), ptr(params), ptr(gx), _cptr(gld), ptr(bits), ptr(v), ptr(blob), ptr(table),
+               th.ctypes.data, ptr(scratch), B, D, hidden_padded, num_blocks, L.stream())
         return (v, scratch) if return_scratch else v
-    rc = lib.nf_maf_solve_t(ptr(x), ptr(params), ptr(gx), ptr(None if gld is None else gld.contiguous()), ptr(bits), ptr(v), ptr(blob),
-                            ptr(table), ptr(scratch), i64(B), i32(D), i32(hidden_padded), i32(num_blocks), L.stream())
-    L.check(rc, "nf_maf_solve_t")
+    L.call("nf_maf_solve_t", ptr(x), ptr(params), ptr(gx), _cptr(gld), ptr(bits), ptr(v), ptr(blob), ptr(table), ptr(scratch), B,
+           D, hidden_padded, num_blocks, L.stream())
     return (v, scratch) if return_scratch else v
 
 
@@ -1574,9 +1294,8 @@ def maf_scratch_rows(scratch, pos_of_col, B, num_blocks, hidden_padded, sign=1.0
     ldo = pos_of_col.numel()
     Bp = (B + 63) // 64 * 64
     out = torch.empty(2 * num_blocks + 1, Bp, ldo, dtype=torch.float32, device=scratch.device)
-    rc = L.lib().nf_maf_scratch_rows(ptr(scratch), ptr(pos_of_col), ptr(out), i64(B), i32(num_blocks), i32(hidden_padded), i32(ldo),
-                                     f64(sign), i32(int(reverse_layers)), L.stream())
-    L.check(rc, "nf_maf_scratch_rows")
+    L.call("nf_maf_scratch_rows", ptr(scratch), ptr(pos_of_col), ptr(out), B, num_blocks, hidden_padded, ldo, sign,
+           int(reverse_layers), L.stream())
     return out
 
 
@@ -1586,9 +1305,7 @@ def maf_scratch_layer(scratch, pos_of_col, B, num_blocks, hidden_padded, layer):
     ldo = pos_of_col.numel()
     Bp = (B + 63) // 64 * 64
     out = torch.empty(Bp, ldo, dtype=torch.float32, device=scratch.device)
-    rc = L.lib().nf_maf_scratch_layer(ptr(scratch), ptr(pos_of_col), ptr(out), i64(B), i32(num_blocks), i32(hidden_padded), i32(ldo),
-                                      i32(layer), L.stream())
-    L.check(rc, "nf_maf_scratch_layer")
+    L.call("nf_maf_scratch_layer", ptr(scratch), ptr(pos_of_col), ptr(out), B, num_blocks, hidden_padded, ldo, layer, L.stream())
     return out
 
 
@@ -1602,17 +1319,10 @@ def arnsf_inverse(z, blob, table, hidden_padded, K, tails, tail_bound, min_bin_w
     B, D = z.shape
     z = z.contiguous()
     y = torch.empty_like(z)
-    if logdet is None:
-        logdet = torch.empty(B, dtype=z.dtype, device=z.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    n = L.lib().nf_maf_inverse_scratch_floats(i64(B), i32(D), i32(hidden_padded))
-    scratch = torch.empty(max(int(n), 1), dtype=torch.float32, device=z.device)
-    rc = L.lib().nf_arnsf_inverse(ptr(z), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(scratch), i64(B), i32(D),
-                                  i32(hidden_padded), i32(K), i32(L.TAILS[tails]), f64(tail_bound),
-                                  f64(min_bin_width), f64(min_bin_height), f64(min_derivative), i32(acc), L.stream())
-    L.check(rc, "nf_arnsf_inverse")
+    logdet, acc = _ld_buffer(logdet, acc, B, z)
+    scratch = _scratch("nf_maf_inverse_scratch_floats", z.device, B, D, hidden_padded)
+    L.call("nf_arnsf_inverse", ptr(z), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(scratch), B, D, hidden_padded, K,
+           L.TAILS[tails], tail_bound, min_bin_width, min_bin_height, min_derivative, acc, L.stream())
     return y, logdet
 
 
@@ -1621,25 +1331,20 @@ GLOW_CONV_WIDE, GLOW_CONV_SMALL, GLOW_CONV_TINY = 0, 1, 2
 
 def glow_convnet_layout(B, H, W):
     """Which nf_glow_convnet kernel takes (B, *, H, W) inputs: GLOW_CONV_WIDE, _SMALL, _TINY or None."""
-    code = L.lib().nf_glow_convnet_layout(i64(B), i32(H), i32(W))
+    code = L.query("nf_glow_convnet_layout", B, H, W)
     return code if code >= 0 else None
 
 
 def glow_convnet_pack(w1, b1, w2, b2, w3, b3, layout=GLOW_CONV_WIDE):
     """Packed weights of a GlowBlock conditioner for glow_convnet (nf_glow_convnet_pack); None for unsupported shapes."""
-    import ctypes
     L.require_device(w1, b1, w2, b2, w3, b3)
     Cin, Cout, hidden = w1.shape[1], w3.shape[0], w1.shape[0]
-    lib = L.lib()
-    lib.nf_glow_convnet_pack_size.restype = ctypes.c_int64
-    size = lib.nf_glow_convnet_pack_size(i32(Cin), i32(Cout), i32(hidden))
+    size = L.query("nf_glow_convnet_pack_size", Cin, Cout, hidden)
     if size <= 0 or (layout == GLOW_CONV_SMALL and Cout > 48):
         return None
     blob = torch.empty(size // 4, dtype=torch.float32, device=w1.device)
-    rc = lib.nf_glow_convnet_pack(ptr(blob), ptr(w1.contiguous()), ptr(b1.contiguous()), ptr(w2.contiguous()),
-                                  ptr(b2.contiguous()), ptr(w3.contiguous()), ptr(b3.contiguous()), i32(Cin), i32(Cout),
-                                  i32(hidden), i32(layout), L.stream())
-    L.check(rc, "nf_glow_convnet_pack")
+    L.call("nf_glow_convnet_pack", ptr(blob), ptr(w1.contiguous()), ptr(b1.contiguous()), ptr(w2.contiguous()),
+           ptr(b2.contiguous()), ptr(w3.contiguous()), ptr(b3.contiguous()), Cin, Cout, hidden, layout, L.stream())
     return blob
 
 
@@ -1651,9 +1356,8 @@ def glow_convnet(x, blob, Cout, slope, layout=GLOW_CONV_WIDE, hidden=256):
     if x.dtype != torch.float32 or x.stride(3) != 1 or x.stride(2) != W or x.stride(1) != H * W:
         raise NotImplementedError("glow_convnet: float32 with contiguous (H, W) planes")
     out = torch.empty(B, Cout, H, W, dtype=x.dtype, device=x.device)
-    rc = L.lib().nf_glow_convnet(ptr_any(x), i64(x.stride(0) if B > 1 else Cin * H * W), ptr(out), ptr(blob), i64(B),
-                                 i32(Cin), i32(H), i32(W), i32(Cout), i32(hidden), f64(slope), i32(layout), L.stream())
-    L.check(rc, "nf_glow_convnet")
+    L.call("nf_glow_convnet", ptr_any(x), x.stride(0) if B > 1 else Cin * H * W, ptr(out), ptr(blob), B, Cin, H, W, Cout, hidden,
+           slope, layout, L.stream())
     return out
 
 
@@ -1696,16 +1400,10 @@ def glow_level(in0, in1, in_squeezed, C, H, W, table, nblocks, layout, slope, sc
     else:
         out0 = torch.empty(B, cout0, H, W, dtype=in0.dtype, device=in0.device)
         out1 = torch.empty(B, C - cout0, H, W, dtype=in0.dtype, device=in0.device) if cout0 < C else None
-    if logdet is None:
-        logdet = torch.empty(B, dtype=in0.dtype, device=in0.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_glow_level(ptr(in0), ptr(in1), i32(cin0), i32(1 if in_squeezed else 0), ptr(out0), ptr(out1), i32(cout0),
-                               i32(1 if out_squeezed else 0), ptr(logdet), ptr(table), i32(nblocks), i64(B), i32(C), i32(H),
-                               i32(W), i32(hidden), f64(slope), i32(L.SCALE[scale_map]), i32(direction), i32(acc), i32(layout),
-                               L.stream())
-    L.check(rc, "nf_glow_level")
+    logdet, acc = _ld_buffer(logdet, acc, B, in0)
+    L.call("nf_glow_level", ptr(in0), ptr(in1), cin0, 1 if in_squeezed else 0, ptr(out0), ptr(out1), cout0,
+           1 if out_squeezed else 0, ptr(logdet), ptr(table), nblocks, B, C, H, W, hidden, slope, L.SCALE[scale_map], direction,
+           acc, layout, L.stream())
     return out0, out1, logdet
 
 
@@ -1730,14 +1428,8 @@ def logit(z, alpha, direction, logdet=None, acc=None):
     B = z.shape[0]
     inner = z[0].numel() if B else int(math.prod(z.shape[1:]))
     y = torch.empty_like(z)
-    if logdet is None:
-        logdet = torch.empty(B, dtype=z.dtype, device=z.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_logit(ptr(z), ptr(y), ptr(logdet), i64(B), i64(inner), f64(alpha), i32(direction), i32(acc),
-                          i32(L.dtype_code(z)), L.stream())
-    L.check(rc, "nf_logit")
+    logdet, acc = _ld_buffer(logdet, acc, B, z)
+    L.call("nf_logit", ptr(z), ptr(y), ptr(logdet), B, inner, alpha, direction, acc, L.dtype_code(z), L.stream())
     return y, logdet
 
 
@@ -1749,17 +1441,11 @@ def diag_gaussian_log_prob_rows(z, loc_rows, log_scale_rows, row_idx=None, ls_sh
     d = z[0].numel() if B else int(math.prod(z.shape[1:]))
     loc_rows = loc_rows.contiguous().view(-1, d)
     log_scale_rows = log_scale_rows.contiguous().view(-1, d)
-    if out is None:
-        out = torch.empty(B, dtype=z.dtype, device=z.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
+    out, acc = _ld_buffer(out, acc, B, z)
     if row_idx is not None:
         row_idx = row_idx.to(torch.long).contiguous()
-    rc = L.lib().nf_diag_gaussian_log_prob_rows(ptr(z), ptr(loc_rows), ptr(log_scale_rows), ptr(row_idx),
-                                                i64(loc_rows.shape[0]), f64(ls_shift), ptr(out), i64(B), i64(d), i32(acc),
-                                                i32(L.dtype_code(z)), L.stream())
-    L.check(rc, "nf_diag_gaussian_log_prob_rows")
+    L.call("nf_diag_gaussian_log_prob_rows", ptr(z), ptr(loc_rows), ptr(log_scale_rows), ptr(row_idx), loc_rows.shape[0],
+           ls_shift, ptr(out), B, d, acc, L.dtype_code(z), L.stream())
     return out
 
 
@@ -1775,11 +1461,9 @@ def linear_wgrad(dy, x, want_bias=True, relu_x=False, skip_every=0):
     Mo = M - M // skip_every if skip_every else M
     dW = torch.empty(Mo, N, dtype=torch.float32, device=dy.device)
     db = torch.empty(Mo, dtype=torch.float32, device=dy.device) if want_bias else None
-    n = L.lib().nf_linear_wgrad_scratch_floats(i64(B), i32(M), i32(N))
-    scratch = torch.empty(max(int(n), 1), dtype=torch.float32, device=dy.device)
-    rc = L.lib().nf_linear_wgrad_skip(ptr(dy), ptr(x), ptr(dW), ptr(db), ptr(scratch), i64(B), i32(M), i32(N), i32(0),
-                                      i32(int(relu_x)), i32(int(skip_every)), L.stream())
-    L.check(rc, "nf_linear_wgrad_skip")
+    scratch = _scratch("nf_linear_wgrad_scratch_floats", dy.device, B, M, N)
+    L.call("nf_linear_wgrad_skip", ptr(dy), ptr(x), ptr(dW), ptr(db), ptr(scratch), B, M, N, 0, int(relu_x), int(skip_every),
+           L.stream())
     return dW, db
 
 
@@ -1792,12 +1476,11 @@ def linear_wgrad_pair(dy0, x0, dy1, x1, relu_x=False):
     B, M = dy0.shape
     N = x0.shape[1]
     out = torch.empty(2, M * N + M, dtype=torch.float32, device=dy0.device)     # dW | db per problem
-    n = int(L.lib().nf_linear_wgrad_scratch_floats(i64(B), i32(M), i32(N)))
+    n = L.query("nf_linear_wgrad_scratch_floats", B, M, N)
     scratch = torch.empty(max(2 * n, 1), dtype=torch.float32, device=dy0.device)
     w0, b0, w1, b1 = out[0, :M * N], out[0, M * N:], out[1, :M * N], out[1, M * N:]
-    rc = L.lib().nf_linear_wgrad_pair(ptr(dy0), ptr(x0), ptr(w0), ptr(b0), ptr(dy1), ptr(x1), ptr(w1), ptr(b1), ptr(scratch),
-                                      i64(B), i32(M), i32(N), i32(0), i32(int(relu_x)), L.stream())
-    L.check(rc, "nf_linear_wgrad_pair")
+    L.call("nf_linear_wgrad_pair", ptr(dy0), ptr(x0), ptr(w0), ptr(b0), ptr(dy1), ptr(x1), ptr(w1), ptr(b1), ptr(scratch), B, M,
+           N, 0, int(relu_x), L.stream())
     return w0.view(M, N), b0, w1.view(M, N), b1
 
 
@@ -1805,7 +1488,7 @@ def mfma_clock_mhz(device, iters=20000):
     """Shader clock (MHz) under fp32-MFMA load (nf_mfma_clock_probe): what the matrix pipe runs at while a kernel keeps it busy."""
     out = torch.zeros(2, dtype=torch.int64, device=device)
     sink = torch.zeros(1, dtype=torch.float32, device=device)
-    L.check(L.lib().nf_mfma_clock_probe(ptr(out), ptr(sink), i32(iters), L.stream()), "nf_mfma_clock_probe")
+    L.call("nf_mfma_clock_probe", ptr(out), ptr(sink), iters, L.stream())
     c, w = out.tolist()
     return 100.0 * c / max(w, 1)
 
@@ -1817,14 +1500,9 @@ def lu_fwd(x, UpT, LT, bias=None, ld_const=None, ld_sign=1.0, logdet=None, acc=N
     x = x.contiguous()
     B, D = x.shape
     u, y = torch.empty_like(x), torch.empty_like(x)
-    if ld_const is not None and logdet is None:
-        logdet, acc = torch.empty(B, dtype=x.dtype, device=x.device), L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_lu_fwd(ptr(x), ptr(UpT.contiguous()), ptr(LT.contiguous()), ptr(bias), ptr(u), ptr(y),
-                           ptr(logdet if ld_const is not None else None), ptr(ld_const), f64(ld_sign), i32(acc), i64(B), i32(D),
-                           L.stream())
-    L.check(rc, "nf_lu_fwd")
+    logdet, acc = _ld_buffer(logdet, acc, B, x, want=ld_const is not None)
+    L.call("nf_lu_fwd", ptr(x), ptr(UpT.contiguous()), ptr(LT.contiguous()), ptr(bias), ptr(u), ptr(y),
+           ptr(logdet if ld_const is not None else None), ptr(ld_const), ld_sign, acc, B, D, L.stream())
     return u, y, logdet
 
 
@@ -1834,9 +1512,7 @@ def lu_bwd(gy, u, x, Lm, Up, db_out=None):
     L.require_device(gy, u, x, Lm, Up)
     gy, u, x, Lm, Up = gy.contiguous(), u.contiguous(), x.contiguous(), Lm.contiguous(), Up.contiguous()
     B, D = gy.shape
-    lib = L.lib()
-    lib.nf_lu_bwd_scratch_floats.restype = C.c_int64
-    n = int(lib.nf_lu_bwd_scratch_floats(i64(B)))
+    n = L.query("nf_lu_bwd_scratch_floats", B)
     if n <= 0 or D != 64 or gy.dtype != torch.float32:
         raise NotImplementedError("lu_bwd: float32, D = 64, batch a multiple of 64")
     scratch = torch.empty(n, dtype=torch.float32, device=gy.device)
@@ -1847,9 +1523,8 @@ def lu_bwd(gy, u, x, Lm, Up, db_out=None):
             raise ValueError("lu_bwd: db_out = a contiguous float32 (D) tensor on the inputs' device")
         db = db_out
     gx = torch.empty_like(gy)
-    rc = lib.nf_lu_bwd(ptr(gy), ptr(u), ptr(x), ptr(Lm), ptr(Up), ptr(gx), ptr(dL), ptr(db), ptr(dUp), ptr(scratch), i64(B),
-                       i32(D), L.stream())
-    L.check(rc, "nf_lu_bwd")
+    L.call("nf_lu_bwd", ptr(gy), ptr(u), ptr(x), ptr(Lm), ptr(Up), ptr(gx), ptr(dL), ptr(db), ptr(dUp), ptr(scratch), B, D,
+           L.stream())
     return gx, dL.view(D, D), db, dUp.view(D, D)
 
 
@@ -1865,9 +1540,7 @@ def resblock_bwd(gh, t, h_in, w1, w2, x=None, wfull=None, gx=None, col_map=None,
         raise ValueError("resblock_bwd: float32 only")
     B, H = gh.shape
     init = x is not None
-    lib = L.lib()
-    lib.nf_resblock_bwd_scratch_floats.restype = C.c_int64
-    n = int(lib.nf_resblock_bwd_scratch_floats(i64(B), i32(int(init))))
+    n = L.query("nf_resblock_bwd_scratch_floats", B, int(init))
     if n <= 0 or H != 128:
         raise NotImplementedError("resblock_bwd: hidden 128, batch a multiple of 64")
     scratch = torch.empty(n, dtype=torch.float32, device=gh.device)
@@ -1882,10 +1555,8 @@ def resblock_bwd(gh, t, h_in, w1, w2, x=None, wfull=None, gx=None, col_map=None,
         gh_in, w0g, b0g = None, out0[:H * nc], out0[H * nc:]
     else:
         gh_in, w0g, b0g = torch.empty_like(gh), None, None
-    rc = lib.nf_resblock_bwd(ptr(gh), ptr(t), ptr(h_in), ptr(w1), ptr(w2), ptr(gh_in), ptr(w1g), ptr(b1g), ptr(w2g), ptr(b2g),
-                             ptr(x), ptr(wfull), ptr(gx), ptr(w0g), ptr(b0g), ptr(col_map), i32(int(n_cols)), ptr(scratch),
-                             i64(B), i32(H), i32(64), L.stream())
-    L.check(rc, "nf_resblock_bwd")
+    L.call("nf_resblock_bwd", ptr(gh), ptr(t), ptr(h_in), ptr(w1), ptr(w2), ptr(gh_in), ptr(w1g), ptr(b1g), ptr(w2g), ptr(b2g),
+           ptr(x), ptr(wfull), ptr(gx), ptr(w0g), ptr(b0g), ptr(col_map), int(n_cols), ptr(scratch), B, H, 64, L.stream())
     if init:
         return None, w1g.view(H, H), b1g, w2g.view(H, H), b2g, w0g.view(H, nc), b0g
     return gh_in, w1g.view(H, H), b1g, w2g.view(H, H), b2g
@@ -1898,9 +1569,7 @@ def bias_leaky_relu_(y, bias, negative_slope):
         raise ValueError("bias_leaky_relu_: contiguous NCHW tensor required")
     B, Cc = y.shape[0], y.shape[1]
     HW = int(math.prod(y.shape[2:]))
-    rc = L.lib().nf_bias_leaky_relu(ptr(y), ptr(bias.contiguous()), i64(B), i32(Cc), i64(HW), f64(negative_slope),
-                                    i32(L.dtype_code(y)), L.stream())
-    L.check(rc, "nf_bias_leaky_relu")
+    L.call("nf_bias_leaky_relu", ptr(y), ptr(bias.contiguous()), B, Cc, HW, negative_slope, L.dtype_code(y), L.stream())
     return y
 
 
@@ -1912,12 +1581,6 @@ def realnvp_chain(z, blob, d, hmax, direction, logdet=None, acc=None):
     z = z.contiguous()
     B = z.shape[0]
     y = torch.empty_like(z)
-    if logdet is None:
-        logdet = torch.empty(B, dtype=z.dtype, device=z.device)
-        acc = L.LD_WRITE
-    elif acc is None:
-        acc = L.LD_ADD
-    rc = L.lib().nf_realnvp_chain(ptr(z), ptr(y), ptr(logdet), ptr(blob), i64(B), i32(d), i32(hmax), i32(direction),
-                                  i32(acc), L.stream())
-    L.check(rc, "nf_realnvp_chain")
+    logdet, acc = _ld_buffer(logdet, acc, B, z)
+    L.call("nf_realnvp_chain", ptr(z), ptr(y), ptr(logdet), ptr(blob), B, d, hmax, direction, acc, L.stream())
     return y, logdet

@@ -75,6 +75,38 @@ def test_every_int64_function_of_the_header_is_bound_as_int64(nfa):
     assert lib.nf_maf_inverse_h_scratch_floats(i64(999936), i32(128), i32(512), i32(2)) == 999936 * (5 * 512 + 128 + 5 * 32)
 
 
+def test_every_function_of_the_header_is_bound_with_its_argument_types(nfa):
+    """_lib.lib() gives every function of include/nf_mi355x.h its `argtypes` from the header: as many as the prototype has parameters,
+    pointers and nf_stream_t as c_void_p, int / int64_t / double / float as c_int / c_int64 / c_double / c_float -- so a bare Python
+    number arrives in the width the C side reads, and a wrong count or kind of argument raises before anything is launched."""
+    import re
+    lib = nfa._lib.lib()
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "nf_mi355x.h")).read(), flags=re.S)
+    scalars = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double, "float": ctypes.c_float,
+               "nf_stream_t": ctypes.c_void_p}
+    declared = nfa._lib.exported_symbols_declared()
+    for fn in declared:
+        params = [p.strip() for p in re.search(r"\b%s\s*\(([^)]*)\)" % fn, txt).group(1).split(",")]
+        if params == ["void"]:
+            params = []
+        argtypes = getattr(lib, fn).argtypes
+        assert argtypes is not None and len(argtypes) == len(params), (fn, argtypes, params)
+        for p, t in zip(params, argtypes):
+            want = ctypes.c_void_p if "*" in p else scalars[p.replace("const ", "").split()[0]]
+            assert t is want, (fn, p, t)
+    assert lib.nf_rqs_fused_pack_size(32, 32, 128, 2, 8) > 600 * 1024                     # bare Python ints, no wrappers
+    assert lib.nf_maf_solve_t_scratch_floats(999936, 128, 512, 2) == 999936 * (5 * 512 + 256 + 5 * 32)
+    with pytest.raises(TypeError):
+        lib.nf_rqs_fused_pack_size(32, 32, 128, 2)                                         # one argument too few
+    with pytest.raises(ctypes.ArgumentError):
+        lib.nf_rqs_fused_pack_size(32.0, 32, 128, 2, 8)                                    # a float where the header says int
+    with pytest.raises(ctypes.ArgumentError):
+        lib.nf_rqs_fused_pack_size(ctypes.c_int64(32), 32, 128, 2, 8)                      # a wrapper of the wrong width
+    assert nfa._lib.query("nf_rqs_fused_pack_size", 8, 8, 32, 2, 8) == -95
+    with pytest.raises(ValueError, match="nf_masked_affine: invalid argument"):            # the helper's label is the entry point's name
+        nfa._lib.call("nf_masked_affine", 16, 16, None, None, 16, 16, 4, 2, 3, 0, 0, None)   # (bad direction: nothing is dereferenced)
+
+
 def test_c_abi_argument_validation_newer_entry_points(nfa):
     """Same discipline for the entry points added after the first bench: nothing is launched on bad arguments."""
     lib = nfa._lib.lib()
