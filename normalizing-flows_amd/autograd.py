@@ -13,6 +13,8 @@ anything else (contexts, batch norm, other activations) stays an ordinary torch 
 switch to these Functions only when gradients are needed (`needs_grad`); under torch.no_grad() the fused inference kernels run.
 """
 import contextlib
+import functools
+import inspect
 import math
 
 import torch
@@ -53,6 +55,80 @@ def _check_stamp(ctx, what):
                            "layer's use_fused_train) change, or run the forward again." % what)
 
 
+def _record_stamp(ctx, holder, kind, *tensors):
+    """Forward side of _check_stamp: the stamp (prefixed by the training path, `kind`, where two paths share a holder) on ctx and in
+    the layer's holder."""
+    ctx.holder, ctx.stamp = holder, kind + _stamp(*tensors)
+    if holder is not None:
+        holder["stamp"] = ctx.stamp
+
+
+def _spline_kw(kw):
+    """The four spline constants every fused pack / forward / backward entry point takes, out of a layer's keyword dict."""
+    return {k: kw[k] for k in ("tail_bound", "min_bin_width", "min_bin_height", "min_derivative")}
+
+
+def _ld_mode(ctx, ld_acc, acc):
+    """The running-log-density convention, forward side: `ld_acc` (the caller's running log-density, or None) is updated in place
+    -- inside the launch where possible, so autograd sees an in-place op -- added for acc > 0, subtracted otherwise.  Returns the
+    launch's accumulate mode (None without ld_acc); _ld_cotangents is the backward side."""
+    ctx.acc, ctx.has_acc = acc, ld_acc is not None
+    if ld_acc is None:
+        return None
+    ctx.mark_dirty(ld_acc)
+    return L.LD_ADD if acc > 0 else L.LD_SUB
+
+
+def _ld_cotangents(ctx, gld):
+    """(this layer's own log-det cotangent: sign flipped where the forward subtracted, the cotangent of ld_acc: the running
+    log-density passes its own straight through)."""
+    own = -gld if (ctx.has_acc and ctx.acc < 0 and gld is not None) else gld
+    return own, (gld if ctx.has_acc else None)
+
+
+def _gy_or_zeros(gy, like):
+    """A missing cotangent (that output was not used) as zeros shaped like `like`.  (No .contiguous() here: a site that needs it says
+    so, the others must not grow a copy kernel for a strided cotangent.)"""
+    return torch.zeros_like(like) if gy is None else gy
+
+
+def _gld_or_zeros(gld, x):
+    """_gy_or_zeros for the per-row log-det cotangent of a Function on the rows of `x`."""
+    return torch.zeros(x.shape[0], dtype=x.dtype, device=x.device) if gld is None else gld
+
+
+@functools.lru_cache(maxsize=None)
+def _positions(forward):
+    """{parameter name: position in .apply's arguments} of a Function's forward, its *args left out (read once per Function)."""
+    names = list(inspect.signature(forward).parameters.values())[1:]          # (after ctx)
+    if names and names[-1].kind is inspect.Parameter.VAR_POSITIONAL:
+        names.pop()
+    return {p_.name: i for i, p_ in enumerate(names)}
+
+
+def _grads(forward, rest=(), **named):
+    """A backward's return tuple laid out by the NAMES of `forward`'s own parameters: `named` gradients at their parameters'
+    positions, None everywhere else, `rest` for forward's *args.  (An unknown name is a KeyError, not a shifted gradient.)"""
+    pos = _positions(forward)
+    out = [None] * len(pos)
+    for name, g in named.items():
+        out[pos[name]] = g
+    return (*out, *rest)
+
+
+def _carve(flat, off, shape):
+    """One parameter's gradient out of a flat weight-gradient buffer."""
+    return flat[off:off + math.prod(shape)].view(shape)
+
+
+def _made_param_grads(flat, offsets):
+    """[gW, gb] per linear out of nf_made_wgrad's flat result (offsets: flows/made_pack.py)."""
+    grads = []
+    for woff, shape, boff, n in offsets:
+        grads += [_carve(flat, woff, shape), flat[boff:boff + n]]
+    return grads
+
+
 def needs_grad(*tensors_or_modules):
     if not torch.is_grad_enabled():
         return False
@@ -65,6 +141,13 @@ def needs_grad(*tensors_or_modules):
         elif torch.is_tensor(t) and t.requires_grad:
             return True
     return False
+
+
+def _rqs_backward(ctx, gy, gld):
+    """(gx, gcond, guw, guh, gud) of SplineFn / CouplingDensityFn: one launch (nf_rqs_coupling_bwd)."""
+    x, cond, uw, uh, ud, iidx, tidx = ctx.saved_tensors
+    return ops.rqs_coupling_bwd(x, _gy_or_zeros(gy, x), _gld_or_zeros(gld, x), cond, uw, uh, ud, iidx, tidx, ctx.K, ctx.mode,
+                                **ctx.kw)
 
 
 class SplineFn(torch.autograd.Function):
@@ -92,13 +175,7 @@ class SplineFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, gld):
-        x, cond, uw, uh, ud, ii, ti = ctx.saved_tensors
-        if gy is None:
-            gy = torch.zeros_like(x)
-        if gld is None:
-            gld = torch.zeros(x.shape[0], dtype=x.dtype, device=x.device)
-        gx, gcond, guw, guh, gud = ops.rqs_coupling_bwd(x, gy, gld, cond, uw, uh, ud, ii, ti, ctx.K, ctx.mode, **ctx.kw)
-        return gx, gcond, guw, guh, gud, None, None, None
+        return (*_rqs_backward(ctx, gy, gld), None, None, None)
 
 
 class CouplingDensityFn(torch.autograd.Function):
@@ -110,19 +187,12 @@ class CouplingDensityFn(torch.autograd.Function):
     def forward(ctx, x, cond, uw, uh, ud, iidx, tidx, K, kw):
         y, ld = ops.rqs_coupling(x, cond.contiguous(), uw, uh, ud, iidx, tidx, K, L.RQS_DENSITY, **kw)
         ctx.save_for_backward(x, cond, uw, uh, ud, iidx, tidx)
-        ctx.K, ctx.kw = K, kw
+        ctx.K, ctx.mode, ctx.kw = K, L.RQS_DENSITY, kw
         return y, ld
 
     @staticmethod
     def backward(ctx, gy, gld):
-        x, cond, uw, uh, ud, iidx, tidx = ctx.saved_tensors
-        if gy is None:
-            gy = torch.zeros_like(x)
-        if gld is None:
-            gld = torch.zeros(x.shape[0], dtype=x.dtype, device=x.device)
-        gx, gcond, guw, guh, gud = ops.rqs_coupling_bwd(x, gy, gld, cond, uw, uh, ud, iidx, tidx, ctx.K, L.RQS_DENSITY,
-                                                        **ctx.kw)
-        return gx, gcond, guw, guh, gud, None, None, None, None
+        return (*_rqs_backward(ctx, gy, gld), None, None, None, None)
 
 
 class FinalSplineDensityFn(torch.autograd.Function):
@@ -135,16 +205,10 @@ class FinalSplineDensityFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h2, wf, bf, uw, uh, ud, iidx, tidx, blob, parity, nblocks, kw, wpad, ld_acc=None, acc=1):
-        ops.rqs_fused_pack_final(blob, wf.detach(), bf.detach(), uw.detach(), uh.detach(), ud.detach(), nblocks,
-                                 tail_bound=kw["tail_bound"], min_bin_width=kw["min_bin_width"],
-                                 min_bin_height=kw["min_bin_height"], min_derivative=kw["min_derivative"])
-        # the caller's running log-density is updated inside the launch (no (B) add per layer); autograd sees an in-place op
-        y, ld, cond24 = ops.rqs_fused_train_fwd(x, h2, blob, parity, nblocks, tail_bound=kw["tail_bound"],
-                                                min_bin_width=kw["min_bin_width"], min_bin_height=kw["min_bin_height"],
-                                                min_derivative=kw["min_derivative"], logdet=ld_acc,
-                                                acc=None if ld_acc is None else (L.LD_ADD if acc > 0 else L.LD_SUB))
-        if ld_acc is not None:
-            ctx.mark_dirty(ld_acc)
+        fk = _spline_kw(kw)
+        ops.rqs_fused_pack_final(blob, wf.detach(), bf.detach(), uw.detach(), uh.detach(), ud.detach(), nblocks, **fk)
+        # the caller's running log-density is updated inside the launch (no (B) add per layer)
+        y, ld, cond24 = ops.rqs_fused_train_fwd(x, h2, blob, parity, nblocks, logdet=ld_acc, acc=_ld_mode(ctx, ld_acc, acc), **fk)
         # final-layer weight on the 24-row layout of cond24 (pad row of every feature zero): `wpad` (nT, 24, H) is a zero
         # buffer OWNED BY THE LAYER (only its 23 real rows per feature are ever written), one strided copy per step, read by
         # the backward's input-gradient GEMM
@@ -152,31 +216,22 @@ class FinalSplineDensityFn(torch.autograd.Function):
         wpad[:, :23].copy_(wf.detach().view(nT, 23, H))
         wpad[:, 23].zero_()       # (the whole-layer path's pack leaves another image of the final weight in this buffer)
         ctx.save_for_backward(x, h2, wf, cond24, uw, uh, ud, iidx, tidx)
-        ctx.kw, ctx.wpad, ctx.acc, ctx.has_acc = kw, wpad, acc, ld_acc is not None
-        ctx.holder, ctx.stamp = kw.get("holder"), ("final",) + _stamp(wf, bf, uw, uh, ud)
-        if ctx.holder is not None:
-            ctx.holder["stamp"] = ctx.stamp
+        ctx.kw, ctx.wpad = kw, wpad
+        _record_stamp(ctx, kw.get("holder"), ("final",), wf, bf, uw, uh, ud)
         return y, ld
 
     @staticmethod
     def backward(ctx, gy, gld):
         x, h2, wf, cond24, uw, uh, ud, iidx, tidx = ctx.saved_tensors
         _check_stamp(ctx, "FinalSplineDensityFn")
-        kw = ctx.kw
-        if gy is None:
-            gy = torch.zeros_like(x)
-        if gld is None:
-            gld = torch.zeros(x.shape[0], dtype=x.dtype, device=x.device)
-        gld_own = -gld if (ctx.has_acc and ctx.acc < 0) else gld
-        gx, gcond24, guw, guh, gud = ops.rqs_coupling_bwd_p24(x, gy, gld_own, cond24, uw, uh, ud, iidx, tidx,
-                                                              tail_bound=kw["tail_bound"], min_bin_width=kw["min_bin_width"],
-                                                              min_bin_height=kw["min_bin_height"],
-                                                              min_derivative=kw["min_derivative"], wh_div=kw["wh_div"])
+        gld_own, g_acc = _ld_cotangents(ctx, _gld_or_zeros(gld, x))
+        gx, gcond24, guw, guh, gud = ops.rqs_coupling_bwd_p24(x, _gy_or_zeros(gy, x), gld_own, cond24, uw, uh, ud, iidx, tidx,
+                                                              wh_div=ctx.kw["wh_div"], **_spline_kw(ctx.kw))
         B, nT, H = x.shape[0], cond24.shape[1], wf.shape[1]
         g2 = gcond24.view(B, nT * 24)
         gh2 = g2 @ ctx.wpad.view(nT * 24, H)                 # input gradient of the final layer (library GEMM, padded rows)
         gwf, gbf = ops.linear_wgrad(g2, h2, want_bias=True, skip_every=24)   # pad rows dropped in the reduction
-        return gx, gh2, gwf, gbf, guw, guh, gud, None, None, None, None, None, None, None, (gld if ctx.has_acc else None), None
+        return _grads(FinalSplineDensityFn.forward, x=gx, h2=gh2, wf=gwf, bf=gbf, uw=guw, uh=guh, ud=gud, ld_acc=g_acc)
 
 
 _tri_cache = {}
@@ -217,9 +272,8 @@ class LULinearPermuteFn(torch.autograd.Function):
                 holder=None):
         D = x.shape[1]
         _gradbuf.use((lower_entries, upper_entries, udiag_raw, bias))     # (a second use before zero_grad: see _pair_side_ok)
-        ctx.acc, ctx.has_acc = acc, ld_acc is not None
-        if ld_acc is not None:
-            ctx.mark_dirty(ld_acc)      # the caller's running log-density, updated in place (inside the launch where possible)
+        lacc = _ld_mode(ctx, ld_acc, acc)
+        ctx.eps, ctx.direction = eps, direction
         if direction == 0 and x.is_cuda and x.dtype == torch.float32 and D <= 128:
             # density direction on the fp32-MFMA row mat-vec kernel: u = U x[perm] (kept for the backward), y = L u + b with
             # the constant log-det in the same launch -- two 13 us launches against 64 us for the LDS-tile kernel (D = 128: two
@@ -231,27 +285,20 @@ class LULinearPermuteFn(torch.autograd.Function):
                     Lm, Um, Up, diag, lad, LT, UpT = ops.lu_factors(perm, lower_entries.detach(), upper_entries.detach(),
                                                                     udiag_raw.detach(), eps=eps)      # one launch (nf_lu_factors)
                 # u = U x[perm] (kept for the backward) and y = L u + b with the constant log-det: one launch (nf_rows_matvec2)
-                from . import config
-                lacc = None if ld_acc is None else (L.LD_ADD if acc > 0 else L.LD_SUB)
-                if config.lu_bwd_fused and D == 64 and x.shape[0] % 64 == 0 and x.shape[0] >= 1024:
+                if _config.lu_bwd_fused and D == 64 and x.shape[0] % 64 == 0 and x.shape[0] >= 1024:
                     u, y, ld = ops.lu_fwd(x, UpT, LT, bias.detach(), lad, +1.0, logdet=ld_acc, acc=lacc)   # LDS-DMA tiles (nf_lu_fwd)
-                elif config.lu_matvec2 and D <= 64:
+                elif _config.lu_matvec2 and D <= 64:
                     u, y, ld = ops.rows_matvec2(x, Up, Lm, bias.detach(), lad, +1.0, logdet=ld_acc, acc=lacc)
                 else:
                     u = ops.rows_matvec(x, Up)
                     y, ld = ops.rows_matvec_affine(u, Lm, bias.detach(), lad, +1.0, logdet=ld_acc, acc=lacc)
             ctx.save_for_backward(x, y, perm, lower_entries, upper_entries, udiag_raw, bias, u)
-            ctx.eps, ctx.direction = eps, direction
             ctx.factors = (Lm, Um, diag, Up, LT, UpT)      # assembled once per step: the backward reuses them
             # (views of a LAYER-OWNED buffer when a multi-layer launch assembled them: see _stamp)
-            ctx.holder = holder if factors_out is not None else None
-            ctx.stamp = _stamp(lower_entries, upper_entries, udiag_raw)
-            if ctx.holder is not None:
-                ctx.holder["stamp"] = ctx.stamp
+            _record_stamp(ctx, holder if factors_out is not None else None, (), lower_entries, upper_entries, udiag_raw)
             return y, ld
         y, ld = ops.lu_linear_permute(x, perm, lower_entries, upper_entries, udiag_raw, bias, direction, eps=eps)
         ctx.save_for_backward(x, y, perm, lower_entries, upper_entries, udiag_raw, bias, None)
-        ctx.eps, ctx.direction = eps, direction
         if ld_acc is not None:
             ld = ld_acc.add_(ld) if acc > 0 else ld_acc.sub_(ld)
         return y, ld
@@ -262,40 +309,35 @@ class LULinearPermuteFn(torch.autograd.Function):
         fac = getattr(ctx, "factors", None)
         _check_stamp(ctx, "LULinearPermuteFn")
         D_ = x.shape[1]
-        g_acc = gld if ctx.has_acc else None            # the running log-density passes its cotangent straight through
-        if ctx.has_acc and ctx.acc < 0 and gld is not None:
-            gld = -gld
+        gld, g_acc = _ld_cotangents(ctx, gld)
+        grads = functools.partial(_grads, LULinearPermuteFn.forward, ld_acc=g_acc)
         if fac is not None and ctx.direction == 0:
             # the density direction of the training step, all on hand-written kernels: three row mat-vecs, two split-K batch
             # reductions, one launch for the packed parameter gradients
             Lm, Um, diag, Up, LT, UpT = fac
-            gy = torch.zeros_like(y) if gy is None else gy.contiguous()
-            from . import config
-            if config.lu_bwd_fused and D_ == 64 and gy.shape[0] % 64 == 0 and gy.shape[0] >= 1024 and u_saved is not None:
+            gy = _gy_or_zeros(gy, y).contiguous()
+            if _config.lu_bwd_fused and D_ == 64 and gy.shape[0] % 64 == 0 and gy.shape[0] >= 1024 and u_saved is not None:
                 # both row products and both batch reductions in one pass over the rows (nf_lu_bwd)
                 # (gradients go straight to their destinations: views of dp.FlatParameters' buffer when registered, _gradbuf.py)
                 gx, gL, g_bias, gUx = ops.lu_bwd(gy, u_saved, x, Lm, Up, db_out=_gradbuf.out(bias))
-                g_lower, g_upper, g_udiag = ops.lu_param_grads(gL, gUx, gld, udiag_raw.detach(), lower_entries.numel(),
-                                                               eps=ctx.eps, sign=1.0, perm=perm,
-                                                               out=(_gradbuf.out(lower_entries), _gradbuf.out(upper_entries),
-                                                                    _gradbuf.out(udiag_raw)))
-                return gx, None, g_lower, g_upper, g_udiag, g_bias, None, None, g_acc, None, None, None
-            if config.lu_matvec2 and D_ <= 64:
-                gu, gx, _ = ops.rows_matvec2(gy, LT, UpT)   # d/du = L^T gy, d/dx = P (U^T gu): one launch
+                out = dict(out=(_gradbuf.out(lower_entries), _gradbuf.out(upper_entries), _gradbuf.out(udiag_raw)))
             else:
-                gu = ops.rows_matvec(gy, LT)
-                gx = ops.rows_matvec(gu, UpT)
-            # gy^T u (+ the column sums of gy = the bias gradient) and gu^T x as ONE pair launch; gU = (gu^T x)[:, perm] is
-            # taken through perm inside nf_lu_param_grads
-            from . import config
-            if config.wgrad_pair and gy.shape[0] >= 1024:
-                gL, g_bias, gUx, _ = ops.linear_wgrad_pair(gy, u_saved, gu, x)
-            else:
-                gL, g_bias = _batch_outer(gy, u_saved, want_colsum=True)
-                gUx, _ = _batch_outer(gu, x)
-            g_lower, g_upper, g_udiag = ops.lu_param_grads(gL, gUx, gld, udiag_raw.detach(), lower_entries.numel(),
-                                                           eps=ctx.eps, sign=1.0, perm=perm)
-            return gx, None, g_lower, g_upper, g_udiag, g_bias, None, None, g_acc, None, None, None
+                out = {}
+                if _config.lu_matvec2 and D_ <= 64:
+                    gu, gx, _ = ops.rows_matvec2(gy, LT, UpT)   # d/du = L^T gy, d/dx = P (U^T gu): one launch
+                else:
+                    gu = ops.rows_matvec(gy, LT)
+                    gx = ops.rows_matvec(gu, UpT)
+                # gy^T u (+ the column sums of gy = the bias gradient) and gu^T x as ONE pair launch; gU = (gu^T x)[:, perm] is
+                # taken through perm inside nf_lu_param_grads
+                if _config.wgrad_pair and gy.shape[0] >= 1024:
+                    gL, g_bias, gUx, _ = ops.linear_wgrad_pair(gy, u_saved, gu, x)
+                else:
+                    gL, g_bias = _batch_outer(gy, u_saved, want_colsum=True)
+                    gUx, _ = _batch_outer(gu, x)
+            g_lower, g_upper, g_udiag = ops.lu_param_grads(gL, gUx, gld, udiag_raw.detach(), lower_entries.numel(), eps=ctx.eps,
+                                                           sign=1.0, perm=perm, **out)
+            return grads(x=gx, lower_entries=g_lower, upper_entries=g_upper, udiag_raw=g_udiag, bias=g_bias)
         li, ui = _tri_indices(D_, x.device)
         if fac is not None:
             Lm, Um, diag, Up_saved = fac[:4]
@@ -304,9 +346,7 @@ class LULinearPermuteFn(torch.autograd.Function):
             Up_saved = None
         sig = torch.sigmoid(udiag_raw)
         sig = torch.where(udiag_raw > 20, torch.ones_like(sig), sig)  # softplus threshold
-        if gy is None:
-            gy = torch.zeros_like(y)
-        gy = gy.contiguous()
+        gy = _gy_or_zeros(gy, y).contiguous()
         gl_sum = gld.sum() if gld is not None else torch.zeros((), dtype=x.dtype, device=x.device)
         D = x.shape[1]
         # Row-wise products with the D x D factors run on nf_rows_matvec (exact-fp32 MFMA, csrc/rows_matvec.hip) -- no library
@@ -348,7 +388,7 @@ class LULinearPermuteFn(torch.autograd.Function):
         g_lower = gL[li[0], li[1]]
         g_upper = gU[ui[0], ui[1]]
         g_udiag = gdiag * sig
-        return gx, None, g_lower, g_upper, g_udiag, g_bias, None, None, g_acc, None, None, None
+        return grads(x=gx, lower_entries=g_lower, upper_entries=g_upper, udiag_raw=g_udiag, bias=g_bias)
 
 
 class DiagGaussianLogProbFn(torch.autograd.Function):
@@ -412,6 +452,26 @@ def linear(x, weight, bias):
     return torch.nn.functional.linear(x, weight, bias)
 
 
+def _block_tensors(blk, nb, cols):
+    """Detached entries `cols` (0, 2: the weights; 1, 3: the biases) of every residual block's (w1, b1, w2, b2) in `blk`."""
+    return [blk[4 * b + j].detach() for b in range(nb) for j in cols]
+
+
+def _train_dest(blk, **params):
+    """Where a one-call backward (ops.coupling_train_bwd / pair_train_bwd) writes every gradient, under the NAME the parameter has
+    in the Function's forward: a view of dp.FlatParameters' flat buffer when the parameter is registered there (_gradbuf.py)."""
+    coupling = ("w0", "b0", "wf", "bf", "uw", "uh", "ud")
+    dest = {k: _gradbuf.out(params.pop(k)) for k in coupling}
+    dest["blocks"] = [_gradbuf.out(p_) for p_ in blk]
+    dest.update((k, _gradbuf.out(p_)) for k, p_ in params.items())
+    return dest
+
+
+def _dest_grads(forward, gx, g_acc, dest):
+    """The return tuple of a one-call backward: every destination of _train_dest at its parameter's position."""
+    return _grads(forward, dest["blocks"], x=gx, ld_acc=g_acc, **{k: g for k, g in dest.items() if k != "blocks"})
+
+
 class CouplingTrainFn(torch.autograd.Function):
     """A whole CoupledRationalQuadraticSpline layer of the benchmark shape under autograd (density direction): ONE forward launch
     (nf_rqs_fused_train_full_fwd: initial layer, residual blocks, final layer, spline -- exactly the inference kernel -- writing
@@ -425,25 +485,18 @@ class CouplingTrainFn(torch.autograd.Function):
     def forward(ctx, x, w0, b0, wf, bf, uw, uh, ud, iidx, tidx, blob, parity, kw, wfull, wpad, ld_acc, acc, *blk):
         nb = len(blk) // 4
         _gradbuf.use((w0, b0, wf, bf, uw, uh, ud) + blk)
-        wb = [blk[4 * i + j].detach() for i in range(nb) for j in (0, 2)]
-        bb = [blk[4 * i + j].detach() for i in range(nb) for j in (1, 3)]
-        fk = dict(tail_bound=kw["tail_bound"], min_bin_width=kw["min_bin_width"], min_bin_height=kw["min_bin_height"],
-                  min_derivative=kw["min_derivative"])
+        wb, bb = _block_tensors(blk, nb, (0, 2)), _block_tensors(blk, nb, (1, 3))
+        fk = _spline_kw(kw)
         # the same launch leaves wfull / wpad (the zero-padded weight images of the backward's products) current
         if not kw.get("prepacked"):
             ops.rqs_fused_pack_all(blob, w0.detach(), b0.detach(), wb, bb, wf.detach(), bf.detach(), uw.detach(), uh.detach(),
                                    ud.detach(), wfull=wfull, wpad=wpad, identity_idx=iidx, **fk)
-        y, ld, cond24, acts = ops.rqs_fused_train_full_fwd(x, blob, parity, nb, logdet=ld_acc,
-                                                           acc=None if ld_acc is None else (L.LD_ADD if acc > 0 else L.LD_SUB), **fk)
-        if ld_acc is not None:
-            ctx.mark_dirty(ld_acc)
+        y, ld, cond24, acts = ops.rqs_fused_train_full_fwd(x, blob, parity, nb, logdet=ld_acc, acc=_ld_mode(ctx, ld_acc, acc), **fk)
         ctx.save_for_backward(x, cond24, acts, w0, wf, uw, uh, ud, iidx, tidx, *blk)
-        ctx.kw, ctx.wfull, ctx.wpad, ctx.acc, ctx.has_acc, ctx.nb = kw, wfull, wpad, acc, ld_acc is not None, nb
+        ctx.kw, ctx.wfull, ctx.wpad, ctx.nb = kw, wfull, wpad, nb
         ctx.biases = (b0, bf)       # (identity only: where their gradients are written, _gradbuf.out)
         ctx.blob, ctx.parity = blob, parity
-        ctx.holder, ctx.stamp = kw.get("holder"), ("full",) + _stamp(w0, b0, wf, bf, uw, uh, ud, *blk)
-        if ctx.holder is not None:
-            ctx.holder["stamp"] = ctx.stamp
+        _record_stamp(ctx, kw.get("holder"), ("full",), w0, b0, wf, bf, uw, uh, ud, *blk)
         return y, ld
 
     @staticmethod
@@ -451,26 +504,19 @@ class CouplingTrainFn(torch.autograd.Function):
         x, cond24, acts, w0, wf, uw, uh, ud, iidx, tidx, *blk = ctx.saved_tensors
         _check_stamp(ctx, "CouplingTrainFn")
         kw, nb = ctx.kw, ctx.nb
-        if gy is None:
-            gy = torch.zeros_like(x)
-        if gld is None:
-            gld = torch.zeros(x.shape[0], dtype=x.dtype, device=x.device)
-        gld_own = -gld if (ctx.has_acc and ctx.acc < 0) else gld
+        gy = _gy_or_zeros(gy, x)
+        gld_own, g_acc = _ld_cotangents(ctx, _gld_or_zeros(gld, x))
         B, nT, H = x.shape[0], cond24.shape[1], wf.shape[1]
-        fk = dict(tail_bound=kw["tail_bound"], min_bin_width=kw["min_bin_width"], min_bin_height=kw["min_bin_height"],
-                  min_derivative=kw["min_derivative"])
+        fk = _spline_kw(kw)
         if (_config.train_bwd_onecall and _config.final_bwd_fused and _config.resblock_bwd and 1 <= nb <= 5 and B % 64 == 0
                 and H == 128 and x.shape[1] == 64):
             # round 6: the layer's whole backward behind one call -- four passes over the rows, ONE reduction launch, every gradient
             # written straight to its destination (a view of dp.FlatParameters' flat buffer when the parameter is registered there)
             b0, bf = ctx.biases
-            dest = dict(w0=_gradbuf.out(w0), b0=_gradbuf.out(b0), wf=_gradbuf.out(wf), bf=_gradbuf.out(bf), uw=_gradbuf.out(uw),
-                        uh=_gradbuf.out(uh), ud=_gradbuf.out(ud), blocks=[_gradbuf.out(p_) for p_ in blk])
-            gx = ops.coupling_train_bwd(x, gy, gld_own, cond24, acts, ctx.wpad, ctx.blob, ctx.wfull,
-                                        [blk[4 * b + j].detach() for b in range(nb) for j in (0, 2)], uw.detach(), uh.detach(),
-                                        ud.detach(), kw["col_map"], iidx.numel(), ctx.parity, nb, dest, **fk)
-            return (gx, dest["w0"], dest["b0"], dest["wf"], dest["bf"], dest["uw"], dest["uh"], dest["ud"], None, None, None, None,
-                    None, None, None, (gld if ctx.has_acc else None), None, *dest["blocks"])
+            dest = _train_dest(blk, w0=w0, b0=b0, wf=wf, bf=bf, uw=uw, uh=uh, ud=ud)
+            gx = ops.coupling_train_bwd(x, gy, gld_own, cond24, acts, ctx.wpad, ctx.blob, ctx.wfull, _block_tensors(blk, nb, (0, 2)),
+                                        uw.detach(), uh.detach(), ud.detach(), kw["col_map"], iidx.numel(), ctx.parity, nb, dest, **fk)
+            return _dest_grads(CouplingTrainFn.forward, gx, g_acc, dest)
         if _config.final_bwd_fused:
             # ONE pass over the rows: spline backward on the vector ALU, its gradient rows straight into the MFMAs of the final
             # layer's input gradient (nf_final_bwd; ctx.wpad = the transposed stage image the forward's pack launch left)
@@ -506,8 +552,7 @@ class CouplingTrainFn(torch.autograd.Function):
             gx.addmm_(gh, ctx.wfull.t())                           # + the conditioner's input gradient on the identity columns
             gw0f, gb0 = ops.linear_wgrad(gh, x, want_bias=True)
             gw0 = gw0f.index_select(1, iidx)
-        return (gx, gw0, gb0, gwf, gbf, guw, guh, gud, None, None, None, None, None, None, None,
-                (gld if ctx.has_acc else None), None, *gblk)
+        return _grads(CouplingTrainFn.forward, gblk, x=gx, w0=gw0, b0=gb0, wf=gwf, bf=gbf, uw=guw, uh=guh, ud=gud, ld_acc=g_acc)
 
 
 def _pair_side_ok(params, dests):
@@ -532,19 +577,13 @@ class PairTrainFn(torch.autograd.Function):
                 wfull, wpad, ld_acc, acc, *blk):
         nb = len(blk) // 4
         _gradbuf.use((w0, b0, wf, bf, uw, uh, ud, lower, upper, udiag, lbias) + blk)
-        fk = dict(tail_bound=kw["tail_bound"], min_bin_width=kw["min_bin_width"], min_bin_height=kw["min_bin_height"],
-                  min_derivative=kw["min_derivative"])
-        xlu, y, ld, cond24, acts = ops.rqs_fused_train_pair_fwd(x, blob, parity, nb, logdet=ld_acc,
-                                                                acc=None if ld_acc is None else (L.LD_ADD if acc > 0 else L.LD_SUB), **fk)
-        if ld_acc is not None:
-            ctx.mark_dirty(ld_acc)
+        xlu, y, ld, cond24, acts = ops.rqs_fused_train_pair_fwd(x, blob, parity, nb, logdet=ld_acc, acc=_ld_mode(ctx, ld_acc, acc),
+                                                                **_spline_kw(kw))
         ctx.save_for_backward(x, xlu, cond24, acts, perm, lower, upper, udiag, w0, wf, uw, uh, ud, iidx, *blk)
-        ctx.kw, ctx.wfull, ctx.wpad, ctx.acc, ctx.has_acc, ctx.nb = kw, wfull, wpad, acc, ld_acc is not None, nb
+        ctx.kw, ctx.wfull, ctx.wpad, ctx.nb = kw, wfull, wpad, nb
         ctx.blob, ctx.parity, ctx.biases = blob, parity, (b0, bf, lbias)
         ctx.lu = (lu_eps, lu_fbuf, lu_wd)
-        ctx.holder, ctx.stamp = kw.get("holder"), ("pair",) + _stamp(lower, upper, udiag, lbias, w0, b0, wf, bf, uw, uh, ud, *blk)
-        if ctx.holder is not None:
-            ctx.holder["stamp"] = ctx.stamp
+        _record_stamp(ctx, kw.get("holder"), ("pair",), lower, upper, udiag, lbias, w0, b0, wf, bf, uw, uh, ud, *blk)
         return y, ld
 
     @staticmethod
@@ -552,18 +591,11 @@ class PairTrainFn(torch.autograd.Function):
         x, xlu, cond24, acts, perm, lower, upper, udiag, w0, wf, uw, uh, ud, iidx, *blk = ctx.saved_tensors
         _check_stamp(ctx, "PairTrainFn")
         kw, nb = ctx.kw, ctx.nb
-        if gy is None:
-            gy = torch.zeros_like(x)
-        if gld is None:
-            gld = torch.zeros(x.shape[0], dtype=x.dtype, device=x.device)
-        gld_own = -gld if (ctx.has_acc and ctx.acc < 0) else gld
-        fk = dict(tail_bound=kw["tail_bound"], min_bin_width=kw["min_bin_width"], min_bin_height=kw["min_bin_height"],
-                  min_derivative=kw["min_derivative"])
+        gy = _gy_or_zeros(gy, x)
+        gld_own, g_acc = _ld_cotangents(ctx, _gld_or_zeros(gld, x))
         b0, bf, lbias = ctx.biases
         lu_eps, lu_fbuf, lu_wd = ctx.lu
-        dest = dict(w0=_gradbuf.out(w0), b0=_gradbuf.out(b0), wf=_gradbuf.out(wf), bf=_gradbuf.out(bf), uw=_gradbuf.out(uw),
-                    uh=_gradbuf.out(uh), ud=_gradbuf.out(ud), blocks=[_gradbuf.out(p_) for p_ in blk], lower=_gradbuf.out(lower),
-                    upper=_gradbuf.out(upper), udiag=_gradbuf.out(udiag), lbias=_gradbuf.out(lbias))
+        dest = _train_dest(blk, w0=w0, b0=b0, wf=wf, bf=bf, uw=uw, uh=uh, ud=ud, lower=lower, upper=upper, udiag=udiag, lbias=lbias)
         D = x.shape[1]
         Lm, Um = lu_fbuf[:D * D].view(D, D), lu_fbuf[D * D:2 * D * D].view(D, D)
         # The last two of the seven launches only produce parameter gradients: on the side stream when nobody can read them before the
@@ -577,17 +609,13 @@ class PairTrainFn(torch.autograd.Function):
                 side = _sidestream.stream(x.device)
         # ONE C-ABI call, seven launches: the coupling's four passes, the composed LU's pass, one reduction for both, the LU's factors
         # (two calls when the last two launches go to the side stream)
-        gx = ops.pair_train_bwd(x, xlu, gy, gld_own, cond24, acts, ctx.wpad, ctx.blob, ctx.wfull,
-                                [blk[4 * b + j].detach() for b in range(nb) for j in (0, 2)], uw.detach(), uh.detach(), ud.detach(),
-                                kw["col_map"], iidx.numel(), ctx.parity, nb, lu_wd, Lm, Um, perm, udiag.detach(), lu_eps, dest, side=side,
-                                **fk)
+        gx = ops.pair_train_bwd(x, xlu, gy, gld_own, cond24, acts, ctx.wpad, ctx.blob, ctx.wfull, _block_tensors(blk, nb, (0, 2)),
+                                uw.detach(), uh.detach(), ud.detach(), kw["col_map"], iidx.numel(), ctx.parity, nb, lu_wd, Lm, Um, perm,
+                                udiag.detach(), lu_eps, dest, side=side, **_spline_kw(kw))
         if side is not None:
             _sidestream.mark(x.device)
             _sidestream.queue_join()
-        g_lower, g_upper, g_udiag, g_lbias = dest["lower"], dest["upper"], dest["udiag"], dest["lbias"]
-        return (gx, None, g_lower, g_upper, g_udiag, g_lbias, None, None, None, dest["w0"], dest["b0"], dest["wf"], dest["bf"],
-                dest["uw"], dest["uh"], dest["ud"], None, None, None, None, None, None, None, (gld if ctx.has_acc else None), None,
-                *dest["blocks"])
+        return _dest_grads(PairTrainFn.forward, gx, g_acc, dest)
 
 
 class IdentLinearFn(torch.autograd.Function):
@@ -634,8 +662,7 @@ class ResidualBlockFn(torch.autograd.Function):
         gy = gy.contiguous()
         # gt = (gy W2) * (t > 0);  gx = gy + (gt W1) * (x > 0)
         gt, gx = ops.rows_block(gy, w2.detach(), None, w1.detach(), None, trans=True, mask1=t, mask2=x, relu=False)
-        from . import config
-        if config.wgrad_pair:
+        if _config.wgrad_pair:
             gw2, gb2, gw1, gb1 = ops.linear_wgrad_pair(gy, t, gt, x, relu_x=True)     # both layers: one launch + one reduction
         else:
             gw2, gb2 = ops.linear_wgrad(gy, t, want_bias=True, relu_x=True)
@@ -688,9 +715,7 @@ class MaskedAffineFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy, gld):
         z, b, s, t = ctx.saved_tensors
-        if gy is None:
-            gy = torch.zeros_like(z)
-        gz, gs, gt = ops.masked_affine_bwd(z, b, s, t, gy, gld, ctx.direction)     # csrc/affine_bwd.hip
+        gz, gs, gt = ops.masked_affine_bwd(z, b, s, t, _gy_or_zeros(gy, z), gld, ctx.direction)     # csrc/affine_bwd.hip
         return gz, None, gs, gt, None
 
 
@@ -756,8 +781,7 @@ class AffineCouplingFn(torch.autograd.Function):
     def backward(ctx, gy, gld):
         z, param = ctx.saved_tensors
         c1, flip, scale_map, direction = ctx.cfg
-        if gy is None:
-            gy = torch.zeros_like(z)
+        gy = _gy_or_zeros(gy, z)
         if z.dim() < 2 or scale_map not in L.SCALE:
             gz, gp = _vjp(lambda z_, p_: _coupling_formula(z_, p_, *ctx.cfg), (z, param), (gy, gld))
         else:
@@ -779,9 +803,7 @@ class ActNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy, gld):
         z, s, t = ctx.saved_tensors
-        if gy is None:
-            gy = torch.zeros_like(z)
-        gz, gs, gt = ops.actnorm_bwd(z, s.detach(), t.detach(), gy, gld, ctx.direction)   # csrc/affine_bwd.hip
+        gz, gs, gt = ops.actnorm_bwd(z, s.detach(), t.detach(), _gy_or_zeros(gy, z), gld, ctx.direction)   # csrc/affine_bwd.hip
         return gz, gs.view_as(s), gt.view_as(t), None
 
 
@@ -801,8 +823,7 @@ class Inv1x1WeightFn(torch.autograd.Function):
     @once_differentiable          # (the backward is a set of kernels, not a differentiable graph: double backward raises)
     def backward(ctx, gW, gl):
         P, Lm, U, sign_S, log_S = ctx.saved_tensors
-        if gW is None:
-            gW = torch.zeros_like(Lm)
+        gW = _gy_or_zeros(gW, Lm)
         # (gW / gl may come from Inv1x1Fn's side-stream launch: stay on that stream, or join before reading them)
         side = _leaf_fork(Lm.device, (Lm, U, log_S), keep=(gW, gl))
         if side is None:
@@ -851,7 +872,7 @@ class Inv1x1WeightsFn(torch.autograd.Function):
         n = ctx.n
         layers = [tuple(t.detach() for t in tensors[5 * i:5 * i + 5]) for i in range(n)]
         _sidestream.join()          # (a gW may come from Inv1x1Fn's side-stream launch, config.train_leaf_async)
-        gWs = [grads[2 * i] if grads[2 * i] is not None else torch.zeros_like(layers[i][1]) for i in range(n)]
+        gWs = [_gy_or_zeros(grads[2 * i], layers[i][1]) for i in range(n)]
         gls = [grads[2 * i + 1] for i in range(n)]
         res = ops.inv1x1_lu_grads_multi(layers, gWs, gls)
         out = [None]
@@ -891,8 +912,7 @@ class Inv1x1Fn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy, gld):
         z, W, ldu = ctx.saved_tensors
-        if gy is None:
-            gy = torch.zeros_like(z)
+        gy = _gy_or_zeros(gy, z)
         gz = gW = gl = None
         if z.shape[1] <= 64:
             if ctx.needs_input_grad[0]:      # gz = W^T gy per pixel: the forward kernel reading W transposed (no copy)
@@ -985,9 +1005,7 @@ class MadeFn(torch.autograd.Function):
         if any(ctx.needs_input_grad[3:]):
             flat = ops.made_wgrad(gout, x, G, save, bwd["wtable"], bwd["stable"], bwd["mask"], bwd["ntiles"], bwd["nflat"],
                                   bwd["Mp"], bwd["Dx"])
-            for k, (woff, shape, boff, n) in enumerate(bwd["offsets"]):
-                grads[2 * k] = flat[woff:woff + shape[0] * shape[1]].view(shape)
-                grads[2 * k + 1] = flat[boff:boff + n]
+            grads = _made_param_grads(flat, bwd["offsets"])
         return (None, None, gx if ctx.needs_input_grad[2] else None) + tuple(grads)
 
 
@@ -1020,10 +1038,7 @@ class ResNetCtxFn(torch.autograd.Function):
             flat = ops.resnet_ctx_wgrad(gout, save, G, table, jobs, st)
             for k, (off, shape) in enumerate(zip(st["poff"], st["shapes"])):
                 if need[3 + k]:
-                    n = 1
-                    for d in shape:
-                        n *= d
-                    grads[k] = flat[off:off + n].view(shape)
+                    grads[k] = _carve(flat, off, shape)
         return (None, gx if need[1] else None, gc if need[2] else None) + tuple(grads)
 
 
@@ -1069,11 +1084,11 @@ class ConvNetFn(torch.autograd.Function):
             flat = ops.made_wgrad(gP, col, G, save, bwd["wtable"], bwd["stable"], bwd["mask"], bwd["ntiles"], bwd["nflat"], bwd["Mp"],
                                   bwd["Dx"], rows=R)
             gb3 = ops.channel_sum(gout)
-        (o0, s0, c0, n0), (o1, s1, c1, n1), (o2, s2, _, _) = bwd["offsets"]
+        (o0, _, c0, n0), (o1, _, c1, n1), (o2, _, _, _) = bwd["offsets"]
         # (the reduction scatters straight into the conv parameters' own (o, c, ky, kx) layouts: made_pack.convnet_train_structure)
-        gw1 = flat[o0:o0 + s0[0] * s0[1]].view(hid, Cin, 3, 3)
-        gw2 = flat[o1:o1 + s1[0] * s1[1]].view(hid, hid, 1, 1)
-        gw3 = flat[o2:o2 + s2[0] * s2[1]].view(Cout, hid, 3, 3)
+        gw1 = _carve(flat, o0, (hid, Cin, 3, 3))
+        gw2 = _carve(flat, o1, (hid, hid, 1, 1))
+        gw3 = _carve(flat, o2, (Cout, hid, 3, 3))
         return None, None, gx, gw1, flat[c0:c0 + n0], gw2, flat[c1:c1 + n1], gw3, gb3
 
 
@@ -1137,8 +1152,7 @@ class MafInverseFn(torch.autograd.Function):
         x = ctx.saved_tensors[0]
         fwd, bwd = ctx.fwd, ctx.bwd
         B, D = x.shape
-        gx = torch.zeros_like(x) if gx is None else gx.contiguous()
-        gld = torch.zeros(B, dtype=x.dtype, device=x.device) if gld is None else gld.contiguous()
+        gx, gld = _gy_or_zeros(gx, x).contiguous(), _gld_or_zeros(gld, x).contiguous()
         fpack = getattr(ctx, "fpack", None)
         if ctx.tpack is not None and fpack is not None and ctx.tpack[4] is not None:
             # round 5: nothing of MADE runs forward again -- `save` (the linears' inputs) from the inverse pass's own scratch, the
@@ -1231,9 +1245,7 @@ class MafInverseFn(torch.autograd.Function):
                     _, G = ops.made_backward(gp, bits, bwd["blob"], bwd["table"], D, bwd["Hp"], bwd["NB"])
                 flat = ops.made_wgrad(gp, x, G, save, bwd["wtable"], bwd["stable"], bwd["mask"], bwd["ntiles"], bwd["nflat"], bwd["Mp"],
                                       bwd["Dx"])
-            for k, (woff, shape, boff, n) in enumerate(bwd["offsets"]):
-                grads[2 * k] = flat[woff:woff + shape[0] * shape[1]].view(shape)
-                grads[2 * k + 1] = flat[boff:boff + n]
+            grads = _made_param_grads(flat, bwd["offsets"])
         return (None, None, None, v if ctx.needs_input_grad[3] else None) + tuple(grads)
 
 
