@@ -34,7 +34,7 @@ typedef void *nf_stream_t; /* hipStream_t */
 enum { NF_OK = 0, NF_EIO = -5, NF_EFAULT = -14, NF_EINVAL = -22, NF_ERANGE = -34, NF_ENOTSUP = -95 };
 enum { NF_F32 = 0, NF_F64 = 1 };
 enum { NF_LD_WRITE = 0, NF_LD_ADD = 1, NF_LD_SUB = -1 };
-enum { NF_TAILS_NONE = 0, NF_TAILS_LINEAR = 1, NF_TAILS_CIRCULAR = 2, NF_TAILS_FEATURE = 3 /* nf_rqs_coupling_ft only */ };
+enum { NF_TAILS_NONE = 0, NF_TAILS_LINEAR = 1, NF_TAILS_CIRCULAR = 2, NF_TAILS_FEATURE = 3 /* nf_rqs_coupling_ft, nf_arnsf_inverse_ft only */ };
 enum { NF_SCALE_EXP = 0, NF_SCALE_SIGMOID = 1, NF_SCALE_SIGMOID_INV = 2, NF_SCALE_NONE = 3 };
 enum { NF_RQS_DENSITY = 0, NF_RQS_SAMPLE_IDENTITY = 1, NF_RQS_SAMPLE_TRANSFORM = 2 };
 
@@ -858,6 +858,23 @@ int nf_maf_scratch_layer(const void *scratch, const int32_t *pos_of_col, void *o
 int nf_arnsf_inverse(const void *z, void *y, void *logdet, const void *blob, const int32_t *table, void *scratch,
                      int64_t B, int D, int hidden_padded, int K, int tails, double tail_bound, double min_bin_width,
                      double min_bin_height, double min_derivative, int acc, nf_stream_t stream);
+/* The same one-pass inverse with everything that may differ from feature to feature read from a per-feature table: the layers whose
+ * MADE has a permuted mask (nets/made.py:250-252 with permute_mask: the input degrees are a permutation of 1..D), per-feature tails
+ * or a tensor tail bound (neural_spline/autoregressive.py:44-55, :94-134 over utils/splines.py:48-66) and the periodic preprocessing
+ * of the circular coordinates in front of the conditioner (utils/nn.py:64-129, Identity activation) -- what
+ * CircularAutoregressiveRationalQuadraticSpline (neural_spline/wrapper.py:247-311) builds.  The schedule walks the features in DEGREE
+ * order: step f reads column col[f] of z, inverts that feature's spline, writes column col[f] of y and feeds the conditioner
+ * w_sin sin(scale x) + w_cos cos(scale x) + bias for a periodic feature, x itself otherwise.
+ *   blob, table, ftable : maf_pack.pack_made(made, mult, rows=True, features=(tails, tail_bound)); ftable = 8 rows of D 32-bit words
+ *                 in degree order (layout documented there): column, tails code, bound, scale, w_sin, w_cos, bias, periodic flag.
+ *   tails       : NF_TAILS_FEATURE: the table's code per feature (NF_TAILS_LINEAR | NF_TAILS_CIRCULAR), K + 1 derivative logits per
+ *                 feature (mult = 3K+1), inputs outside a feature's interval give 0 with log-det 0 (utils/splines.py:48-57);
+ *                 NF_TAILS_NONE | _LINEAR | _CIRCULAR: that type for every feature, mult as for nf_arnsf_inverse.  The tail bound is
+ *                 always the table's (per feature); mult <= 32, otherwise NF_ENOTSUP.
+ *   scratch, z, y, logdet, acc, min_* : as nf_arnsf_inverse (scratch: nf_maf_inverse_scratch_floats). */
+int nf_arnsf_inverse_ft(const void *z, void *y, void *logdet, const void *blob, const int32_t *table, const void *ftable,
+                        void *scratch, int64_t B, int D, int hidden_padded, int K, int tails, double min_bin_width,
+                        double min_bin_height, double min_derivative, int acc, nf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * GlowBlock conditioner in one launch.  Replaces ConvNet2d.forward (normflows/nets/cnn.py:5-63) for the network

@@ -276,12 +276,27 @@ static inline size_t arnsf_lds_floats(int R) {
     return (size_t)MW * MT * 64 + 5 * MT + MT * MS + 4 * MT * MT + MS * MT + (size_t)MS * R * MT;
 }
 
+// Per-feature table of the FT variant (flows/maf_pack.py): 8 rows of D 32-bit words, feature f of the schedule = degree f + 1.
+enum { FT_COL = 0, FT_TAILS, FT_BOUND, FT_SCALE, FT_WSIN, FT_WCOS, FT_BIAS, FT_PERIODIC };
+
+// What the conditioner reads of a finished feature (nets/made.py:250-252: every pass starts with the preprocessing): the periodic
+// features of utils/nn.py:64-129 for a circular coordinate, the value itself otherwise.  The table reads have wave-uniform addresses.
+// sinf / cosf, not the fast intrinsics: the reference evaluates torch.sin / torch.cos.
+__device__ __forceinline__ float ft_feed(const float *__restrict__ ft, int D, int f, float x) {
+    if (__float_as_int(ft[FT_PERIODIC * D + f]) == 0) return x;
+    const float a = ft[FT_SCALE * D + f] * x;
+    return ft[FT_WSIN * D + f] * sinf(a) + ft[FT_WCOS * D + f] * cosf(a) + ft[FT_BIAS * D + f];
+}
+
 // SPL = false: affine element (MAF); true: rational-quadratic spline element with `sp` and R final rows per feature.
-template <bool SPL>
+// FT (with SPL): the schedule's feature f lives in column ft[FT_COL][f] of z and y, its tails type (sp.dfull) and bound come from the
+// table (rqs_feature_params) and the conditioner is fed ft_feed of it -- permuted masks, per-feature tails, circular coordinates.
+template <bool SPL, bool FT = false>
 __global__ void __launch_bounds__(64 * MW)
 maf_inverse_kernel(const float *__restrict__ z, float *__restrict__ y, float *__restrict__ logdet,
                    const float *__restrict__ blob, const int *__restrict__ table, float *S, float *Xs, float *Ps, int64_t B,
-                   int acc, RqsParams<float> sp, int R) {
+                   int acc, RqsParams<float> sp, int R, const float *__restrict__ ftable) {
+    static_assert(SPL || !FT, "the per-feature table belongs to the spline variant");
     __shared__ float lds[SPL ? 1 : MW][SPL ? 4 : MT * 64];
     __shared__ __attribute__((aligned(16))) float seqs[SPL ? 4 : M_SEQ];  // the tile's biases and diagonal blocks, shared by the 4 waves
     extern __shared__ __attribute__((aligned(16))) float dyn[];            // spline variant: everything lives here
@@ -305,17 +320,29 @@ maf_inverse_kernel(const float *__restrict__ z, float *__restrict__ y, float *__
     float *Xw = Xs + wts * ((int64_t)Dp * 64);      // [Dp/8][2][64][4]
     float *Pw = Ps ? Ps + wts * ((int64_t)5 * MT * 64) : nullptr;   // pair stash: [product][8][64][4] raw accumulators
     float ld = 0.0f, xcarry;
+    // FT: the columns, and where the launch has them per feature the tails types and bounds, in degree order
+    const int *ftc = reinterpret_cast<const int *>(ftable) + FT_COL * D;
+    const int *ftt = FT && sp.dfull ? reinterpret_cast<const int *>(ftable) + FT_TAILS * D : nullptr;
+    const float *ftb = FT && sp.tails != NF_TAILS_NONE ? ftable + FT_BOUND * D : nullptr;
+    (void)ftc; (void)ftt; (void)ftb;
+    int col0 = 0;
     if constexpr (SPL) {   // feature 0 depends on no hidden unit: its parameters are the final layer's bias
         const int K = sp.K;
-        float lad;
-        rqs_element<float>(sp, zr[0], [&](int k) { return blob[k]; }, [&](int k) { return blob[K + k]; },
-                           [&](int j) { return blob[2 * K + j]; }, true, xcarry, lad);
+        float lad, x0;
+        if constexpr (FT) col0 = ftc[0];
+        rqs_element<float>(FT ? rqs_feature_params(sp, ftt, ftb, 0) : sp, zr[col0], [&](int k) { return blob[k]; },
+                           [&](int k) { return blob[K + k]; }, [&](int j) { return blob[2 * K + j]; }, true, x0, lad);
         ld += lad;
+        if constexpr (FT) {
+            if (valid) y[sample * D + col0] = x0;
+            x0 = ft_feed(ftable, D, 0, x0);
+        }
+        xcarry = x0;
     } else {
         maf_finish(blob[0], blob[1], zr[0], xcarry, ld);
     }
     if (active) Xw[lane * 4] = xcarry;
-    if (valid) y[sample * D] = xcarry;
+    if constexpr (!FT) if (valid) y[sample * D] = xcarry;
 
     for (int t = 0; t < T; ++t) {
         const int *te = table + M_HDR + M_ENT * t;
@@ -341,9 +368,11 @@ maf_inverse_kernel(const float *__restrict__ z, float *__restrict__ y, float *__
         const float *WFd = SPL ? Wd + 4 * MT * MT + ns * MT : Wd + 4 * MT * MT;
         const float *biasFs = Wd + 4 * MT * MT;                       // spline layout: [ns][32]
 
-        f32x16 zin;
+        f32x16 zin;          // (FT: every step loads its own column of z)
+        if constexpr (!FT) {
 #pragma unroll
-        for (int j = 0; j < MS; ++j) zin[j] = (j < ns) ? zr[dlo + j] : 0.0f;
+            for (int j = 0; j < MS; ++j) zin[j] = (j < ns) ? zr[dlo + j] : 0.0f;
+        }
 
         __threadfence_block();  // the activation scratch written by the other lanes of this wave is read below
         f32x32 p0, p1, p2, p3, p4, pF;
@@ -397,6 +426,12 @@ maf_inverse_kernel(const float *__restrict__ z, float *__restrict__ y, float *__
         for (int s = 0; s < ns; ++s) {
 #endif
             const unsigned m = (unsigned)te[4 + s];
+            int colf = dlo + s;
+            float zf = 0.0f;
+            if constexpr (FT) {   // requested here, needed after the five hidden layers of the step
+                colf = ftc[dlo + s];
+                zf = zr[colf];
+            }
             // initial layer: h0 = pre + W0[window] . x ; the residual h0 is folded into the pre-activation of block 1's
             // second linear (p2), p0 keeps relu(h0) = input of block 1's first linear
             for (unsigned mm = m; mm; mm &= mm - 1) {
@@ -458,11 +493,16 @@ maf_inverse_kernel(const float *__restrict__ z, float *__restrict__ y, float *__
                     }
                     const int K = sp.K;
                     float lad;
-                    rqs_element<float>(sp, zin[s], [&](int k) { return ldsw[k * 64 + lane]; },
+                    rqs_element<float>(FT ? rqs_feature_params(sp, ftt, ftb, dlo + s) : sp, FT ? zf : zin[s],
+                                       [&](int k) { return ldsw[k * 64 + lane]; },
                                        [&](int k) { return ldsw[(K + k) * 64 + lane]; },
                                        [&](int j) { return ldsw[(2 * K + j) * 64 + lane]; }, true, xn, lad);
                     ld += lad;
                     __builtin_amdgcn_wave_barrier();
+                    if constexpr (FT) {   // y keeps the feature, everything downstream (window, carry, feature scratch) its feed
+                        if (valid) y[sample * D + colf] = xn;
+                        xn = ft_feed(ftable, D, dlo + s, xn);
+                    }
                 } else {
                     float us, sh;
                     {
@@ -484,7 +524,7 @@ maf_inverse_kernel(const float *__restrict__ z, float *__restrict__ y, float *__
                 xcarry = xn;
                 const int f = dlo + s;
                 Xw[((size_t)((f >> 3) * 2 + ((f >> 2) & 1)) * 64 + lane) * 4 + (f & 3)] = xn;
-                if (valid) y[sample * D + f] = xn;
+                if constexpr (!FT) if (valid) y[sample * D + f] = xn;
             }
         }
         // ---- publish the tile: activations in B-operand order ----
@@ -538,7 +578,8 @@ extern "C" int nf_maf_inverse(const void *z, void *y, void *logdet, const void *
     if (nf::opt_in_lds(reinterpret_cast<const void *>(&nf::maf_inverse_kernel<false>), lds_ring, opted_aff) != NF_OK)
         return NF_ENOTSUP;
     hipLaunchKernelGGL(nf::maf_inverse_kernel<false>, dim3(grid), dim3(64 * nf::MW), lds_ring, st, (const float *)z, (float *)y,
-                       (float *)logdet, (const float *)blob, (const int *)table, S, Xs, Ps, B, acc, nf::RqsParams<float>{}, 2);
+                       (float *)logdet, (const float *)blob, (const int *)table, S, Xs, Ps, B, acc, nf::RqsParams<float>{}, 2,
+                       (const float *)nullptr);
     NF_CHECK_LAUNCH();
     return NF_OK;
 }
@@ -568,7 +609,40 @@ extern "C" int nf_arnsf_inverse(const void *z, void *y, void *logdet, const void
     if (nf::opt_in_lds(reinterpret_cast<const void *>(&nf::maf_inverse_kernel<true>), lds, opted) != NF_OK) return NF_ENOTSUP;
     const int grid = (int)((nwt + nf::MW - 1) / nf::MW);
     hipLaunchKernelGGL(nf::maf_inverse_kernel<true>, dim3(grid), dim3(64 * nf::MW), lds, st, (const float *)z, (float *)y,
-                       (float *)logdet, (const float *)blob, (const int *)table, S, Xs, (float *)nullptr, B, acc, sp, R);
+                       (float *)logdet, (const float *)blob, (const int *)table, S, Xs, (float *)nullptr, B, acc, sp, R,
+                       (const float *)nullptr);
+    NF_CHECK_LAUNCH();
+    return NF_OK;
+}
+
+extern "C" int nf_arnsf_inverse_ft(const void *z, void *y, void *logdet, const void *blob, const int32_t *table,
+                                   const void *ftable, void *scratch, int64_t B, int D, int hidden_padded, int K, int tails,
+                                   double min_bin_width, double min_bin_height, double min_derivative, int acc,
+                                   nf_stream_t stream) {
+    if (K < 1 || tails < NF_TAILS_NONE || tails > NF_TAILS_FEATURE) return NF_EINVAL;
+    if (min_bin_width * K > 1.0 || min_bin_height * K > 1.0) return NF_EINVAL;   // utils/splines.py:121-124
+    const int R = tails == NF_TAILS_LINEAR ? 3 * K - 1 : (tails == NF_TAILS_CIRCULAR ? 3 * K : 3 * K + 1);
+    if (R > nf::MT) return NF_ENOTSUP;
+    if (B < 0 || D < 2 || hidden_padded < 32 || hidden_padded % 32) return NF_EINVAL;
+    if (acc < NF_LD_SUB || acc > NF_LD_ADD) return NF_EINVAL;
+    if (B == 0) return NF_OK;
+    if (!z || !y || !logdet || !blob || !table || !ftable || !scratch) return NF_EFAULT;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nwt = (B + 63) / 64;
+    const int64_t Dp = (D + 31) / 32 * 32;
+    float *S = (float *)scratch;
+    float *Xs = S + nwt * 64 * (int64_t)5 * hidden_padded;
+    if (hipMemsetAsync(Xs, 0, (size_t)nwt * 64 * Dp * sizeof(float), st) != hipSuccess) return NF_EIO;
+    // the bound is the table's for every feature (rqs_feature_params); 1.0 only fills the launch-wide fields
+    auto sp = nf::make_rqs_params<float>(K, tails, 1.0, 0, 1, 0, 1, min_bin_width, min_bin_height, min_derivative, 1.0);
+    const size_t lds = nf::arnsf_lds_floats(R) * sizeof(float);
+    static nf::LdsOptIn opted;
+    if (nf::opt_in_lds(reinterpret_cast<const void *>(&nf::maf_inverse_kernel<true, true>), lds, opted) != NF_OK)
+        return NF_ENOTSUP;
+    const int grid = (int)((nwt + nf::MW - 1) / nf::MW);
+    hipLaunchKernelGGL((nf::maf_inverse_kernel<true, true>), dim3(grid), dim3(64 * nf::MW), lds, st, (const float *)z, (float *)y,
+                       (float *)logdet, (const float *)blob, (const int *)table, S, Xs, (float *)nullptr, B, acc, sp, R,
+                       (const float *)ftable);
     NF_CHECK_LAUNCH();
     return NF_OK;
 }

@@ -11,7 +11,10 @@ structures outside flows/made_pack.py, MADE's masked linears are library GEMMs o
 
 The inverse of MaskedAffineAutoregressive runs as ONE launch of nf_maf_inverse when
 the MADE has the supported structure (flows/maf_pack.py): every hidden unit is finalised once, total work = one MADE
-pass instead of D; the autoregressive spline layer (AR-NSF sampling) does the same through nf_arnsf_inverse.  Under autograd the
+pass instead of D; the autoregressive spline layer (AR-NSF sampling) does the same through nf_arnsf_inverse, and through
+nf_arnsf_inverse_ft when its mask is permuted, its tails or its tail bound are given per feature or circular coordinates put the
+periodic preprocessing in front of the conditioner (CircularAutoregressiveRationalQuadraticSpline: the kernel walks the features in
+degree order with a per-feature table, flows/maf_pack.py).  Under autograd the
 affine layer's inverse is differentiated implicitly (autograd.MafInverseFn: the one-pass kernel forward, chain sweeps + one
 weight-gradient launch backward); other structures, float64 and the spline layer's gradient-tracking inverse keep the reference's
 D-pass loop.
@@ -214,7 +217,9 @@ class MaskedPiecewiseRationalQuadraticAutoregressive(Autoregressive):
     3K-1 | 3K | 3K+1 numbers per feature (linear | circular | no tails); the element-wise spline and its row-summed
     log-det are ONE launch of nf_rqs_coupling with every column a transform column (no identity half).  The widths and
     heights are NOT divided by sqrt(hidden): the reference tests `hasattr(net, "hidden_features")` (:107-109) and its
-    MADE never sets that attribute."""
+    MADE never sets that attribute.  `inverse` (sampling) is one launch for the MADE structures flows/maf_pack.py takes:
+    nf_arnsf_inverse for scalar tails with a scalar bound on an unpermuted mask, nf_arnsf_inverse_ft for list tails (circular
+    coordinates, with their periodic preprocessing), a tensor tail bound or `permute_mask=True`; the D-pass loop otherwise."""
 
     def __init__(self, features, hidden_features, context_features=None, num_bins=10, tails=None, tail_bound=1.0,
                  num_blocks=2, use_residual_blocks=True, random_mask=False, permute_mask=False, activation=F.relu,
@@ -267,6 +272,33 @@ class MaskedPiecewiseRationalQuadraticAutoregressive(Autoregressive):
             self._arnsf_pack_cache = cache = (key, packed)
         return cache[1]
 
+    def _permuted(self):
+        """True when MADE's input degrees are not 1..D in column order (permute_mask; the final layer's degrees repeat them)."""
+        fin = self.autoregressive_net.final_layer
+        key = (fin.degrees.data_ptr(), fin.degrees._version)
+        c = self.__dict__.get("_perm_cache")
+        if c is None or c[0] != key:
+            deg = fin.degrees.cpu()
+            mult = max(deg.numel() // self.features, 1)
+            c = self.__dict__["_perm_cache"] = (key, not torch.equal(deg[::mult], torch.arange(1, self.features + 1)))
+        return c[1]
+
+    def _packed_ft(self, device):
+        """Device copies of the per-feature pack (rows layout + feature table, nf_arnsf_inverse_ft), rebuilt when a MADE parameter
+        (the periodic weights are among them) or the tail bound changes; None outside the kernel's structures."""
+        tb = self.tail_bound
+        key = _keys.pkey(list(self.autoregressive_net.parameters()) + ([tb] if torch.is_tensor(tb) else [])) + (str(device),)
+        cache = getattr(self, "_arnsf_ft_pack_cache", None)
+        if cache is None or cache[0] != key:
+            packed = maf_pack.pack_made(self.autoregressive_net, mult=self._output_dim_multiplier(), rows=True,
+                                        features=(self.tails, tb))
+            if packed is not None:
+                blob, table, ftable = packed
+                packed = (torch.from_numpy(blob).to(device), torch.from_numpy(table).to(device),
+                          torch.from_numpy(ftable).to(device), int(table[3]))
+            self._arnsf_ft_pack_cache = cache = (key, packed)
+        return cache[1]
+
     def forward(self, inputs, context=None):
         """Density direction (autoregressive.py:24-27 + neural_spline/autoregressive.py:94-134): MADE + the element-wise spline as
         ONE launch (nf_made_forward_spline) for 8 bins, linear tails, a scalar tail bound and the MADE structures
@@ -283,17 +315,25 @@ class MaskedPiecewiseRationalQuadraticAutoregressive(Autoregressive):
         return super().forward(inputs, context)
 
     def inverse(self, inputs, context=None):
-        """One launch of nf_arnsf_inverse for the supported MADE structure (scalar tails, float32, no context, no
-        sqrt(hidden) scaling, no gradient tracking); the reference's D-pass loop otherwise."""
+        """One launch for the supported MADE structure (float32, no context, no sqrt(hidden) scaling, no gradient tracking):
+        nf_arnsf_inverse for scalar tails with a scalar bound on an unpermuted mask; nf_arnsf_inverse_ft for list tails, a tensor
+        bound or a permuted mask (3K+1 <= 32 rows per feature with list tails); the reference's D-pass loop otherwise."""
         if (context is None and inputs.dim() == 2 and inputs.dtype == torch.float32 and inputs.is_cuda
-                and (self.tails is None or isinstance(self.tails, str)) and not torch.is_tensor(self.tail_bound)
                 and not hasattr(self.autoregressive_net, "hidden_features")
                 and not autograd.needs_grad(inputs, *self.autoregressive_net.parameters())):
-            packed = self._packed(inputs.device)
-            if packed is not None:
-                return ops.arnsf_inverse(inputs, packed[0], packed[1], packed[2], self.num_bins, self.tails,
-                                         float(self.tail_bound), self.min_bin_width, self.min_bin_height,
-                                         self.min_derivative)
+            listed = isinstance(self.tails, (list, tuple))
+            if listed or torch.is_tensor(self.tail_bound) or self._permuted():
+                packed = None if (self.tails is None and torch.is_tensor(self.tail_bound)) else self._packed_ft(inputs.device)
+                if packed is not None:
+                    return ops.arnsf_inverse_ft(inputs, packed[0], packed[1], packed[2], packed[3], self.num_bins,
+                                                "feature" if listed else self.tails, self.min_bin_width, self.min_bin_height,
+                                                self.min_derivative)
+            else:
+                packed = self._packed(inputs.device)
+                if packed is not None:
+                    return ops.arnsf_inverse(inputs, packed[0], packed[1], packed[2], self.num_bins, self.tails,
+                                             float(self.tail_bound), self.min_bin_width, self.min_bin_height,
+                                             self.min_derivative)
         return super().inverse(inputs, context)
 
     def _elementwise(self, inputs, params, direction, want_logdet=True):

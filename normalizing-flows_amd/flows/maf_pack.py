@@ -29,6 +29,22 @@ nf_arnsf_inverse) every feature gets its own 32-row block, zero-padded:
   per tile t                  A0 | A1..A4 [4t][2][32][4] | AF_s [4t][2][32][4] for each step s | bias[5][32]
                               | W0d[32][16] | Wd[4][32][32] | biasF[nsteps][32] | WFd[nsteps][mult][32]
 
+Per-feature variant of the rows layout (`features=(tails, tail_bound)`; nf_arnsf_inverse_ft): MADE's input degrees may be ANY
+permutation of 1..D (nets/made.py:250-252 with permute_mask) and its preprocessing a PeriodicFeaturesElementwise with an Identity
+activation (utils/nn.py:64-129: what neural_spline/autoregressive.py:44-55 puts in front of the conditioner for circular coordinates).
+The schedule walks the features in DEGREE order: with col[f] = the input column of degree f + 1, the initial layer's columns and the
+final layer's `mult`-row groups are packed in that order, so blob and table are exactly the rows layout above with "feature f" read as
+"the feature of degree f + 1".  What the kernel needs per feature travels beside the blob in `ftable`, float32 [8][D] (the integer rows
+hold int32 bit patterns), column f = the feature of degree f + 1:
+  row 0  col       int32  column of z / y the feature is read from / written to
+  row 1  tails     int32  NF_TAILS_* code (utils/splines.py:48-57 per feature for list tails, the layer's one type otherwise; 0 = none)
+  row 2  bound     tail bound (utils/splines.py:61-66; a scalar bound repeated)
+  row 3  scale     |  periodic features only (zero otherwise): the conditioner reads  w_sin sin(scale x) + w_cos cos(scale x) + bias
+  row 4  w_sin     |  of the feature x instead of x itself (bias = 0 without apply_bias)
+  row 5  w_cos     |
+  row 6  bias      |
+  row 7  periodic  int32  1 for a periodic feature
+
 Format 1 (`tri=True`, table[7] = 1; nf_maf_inverse_h only, round 5): REGULAR tiles -- at most FAST_STEPS = 8 degrees of at most 4
 units each (config 5: 15 of the 16 tiles) -- carry their sequential part's weights TRIANGULAR and in the order the kernel's
 statically unrolled steps read them; table entry [20] = 1 marks such a tile.  Unit i of step g sits at the MFMA row whose
@@ -130,11 +146,16 @@ def _a_operand(w_rows_by_k):
     return np.ascontiguousarray(w_rows_by_k.reshape(TILE, K // 8, 2, 4).transpose(1, 2, 0, 3)).reshape(-1)
 
 
-def supported(made, mult=2, blocks=(2,)):
+def supported(made, mult=2, blocks=(2,), periodic=False):
+    """`periodic`: also take a PeriodicFeaturesElementwise preprocessing with an Identity activation (the per-feature rows layout)."""
     from .. import nets
     if not isinstance(made, nets.MADE):
         return False
-    if not isinstance(made.preprocessing, torch.nn.Identity) or hasattr(made, "context_layer"):
+    pre = made.preprocessing
+    if not isinstance(pre, torch.nn.Identity):
+        if not (periodic and isinstance(pre, nets.PeriodicFeaturesElementwise) and isinstance(pre.activation, torch.nn.Identity)):
+            return False
+    if hasattr(made, "context_layer"):
         return False
     if len(made.blocks) not in blocks or not all(isinstance(b, nets.MaskedResidualBlock) for b in made.blocks):
         return False
@@ -147,12 +168,16 @@ def supported(made, mult=2, blocks=(2,)):
     return 2 <= mult <= TILE
 
 
-def pack_made(made, mult=2, rows=False, blocks=(2,), tri=False):
+def pack_made(made, mult=2, rows=False, blocks=(2,), tri=False, features=None):
     """Returns (blob float32 ndarray, table int32 ndarray) or None if the MADE is not the supported structure.
     `mult` = final-layer outputs per feature (MADE's output_multiplier); `rows` selects the one-block-per-feature
     layout of nf_arnsf_inverse; `blocks`: the residual-block counts the caller's kernel takes; `tri`: format 1 (module docstring;
-    nf_maf_inverse_h only)."""
-    if not supported(made, mult, blocks) or (rows and len(made.blocks) != 2):
+    nf_maf_inverse_h only); `features` = (tails, tail_bound) of the spline layer (rows layout only): the per-feature variant of
+    nf_arnsf_inverse_ft -- permuted input degrees and the periodic preprocessing are taken and (blob, table, ftable) is returned."""
+    ft = features is not None
+    if ft and not rows:
+        return None
+    if not supported(made, mult, blocks, periodic=ft) or (rows and len(made.blocks) != 2):
         return None
     if tri and (rows or mult != 2):
         return None
@@ -165,12 +190,21 @@ def pack_made(made, mult=2, rows=False, blocks=(2,), tri=False):
         if not np.array_equal(l.degrees.cpu().numpy(), hid_deg):
             return None
     fin = made.final_layer
-    # input degrees must be arange(1..D) and the output rows feature-major (`mult` rows per feature)
+    # input degrees must be arange(1..D) (per-feature variant: any permutation of it) and the output rows feature-major (`mult` rows
+    # per feature, of its input's degree)
+    in_deg = np.arange(1, D + 1)
+    if ft:
+        if fin.degrees.numel() != mult * D:
+            return None
+        in_deg = fin.degrees.cpu().numpy().astype(np.int64)[::mult]
+        if not np.array_equal(np.sort(in_deg), np.arange(1, D + 1)):
+            return None
+    col = np.argsort(in_deg, kind="stable")          # col[i] = the input column whose degree is i + 1 (arange(D) unless permuted)
     m0 = made.initial_layer.mask.cpu().numpy()
-    if not np.array_equal(m0, (hid_deg[:, None] >= np.arange(1, D + 1)[None, :]).astype(m0.dtype)):
+    if not np.array_equal(m0, (hid_deg[:, None] >= in_deg[None, :]).astype(m0.dtype)):
         return None
     mf = fin.mask.cpu().numpy()
-    out_deg = np.repeat(np.arange(1, D + 1), mult)
+    out_deg = np.repeat(in_deg, mult)
     if not np.array_equal(mf, (out_deg[:, None] > hid_deg[None, :]).astype(mf.dtype)):
         return None
     plan = plan_tiles(D, hid_deg)
@@ -215,7 +249,7 @@ def pack_made(made, mult=2, rows=False, blocks=(2,), tri=False):
         Bv[rows] = b[unit_of_slot[rows]]
         return W, Bv
 
-    feat_map = np.arange(D)
+    feat_map = in_deg - 1           # input column -> its position in degree order
     hid_map = np.zeros(H, dtype=np.int64)
     hid_map[order] = pos            # original hidden index -> padded slot
     W0, b0 = padded(lin[0], feat_map, Dp)
@@ -232,7 +266,7 @@ def pack_made(made, mult=2, rows=False, blocks=(2,), tri=False):
     if mult != 2 and not rows:
         return None                        # the per-tile final block holds exactly two rows per feature
     head = np.zeros(TILE if rows else 4, dtype=np.float32)   # 16-byte multiples keep every section aligned
-    head[:mult] = bf[:mult]
+    head[:mult] = bf[mult * col[0]:mult * (col[0] + 1)]
     chunks = [head]
     off = head.size
     table = np.zeros(TABLE_HDR + TABLE_ENT * T, dtype=np.int32)
@@ -252,7 +286,7 @@ def pack_made(made, mult=2, rows=False, blocks=(2,), tri=False):
             fo = np.zeros((ns, TILE, Hp), dtype=np.float32)
             bfo = np.zeros((ns, TILE), dtype=np.float32)
             for j in range(ns):
-                f = dlo + j
+                f = col[dlo + j]
                 fo[j, :mult] = WF[mult * f:mult * (f + 1)]
                 bfo[j, :mult] = bf[mult * f:mult * (f + 1)]
                 if t:
@@ -357,7 +391,61 @@ def pack_made(made, mult=2, rows=False, blocks=(2,), tri=False):
         chunks.append(rec)
         off += rec.size
     blob = np.concatenate(chunks).astype(np.float32)
+    if ft:
+        ftable = feature_table(made, col, *features)
+        return None if ftable is None else (blob, table, ftable)
     return blob, table
+
+
+FT_ROWS = 8
+TAIL_CODE = {None: 0, "linear": 1, "circular": 2}     # NF_TAILS_* of include/nf_mi355x.h
+
+
+def feature_table(made, col, tails, tail_bound):
+    """The per-feature table of the module docstring for input columns `col` in degree order; None for tails / bounds / a
+    preprocessing it cannot express."""
+    from .. import nets
+    D = len(col)
+    if isinstance(tails, (list, tuple)):
+        if len(tails) != D or any(t not in ("linear", "circular") for t in tails):
+            return None
+        codes = np.array([TAIL_CODE[t] for t in tails], dtype=np.int32)
+    elif tails in TAIL_CODE:
+        codes = np.full(D, TAIL_CODE[tails], dtype=np.int32)
+    else:
+        return None
+    if torch.is_tensor(tail_bound):
+        if tail_bound.numel() not in (1, D):
+            return None
+        bound = np.broadcast_to(tail_bound.detach().cpu().numpy().astype(np.float32).reshape(-1), (D,))
+    else:
+        bound = np.full(D, float(tail_bound), dtype=np.float32)
+    tab = np.zeros((FT_ROWS, D), dtype=np.float32)
+    itab = tab.view(np.int32)
+    itab[0] = col
+    itab[1] = codes[col]
+    tab[2] = bound[col]
+    pre = made.preprocessing
+    if isinstance(pre, nets.PeriodicFeaturesElementwise):
+        ind = pre.ind.cpu().numpy().astype(np.int64)
+        if pre.ndim != D or len(set(ind.tolist())) != ind.size or (ind.size and (ind.min() < 0 or ind.max() >= D)):
+            return None
+        by_col = np.zeros((4, D), dtype=np.float32)          # scale, w_sin, w_cos, bias per input COLUMN
+        flag = np.zeros(D, dtype=np.int32)
+        scale = pre.scale
+        if torch.is_tensor(scale):
+            if scale.numel() not in (1, ind.size):
+                return None
+            scale = np.broadcast_to(scale.detach().cpu().numpy().astype(np.float32).reshape(-1), (ind.size,))
+        w = pre.weights.detach().cpu().numpy().astype(np.float32)
+        by_col[0, ind] = scale
+        by_col[1, ind], by_col[2, ind] = w[:, 0], w[:, 1]
+        if pre.apply_bias:
+            by_col[3, ind] = pre.bias.detach().cpu().numpy().astype(np.float32)
+        flag[ind] = 1
+        tab[3:7] = by_col[:, col]
+        itab[7] = flag[col]
+    return tab
 
 
 # ---- format 2 (round 5): the TRANSPOSED one-pass solve of the implicit backward (csrc/maf_solve_t.hip, autograd.MafInverseFn) ----

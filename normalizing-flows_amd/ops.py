@@ -1326,6 +1326,26 @@ def arnsf_inverse(z, blob, table, hidden_padded, K, tails, tail_bound, min_bin_w
     return y, logdet
 
 
+def arnsf_inverse_ft(z, blob, table, ftable, hidden_padded, K, tails, min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3,
+                     logdet=None, acc=None):
+    """arnsf_inverse with a per-feature table (nf_arnsf_inverse_ft): permuted masks, per-feature tails ("feature") and bounds and the
+    periodic preprocessing of circular coordinates (neural_spline/autoregressive.py:44-55, :94-134; utils/splines.py:48-66;
+    utils/nn.py:64-129); blob/table/ftable from flows/maf_pack.pack_made(made, mult, rows=True, features=(tails, tail_bound))."""
+    L.require_device(z, blob, table, ftable)
+    if z.dtype != torch.float32:
+        raise NotImplementedError("arnsf_inverse_ft: float32 only")
+    B, D = z.shape
+    if ftable.dtype != torch.float32 or tuple(ftable.shape) != (8, D):
+        raise ValueError("arnsf_inverse_ft: ftable is the (8, D) float32 table of flows/maf_pack.py")
+    z = z.contiguous()
+    y = torch.empty_like(z)
+    logdet, acc = _ld_buffer(logdet, acc, B, z)
+    scratch = _scratch("nf_maf_inverse_scratch_floats", z.device, B, D, hidden_padded)
+    L.call("nf_arnsf_inverse_ft", ptr(z), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(ftable), ptr(scratch), B, D, hidden_padded,
+           K, 3 if tails == "feature" else L.TAILS[tails], min_bin_width, min_bin_height, min_derivative, acc, L.stream())
+    return y, logdet
+
+
 GLOW_CONV_WIDE, GLOW_CONV_SMALL, GLOW_CONV_TINY = 0, 1, 2
 
 

@@ -1,17 +1,27 @@
 """AR-NSF sampling direction (second half): nf_arnsf_inverse against the D-pass loop.
-usage: python tools/arnsf_bench.py [D H K B layers]"""
-import importlib.util, os, sys, time
+usage: python tools/arnsf_bench.py [D H K B layers] [--circular N] [--permute] [--passes P]
+
+--circular N / --permute: ONE layer of the per-feature kernel (nf_arnsf_inverse_ft) -- CircularAutoregressiveRationalQuadraticSpline with
+the first N features circular (bound pi, the others 3) and / or a permuted mask -- timed with HIP events in the same process against
+(i) the D-pass loop on the same layer (`Autoregressive.inverse(layer, z)`) and (iii) the linear-tails nf_arnsf_inverse at the same
+D / H / K; medians over P >= 20 passes after warm-up, written to profiles/circ_arnsf_bench.json."""
+import argparse, importlib.util, json, os, statistics, sys, time
+import numpy as np
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 spec = importlib.util.spec_from_file_location("normflows_amd", os.path.join(ROOT, "normalizing-flows_amd", "__init__.py"))
 nfa = importlib.util.module_from_spec(spec); sys.modules["normflows_amd"] = nfa; spec.loader.exec_module(nfa)
 from normflows_amd.flows.autoregressive import Autoregressive
 
-D, H, K, B, L = [int(a) for a in sys.argv[1:6]] if len(sys.argv) > 5 else (64, 256, 8, 65536, 4)
+ap = argparse.ArgumentParser()
+ap.add_argument("shape", nargs="*", type=int, help="D H K B layers")
+ap.add_argument("--circular", type=int, default=0, metavar="N")
+ap.add_argument("--permute", action="store_true")
+ap.add_argument("--passes", type=int, default=20)
+args = ap.parse_args()
+D, H, K, B, L = args.shape if len(args.shape) == 5 else (64, 256, 8, 65536, 4)
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
-layers = [nfa.flows.AutoregressiveRationalQuadraticSpline(D, 2, H, num_bins=K, init_identity=False).to(dev) for _ in range(L)]
-z = torch.randn(B, D, device=dev)
 
 
 def run(fn, reps):
@@ -20,6 +30,62 @@ def run(fn, reps):
         out = fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / reps * 1e3, out
+
+
+def median_ms(fn, passes, warmup=2):
+    """Median over `passes` runs, each between two HIP events."""
+    for _ in range(warmup):
+        fn()
+    times = []
+    for _ in range(passes):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); fn(); b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    return statistics.median(times), min(times)
+
+
+if args.circular or args.permute:
+    passes = max(args.passes, 20)
+    n = args.circular
+    bound = torch.full((D,), 3.0)
+    bound[:n] = float(np.pi)
+    if n:
+        circ = nfa.flows.CircularAutoregressiveRationalQuadraticSpline(D, 2, H, ind_circ=list(range(n)), num_bins=K, tail_bound=bound,
+                                                                       permute_mask=args.permute, init_identity=False).to(dev)
+    else:
+        circ = nfa.flows.AutoregressiveRationalQuadraticSpline(D, 2, H, num_bins=K, permute_mask=True, init_identity=False).to(dev)
+    lin = nfa.flows.AutoregressiveRationalQuadraticSpline(D, 2, H, num_bins=K, init_identity=False).to(dev)
+    z = ((torch.rand(B, D) * 2 - 1) * bound * 0.98).to(dev)
+    calls = {"ft": 0}
+    ft = nfa.ops.arnsf_inverse_ft
+
+    def counted(*a, **k):
+        calls["ft"] += 1
+        return ft(*a, **k)
+    nfa.ops.arnsf_inverse_ft = counted
+    with torch.no_grad():
+        xf, _ = circ.forward(z)
+        assert calls["ft"] == 1 and lin.mprqat._packed(dev) is not None, "the one-launch paths were not taken"
+        xd, _ = Autoregressive.inverse(circ.mprqat, z)
+        t_ft = median_ms(lambda: circ.forward(z), passes)
+        t_lin = median_ms(lambda: lin.forward(z), passes)
+        t_loop = median_ms(lambda: Autoregressive.inverse(circ.mprqat, z), passes, warmup=1)
+        t_ft2 = median_ms(lambda: circ.forward(z), passes)          # again after the others: drift of the device between the blocks
+    rec = {"shape": {"D": D, "hidden": H, "K": K, "B": B, "circular": n, "permute": bool(args.permute)}, "passes": passes,
+           "timer": "HIP events around one call, median (min) in ms",
+           "d_pass_loop_ms": t_loop, "one_launch_ft_ms": t_ft, "one_launch_ft_again_ms": t_ft2, "linear_arnsf_inverse_ms": t_lin,
+           "ft_over_loop": t_ft[0] / t_loop[0], "ft_over_linear": t_ft[0] / t_lin[0],
+           "max_abs_dx_vs_loop": float((xf - xd).abs().max()), "device": torch.cuda.get_device_name(0)}
+    print(json.dumps(rec))
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "circ_arnsf_bench.json"), "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    sys.exit(0)
+
+layers = [nfa.flows.AutoregressiveRationalQuadraticSpline(D, 2, H, num_bins=K, init_identity=False).to(dev) for _ in range(L)]
+z = torch.randn(B, D, device=dev)
 
 
 def fused():
