@@ -637,6 +637,28 @@ int nf_nsf_wide_k(const void *x, void *y, void *logdet, const void *blob, const 
 int nf_nsf_wide_ctx(const void *x, const void *context, void *y, void *logdet, const void *blob, const int32_t *table,
                     const void *tabs, int64_t B, int64_t ldc, int D, int C, int hidden_padded, int K, int direction, int acc,
                     double tail_bound, double min_bin_width, double min_bin_height, double min_derivative, nf_stream_t stream);
+/* The CIRCULAR coupling layer (CircularCoupledRationalQuadraticSpline) in one launch, inference only, float32: nf_nsf_wide_k's layer with
+ * tails and bound per feature and the periodic preprocessing in front of the conditioner.  Replaces normflows/flows/neural_spline/
+ * wrapper.py:88-185 (the layer; :175-185 its two directions) -> nsf/coupling.py:71-128 and :283-318 (the per-feature tails / bounds split
+ * between the halves), utils/splines.py:28-32 and :48-66 (list tails: K + 1 derivative logits per feature with the edge ones overwritten by
+ * type; an input outside its interval gives output 0 and log-det 0, in both halves), utils/nn.py:64-129 (PeriodicFeaturesElementwise: the
+ * conditioner reads w_sin sin(scale x) + w_cos cos(scale x) + bias of a circular identity feature) and nets/resnet.py:92-104.
+ *   blob, table : normalizing-flows_amd/flows/nsf_circ_pack.py (nsf_wide_pack's streams and header; the final Linear's 3K + 1 rows per
+ *                 feature packed as 3K: the last derivative row is always overwritten and dropped).
+ *   ftable      : (8, Dp) 32-bit words, Dp = table[1]: the per-feature table of nf_arnsf_inverse_ft (rows: column, tails code, bound,
+ *                 scale, w_sin, w_cos, bias, periodic flag) in the tile's position order, identity positions [0, PI) then transform
+ *                 positions [PI, Dp); the column row is -1 at padding positions.  A scalar tail bound is repeated.
+ *   tabs        : nf_nsf_wide_tables_ft: the batch-shared spline's knot tables from unnormalized_widths / heights (n_identity, K),
+ *                 unnormalized_derivatives (n_identity, K + 1), tails_i (n_identity int32 NF_TAILS_LINEAR | NF_TAILS_CIRCULAR) and
+ *                 bound_i (n_identity float32).
+ *   -EINVAL for B < 0, D outside 2..128, a bad direction / acc, min_bin_width * K > 1; -ENOTSUP for hidden_padded other than 128 | 256
+ *   (512 is not built) and K outside 4 | 8 | 16; -EFAULT for a NULL pointer; B == 0: NF_OK. */
+int nf_nsf_wide_tables_ft(const void *uw, const void *uh, const void *ud, const int32_t *tails_i, const void *bound_i, void *tabs,
+                          int n_identity, int K, double min_bin_width, double min_bin_height, double min_derivative,
+                          nf_stream_t stream);
+int nf_nsf_wide_ft(const void *x, void *y, void *logdet, const void *blob, const int32_t *table, const void *ftable, const void *tabs,
+                   int64_t B, int D, int hidden_padded, int K, int direction, int acc, double min_bin_width, double min_bin_height,
+                   double min_derivative, nf_stream_t stream);
 
 /* The GLU-gated ResidualNet conditioner (nets/resnet.py:7-104 with context_features: the conditioner of a conditional
  * CoupledRationalQuadraticSpline) under autograd, float32 (csrc/resnet_ctx_train.hip):

@@ -10,7 +10,7 @@ at the repository root).
 """
 from . import _lib, config, ops, nets, flows, distributions, transforms, utils, dp
 from .core import NormalizingFlow, ConditionalNormalizingFlow, MultiscaleFlow, invalidate_caches
-from .distributions import DiagGaussian, ConditionalDiagGaussian, ClassCondDiagGaussian, GlowBase
+from .distributions import DiagGaussian, ConditionalDiagGaussian, ClassCondDiagGaussian, GlowBase, UniformGaussian
 
 __version__ = "0.1.0"
 

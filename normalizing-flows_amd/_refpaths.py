@@ -22,7 +22,7 @@ _TABLE = {
     "nets.mlp": ("nets", ["MLP"]),
     "nets.cnn": ("nets", ["ConvNet2d"]),
     "nets.made": ("nets", ["MaskedLinear", "MaskedFeedforwardBlock", "MaskedResidualBlock", "MADE"]),
-    "distributions.base": ("distributions", ["BaseDistribution", "DiagGaussian", "ConditionalDiagGaussian", "ClassCondDiagGaussian", "GlowBase"]),
+    "distributions.base": ("distributions", ["BaseDistribution", "DiagGaussian", "ConditionalDiagGaussian", "ClassCondDiagGaussian", "GlowBase", "UniformGaussian"]),
 }
 
 

@@ -325,6 +325,16 @@ def set_nsf_context(mode=True):
     nsf_context = bool(mode)
 
 
+# CircularCoupledRationalQuadraticSpline (list tails, periodic preprocessing of the circular identity coordinates) at inference as ONE
+# launch (nf_nsf_wide_ft, csrc/nsf_circ.hip); False = library GEMMs for the conditioner + nf_rqs_coupling_ft (A/B runs, differential tests).
+nsf_circular = True
+
+
+def set_nsf_circular(mode=True):
+    global nsf_circular
+    nsf_circular = bool(mode)
+
+
 # The GLU-gated conditioner of a conditional CoupledRationalQuadraticSpline (ResidualNet with context_features) under autograd on
 # HIP kernels (autograd.ResNetCtxFn, csrc/resnet_ctx_train.hip); False = the conditioner as eager torch modules.  The route also
 # follows made_train, so inside higher_order_gradients() the torch modules run and double backward keeps working.

@@ -24,6 +24,7 @@
 // (utils/splines.py:16-219 through common.hpp::rqs_element).
 #include "common.hpp"
 #include "fused_common.hpp"
+#include "ft_table.hpp"
 
 namespace nf {
 
@@ -276,17 +277,8 @@ static inline size_t arnsf_lds_floats(int R) {
     return (size_t)MW * MT * 64 + 5 * MT + MT * MS + 4 * MT * MT + MS * MT + (size_t)MS * R * MT;
 }
 
-// Per-feature table of the FT variant (flows/maf_pack.py): 8 rows of D 32-bit words, feature f of the schedule = degree f + 1.
-enum { FT_COL = 0, FT_TAILS, FT_BOUND, FT_SCALE, FT_WSIN, FT_WCOS, FT_BIAS, FT_PERIODIC };
-
-// What the conditioner reads of a finished feature (nets/made.py:250-252: every pass starts with the preprocessing): the periodic
-// features of utils/nn.py:64-129 for a circular coordinate, the value itself otherwise.  The table reads have wave-uniform addresses.
-// sinf / cosf, not the fast intrinsics: the reference evaluates torch.sin / torch.cos.
-__device__ __forceinline__ float ft_feed(const float *__restrict__ ft, int D, int f, float x) {
-    if (__float_as_int(ft[FT_PERIODIC * D + f]) == 0) return x;
-    const float a = ft[FT_SCALE * D + f] * x;
-    return ft[FT_WSIN * D + f] * sinf(a) + ft[FT_WCOS * D + f] * cosf(a) + ft[FT_BIAS * D + f];
-}
+// Per-feature table of the FT variant (flows/maf_pack.py): 8 rows of D 32-bit words, feature f of the schedule = degree f + 1; the
+// FT_* rows and ft_feed (what the conditioner reads of a finished feature) live in ft_table.hpp, shared with nsf_circ.hip.
 
 // SPL = false: affine element (MAF); true: rational-quadratic spline element with `sp` and R final rows per feature.
 // FT (with SPL): the schedule's feature f lives in column ft[FT_COL][f] of z and y, its tails type (sp.dfull) and bound come from the

@@ -1,6 +1,7 @@
 // nsf_tile_final.hpp -- a FRAGMENT of the tile loop of nsf_wide_kernel and nsf_ctx_kernel, included inside the kernel body (nsf_tile.hpp says why
 // it is text and not a function).  Reads ring, items, fin0 (index of the first final entry), nfi, G, acts, xreg, ldp, tabs, p, h, lane_b, hh,
-// n, nI, nT, PI, tq, MP / FPL / FPG / NFI; reads and writes ld_ident.
+// n, nI, nT, PI, tq, MP / FPL / FPG / NFI; reads and writes ld_ident.  With NSF_TILE_FT (nsf_circ.hip: per-feature tails and bounds) also ftl, the
+// kernel's LDS copy of the per-feature table with row stride NSF_FT_STRIDE.
 MF_BARRIER();
 #pragma unroll
 for (int s = 0; s < NHI; ++s) mf_publish<NS, false, TR>(acts, items[3 * s + 1], items[3 * s + 2], hh, n, h[s]);
@@ -28,7 +29,10 @@ for (int j = 0; j < nfi; ++j) {                       // (rolled: one copy of th
             float *xp = xreg + nsf_xidx<TR>(PI + (valid ? tf : 0), 32 * (sbo + sb) + n);
             float yv, lad;
             // round 5: binary bin descent (rqs_regs_t; the packed PAIR version of the benchmark kernel spilled 11-23 registers here)
-#ifdef NF_EPI_SCALAR
+#ifdef NSF_TILE_FT      // list tails: bound and type of the feature from the table; 0 / log-det 0 outside (utils/splines.py:48-57)
+            nsf_regs_ft<DIR == 1, KB>(p, ftl[FT_BOUND * NSF_FT_STRIDE + PI + (valid ? tf : 0)],
+                                      __float_as_int(ftl[FT_TAILS * NSF_FT_STRIDE + PI + (valid ? tf : 0)]), *xp, prm, yv, lad);
+#elif defined(NF_EPI_SCALAR)
             rqs_regs<DIR == 1, KB>(p, *xp, prm, yv, lad);
 #elif defined(NF_EPI_FULL_KNOTS)
             rqs_regs_t<DIR == 1, KB>(p, *xp, prm, yv, lad);
@@ -66,7 +70,11 @@ for (int j = 0; j < NFI; ++j) {
 }
 if constexpr (DIR == 0) {                            // density: the identity half's spline after the conditioner (:88-92)
     MF_BARRIER();
+#ifdef NSF_TILE_FT
+    ld_ident = nsf_identity_ft<false, TR, KB>(xreg, acts, nI, tq);
+#else
     ld_ident = nsf_identity<false, TR, KB>(xreg, acts, p, nI, tq);
+#endif
 }
 ldp[(G + tq / TR) * TR + tq % TR] = ld_ident;
 MF_BARRIER();

@@ -89,6 +89,45 @@ class DiagGaussian(BaseDistribution):
         return log_q
 
 
+class UniformGaussian(BaseDistribution):
+    """1-D random variable whose entries `ind` are uniform on [-scale / 2, scale / 2] and the others Gaussian with standard deviation
+    scale (base.py:198-270): the base of the reference's circular examples.  Buffers ind, ind_, inv_perm, scale as there.  Two
+    element-wise statements per model call outside the layer chain: torch formulas, no kernel."""
+
+    def __init__(self, ndim, ind, scale=None):
+        super().__init__()
+        self.ndim = ndim
+        if isinstance(ind, int):
+            ind = [ind]
+        if torch.is_tensor(ind):
+            self.register_buffer("ind", ind.long())
+        else:
+            self.register_buffer("ind", torch.tensor(ind, dtype=torch.long))
+        uniform = set(self.ind.tolist())
+        self.register_buffer("ind_", torch.tensor([i for i in range(self.ndim) if i not in uniform], dtype=torch.long))
+        perm_ = torch.cat((self.ind, self.ind_))
+        inv_perm_ = torch.zeros_like(perm_)
+        inv_perm_[perm_] = torch.arange(self.ndim)
+        self.register_buffer("inv_perm", inv_perm_)
+        self.register_buffer("scale", torch.ones(self.ndim) if scale is None else scale)
+
+    def forward(self, num_samples=1, context=None):
+        z = self.sample(num_samples)
+        return z, self.log_prob(z)
+
+    def sample(self, num_samples=1, context=None):
+        eps_u = torch.rand((num_samples, len(self.ind)), dtype=self.scale.dtype, device=self.scale.device) - 0.5
+        eps_g = torch.randn((num_samples, len(self.ind_)), dtype=self.scale.dtype, device=self.scale.device)
+        z = torch.cat((eps_u, eps_g), -1)[..., self.inv_perm]
+        return self.scale * z
+
+    def log_prob(self, z, context=None):
+        log_p_u = torch.broadcast_to(-torch.log(self.scale[self.ind]), (len(z), -1))
+        log_p_g = (-0.5 * np.log(2 * np.pi) - torch.log(self.scale[self.ind_])
+                   - 0.5 * torch.pow(z[..., self.ind_] / self.scale[self.ind_], 2))
+        return torch.sum(log_p_u, -1) + torch.sum(log_p_g, -1)
+
+
 class ClassCondDiagGaussian(BaseDistribution):
     """Class-conditional diagonal Gaussian (base.py:273-345).  Parameters keep the reference layout (*shape,
     num_classes) so state_dicts interchange; the kernel reads the transposed (num_classes, d) rows, refreshed when a

@@ -401,37 +401,31 @@ FT_ROWS = 8
 TAIL_CODE = {None: 0, "linear": 1, "circular": 2}     # NF_TAILS_* of include/nf_mi355x.h
 
 
-def feature_table(made, col, tails, tail_bound):
-    """The per-feature table of the module docstring for input columns `col` in degree order; None for tails / bounds / a
-    preprocessing it cannot express."""
+def feature_rows(n, tails, tail_bound, pre):
+    """What the per-feature table of the module docstring holds, per INPUT COLUMN of an n-feature conditioner input whose preprocessing
+    is `pre`: (tails codes int32 (n,), bounds float32 (n,), [scale, w_sin, w_cos, bias] float32 (4, n), periodic flags int32 (n,)); None
+    for tails / bounds / a preprocessing the table cannot express.  (Also the rows of flows/nsf_circ_pack.py's table.)"""
     from .. import nets
-    D = len(col)
     if isinstance(tails, (list, tuple)):
-        if len(tails) != D or any(t not in ("linear", "circular") for t in tails):
+        if len(tails) != n or any(t not in ("linear", "circular") for t in tails):
             return None
         codes = np.array([TAIL_CODE[t] for t in tails], dtype=np.int32)
     elif tails in TAIL_CODE:
-        codes = np.full(D, TAIL_CODE[tails], dtype=np.int32)
+        codes = np.full(n, TAIL_CODE[tails], dtype=np.int32)
     else:
         return None
     if torch.is_tensor(tail_bound):
-        if tail_bound.numel() not in (1, D):
+        if tail_bound.numel() not in (1, n):
             return None
-        bound = np.broadcast_to(tail_bound.detach().cpu().numpy().astype(np.float32).reshape(-1), (D,))
+        bound = np.broadcast_to(tail_bound.detach().cpu().numpy().astype(np.float32).reshape(-1), (n,))
     else:
-        bound = np.full(D, float(tail_bound), dtype=np.float32)
-    tab = np.zeros((FT_ROWS, D), dtype=np.float32)
-    itab = tab.view(np.int32)
-    itab[0] = col
-    itab[1] = codes[col]
-    tab[2] = bound[col]
-    pre = made.preprocessing
+        bound = np.full(n, float(tail_bound), dtype=np.float32)
+    by_col = np.zeros((4, n), dtype=np.float32)          # scale, w_sin, w_cos, bias per input COLUMN
+    flag = np.zeros(n, dtype=np.int32)
     if isinstance(pre, nets.PeriodicFeaturesElementwise):
         ind = pre.ind.cpu().numpy().astype(np.int64)
-        if pre.ndim != D or len(set(ind.tolist())) != ind.size or (ind.size and (ind.min() < 0 or ind.max() >= D)):
+        if pre.ndim != n or len(set(ind.tolist())) != ind.size or (ind.size and (ind.min() < 0 or ind.max() >= n)):
             return None
-        by_col = np.zeros((4, D), dtype=np.float32)          # scale, w_sin, w_cos, bias per input COLUMN
-        flag = np.zeros(D, dtype=np.int32)
         scale = pre.scale
         if torch.is_tensor(scale):
             if scale.numel() not in (1, ind.size):
@@ -443,9 +437,30 @@ def feature_table(made, col, tails, tail_bound):
         if pre.apply_bias:
             by_col[3, ind] = pre.bias.detach().cpu().numpy().astype(np.float32)
         flag[ind] = 1
-        tab[3:7] = by_col[:, col]
-        itab[7] = flag[col]
+    return codes, bound, by_col, flag
+
+
+def table_from_rows(col, codes, bound, by_col, flag):
+    """float32 [FT_ROWS][len(col)] table (the integer rows hold int32 bit patterns) whose column f describes input column col[f];
+    col[f] < 0: a column without a feature (row 0 = -1, the rest zero)."""
+    col = np.asarray(col, dtype=np.int64)
+    live = col >= 0
+    src = col[live]
+    tab = np.zeros((FT_ROWS, len(col)), dtype=np.float32)
+    itab = tab.view(np.int32)
+    itab[0] = col
+    itab[1, live] = codes[src]
+    tab[2, live] = bound[src]
+    tab[3:7, live] = by_col[:, src]
+    itab[7, live] = flag[src]
     return tab
+
+
+def feature_table(made, col, tails, tail_bound):
+    """The per-feature table of the module docstring for input columns `col` in degree order; None for tails / bounds / a
+    preprocessing it cannot express."""
+    rows = feature_rows(len(col), tails, tail_bound, made.preprocessing)
+    return None if rows is None else table_from_rows(col, *rows)
 
 
 # ---- format 2 (round 5): the TRANSPOSED one-pass solve of the implicit backward (csrc/maf_solve_t.hip, autograd.MafInverseFn) ----

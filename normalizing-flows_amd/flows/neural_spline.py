@@ -24,7 +24,7 @@ from .. import ops
 from ..autograd import CouplingDensityFn, CouplingTrainFn, FinalSplineDensityFn, IdentLinearFn, SplineFn, needs_grad
 from ..nets import PeriodicFeaturesElementwise, ResidualNet
 from ..utils.masks import create_alternating_binary_mask
-from . import nsf_ctx_pack, nsf_wide_pack
+from . import nsf_circ_pack, nsf_ctx_pack, nsf_wide_pack
 from .base import Flow, fold_logdet, ld_sign
 
 DEFAULT_MIN_BIN_WIDTH = 1e-3
@@ -282,7 +282,7 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
 
     def _route(self, inputs, context, direction, ld, acc):
         """One coupling layer in `direction` (0 density = prqct.forward, 1 sampling = prqct.inverse): images, autograd, then the
-        one-launch kernels in the order conditional -> benchmark shape -> wide, else layer-wise."""
+        one-launch kernels in the order conditional -> circular (list tails) -> benchmark shape -> wide, else layer-wise."""
         self._check(inputs)
         if inputs.dim() == 4:
             return self._image(inputs, context, bool(direction), ld, acc)
@@ -292,6 +292,9 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
             ctx_pack = self._ctx_pack(inputs, context)
             if ctx_pack is not None:
                 return self._wide_ctx(inputs, context, ctx_pack, direction, ld, acc)
+        circ = self._circ_pack(inputs, context)
+        if circ is not None:
+            return self._wide_ft(inputs, circ, direction, ld, acc)
         if self.use_fused and self._fused_eligible(inputs, context):
             return self._fused(inputs, direction, ld, acc)
         wide = self._wide_pack(inputs, context)
@@ -396,6 +399,38 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         blob, table, tabs, hp, table_host = packed
         return ops.nsf_wide_ctx(inputs, context, blob, table, tabs, hp, direction, self.tail_bound, self.min_bin_width,
                                 self.min_bin_height, self.min_derivative, logdet=ld, acc=acc, K=self.num_bins, table_host=table_host)
+
+    # -- list tails + periodic preprocessing (CircularCoupledRationalQuadraticSpline) at inference as one launch (csrc/nsf_circ.hip) ----
+    def _circ_pack(self, inputs, context):
+        """Device copies of flows/nsf_circ_pack.py's streams and per-feature table + the batch-shared spline's knot tables, rebuilt
+        when a parameter changes; None when the layer or the call is outside nf_nsf_wide_ft's structure (then: library GEMMs +
+        nf_rqs_coupling_ft)."""
+        if not (self.use_fused and _config.nsf_circular and context is None and isinstance(self.tails, list) and inputs.dim() == 2
+                and inputs.dtype == torch.float32 and inputs.is_cuda):
+            return None
+        net, u = self.transform_net, self.unconditional_transform
+        if u is None or not isinstance(net, ResidualNet):
+            return None
+        tensors = list(net.parameters()) + [u.unnormalized_widths, u.unnormalized_heights, u.unnormalized_derivatives]
+        tensors += [b for b in (self.tail_bound, u.tail_bound) if torch.is_tensor(b)]
+        key = _keys.pkey(tensors) + (str(inputs.device), net.training)
+        cache = self.__dict__.get("_circ_cache")
+        if cache is None or cache[0] != key:
+            packed = nsf_circ_pack.pack_nsf_circ(self)
+            if packed is not None:
+                blob, table, ftable = (torch.from_numpy(a).to(inputs.device) for a in packed)
+                nI = len(self.identity_features)
+                tabs = ops.nsf_wide_tables_ft(u.unnormalized_widths.detach(), u.unnormalized_heights.detach(),
+                                              u.unnormalized_derivatives.detach(), ftable[1, :nI].view(torch.int32), ftable[2, :nI],
+                                              self.num_bins, self.min_bin_width, self.min_bin_height, self.min_derivative)
+                packed = (blob, table, ftable, tabs, int(packed[1][3]))
+            cache = self.__dict__["_circ_cache"] = (key, packed)
+        return cache[1]
+
+    def _wide_ft(self, inputs, packed, direction, ld, acc):
+        blob, table, ftable, tabs, hp = packed
+        return ops.nsf_wide_ft(inputs, blob, table, ftable, tabs, hp, direction, self.min_bin_width, self.min_bin_height,
+                               self.min_derivative, logdet=ld, acc=acc, K=self.num_bins)
 
     # -- images (nsf/coupling.py:150-160): every pixel is a row of C channel features for the 2-D coupling kernel ----
     def _image(self, inputs, context, sample, ld, acc):

@@ -66,23 +66,35 @@ def hidden_item(Hp, w, i):
     return w + 8 * i, 0
 
 
-def final_row(g, r3, rho, nT, K=K_BINS):
-    """Row of the ((3 K - 1) nT, hidden) final weight held by MFMA row rho of row-block r3 of group g, or -1 (padding)."""
+def final_row(g, r3, rho, nT, K=K_BINS, list_tails=False):
+    """Row of the ((3 K - 1) nT, hidden) final weight held by MFMA row rho of row-block r3 of group g, or -1 (padding).
+    list_tails (flows/nsf_circ_pack.py): the weight has 3 K + 1 rows per feature (utils/splines.py:48-57); the last derivative row is
+    always overwritten and has no slot, derivatives 1 .. K - 1 keep the linear layout's slots and derivative 0 takes the slot it pads."""
     m, mp, fpl, fpg, _ = bins_geometry(K)
     q, hh, i = rho >> 3, (rho >> 2) & 1, rho & 3
     v = 16 * r3 + 4 * q + i
     f, prm = v // mp, v % mp
     tf = fpg * g + fpl * hh + f
+    if list_tails:
+        if tf >= nT:
+            return -1
+        return tf * (mp + 1) + (prm if prm < 2 * K else (2 * K if prm == m else prm + 1))
     if prm >= m or tf >= nT:
         return -1
     return tf * m + prm
 
 
-def layer_conditions(prqct, weights_f32=True):
-    """What nf_nsf_wide, nf_nsf_wide_ctx and the benchmark kernel (csrc/rqs_fused.hip) ask of the coupling transform alike: linear
-    tails shared by all features, the batch-shared spline on the identity half, 4 / 8 / 16 bins whose minimum widths / heights leave
-    room, float32 weights (weights_f32), an alternating mask.  Returns the mask's parity (the first identity feature: 0 | 1), or None."""
-    if prqct.tails != "linear" or getattr(prqct, "_per_feature", False) or prqct.unconditional_transform is None:
+def layer_conditions(prqct, weights_f32=True, list_tails=False):
+    """What nf_nsf_wide, nf_nsf_wide_ctx, nf_nsf_wide_ft and the benchmark kernel (csrc/rqs_fused.hip) ask of the coupling transform
+    alike: linear tails shared by all features (list_tails, flows/nsf_circ_pack.py: tails given per feature as a list instead, which
+    that packer reads), the batch-shared spline on the identity half, 4 / 8 / 16 bins whose minimum widths / heights leave room,
+    float32 weights (weights_f32), an alternating mask.  Returns the mask's parity (the first identity feature: 0 | 1), or None."""
+    if prqct.unconditional_transform is None:
+        return None
+    if list_tails:
+        if not isinstance(prqct.tails, (list, tuple)):
+            return None
+    elif prqct.tails != "linear" or getattr(prqct, "_per_feature", False):
         return None
     K = prqct.num_bins
     if K not in SUPPORTED_BINS or prqct.min_bin_width * K > 1.0 or prqct.min_bin_height * K > 1.0:
@@ -121,11 +133,14 @@ def padded_linear(lin, Hp, cols, w=None):
     return W, b
 
 
-def final_groups(lin, nT, K, H, TR):
+def final_groups(lin, nT, K, H, TR, list_tails=False):
     """(WF (G, 3, 32, Kh), BF (G, 3, 32), G, nfi): the final Linear cut into groups of 3 row-blocks in final_row's order, log2(e) /
     sqrt(hidden) folded into the width / height rows (rqs_regs takes exp2); a wave owns nfi final items = (group, pair of sample
-    blocks).  None when a wave would own more than the kernel keeps log-det sums for, or the Linear is not the (3 K - 1) nT rows."""
+    blocks).  None when a wave would own more than the kernel keeps log-det sums for, or the Linear is not the (3 K - 1) nT rows
+    ((3 K + 1) nT with list_tails: final_row)."""
     M_, _, _, FPG, nfi_max = bins_geometry(K)
+    if list_tails:
+        M_ = 3 * K + 1
     G = (nT + FPG - 1) // FPG
     nfi = (G * (TR // 64) + 7) // 8
     wf, bf = _f32(lin.weight), _f32(lin.bias)
@@ -141,7 +156,7 @@ def final_groups(lin, nT, K, H, TR):
     for g in range(G):
         for r3 in range(3):
             for rho in range(ROWS):
-                row = final_row(g, r3, rho, nT, K)
+                row = final_row(g, r3, rho, nT, K, list_tails)
                 if row >= 0:
                     sc = wh_scale if (row % M_) < 2 * K else np.float32(1.0)
                     WF[g, r3, rho, :H] = wf[row] * sc

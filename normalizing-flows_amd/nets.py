@@ -220,10 +220,10 @@ class ResidualNet(nn.Module):
         blob = ops.pack_gather([p.detach() for p in params], src)
         return blob, table, jobs, st
 
-    def is_plain_relu(self):
-        """True when the net is the plain ReLU MLP the fused HIP kernel implements."""
+    def is_plain_relu(self, preprocessing=False):
+        """True when the net is the plain ReLU MLP the fused HIP kernel implements (preprocessing: the caller handles one itself)."""
         act_ok = all(isinstance(b.activation, nn.ReLU) or b.activation is F.relu for b in self.blocks)
-        return (act_ok and self.context_features is None and self.preprocessing is None and not self.use_batch_norm
+        return (act_ok and self.context_features is None and (preprocessing or self.preprocessing is None) and not self.use_batch_norm
                 and (self.dropout_probability == 0.0 or not self.training))
 
 

@@ -986,6 +986,36 @@ def nsf_wide_ctx(x, context, blob, table, tabs, hidden_padded, direction, tail_b
     return y, logdet
 
 
+def nsf_wide_tables_ft(uw, uh, ud, tails_i, bound_i, K, min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3):
+    """Knot tables (n_identity, 3 (K + 1)) of the batch-shared spline under list tails for nf_nsf_wide_ft: derivatives
+    (n_identity, K + 1), tails_i int32 / bound_i float32 (n_identity,) per identity feature (utils/splines.py:48-66)."""
+    L.require_device(uw, uh, ud, tails_i, bound_i)
+    nI = uw.shape[0]
+    if tuple(ud.shape) != (nI, K + 1) or tails_i.numel() != nI or bound_i.numel() != nI:
+        raise ValueError("nsf_wide_tables_ft: derivatives (%d, %d), tails_i and bound_i (%d,) expected" % (nI, K + 1, nI))
+    tabs = torch.empty(nI, 3 * (K + 1), dtype=torch.float32, device=uw.device)
+    L.call("nf_nsf_wide_tables_ft", ptr(uw.contiguous()), ptr(uh.contiguous()), ptr(ud.contiguous()), ptr(tails_i), ptr(bound_i),
+           ptr(tabs), nI, K, min_bin_width, min_bin_height, min_derivative, L.stream())
+    return tabs
+
+
+def nsf_wide_ft(x, blob, table, ftable, tabs, hidden_padded, direction, min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3,
+                logdet=None, acc=None, K=8):
+    """CircularCoupledRationalQuadraticSpline as one launch (nf_nsf_wide_ft); blob / table / ftable from
+    flows/nsf_circ_pack.pack_nsf_circ (ftable (8, Dp): tails, bounds and periodic features by tile position), tabs from
+    nsf_wide_tables_ft."""
+    L.require_device(x, blob, table, ftable, tabs)
+    if x.dtype != torch.float32:
+        raise NotImplementedError("nsf_wide_ft: float32 only")
+    B, D = x.shape
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    logdet, acc = _ld_buffer(logdet, acc, B, x)
+    L.call("nf_nsf_wide_ft", ptr(x), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(ftable), ptr(tabs), B, D, hidden_padded, int(K),
+           direction, acc, min_bin_width, min_bin_height, min_derivative, L.stream())
+    return y, logdet
+
+
 def resnet_ctx_forward_train(x, context, blob, table, st):
     """The GLU-gated ResidualNet under autograd (nf_resnet_ctx_forward_train): (out (B, O), save) -- save holds what
     resnet_ctx_backward / resnet_ctx_wgrad read.  st: flows/ctx_train_pack.structure; context (B, C) float32 with unit inner stride
