@@ -897,6 +897,22 @@ int nf_arnsf_inverse(const void *z, void *y, void *logdet, const void *blob, con
 int nf_arnsf_inverse_ft(const void *z, void *y, void *logdet, const void *blob, const int32_t *table, const void *ftable,
                         void *scratch, int64_t B, int D, int hidden_padded, int K, int tails, double min_bin_width,
                         double min_bin_height, double min_derivative, int acc, nf_stream_t stream);
+/* The DENSITY direction of the same layers in one launch (csrc/made_fwd_ft.hip): one MADE pass + the per-feature spline.  Replaces
+ * neural_spline/autoregressive.py:94-134 over flows/affine/autoregressive.py:24-27 for the layers neural_spline/wrapper.py:247-311
+ * (CircularAutoregressiveRationalQuadraticSpline) and :186-244 with permute_mask=True build; float32, no context, inference only.
+ *   blob, table : made_pack.pack_made_forward_ft(made, mult, K, tails, tail_bound): the streams of nf_made_forward with the initial
+ *                 layer's columns in DEGREE order and the final layer as one 32-row item per feature in degree order, rows in fixed
+ *                 slots (width k -> k, height k -> 11 + k, derivative logit j of K + 1 -> 21 + j); table[8] = final items per wave.
+ *   ftable      : (8, D) 32-bit words in degree order, the table of nf_arnsf_inverse_ft: column, tails code, bound, scale, w_sin,
+ *                 w_cos, bias, periodic flag.  Position f of the tile is column ftable[0][f] of x and y; the conditioner reads
+ *                 w_sin sin(scale x) + w_cos cos(scale x) + bias of a periodic feature, the spline the raw x.
+ *   tails       : as nf_arnsf_inverse_ft (NF_TAILS_FEATURE: 3K + 1 rows per feature, 0 / log-det 0 outside a feature's interval;
+ *                 a scalar type: 3K - 1 | 3K | 3K + 1 rows and that type's outside behaviour); the bound is always the table's.
+ *                 More than 32 rows per feature: NF_ENOTSUP; D <= 128; hidden_padded 256 | 512.
+ *   logdet, acc : the row-summed log-det combined with the caller's buffer according to acc (NF_LD_*). */
+int nf_made_forward_spline_ft(const void *x, void *y, void *logdet, const void *blob, const int32_t *table, const void *ftable,
+                              int64_t B, int D, int hidden_padded, int K, int tails, double min_bin_width, double min_bin_height,
+                              double min_derivative, int acc, nf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * GlowBlock conditioner in one launch.  Replaces ConvNet2d.forward (normflows/nets/cnn.py:5-63) for the network

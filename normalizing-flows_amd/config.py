@@ -335,6 +335,17 @@ def set_nsf_circular(mode=True):
     nsf_circular = bool(mode)
 
 
+# The density direction of the autoregressive spline layers with list tails (circular coordinates), a tensor tail bound or a permuted
+# mask at inference as ONE launch (nf_made_forward_spline_ft, csrc/made_fwd_ft.hip); False = eager MaskedLinear modules +
+# nf_rqs_coupling_ft (A/B runs, differential tests).
+arnsf_density_ft = True
+
+
+def set_arnsf_density_ft(mode=True):
+    global arnsf_density_ft
+    arnsf_density_ft = bool(mode)
+
+
 # The GLU-gated conditioner of a conditional CoupledRationalQuadraticSpline (ResidualNet with context_features) under autograd on
 # HIP kernels (autograd.ResNetCtxFn, csrc/resnet_ctx_train.hip); False = the conditioner as eager torch modules.  The route also
 # follows made_train, so inside higher_order_gradients() the torch modules run and double backward keeps working.

@@ -299,10 +299,27 @@ class MaskedPiecewiseRationalQuadraticAutoregressive(Autoregressive):
             self._arnsf_ft_pack_cache = cache = (key, packed)
         return cache[1]
 
+    def _packed_fwd_ft(self, device):
+        """Device copies of the per-feature density pack (nf_made_forward_spline_ft), cached like _packed_ft: rebuilt when a MADE
+        parameter (the periodic weights are among them) or the tail bound changes; None outside the kernel's structures."""
+        from . import made_pack
+        tb = self.tail_bound
+        key = _keys.pkey(list(self.autoregressive_net.parameters()) + ([tb] if torch.is_tensor(tb) else [])) + (str(device), self.training)
+        cache = getattr(self, "_arnsf_fwd_ft_pack_cache", None)
+        if cache is None or cache[0] != key:
+            packed = made_pack.pack_made_forward_ft(self.autoregressive_net, self._output_dim_multiplier(), self.num_bins, self.tails, tb)
+            if packed is not None:
+                blob, table, ftable = packed
+                packed = (torch.from_numpy(blob).to(device), torch.from_numpy(table).to(device),
+                          torch.from_numpy(ftable).to(device), int(table[3]))
+            self._arnsf_fwd_ft_pack_cache = cache = (key, packed)
+        return cache[1]
+
     def forward(self, inputs, context=None):
         """Density direction (autoregressive.py:24-27 + neural_spline/autoregressive.py:94-134): MADE + the element-wise spline as
-        ONE launch (nf_made_forward_spline) for 8 bins, linear tails, a scalar tail bound and the MADE structures
-        flows/made_pack.py takes; otherwise one MADE pass (one launch where possible) + nf_rqs_coupling."""
+        ONE launch -- nf_made_forward_spline for 8 bins, linear tails, a scalar tail bound and the MADE structures flows/made_pack.py
+        takes; nf_made_forward_spline_ft for list tails, a tensor bound or a permuted mask (what `inverse` samples in one launch) --
+        otherwise one MADE pass (one launch where possible) + nf_rqs_coupling."""
         if (context is None and inputs.dim() == 2 and inputs.dtype == torch.float32 and inputs.is_cuda and self.tails == "linear"
                 and self.num_bins == 8 and not torch.is_tensor(self.tail_bound)
                 and not hasattr(self.autoregressive_net, "hidden_features")
@@ -312,6 +329,19 @@ class MaskedPiecewiseRationalQuadraticAutoregressive(Autoregressive):
             if packed is not None:
                 return ops.made_forward_spline(inputs, packed[0], packed[1], packed[2], float(self.tail_bound), self.min_bin_width,
                                                self.min_bin_height, self.min_derivative)
+        from .. import config
+        listed = isinstance(self.tails, (list, tuple))
+        if (config.arnsf_density_ft and context is None and inputs.dim() == 2 and inputs.dtype == torch.float32 and inputs.is_cuda
+                and not hasattr(self.autoregressive_net, "hidden_features")
+                and (listed or torch.is_tensor(self.tail_bound) or self._permuted())
+                and not (self.tails is None and torch.is_tensor(self.tail_bound))
+                and self.min_bin_width * self.num_bins <= 1.0 and self.min_bin_height * self.num_bins <= 1.0
+                and not autograd.needs_grad(inputs, *self.autoregressive_net.parameters())):
+            packed = self._packed_fwd_ft(inputs.device)
+            if packed is not None:
+                return ops.made_forward_spline_ft(inputs, packed[0], packed[1], packed[2], packed[3], self.num_bins,
+                                                  "feature" if listed else self.tails, self.min_bin_width, self.min_bin_height,
+                                                  self.min_derivative)
         return super().forward(inputs, context)
 
     def inverse(self, inputs, context=None):

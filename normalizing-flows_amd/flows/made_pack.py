@@ -310,6 +310,129 @@ def _pack_spline(layers, D, Dp, H, Hp, NSB, NB, mult):
     return blob, np.concatenate([hdr, tab.reshape(-1)]).astype(np.int32)
 
 
+# ---- per-feature density direction (csrc/made_fwd_ft.hip, nf_made_forward_spline_ft) ------------------------------------------------
+FT_KMAX = 11                    # bins the slot layout holds (mult <= 32: K = 11 only with scalar linear tails, 3K - 1 rows)
+FT_SLOT_H, FT_SLOT_D = 11, 21   # first slot of the heights / of derivative logit 0 (made_fwd_ft.hip FTD_H0, FTD_D0)
+
+
+def ft_slot(p, K, mult):
+    """Slot (row of the feature's 32-row block) of final-layer output p of a feature: width k -> k, height k -> 11 + k, derivative
+    logit j of the K + 1 knots -> 21 + j.  mult = 3K - 1 (scalar linear tails) carries the logits 1 .. K - 1, every other layout
+    starts at logit 0."""
+    if p < K:
+        return p
+    if p < 2 * K:
+        return FT_SLOT_H + p - K
+    return FT_SLOT_D + p - 2 * K + (1 if mult == 3 * K - 1 else 0)
+
+
+def pack_made_forward_ft(made, mult, K, tails, tail_bound):
+    """(blob, table, ftable) of nf_made_forward_spline_ft, or None outside its structures (the layer-wise path stays).  Takes what
+    maf_pack.pack_made(..., rows=True, features=(tails, tail_bound)) takes for the sampling direction -- a permuted mask, a
+    PeriodicFeaturesElementwise preprocessing with an Identity activation, list tails, a tensor bound -- within this engine's sizes
+    (2 <= D <= 128, hidden <= 512, mult <= 32).  Everything is laid out in DEGREE order: position f of the tile is input column col[f]
+    (ftable row 0); the hidden items are pack_made_forward's; the final layer is ONE item per feature, its rows in ft_slot order,
+    dealt to the waves in a snake over their k-group counts; hdr[8] = final items per wave, hdr[11] = 2, entries [nkg, f]."""
+    from . import maf_pack
+    if mult not in (3 * K - 1, 3 * K, 3 * K + 1) or not 1 <= K <= FT_KMAX or mult > ROWS:
+        return None
+    if not maf_pack.supported(made, mult, blocks=range(1, (MAX_LAYERS - 2) // 2 + 1), periodic=True):
+        return None
+    D, H = made.initial_layer.in_features, made.initial_layer.out_features
+    if not (2 <= D <= MAX_D and 1 <= H <= 512):
+        return None
+    NB = len(made.blocks)
+    hid_deg = made.initial_layer.degrees.cpu().numpy()
+    lin = [made.initial_layer] + [l for b in made.blocks for l in b.linear_layers]
+    fin = made.final_layer
+    if any(not np.array_equal(l.degrees.cpu().numpy(), hid_deg) for l in lin[1:]) or fin.degrees.numel() != mult * D:
+        return None
+    in_deg = fin.degrees.cpu().numpy().astype(np.int64)[::mult]
+    if not np.array_equal(np.sort(in_deg), np.arange(1, D + 1)):
+        return None
+    m0 = made.initial_layer.mask.cpu().numpy()
+    mf = fin.mask.cpu().numpy()
+    if not np.array_equal(m0, (hid_deg[:, None] >= in_deg[None, :]).astype(m0.dtype)):
+        return None
+    if not np.array_equal(mf, (np.repeat(in_deg, mult)[:, None] > hid_deg[None, :]).astype(mf.dtype)):
+        return None
+    col = np.argsort(in_deg, kind="stable")               # col[f] = the input column of degree f + 1
+    ftable = maf_pack.feature_table(made, col, tails, tail_bound)
+    if ftable is None:
+        return None
+    Hp = 256 if H <= 256 else 512
+    NSB, Dp = Hp // 256, (D + 31) // 32 * 32
+    order = np.argsort(hid_deg, kind="stable")            # slot i holds unit order[i]
+    slot_of = np.zeros(H, dtype=np.int64)
+    slot_of[order] = np.arange(H)
+
+    def slots(lyr, in_map, in_size):
+        w = (lyr.weight.detach() * lyr.mask).cpu().numpy().astype(np.float32)
+        W = np.zeros((Hp, in_size), dtype=np.float32)
+        M = np.zeros((Hp, in_size), dtype=bool)
+        Bv = np.zeros(Hp, dtype=np.float32)
+        W[np.ix_(slot_of, in_map)] = w
+        M[np.ix_(slot_of, in_map)] = lyr.mask.cpu().numpy() != 0
+        Bv[slot_of] = lyr.bias.detach().cpu().numpy().astype(np.float32)
+        return W, M, Bv
+
+    layers = [slots(lin[0], in_deg - 1, Dp)] + [slots(l, slot_of, Hp) for l in lin[1:]]
+    wf = (fin.weight.detach() * fin.mask).cpu().numpy().astype(np.float32)
+    bf = fin.bias.detach().cpu().numpy().astype(np.float32)
+    WF = np.zeros((D, ROWS, Hp), dtype=np.float32)
+    BF = np.zeros((D, ROWS), dtype=np.float32)
+    nkg_f = np.zeros(D, dtype=np.int64)
+    for f in range(D):
+        for p in range(mult):
+            row = mult * int(col[f]) + p
+            WF[f, ft_slot(p, K, mult), slot_of] = wf[row]
+            BF[f, ft_slot(p, K, mult)] = bf[row]
+        seen = np.nonzero(hid_deg[order] < f + 1)[0]      # (sorted: a prefix of the slots)
+        nkg_f[f] = 0 if seen.size == 0 else (int(seen.max()) // KG + 4) // 4 * 4
+    deal = np.argsort(-nkg_f, kind="stable")
+    per_wave = [[] for _ in range(8)]
+    for k, f in enumerate(deal):
+        r, c = divmod(k, 8)
+        per_wave[c if r % 2 == 0 else 7 - c].append(int(f))
+    nfi = max(len(v) for v in per_wave)
+    hidden = wave_items(NSB, NB, 0)
+    nh = len(hidden[0])
+    nitems = nh + nfi
+    hdr = np.zeros(HDR, dtype=np.int32)
+    tab = np.zeros((8, nitems, 2), dtype=np.int32)
+    chunks, off = [], 0
+    for w in range(8):
+        hdr[16 + w] = off
+        stream = []
+        for i, (l, rb) in enumerate(hidden[w]):
+            W, M, Bv = layers[l]
+            r0 = rb * ROWS
+            cols = np.nonzero(M[r0:r0 + ROWS].any(axis=0))[0]
+            nkg = 0 if cols.size == 0 else (int(cols.max()) // KG + 4) // 4 * 4
+            tab[w, i] = (nkg, rb)
+            stream.append(bias_group(Bv[r0:r0 + ROWS]))
+            if nkg:
+                stream.append(a_stream(W[r0:r0 + ROWS, :KG * nkg]))
+        for j in range(nfi):
+            if j >= len(per_wave[w]):
+                tab[w, nh + j] = (0, -1)
+                continue
+            f = per_wave[w][j]
+            nkg = int(nkg_f[f])
+            tab[w, nh + j] = (nkg, f)
+            stream.append(bias_group(BF[f]))
+            if nkg:
+                stream.append(a_stream(WF[f][:, :KG * nkg]))
+        stream = np.concatenate(stream)
+        stream = np.concatenate([stream, np.resize(stream, RING * 256)])      # the ring wraps into the next tile
+        chunks.append(stream)
+        off += stream.size
+    hdr[:12] = [D, Dp, H, Hp, NSB, NB, mult, 0, nfi, off, nitems, 2]
+    blob = np.concatenate(chunks).astype(np.float32)
+    assert blob.size == off and off < 2 ** 31
+    return blob, np.concatenate([hdr, tab.reshape(-1)]).astype(np.int32), ftable
+
+
 # ---- backward pass (csrc/made_bwd.hip) ------------------------------------------------------------------------------------------------
 W_TILE = 128     # made_wgrad_kernel: edge of an output tile
 

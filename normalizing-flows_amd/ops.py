@@ -1099,6 +1099,26 @@ def made_forward_spline(x, blob, table, hidden_padded, tail_bound, min_bin_width
     return y, logdet
 
 
+def made_forward_spline_ft(x, blob, table, ftable, hidden_padded, K, tails, min_bin_width=1e-3, min_bin_height=1e-3,
+                           min_derivative=1e-3, logdet=None, acc=None):
+    """made_forward_spline with a per-feature table (nf_made_forward_spline_ft): the density direction of the layers arnsf_inverse_ft
+    samples -- permuted masks, per-feature tails ("feature") and bounds, the periodic preprocessing of circular coordinates
+    (neural_spline/autoregressive.py:44-55, :94-134; utils/splines.py:48-66; utils/nn.py:64-129); blob / table / ftable from
+    flows/made_pack.pack_made_forward_ft."""
+    L.require_device(x, blob, table, ftable)
+    if x.dtype != torch.float32:
+        raise NotImplementedError("made_forward_spline_ft: float32 only")
+    B, D = x.shape
+    if ftable.dtype != torch.float32 or tuple(ftable.shape) != (8, D):
+        raise ValueError("made_forward_spline_ft: ftable is the (8, D) float32 table of flows/maf_pack.py")
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    logdet, acc = _ld_buffer(logdet, acc, B, x)
+    L.call("nf_made_forward_spline_ft", ptr(x), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(ftable), B, D, hidden_padded, K,
+           3 if tails == "feature" else L.TAILS[tails], min_bin_width, min_bin_height, min_derivative, acc, L.stream())
+    return y, logdet
+
+
 def made_forward(x, blob, table, hidden_padded, mult):
     """MADE.forward (nets/made.py:296-304) as one launch (nf_made_forward): (B, mult D) parameters."""
     L.require_device(x, blob, table)

@@ -1,10 +1,15 @@
 """AR-NSF sampling direction (second half): nf_arnsf_inverse against the D-pass loop.
-usage: python tools/arnsf_bench.py [D H K B layers] [--circular N] [--permute] [--passes P]
+usage: python tools/arnsf_bench.py [D H K B layers] [--circular N] [--permute] [--passes P] [--density]
 
 --circular N / --permute: ONE layer of the per-feature kernel (nf_arnsf_inverse_ft) -- CircularAutoregressiveRationalQuadraticSpline with
 the first N features circular (bound pi, the others 3) and / or a permuted mask -- timed with HIP events in the same process against
 (i) the D-pass loop on the same layer (`Autoregressive.inverse(layer, z)`) and (iii) the linear-tails nf_arnsf_inverse at the same
-D / H / K; medians over P >= 20 passes after warm-up, written to profiles/circ_arnsf_bench.json."""
+D / H / K; medians over P >= 20 passes after warm-up, written to profiles/circ_arnsf_bench.json.
+
+--density: the DENSITY direction of the same layer (`layer.inverse`, default --circular 8 on a permuted mask): the layer-wise path
+(config.arnsf_density_ft = False: eager MaskedLinear modules + nf_rqs_coupling), the one-launch per-feature kernel
+(nf_made_forward_spline_ft) and the linear-tails one-launch layer (nf_made_forward_spline) in one process; median of 5 blocks of 50
+calls each (as profiles/context_bench.json was taken), written to profiles/circ_arnsf_density_bench.json."""
 import argparse, importlib.util, json, os, statistics, sys, time
 import numpy as np
 import torch
@@ -18,6 +23,7 @@ ap.add_argument("shape", nargs="*", type=int, help="D H K B layers")
 ap.add_argument("--circular", type=int, default=0, metavar="N")
 ap.add_argument("--permute", action="store_true")
 ap.add_argument("--passes", type=int, default=20)
+ap.add_argument("--density", action="store_true")
 args = ap.parse_args()
 D, H, K, B, L = args.shape if len(args.shape) == 5 else (64, 256, 8, 65536, 4)
 dev = torch.device("cuda:0")
@@ -44,6 +50,66 @@ def median_ms(fn, passes, warmup=2):
         times.append(a.elapsed_time(b))
     return statistics.median(times), min(times)
 
+
+def block_ms(fn, blocks=5, calls=50):
+    """Per-call milliseconds of `blocks` blocks of `calls` back-to-back calls, each block between two HIP events."""
+    for _ in range(5):
+        fn()
+    out = []
+    for _ in range(blocks):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(calls):
+            fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) / calls)
+    return statistics.median(out), out
+
+
+if args.density:
+    n = args.circular or 8
+    bound = torch.full((D,), 3.0)
+    bound[:n] = float(np.pi)
+    circ = nfa.flows.CircularAutoregressiveRationalQuadraticSpline(D, 2, H, ind_circ=list(range(n)), num_bins=K, tail_bound=bound,
+                                                                   permute_mask=True, init_identity=False).to(dev)
+    lin = nfa.flows.AutoregressiveRationalQuadraticSpline(D, 2, H, num_bins=K, init_identity=False).to(dev)
+    x = ((torch.rand(B, D) * 2 - 1) * bound * 0.98).to(dev)
+    calls = {"ft": 0, "lin": 0}
+    ft, ln = nfa.ops.made_forward_spline_ft, nfa.ops.made_forward_spline
+
+    def counted_ft(*a, **k):
+        calls["ft"] += 1
+        return ft(*a, **k)
+
+    def counted_lin(*a, **k):
+        calls["lin"] += 1
+        return ln(*a, **k)
+    nfa.ops.made_forward_spline_ft, nfa.ops.made_forward_spline = counted_ft, counted_lin
+    with torch.no_grad():
+        z1, l1 = circ.inverse(x)
+        lin.inverse(x)
+        assert calls == {"ft": 1, "lin": 1}, "the one-launch paths were not taken"
+        nfa.config.set_arnsf_density_ft(False)
+        z0, l0 = circ.inverse(x)
+        assert calls["ft"] == 1
+        t_layer = block_ms(lambda: circ.inverse(x))
+        nfa.config.set_arnsf_density_ft(True)
+        t_ft = block_ms(lambda: circ.inverse(x))
+        t_lin = block_ms(lambda: lin.inverse(x))
+        t_ft2 = block_ms(lambda: circ.inverse(x))          # again after the others: drift of the device between the blocks
+    rec = {"shape": {"D": D, "hidden": H, "K": K, "B": B, "circular": n, "permute": True}, "blocks": 5, "calls_per_block": 50,
+           "timer": "HIP events around 50 back-to-back calls, per-call ms: median of 5 blocks (and the blocks)",
+           "layerwise_ms": t_layer, "one_launch_ft_ms": t_ft, "one_launch_ft_again_ms": t_ft2, "linear_made_forward_spline_ms": t_lin,
+           "ft_over_layerwise": t_ft[0] / t_layer[0], "ft_over_linear": t_ft[0] / t_lin[0],
+           "max_abs_dz_vs_layerwise": float((z1 - z0).abs().max()), "max_abs_dld_vs_layerwise": float((l1 - l0).abs().max()),
+           "device": torch.cuda.get_device_name(0)}
+    print(json.dumps(rec))
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "circ_arnsf_density_bench.json"), "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    sys.exit(0)
 
 if args.circular or args.permute:
     passes = max(args.passes, 20)
