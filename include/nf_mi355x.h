@@ -741,6 +741,35 @@ int nf_config_made_tr128(int on);
 int64_t nf_made_wgrad_scratch_floats(int64_t B, int ntiles);
 int nf_made_wgrad(const void *gp_pad, const void *x_pad, const void *G, const void *save, void *grads, const void *mask, void *part,
                   const int32_t *wtable, const int32_t *stable, int ntiles, int64_t B, nf_stream_t stream);
+/* MADE under autograd for the autoregressive spline layers whose mask is permuted and / or whose circular coordinates pass the periodic
+ * preprocessing first (CircularAutoregressiveRationalQuadraticSpline, AutoregressiveRationalQuadraticSpline(permute_mask=True)).
+ * Replaces, under core.py:87-102 + loss.backward(), nets/made.py:250-252, 296-304 (the preprocessing call and the MaskedLinear stack,
+ * each linear a weight * mask multiply + a library GEMM per direction) and utils/nn.py:64-129 (index, sin, cos, cat, index per pass).
+ * Everything between the network's input and the spline's output is in DEGREE order: position f = input column col[f], the column of
+ * degree f + 1 (made_pack.made_train_structure_ft packs the initial layer's columns and the final layer's rows in that order, so
+ * nf_made_backward / nf_made_wgrad run unchanged on its tables and the weight gradients land in the parameters' own layout).
+ *   table    : made_pack.made_train_structure_ft: nf_made_forward_train's table followed by ttable = int32 [3][D]: col | scale of the
+ *              periodic feature (float bits) | its index into preprocessing.weights / .bias, -1: not periodic
+ *   blob     : the weight streams followed, at table[9], by feed = float [3][D]: w_sin | w_cos | bias of each position (zeros where
+ *              not periodic) -- gathered from the live parameters together with the streams (nf_pack_gather): no host repack per step
+ *   nf_made_forward_train_ft : nf_made_forward_train on the gathered tile fed with w_sin sin(s x) + w_cos cos(s x) + bias (sinf / cosf);
+ *                              params (B, mult D) in position order, save / bits as nf_made_forward_train leaves them on 64-ROW
+ *                              tiles whatever nf_config_made_tr128 says (the 128-row tile has no register left for the feed): its
+ *                              chain is nf_made_backward_t64 = nf_made_backward on 64-row tiles; x_pad (Bp, 128): the fed values, zeros beyond B and D =
+ *                              nf_made_wgrad's x_pad, x_pos (B, D): the raw values in position order (the spline's input).
+ *   nf_made_feed_ft_bwd      : g_pre (B, D) = nf_made_backward's g_x on that pack, g_xpos (B, D) = the spline's gradient at x_pos or
+ *                              NULL -> g_x[:, col[f]] = g_pre[:, f] d + g_xpos[:, f], d = s (w_sin cos(s x) - w_cos sin(s x)) or 1;
+ *                              g_weights (n_circ, 2) = sums over the rows of g_pre sin(s x), g_pre cos(s x); g_bias (n_circ) or NULL =
+ *                              sums of g_pre; per-workgroup partials added in a fixed order (deterministic, no atomics);
+ *                              part: 512 x 3 x n_circ floats of scratch (n_circ = 0: only the scatter-add runs, feed / g_weights /
+ *                              part may be NULL).
+ * -EINVAL for D < 2 or D > 128, -ENOTSUP for a hidden_padded other than 256 / 512, -EFAULT for a NULL operand, 0 at B = 0. */
+int nf_made_forward_train_ft(const void *x, void *params, void *save, void *bits, void *x_pad, void *x_pos, const void *blob,
+                             const int32_t *table, int64_t B, int D, int hidden_padded, int mult, nf_stream_t stream);
+int nf_made_backward_t64(const void *g_params, const void *bits, void *g_x, void *G, const void *blob, const int32_t *table, int64_t B,
+                         int D, int hidden_padded, int mult, nf_stream_t stream);
+int nf_made_feed_ft_bwd(const void *g_pre, const void *g_xpos, const void *x, const int32_t *ttable, const void *feed, void *g_x,
+                        void *g_weights, void *g_bias, void *part, int64_t B, int D, int n_circ, nf_stream_t stream);
 /* The weight streams of a training step from the parameters as they are now: out[i] = flat[src[i]], flat = [0, every parameter of
  * the network flattened], src = the packer's stream with parameter positions in place of values (made_pack.train_structure) -- the
  * reference re-reads its nn.Parameters in every forward; a host-side repack per optimizer step would cost more than the step. */

@@ -1009,6 +1009,46 @@ class MadeFn(torch.autograd.Function):
         return (None, None, gx if ctx.needs_input_grad[2] else None) + tuple(grads)
 
 
+class MadeFtFn(torch.autograd.Function):
+    """MadeFn for the MADE of an autoregressive spline layer whose mask is permuted and / or whose circular coordinates pass the
+    periodic preprocessing first (nets/made.py:250-252, 296-304 over utils/nn.py:64-129), on a DEGREE-ORDER pack
+    (flows/made_pack.made_train_structure_ft): forward = nf_made_forward_train_ft -> (params in position order, the raw inputs in
+    position order: the spline's operands), backward = nf_made_backward (64-row tiles, as the forward) + nf_made_feed_ft_bwd (the
+    feed's derivative, the scatter back to column order, the periodic parameters' gradients) + nf_made_wgrad (on the fed inputs the
+    forward left in padded shape).  `ft`: the structure's device tables (MaskedPiecewiseRationalQuadraticAutoregressive._train_packs_ft);
+    params = the linears' weight, bias ..., then preprocessing.weights [, .bias]; their gradients come back in their own layouts."""
+
+    @staticmethod
+    def forward(ctx, fwd, bwd, ft, x, *params):
+        blob, table, hp = fwd[:3]
+        x = x.contiguous()
+        out, save, bits, x_pad, x_pos = ops.made_forward_train_ft(x, blob, table, hp, bwd["MD"], bwd["NB"])
+        ctx.save_for_backward(x, save, bits, x_pad)
+        ctx.bwd, ctx.ft, ctx.blob = bwd, ft, blob
+        ctx.pshapes = [tuple(p.shape) for p in params[2 * len(bwd["offsets"]):]]      # (the periodic parameters behind the linears')
+        return out, x_pos
+
+    @staticmethod
+    @once_differentiable          # (the backward is a set of kernels, not a differentiable graph: double backward raises)
+    def backward(ctx, gout, gxpos):
+        x, save, bits, x_pad = ctx.saved_tensors
+        bwd, ft = ctx.bwd, ctx.ft
+        gout = torch.zeros(x.shape[0], bwd["MD"], dtype=x.dtype, device=x.device) if gout is None else gout.contiguous()
+        g_pre, G = ops.made_backward(gout, bits, bwd["blob"], bwd["table"], x.shape[1], bwd["Hp"], bwd["NB"], tile64=True)
+        gx, gw, gb = ops.made_feed_ft_bwd(g_pre, gxpos, x, ft["ttable"], ctx.blob[ft["feed_off"]:], ft["n_circ"], ft["has_bias"])
+        n_lin = 2 * len(bwd["offsets"])
+        grads = [None] * n_lin
+        if any(ctx.needs_input_grad[4:4 + n_lin]):
+            flat = ops.made_wgrad(gout, x_pad, G, save, bwd["wtable"], bwd["stable"], bwd["mask"], bwd["ntiles"], bwd["nflat"],
+                                  bwd["Mp"], bwd["Dx"])
+            grads = _made_param_grads(flat, bwd["offsets"])
+        periodic = [g for g in (gw, gb) if g is not None]
+        if not ft["n_circ"]:          # (a periodic preprocessing without a circular column: empty parameters, empty gradients)
+            periodic = [x.new_zeros(sh) for sh in ctx.pshapes]
+        assert len(periodic) == len(ctx.pshapes)
+        return (None, None, None, gx if ctx.needs_input_grad[3] else None) + tuple(grads) + tuple(periodic)
+
+
 class ResNetCtxFn(torch.autograd.Function):
     """ResidualNet.forward with a context (nets/resnet.py:7-104: initial layer on cat(x, context), per block the GLU gate
     glu(cat(t2, context_layer(context))) = t2 * sigmoid(Wc context + bc)) under autograd: forward = nf_resnet_ctx_forward_train (saves

@@ -346,6 +346,18 @@ def set_arnsf_density_ft(mode=True):
     arnsf_density_ft = bool(mode)
 
 
+# The same layers UNDER AUTOGRAD in the density direction on the MADE training kernels (autograd.MadeFtFn: nf_made_forward_train_ft,
+# nf_made_backward, nf_made_feed_ft_bwd, nf_made_wgrad on a degree-order pack); False = eager MaskedLinear modules + torch.sin /
+# torch.cos in front of SplineFn.  The route also follows made_train and made_fused, so inside higher_order_gradients() the torch
+# modules run and double backward keeps working.
+arnsf_train_ft = True
+
+
+def set_arnsf_train_ft(mode=True):
+    global arnsf_train_ft
+    arnsf_train_ft = bool(mode)
+
+
 # The GLU-gated conditioner of a conditional CoupledRationalQuadraticSpline (ResidualNet with context_features) under autograd on
 # HIP kernels (autograd.ResNetCtxFn, csrc/resnet_ctx_train.hip); False = the conditioner as eager torch modules.  The route also
 # follows made_train, so inside higher_order_gradients() the torch modules run and double backward keeps working.

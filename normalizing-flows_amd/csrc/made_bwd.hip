@@ -530,6 +530,19 @@ extern "C" int nf_made_backward(const void *g_params, const void *bits, void *g_
     return nf::made_bwd_launch<2>(g_params, bits, g_x, G, blob, table, B, st, dp);
 }
 
+// nf_made_backward on 64-row tiles whatever mf_tr128() says: the chain behind nf_made_forward_train_ft, which has no 128-row tile.
+extern "C" int nf_made_backward_t64(const void *g_params, const void *bits, void *g_x, void *G, const void *blob, const int32_t *table,
+                                    int64_t B, int D, int hidden_padded, int mult, nf_stream_t stream) {
+    const int rc = made_bwd_check(B, D, hidden_padded, mult);
+    if (rc != NF_OK) return rc;
+    if (B == 0) return NF_OK;
+    if (!g_params || !bits || !g_x || !blob || !table) return NF_EFAULT;
+    hipStream_t st = (hipStream_t)stream;
+    const int dp = (D + 31) / 32 * 32;
+    if (hidden_padded == 256) return nf::made_bwd_launch<1>(g_params, bits, g_x, G, blob, table, B, st, dp);
+    return nf::made_bwd_launch<2>(g_params, bits, g_x, G, blob, table, B, st, dp);
+}
+
 static int made_wgrad_chunk_rows(int64_t Bp, int ntiles) {
     // measured at config 5's layer (50 tiles, B = 65 536; ablation builds with -DNF_MW_SLOTS / -DNF_MW_TILE_MAJOR): 768 / 1024 / 1536 / 2048 / 3072 workgroups
     // = 1.19 / 1.12 / 0.98 / 1.07 / 0.99 ms for this launch + 18 / 24 / 33 / 40 / 55 us for the reduction: three rounds of 512

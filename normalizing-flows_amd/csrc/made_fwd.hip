@@ -31,258 +31,15 @@
 
 namespace nf {
 
-// EPI 0: z = scale x + shift, logdet = sum log scale (autoregressive.py:101-110, :124-128: rows 2 f = unconstrained scale, 2 f + 1
-// = shift);  EPI 1: the raw MADE output (B, mult D) for the callers that apply another element-wise transform;  EPI 2: the
-// autoregressive rational-quadratic spline of neural_spline/autoregressive.py:94-134 (density direction: one MADE pass, then
-// utils/splines.py:16-219 element-wise with 8 bins and linear tails) on the final layer's accumulators -- the final layer runs in
-// groups of four features whose rows are packed so that a lane holds the 2 x 24 parameters of two features (the layout of
-// nsf_wide.hip; mlp_tile.hpp mf_final_item), the spline runs in registers (rqs_regs), x is read from the tile and y written into it.
-// EPI 3: EPI 1 under autograd (core.py:87-102 through a MADE): every layer's pre-activations are also written row-major to
-// save[l][Bp][Hp] (l = 0: the initial layer's h; 2 b + 1: block b's inner t; 2 b + 2: its output h) and the signs of what a ReLU
-// follows to bits[tile][2 b | 2 b + 1][item][512 lanes] -- the operands of made_bwd.hip.
+// (the body is the text of made_fwd_body.hpp: made_fwd_train_ft.hip compiles it once more behind a gathered, fed x tile)
 template <int NSB, int EPI, int TR = MF_ROWS>
 __global__ void __launch_bounds__(64 * MF_NW, 1)
 made_fwd_kernel(const float *__restrict__ x, float *__restrict__ y, float *__restrict__ logdet, const float *__restrict__ blob,
                 const int *__restrict__ table, int64_t B, int acc_mode, RqsParams<float> p, float *__restrict__ save,
                 unsigned *__restrict__ bits, int64_t Bp) {
-    static_assert(TR == 64 || (TR == 128 && NSB == 1 && EPI == 3), "128-row tiles: the 256-slot training forward only (mf_tr128)");
-    constexpr int NSH = TR / 64;             // sample blocks per HALF of a tile (a 256-slot item covers one half, a final-layer item too)
-    constexpr int NS = NSB * NSH;            // sample blocks per hidden work item
-    constexpr int HP = 256 * NSB;
-    constexpr int HRB = 8 * NSB;             // hidden row-blocks
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    float *acts = lds;                                  // [HRB * 4 k-groups][2][TR][4]
-    float *xreg = lds + (size_t)HRB * 4 * 8 * TR;       // [Dp / 8][2][TR][4]
-    const int tid = threadIdx.x, lane = tid & 63, n = lane & 31, hh = lane >> 5;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int D = table[0], Dp = table[1], NB = table[5], NFB = table[7], nrounds = table[8], nitems = table[10];
-    const int MD = table[12] ? table[12] : table[6] * D;       // raw output row length: mult D for a MADE, out_features for a ResidualNet
-    const int ldx = table[14] ? table[14] : D;                 // row stride of x (the conv path hands over 128-padded rows)
-    const int plain = table[13];     // 1: a plain MLP  x -> W0 -> relu -> W1 -> relu -> Wf  (NB = 1 without the block's second linear and
-                                     // its residual; EPI 1 / 3 only): the 3x3 -> 1x1 -> 3x3 conv conditioner over pixel rows (conv_rows.hip)
-    const int *items = table + MF_HDR + w * nitems * 2;       // [nitems][nkg, rb]
-    const float *stream = blob + table[16 + w];
-    const int rbs[2] = {w, HRB - 1 - w};                      // (the packer's wave_items: the hidden row-blocks of this wave)
-    const int sb0s[2] = {0, NSB == 2 ? 0 : NSH};
-    const int lane_b = (TR * hh + n) * 4;       // the lane's offset inside a k-group of activations (sample block 0)
-    const int64_t ntiles = (B + TR - 1) / TR;
-    MfRing ring;
-    mf_ring_start(ring, stream, lane);
-
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t row0 = tile * TR;
-        const int nrows = (int)((B - row0) < TR ? (B - row0) : TR);
-        ring.ap = stream + lane * 4;            // (the ring already holds the stream's first entries: the wrap-around copy)
-        int tq = tid;                           // per-tile address arithmetic from an index the compiler cannot hoist out of the tile loop
-        asm volatile("" : "+v"(tq));            // (round 6, as in nsf_wide.hip: hoisted, those values stayed live across the products)
-        asm volatile("" : "+v"(ring.ap));       // (likewise the restarted stream's first request addresses: four 64-bit pairs)
-        // ---- x tile -> LDS (B-operand order; rows beyond the batch and features beyond D are zero) ---------------------------------
-        {
-            const int r = tq & (TR - 1), cg = tq / TR;
-            const float *xr = x + (row0 + r) * ldx;
-#pragma unroll 1
-            for (int c = cg; c < Dp / 4; c += 64 * MF_NW / TR) {
-                f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (r < nrows && 4 * c < D) {           // (Dp rounds D up to 32: the last chunks may lie wholly beyond the row)
-                    if ((D & 3) == 0) v = *reinterpret_cast<const f32x4 *>(xr + 4 * c);
-                    else
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) if (4 * c + i < D) v[i] = xr[4 * c + i];
-                }
-                *reinterpret_cast<f32x4 *>(xreg + ((size_t)c * TR + r) * 4) = v;
-            }
-        }
-        f32x16 h[2][NS], t[2][NS];
-        MF_BARRIER();
-        // ---- initial layer: h = b0 + W0 x ----------------------------------------------------------------------------------------------
-#pragma unroll
-        for (int s = 0; s < 2; ++s) mf_item<NS, false, TR>(ring, items[2 * s], xreg + lane_b + 128 * sb0s[s], h[s]);
-        float *stile = nullptr;
-        unsigned *btile = nullptr;
-        if constexpr (EPI == 3) {
-            stile = save + (size_t)row0 * HP;
-            btile = bits + ((size_t)tile * 2 * NB * 2) * 512 + tq;
-#pragma unroll
-            for (int s = 0; s < 2; ++s) mf_save_rows<NS, true>(stile, HP, nrows, rbs[s], sb0s[s], hh, n, h[s]);
-        }
-        // ---- residual blocks (nets/made.py:196-214): t = b1 + W1 relu(h);  h += b2 + W2 relu(t) -------------------------------
-        for (int b = 0; b < NB; ++b) {
-            MF_BARRIER();        // (b > 0: every wave has finished reading relu(t) of the previous block)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) mf_publish<NS, true, TR>(acts, rbs[s], sb0s[s], hh, n, h[s]);
-            if constexpr (EPI == 3)
-#pragma unroll
-                for (int s = 0; s < 2; ++s) btile[((size_t)(2 * b) * 2 + s) * 512] = mf_sign_bits<NS>(h[s]);
-            MF_BARRIER();
-#pragma unroll
-            for (int s = 0; s < 2; ++s) mf_item<NS, false, TR>(ring, items[2 * (2 + 4 * b + s)], acts + lane_b + 128 * sb0s[s], t[s]);
-            MF_BARRIER();
-#pragma unroll
-            for (int s = 0; s < 2; ++s) mf_publish<NS, true, TR>(acts, rbs[s], sb0s[s], hh, n, t[s]);
-            if constexpr (EPI == 3)
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    btile[((size_t)(2 * b + 1) * 2 + s) * 512] = mf_sign_bits<NS>(t[s]);
-                    mf_save_rows<NS, true>(stile + (size_t)(2 * b + 1) * Bp * HP, HP, nrows, rbs[s], sb0s[s], hh, n, t[s]);
-                }
-            MF_BARRIER();
-            if (plain) break;            // (relu(t) is published: the final layer's input)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) mf_item<NS, true, TR>(ring, items[2 * (4 + 4 * b + s)], acts + lane_b + 128 * sb0s[s], h[s]);
-            if constexpr (EPI == 3)
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-                    mf_save_rows<NS, true>(stile + (size_t)(2 * b + 2) * Bp * HP, HP, nrows, rbs[s], sb0s[s], hh, n, h[s]);
-        }
-        // ---- final layer on the RAW block output (:303-304) + epilogue -------------------------------------------------------------
-        if (!plain) {
-            MF_BARRIER();
-#pragma unroll
-            for (int s = 0; s < 2; ++s) mf_publish<NS, false, TR>(acts, rbs[s], sb0s[s], hh, n, h[s]);
-            MF_BARRIER();
-        }
-        if constexpr (EPI == 2) {
-            const int G = NFB, nfi = nrounds;                 // (the header slots of the block variants: groups, final items per wave)
-            const int *fit = items + 2 * (2 + 4 * NB);
-            float ldt[4][2] = {{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}};
-#pragma nounroll
-            for (int j = 0; j < nfi; ++j) {
-                const int g = fit[2 * j + 1];
-                if (g < 0) continue;
-                f32x16 o[3][2];
-                mf_final_item<MF_ROWS>(ring, fit[2 * j], acts + lane_b, o);
-                float lsum[2] = {0.0f, 0.0f};
-#pragma unroll
-                for (int sb = 0; sb < 2; ++sb)
-#pragma unroll
-                    for (int f = 0; f < 2; ++f) {
-                        float prm[24];
-#pragma unroll
-                        for (int v = 0; v < 24; ++v) prm[v] = o[(24 * f + v) >> 4][sb][(24 * f + v) & 15];
-                        const int tf = 4 * g + 2 * hh + f;
-                        const bool valid = tf < D;
-                        const int col = valid ? tf : 0;
-                        float *xp = xreg + ((size_t)(col >> 2) * 64 + 32 * sb + n) * 4 + (col & 3);
-                        float yv, lad;
-                        rqs_regs_h<false>(p, *xp, prm, yv, lad);      // (round 5: binary bin descent; round 6: its first level before the knots exist)
-                        if (valid) {
-                            *xp = yv;
-                            lsum[sb] += lad;
-                        }
-                        __builtin_amdgcn_sched_barrier(0);      // one evaluation at a time: interleaved, the four cost 7 spilled VGPRs at Hp = 512
-                    }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    ldt[q][0] = j == q ? lsum[0] : ldt[q][0];
-                    ldt[q][1] = j == q ? lsum[1] : ldt[q][1];
-                }
-            }
-            MF_BARRIER();                      // every wave is done with the activations: their region now holds the partial sums
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (j >= nfi) break;
-                const int g = fit[2 * j + 1];
-                if (g >= 0) {
-#pragma unroll
-                    for (int sb = 0; sb < 2; ++sb) {
-                        const float v = ldt[j][sb] + __shfl_xor(ldt[j][sb], 32);
-                        if (hh == 0) acts[g * 64 + 32 * sb + n] = v;
-                    }
-                }
-            }
-            MF_BARRIER();
-            if (tq < nrows) {
-                float v = 0.0f;
-                for (int g = 0; g < G; ++g) v += acts[g * 64 + tq];      // fixed order: deterministic
-                ld_store(logdet + row0 + tq, v, acc_mode);
-            }
-            const int r = tq & 63, cg = tq >> 6;
-            float *yr = y + (row0 + r) * D;
-            if (r < nrows)
-                for (int c = cg; 4 * c < D; c += MF_NW) {
-                    const f32x4 v = *reinterpret_cast<const f32x4 *>(xreg + ((size_t)c * 64 + r) * 4);
-                    if ((D & 3) == 0) *reinterpret_cast<f32x4 *>(yr + 4 * c) = v;
-                    else
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) if (4 * c + i < D) yr[4 * c + i] = v[i];
-                }
-            MF_BARRIER();                      // the next tile overwrites the x tile and the activations
-            continue;
-        }
-        float ldsum[2] = {0.0f, 0.0f};
-        for (int rd = 0; rd < nrounds; ++rd) {
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const int *it = items + 2 * (2 + 4 * NB + 2 * rd + s);
-                const int fb = it[1];                         // sample half s (TR = 64: sample block s)
-                if (fb >= 0) {
-                    f32x16 o[NSH];
-                    mf_item<NSH, false, TR>(ring, it[0], acts + lane_b + 128 * NSH * s, o);
-                    if constexpr (EPI == 0) {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const int f0 = 16 * fb + 4 * q + 2 * hh;
-                            float *xp = xreg + ((size_t)((2 * fb + (q >> 1)) * 2 + (q & 1)) * 64 + 32 * s + n) * 4 + 2 * hh;
-#pragma unroll
-                            for (int e = 0; e < 2; ++e) {
-                                if (f0 + e < D) {
-                                    const float scale = 1.0f / (1.0f + __expf(-(o[0][4 * q + 2 * e] + 2.0f))) + 1e-3f;
-                                    xp[e] = scale * xp[e] + o[0][4 * q + 2 * e + 1];
-                                    ldsum[s] += __logf(scale);
-                                }
-                            }
-                        }
-                    } else {
-#pragma unroll
-                        for (int ss = 0; ss < NSH; ++ss) {
-                            const int rl = 32 * (NSH * s + ss) + n;
-                            const int64_t r = row0 + rl;
-                            if (rl < nrows) {
-                                float *yp = y + r * (int64_t)MD + 32 * fb + 4 * hh;
-#pragma unroll
-                                for (int q = 0; q < 4; ++q) {
-                                    const int c = 32 * fb + 8 * q + 4 * hh;
-                                    if ((MD & 3) == 0) {
-                                        if (c < MD) *reinterpret_cast<f32x4 *>(yp + 8 * q) = f32x4{o[ss][4 * q], o[ss][4 * q + 1], o[ss][4 * q + 2], o[ss][4 * q + 3]};
-                                    } else {
-#pragma unroll
-                                        for (int i = 0; i < 4; ++i) if (c + i < MD) yp[8 * q + i] = o[ss][4 * q + i];
-                                    }
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        MF_BARRIER();                          // every wave is done with the activations (and, EPI 0, has written its z values)
-        if constexpr (EPI == 0) {
-            // per-sample log-det: the lane-halves' sums, then the 8 row-blocks' in a FIXED order (deterministic)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const float v = ldsum[s] + __shfl_xor(ldsum[s], 32);
-                const int fb = (s == 0 ? w : 7 - w);
-                if (hh == 0) acts[fb * 64 + 32 * s + n] = v;
-            }
-            MF_BARRIER();
-            if (tq < nrows) {
-                float v = 0.0f;
-                for (int fb = 0; fb < 8; ++fb) v += acts[fb * 64 + tq];
-                ld_store(logdet + row0 + tq, v, acc_mode);
-            }
-            const int r = tq & 63, cg = tq >> 6;
-            float *yr = y + (row0 + r) * D;
-            if (r < nrows)
-                for (int c = cg; 4 * c < D; c += MF_NW) {
-                    const f32x4 v = *reinterpret_cast<const f32x4 *>(xreg + ((size_t)c * 64 + r) * 4);
-                    if ((D & 3) == 0) *reinterpret_cast<f32x4 *>(yr + 4 * c) = v;
-                    else
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) if (4 * c + i < D) yr[4 * c + i] = v[i];
-                }
-            MF_BARRIER();                      // the next tile overwrites the x tile and the activations
-        }
-    }
+    constexpr bool FT = false;
+    float *const x_pad = nullptr;
+#include "made_fwd_body.hpp"
 }
 
 template <int NSB, int EPI, int TR = MF_ROWS>

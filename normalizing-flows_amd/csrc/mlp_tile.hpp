@@ -13,6 +13,7 @@ constexpr int MF_ROWS = 64;       // rows per workgroup and tile
 constexpr int MF_NW = 8;          // waves per workgroup: two per SIMD
 constexpr int MF_HDR = 32;
 constexpr int MF_XFLOATS = 16 * 2 * 64 * 4;      // x tile: Dp <= 128 features
+constexpr int MF_LDP = 128;       // row length of the fed inputs nf_made_forward_train_ft leaves for nf_made_wgrad (D <= 128)
 
 // 128-ROW tiles for the training kernels of a 256-slot network with <= 64 input features (round 6, last session; made_fwd.hip EPI 3,
 // made_bwd.hip): a work item then spans TWO sample blocks (NS = 2) like the 512-slot kernels -- every weight fragment feeds eight MFMAs

@@ -14,7 +14,9 @@ the MADE has the supported structure (flows/maf_pack.py): every hidden unit is f
 pass instead of D; the autoregressive spline layer (AR-NSF sampling) does the same through nf_arnsf_inverse, and through
 nf_arnsf_inverse_ft when its mask is permuted, its tails or its tail bound are given per feature or circular coordinates put the
 periodic preprocessing in front of the conditioner (CircularAutoregressiveRationalQuadraticSpline: the kernel walks the features in
-degree order with a per-feature table, flows/maf_pack.py).  Under autograd the
+degree order with a per-feature table, flows/maf_pack.py); under autograd the density direction of those layers runs on the MADE
+training kernels in degree order (autograd.MadeFtFn: nf_made_forward_train_ft, nf_made_backward, nf_made_feed_ft_bwd, nf_made_wgrad;
+config.arnsf_train_ft).  Under autograd the
 affine layer's inverse is differentiated implicitly (autograd.MafInverseFn: the one-pass kernel forward, chain sweeps + one
 weight-gradient launch backward); other structures, float64 and the spline layer's gradient-tracking inverse keep the reference's
 D-pass loop.
@@ -342,7 +344,64 @@ class MaskedPiecewiseRationalQuadraticAutoregressive(Autoregressive):
                 return ops.made_forward_spline_ft(inputs, packed[0], packed[1], packed[2], packed[3], self.num_bins,
                                                   "feature" if listed else self.tails, self.min_bin_width, self.min_bin_height,
                                                   self.min_derivative)
+        if (config.arnsf_train_ft and config.made_train and config.made_fused and context is None and inputs.dim() == 2
+                and inputs.dtype == torch.float32 and inputs.is_cuda and not hasattr(self.autoregressive_net, "hidden_features")
+                and (listed or torch.is_tensor(self.tail_bound) or self._permuted())
+                and not (self.tails is None and torch.is_tensor(self.tail_bound))
+                and autograd.needs_grad(inputs, *self.autoregressive_net.parameters())):
+            # under autograd: the MADE training kernels on a degree-order pack (autograd.MadeFtFn); the spline runs in position
+            # order on what the forward kernel gathered, only its output goes back to column order
+            packs = self._train_packs_ft(inputs.device)
+            if packs is not None:
+                fwd, bwd, ft, plist = packs
+                params_pos, x_pos = autograd.MadeFtFn.apply(fwd, bwd, ft, inputs, *plist)
+                kw = dict(self._tails_kwargs_pos(ft, inputs.device), min_bin_width=self.min_bin_width,
+                          min_bin_height=self.min_bin_height, min_derivative=self.min_derivative, wh_div=1.0)
+                y_pos, ld = autograd.SplineFn.apply(x_pos, params_pos, None, None, None, self.num_bins, False, kw)
+                return (y_pos if ft["identity"] else y_pos.index_select(1, ft["inv_col"])), ld
         return super().forward(inputs, context)
+
+    def _train_packs_ft(self, device):
+        """(forward pack, backward pack, device tables, parameter list) of autograd.MadeFtFn, or None outside
+        flows/made_pack.made_train_structure_ft.  The value-independent structure is built once per layer and device; the weight
+        streams and the periodic parameters are gathered on the device from the parameters as they are in THIS call."""
+        from . import made_pack
+        net = self.autoregressive_net
+        if not made_pack.supported_ft(net, self._output_dim_multiplier()):       # (re-checked on every call: cheap, mode-dependent)
+            return None
+        plist = [t for l in net._linears() for t in (l.weight, l.bias)] + made_pack.periodic_params(net)
+        if not all(p.is_cuda and p.device == device for p in plist):
+            return None
+        pre = net.preprocessing
+        skey = tuple((l.mask.data_ptr(), l.mask._version) for l in net._linears()) + (id(pre), getattr(pre, "apply_bias", None))
+        struct = nets._train_struct_for(self, lambda: made_pack.made_train_structure_ft(net, self._output_dim_multiplier()), device, skey)
+        if struct is None:
+            return None
+        ft = struct.get("ft_dev")
+        if ft is None:
+            col = torch.from_numpy(struct["col"]).to(device)
+            ft = struct["ft_dev"] = dict(ttable=struct["table"][struct["tt_off"]:], feed_off=struct["feed_off"], n_circ=struct["n_circ"],
+                                         has_bias=struct["has_bias"], col=col, col_host=struct["col"],
+                                         inv_col=torch.from_numpy(struct["inv_col"]).to(device),
+                                         identity=bool((struct["col"] == np.arange(len(struct["col"]))).all()))
+        both = ops.pack_gather([p for p in plist if p.numel()], struct["src"])       # (no circular column: empty periodic parameters)
+        bwd = dict(struct["bwd"])
+        bwd["blob"] = both[struct["nfwd"]:]
+        return (both[:struct["nfwd"]], struct["table"], struct["hp"]), bwd, ft, plist
+
+    def _tails_kwargs_pos(self, ft, device):
+        """_tails_kwargs with the per-feature tails / bounds in POSITION order (permuted by col)."""
+        from .neural_spline import _tails_kwargs
+        tails, tb = self.tails, self.tail_bound
+        if isinstance(tails, (list, tuple)):
+            tails = [tails[int(c)] for c in ft["col_host"]]
+        if torch.is_tensor(tb) and tb.numel() > 1:
+            key = (tb.data_ptr(), tb._version, str(device))
+            c = ft.get("tb_pos")                  # (the caches live with the structure: a new permutation starts new ones)
+            if c is None or c[0] != key:
+                c = ft["tb_pos"] = (key, tb.reshape(-1).to(device).index_select(0, ft["col"]).contiguous())
+            tb = c[1]
+        return _tails_kwargs(tails, tb, "t", device, ft.setdefault("tcache", {}))
 
     def inverse(self, inputs, context=None):
         """One launch for the supported MADE structure (float32, no context, no sqrt(hidden) scaling, no gradient tracking):

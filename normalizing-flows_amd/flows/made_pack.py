@@ -86,11 +86,25 @@ def wave_items(NSB, NB, NFB):
     return out
 
 
-def _slot_layers(made, mult, wb=None):
+def supported_ft(made, mult):
+    """What the degree-order training structure takes (made_train_structure_ft): pack_made_forward_ft's eligibility -- a permuted mask, a
+    PeriodicFeaturesElementwise preprocessing with an Identity activation (with or without its bias) -- within the training kernels'
+    sizes."""
+    from . import maf_pack
+    if not maf_pack.supported(made, mult, blocks=range(1, (MAX_LAYERS - 2) // 2 + 1), periodic=True):
+        return False
+    D, H = made.initial_layer.in_features, made.initial_layer.out_features
+    return 2 <= D <= MAX_D and 1 <= H <= 512
+
+
+def _slot_layers(made, mult, wb=None, ft=False):
     """The MADE's masked linears in SLOT space (hidden units sorted by degree, zero-padded): dict with the sizes, `order` (slot ->
     unit) and `layers` = [(W, M, b)] for the initial layer, the blocks' linears and the final layer; None outside the structure.
-    wb: [(weight, bias)] arrays to rearrange instead of the module's parameters (index_arrays: the packs as gather indices)."""
-    if not supported(made, mult):
+    wb: [(weight, bias)] arrays to rearrange instead of the module's parameters (index_arrays: the packs as gather indices).
+    ft: DEGREE order (supported_ft): position f = input column col[f], the column of degree f + 1 -- the initial layer's columns go
+    through in_deg - 1, the final layer's parameter row mult c + p lands in position row mult pos(c) + p, so every mask is block
+    lower-triangular whatever the permutation; without a permutation the arrays are the ones ft = False builds."""
+    if not (supported_ft(made, mult) if ft else supported(made, mult)):
         return None
     D = made.initial_layer.in_features
     H = made.initial_layer.out_features
@@ -101,14 +115,23 @@ def _slot_layers(made, mult, wb=None):
         if not np.array_equal(l.degrees.cpu().numpy(), hid_deg):
             return None
     fin = made.final_layer
-    # inputs in degree order (no permute_mask) and the output rows feature-major: what the element-wise epilogue assumes
+    # inputs in degree order (ft: any permutation of it) and the output rows feature-major: what the element-wise epilogue assumes
+    in_deg = np.arange(1, D + 1)
+    if ft:
+        if fin.degrees.numel() != mult * D:
+            return None
+        in_deg = fin.degrees.cpu().numpy().astype(np.int64)[::mult]
+        if not np.array_equal(np.sort(in_deg), np.arange(1, D + 1)):
+            return None
     m0 = made.initial_layer.mask.cpu().numpy()
-    if not np.array_equal(m0, (hid_deg[:, None] >= np.arange(1, D + 1)[None, :]).astype(m0.dtype)):
+    if not np.array_equal(m0, (hid_deg[:, None] >= in_deg[None, :]).astype(m0.dtype)):
         return None
     mf = fin.mask.cpu().numpy()
-    out_deg = np.repeat(np.arange(1, D + 1), mult)
+    out_deg = np.repeat(in_deg, mult)
     if not np.array_equal(mf, (out_deg[:, None] > hid_deg[None, :]).astype(mf.dtype)):
         return None
+    col = np.argsort(in_deg, kind="stable")               # col[f] = the input column of degree f + 1
+    pos_rows = (mult * (in_deg - 1)[:, None] + np.arange(mult)[None, :]).reshape(-1)      # parameter row mult c + p -> position row
     Hp = 256 if H <= 256 else 512
     NSB = Hp // 256
     Dp = (D + 31) // 32 * 32
@@ -141,12 +164,12 @@ def _slot_layers(made, mult, wb=None):
         Bv[out_rows] = b
         return W, M, Bv
 
-    layers = [slots(lin[0], np.arange(D), Dp, slot_of, Hp)]
+    layers = [slots(lin[0], in_deg - 1, Dp, slot_of, Hp)]
     for l in lin[1:]:
         layers.append(slots(l, slot_of, Hp, slot_of, Hp))
-    layers.append(slots(fin, slot_of, Hp, np.arange(mult * D), NFB * ROWS))
+    layers.append(slots(fin, slot_of, Hp, pos_rows, NFB * ROWS))
     return dict(D=D, H=H, NB=NB, Hp=Hp, NSB=NSB, Dp=Dp, NFB=NFB, MD=mult * D, mult=mult, order=order, slot_of=slot_of,
-                layers=layers, masks=[l.mask.cpu().numpy() != 0 for l in lin + [fin]])
+                layers=layers, masks=[l.mask.cpu().numpy() != 0 for l in lin + [fin]], col=col)
 
 
 def resnet_supported(net):
@@ -538,6 +561,9 @@ def _pack_backward_from(sl):
     feat_map[:D] = np.arange(D)
     out_map = np.full(Mp, -1, dtype=np.int32)
     out_map[:MD] = np.arange(MD)
+    if sl.get("col") is not None:     # degree order (_slot_layers): position -> the parameter's own column / row (the identity without a permutation)
+        feat_map[:D] = sl["col"]
+        out_map[:MD] = (mult * sl["col"][:, None] + np.arange(mult)[None, :]).reshape(-1)
     # (problem: dY base / matrix / ld, X base / matrix / ld, relu, slot-space mask [M x N], row map, column map, parameter shape)
     probs = [(2, 0, Hp, 1, 0, Dx, 0, layers[0][1], slot_to_unit, feat_map, (H, D))]
     if plain:      # x -> W0 -> relu -> W1 -> relu -> Wf: dW1 = G[1]^T relu(save[0]), dWf = g_p^T relu(save[1])
@@ -704,6 +730,90 @@ def made_train_structure(made, mult):
     if not supported(made, mult):
         return None
     return _shared(("made", mult, _mask_key(made)), build)
+
+
+def train_feature_table(made, col):
+    """int32 [3][D] of nf_made_forward_train_ft / nf_made_feed_ft_bwd for the positions `col` (degree order): the input column, the
+    scale of its periodic feature (float32 bits; utils/nn.py:64-129) and that feature's index into preprocessing.weights / .bias, -1 for
+    a position that is fed as it is; None for a preprocessing the table cannot express."""
+    from .. import nets
+    D = len(col)
+    pre = made.preprocessing
+    scale_c = np.zeros(D, dtype=np.float32)
+    pidx_c = np.full(D, -1, dtype=np.int32)
+    if isinstance(pre, nets.PeriodicFeaturesElementwise):
+        ind = pre.ind.cpu().numpy().astype(np.int64)
+        if pre.ndim != D or len(set(ind.tolist())) != ind.size or (ind.size and (ind.min() < 0 or ind.max() >= D)):
+            return None
+        if tuple(pre.weights.shape) != (ind.size, 2) or pre.weights.dtype != torch.float32:
+            return None
+        scale = pre.scale
+        if torch.is_tensor(scale):
+            if scale.numel() not in (1, ind.size):
+                return None
+            scale = np.broadcast_to(scale.detach().cpu().numpy().astype(np.float32).reshape(-1), (ind.size,))
+        scale_c[ind] = scale
+        pidx_c[ind] = np.arange(ind.size)
+    elif not isinstance(pre, torch.nn.Identity):
+        return None
+    return np.stack([np.asarray(col, dtype=np.int32), scale_c[col].view(np.int32), pidx_c[col]]).astype(np.int32)
+
+
+def periodic_params(made):
+    """[preprocessing.weights, preprocessing.bias] as far as they exist: the parameters that follow the linears' in the flat vector of
+    made_train_structure_ft."""
+    pre = made.preprocessing
+    if isinstance(pre, torch.nn.Identity):
+        return []
+    return [pre.weights] + ([pre.bias] if pre.apply_bias else [])
+
+
+def made_train_structure_ft(made, mult):
+    """made_train_structure in DEGREE order (_slot_layers(ft=True)) for nf_made_forward_train_ft: the same dict, with
+      table   followed by the training feature table (train_feature_table; `tt_off` = its offset),
+      src     followed by the gather indices of feed = [w_sin | w_cos | bias][D] per position (0 = the flat vector's zero where a
+              position is not periodic or there is no bias), so that the forward blob ends with the live periodic parameters
+              (`feed_off` = their offset = table[9]); flat vector = [0, the linears' weight / bias ..., preprocessing.weights, .bias],
+      col, inv_col, n_circ, has_bias.
+    The backward tables' row / column maps scatter the weight gradients into the parameters' own (column-order) layout."""
+    def build():
+        sl = _slot_layers(made, mult, ft=True)
+        if sl is None:
+            return None
+        tt = train_feature_table(made, sl["col"])
+        if tt is None:
+            return None
+        lins = [made.initial_layer] + [l for b in made.blocks for l in b.linear_layers] + [made.final_layer]
+        shapes = [tuple(l.weight.shape) for l in lins]
+        st = train_structure(sl, _slot_layers(made, mult, wb=index_arrays(shapes), ft=True))
+        D = sl["D"]
+        pidx = tt[2]
+        n_circ = int((pidx >= 0).sum())
+        has_bias = bool(n_circ and made.preprocessing.apply_bias)
+        base = 1 + sum(o * i + o for o, i in shapes)          # flat position of preprocessing.weights[0, 0]
+        feed = np.zeros((3 * D + 63) // 64 * 64, dtype=np.int32)      # (padded: the backward streams that follow stay 16-byte aligned)
+        live = np.nonzero(pidx >= 0)[0]
+        feed[live] = base + 2 * pidx[live]
+        feed[D + live] = base + 2 * pidx[live] + 1
+        if has_bias:
+            feed[2 * D + live] = base + 2 * n_circ + pidx[live]
+        assert base + 3 * n_circ < 2 ** 24 and int(st["table"][9]) == st["src"].size
+        st["tt_off"], st["feed_off"] = int(st["table"].size), int(st["src"].size)
+        st["table"] = np.concatenate([st["table"], tt.reshape(-1)]).astype(np.int32)
+        st["src"] = np.concatenate([st["src"], feed]).astype(np.int32)
+        inv_col = np.zeros(D, dtype=np.int64)
+        inv_col[sl["col"]] = np.arange(D)
+        st.update(col=sl["col"].astype(np.int64), inv_col=inv_col, n_circ=n_circ, has_bias=has_bias)
+        return st
+    if not supported_ft(made, mult):
+        return None
+    import hashlib
+    pre = made.preprocessing
+    pkey = ()
+    if not isinstance(pre, torch.nn.Identity):
+        sc = pre.scale.detach().cpu().numpy().tobytes() if torch.is_tensor(pre.scale) else float(pre.scale)
+        pkey = (hashlib.sha1(pre.ind.cpu().numpy().tobytes()).hexdigest(), sc, bool(pre.apply_bias), int(pre.ndim))
+    return _shared(("made_ft", mult, _mask_key(made), pkey), build)
 
 
 def resnet_train_structure(net):

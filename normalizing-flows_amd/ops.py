@@ -1191,10 +1191,49 @@ def made_forward_train(x, blob, table, hidden_padded, out_features, num_blocks, 
     return params, save, bits
 
 
-def made_backward(g_params, bits, blob, table, D, hidden_padded, num_blocks, rows=None, out_features=None, ld_out=None, want_G=True):
+def made_forward_train_ft(x, blob, table, hidden_padded, out_features, num_blocks):
+    """made_forward_train for the degree-order packs of flows/made_pack.made_train_structure_ft (nf_made_forward_train_ft: the tile is
+    gathered through the feature table behind `table` and fed with the periodic features whose live parameters end `blob`): (params
+    (B, out_features) in position order, save, bits, x_pad (Bp, 128): the fed inputs as made_wgrad takes them, x_pos (B, D): the raw
+    inputs in position order).  64-row tiles: its chain is made_backward(..., tile64=True)."""
+    L.require_device(x, blob, table)
+    if x.dtype != torch.float32:
+        raise NotImplementedError("made_forward_train_ft: float32 only")
+    B, D = x.shape
+    x = x.contiguous()
+    Bp = (B + 63) // 64 * 64
+    params = torch.empty(B, out_features, dtype=x.dtype, device=x.device)
+    save = torch.empty(2 * num_blocks + 1, Bp, hidden_padded, dtype=x.dtype, device=x.device)
+    bits = torch.empty(max(Bp // 64, 1), 2 * num_blocks, 2, 512, dtype=torch.int32, device=x.device)
+    x_pad = torch.empty(Bp, 128, dtype=x.dtype, device=x.device)
+    x_pos = torch.empty(B, D, dtype=x.dtype, device=x.device)
+    L.call("nf_made_forward_train_ft", ptr(x), ptr(params), ptr(save), ptr(bits), ptr(x_pad), ptr(x_pos), ptr(blob), ptr(table), B, D,
+           hidden_padded, max(1, out_features // D), L.stream())
+    return params, save, bits, x_pad, x_pos
+
+
+def made_feed_ft_bwd(g_pre, g_xpos, x, ttable, feed, n_circ, has_bias):
+    """The backward of made_forward_train_ft's gather + periodic feed (nf_made_feed_ft_bwd): (g_x (B, D) in column order =
+    g_pre d + g_xpos scattered through the table, g_weights (n_circ, 2), g_bias (n_circ) or None); g_xpos may be None.  Deterministic:
+    per-workgroup partials, fixed-order reduction."""
+    L.require_device(g_pre, g_xpos, x, ttable, feed)
+    B, D = x.shape
+    g_pre = g_pre.contiguous()
+    g_xpos = None if g_xpos is None else g_xpos.contiguous()
+    g_x = torch.empty(B, D, dtype=x.dtype, device=x.device)
+    g_w = torch.zeros(n_circ, 2, dtype=x.dtype, device=x.device) if n_circ else None
+    g_b = torch.zeros(n_circ, dtype=x.dtype, device=x.device) if (n_circ and has_bias) else None
+    part = torch.empty(512 * 3 * n_circ, dtype=x.dtype, device=x.device) if n_circ else None
+    L.call("nf_made_feed_ft_bwd", ptr(g_pre), ptr(g_xpos), ptr(x), ptr(ttable), ptr(feed), ptr(g_x), ptr(g_w), ptr(g_b), ptr(part),
+           B, D, n_circ, L.stream())
+    return g_x, g_w, g_b
+
+
+def made_backward(g_params, bits, blob, table, D, hidden_padded, num_blocks, rows=None, out_features=None, ld_out=None, want_G=True,
+                  tile64=False):
     """The input-gradient chain of MADE (nf_made_backward): g_x (B, D) and every layer's output gradient G (2 NB + 1, Bp, Hp).
     rows / out_features / ld_out: g_params is a padded buffer (row strides in the table's hdr[14], hdr[15]) and so is the returned
-    g_x (rows, ld_out): the conv path."""
+    g_x (rows, ld_out): the conv path.  tile64: nf_made_backward_t64 (the chain of made_forward_train_ft, which has no 128-row tile)."""
     L.require_device(g_params, bits, blob, table)
     B = g_params.shape[0] if rows is None else rows
     md = g_params.shape[1] if out_features is None else out_features
@@ -1202,8 +1241,8 @@ def made_backward(g_params, bits, blob, table, D, hidden_padded, num_blocks, row
     Bp = (B + 63) // 64 * 64
     gx = torch.empty(B, D if ld_out is None else ld_out, dtype=g_params.dtype, device=g_params.device)
     G = torch.empty(2 * num_blocks + 1, Bp, hidden_padded, dtype=g_params.dtype, device=g_params.device) if want_G else None
-    L.call("nf_made_backward", ptr(g_params), ptr(bits), ptr(gx), ptr(G), ptr(blob), ptr(table), B, D, hidden_padded,
-           max(1, md // D), L.stream())
+    L.call("nf_made_backward_t64" if tile64 else "nf_made_backward", ptr(g_params), ptr(bits), ptr(gx), ptr(G), ptr(blob), ptr(table),
+           B, D, hidden_padded, max(1, md // D), L.stream())
     return gx, G
 
 
