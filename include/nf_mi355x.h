@@ -17,6 +17,12 @@
  *   - `acc` (log-det accumulation mode): NF_LD_WRITE  logdet[b]  = ld_b
  *                                        NF_LD_ADD    logdet[b] += ld_b   (core.py:193-195 `log_q += log_det`)
  *                                        NF_LD_SUB    logdet[b] -= ld_b   (core.py:177-179 `log_q -= log_det`)
+ *   - Alignment: unless an entry point's comment carries an `Alignment:` line, every pointer needs only the alignment of its element
+ *     type (4 bytes for float32 / int32, 8 for float64 / int64) and is read and written element by element: a view that starts
+ *     anywhere inside a larger buffer is fine.  Where a kernel moves a buffer as 16-byte vectors or by LDS-DMA the entry point
+ *     returns NF_EINVAL for a pointer off a 16-byte boundary, before any launch, or takes a path that does without vectors; the
+ *     `Alignment:` line says which (summary table: INTEGRATION.md, "Pointer alignment").  Blobs and scratch buffers are held to
+ *     16 bytes throughout (what the *_pack_size / *_scratch_floats sizes are allocated as).
  *   - Direction naming follows normflows: "forward" is generative (z -> x), "inverse" is
  *     normalising (x -> z); log_prob runs every layer's inverse, sample runs every layer's forward.
  */
@@ -99,6 +105,9 @@ int nf_rqs_spline_check(const void *x, const void *y, int64_t N, int tails, doub
  *                                   y[:,T] = spline^{-1}(x[:,T]; cond); ld = its row sum; y[:,I] untouched.
  *   logdet (B): combined with ld according to `acc`.
  */
+/* Alignment: element type.  Choice of kernel: with x, y and cond all 16-byte aligned (and the shape it takes) the pipelined
+ * kernel runs, otherwise the wave kernel, which reads and writes element by element
+ * (the two kernels agree to a few ulp, not bit for bit). */
 int nf_rqs_coupling(const void *x, void *y, void *logdet, const void *cond, const void *uw, const void *uh,
                     const void *ud, const int64_t *identity_idx, int nI, const int64_t *transform_idx,
                     int nT, int64_t B, int D, int K, int tails, double tail_bound, double min_bin_width,
@@ -115,6 +124,7 @@ int nf_rqs_coupling(const void *x, void *y, void *logdet, const void *cond, cons
  *     with any `tails` other than NF_TAILS_NONE.
  * With all four arrays NULL this is nf_rqs_coupling.
  */
+/* Alignment: as nf_rqs_coupling. */
 int nf_rqs_coupling_ft(const void *x, void *y, void *logdet, const void *cond, const void *uw, const void *uh,
                     const void *ud, const int64_t *identity_idx, int nI, const int64_t *transform_idx,
                     int nT, int64_t B, int D, int K, int tails, double tail_bound, double min_bin_width,
@@ -131,6 +141,8 @@ int nf_rqs_coupling_ft(const void *x, void *y, void *logdet, const void *cond, c
  *   gradients of the conditioner output.  grad_uw/uh/ud: gradients of the batch-shared parameters,
  *   ACCUMULATED (atomics) -- the caller zero-initialises them.
  */
+/* Alignment: element type.  Choice of kernel: with x, grad_y, cond, grad_cond and grad_x all 16-byte aligned (and the shape it
+ * takes) the pipelined kernel runs, otherwise the wave kernel, which reads and writes element by element. */
 int nf_rqs_coupling_bwd(const void *x, const void *grad_y, const void *grad_logdet, const void *cond,
                         const void *uw, const void *uh, const void *ud, const int64_t *identity_idx, int nI,
                         const int64_t *transform_idx, int nT, int64_t B, int D, int K, int tails,
@@ -142,6 +154,7 @@ int nf_rqs_coupling_bwd(const void *x, const void *grad_y, const void *grad_logd
  * per-feature branch (tails = NF_TAILS_FEATURE) an input outside its interval produced the constant 0, so its grad_x
  * is 0 (utils/splines.py:48-57 never copies those inputs); the edge derivative logits a feature's tails type
  * overrides receive no gradient (linear) or the gradient of the logit they alias (circular: logit K -> logit 0). */
+/* Alignment: as nf_rqs_coupling_bwd. */
 int nf_rqs_coupling_bwd_ft(const void *x, const void *grad_y, const void *grad_logdet, const void *cond,
                            const void *uw, const void *uh, const void *ud, const int64_t *identity_idx, int nI,
                            const int64_t *transform_idx, int nT, int64_t B, int D, int K, int tails,
@@ -187,6 +200,8 @@ int nf_rqs_fused_pack(void *wpack, const void *w_init, const void *b_init, const
 int nf_rqs_fused_pack_lu(void *wpack, int num_blocks, const int64_t *perm, const void *lower_entries,
                          const void *upper_entries, const void *unconstrained_upper_diag, const void *bias, int D,
                          double eps, int K, nf_stream_t stream);
+/* Alignment: x, y and wpack 16 bytes (NF_EINVAL otherwise: 16-byte vector loads / stores of the rows, LDS-DMA of the blob);
+ * logdet element type. */
 int nf_rqs_fused(const void *x, void *y, void *logdet, const void *wpack, int mask_parity, int fuse_lu, int64_t B,
                  int D, int hidden, int num_blocks, int K, double tail_bound, double min_bin_width,
                  double min_bin_height, double min_derivative, int direction, int acc, nf_stream_t stream);
@@ -194,6 +209,7 @@ int nf_rqs_fused(const void *x, void *y, void *logdet, const void *wpack, int ma
  * iterations of the container loops normflows/core.py:177-179 / :193-195.  wpacks / mask_parities are HOST arrays in
  * PROCESSING order (for log_prob: last flow first).  The rows stay on chip between layers (x read once, y written once,
  * the accumulated log-det written once). */
+/* Alignment: x, y and every wpacks[l] 16 bytes (NF_EINVAL otherwise); logdet element type. */
 int nf_rqs_fused_chain(const void *x, void *y, void *logdet, const void *const *wpacks, const int *mask_parities,
                        int num_layers, int fuse_lu, int64_t B, int D, int hidden, int num_blocks, int K,
                        double tail_bound, double min_bin_width, double min_bin_height, double min_derivative,
@@ -214,6 +230,7 @@ int nf_rqs_fused_small_batch(int enable);
 int nf_rqs_fused_pack_final(void *wpack, const void *w_final, const void *b_final, const void *uw, const void *uh,
                             const void *ud, int hidden, int num_blocks, int K, double tail_bound, double min_bin_width,
                             double min_bin_height, double min_derivative, nf_stream_t stream);
+/* Alignment: x, h2, y, cond_out and wpack 16 bytes (NF_EINVAL otherwise); logdet element type. */
 int nf_rqs_fused_train_fwd(const void *x, const void *h2, void *y, void *logdet, void *cond_out, const void *wpack,
                            int mask_parity, int64_t B, int D, int hidden, int num_blocks, int K, double tail_bound,
                            double min_bin_width, double min_bin_height, double min_derivative, int acc, nf_stream_t stream);
@@ -231,6 +248,7 @@ int nf_rqs_fused_pack_all(void *wpack, const void *w_init, const void *b_init, c
                           const void *ud, int hidden, int num_blocks, int K, double tail_bound, double min_bin_width,
                           double min_bin_height, double min_derivative, void *wfull, void *wpad, const void *identity_idx,
                           nf_stream_t stream);
+/* Alignment: x, y, cond_out, act_out and wpack 16 bytes (NF_EINVAL otherwise); logdet element type. */
 int nf_rqs_fused_train_full_fwd(const void *x, void *y, void *logdet, void *cond_out, void *act_out, const void *wpack,
                                 int mask_parity, int64_t B, int D, int hidden, int num_blocks, int K, double tail_bound,
                                 double min_bin_width, double min_bin_height, double min_derivative, int acc, nf_stream_t stream);
@@ -241,6 +259,8 @@ int nf_rqs_fused_pack_all_multi(const void *table, int n_layers, int hidden, int
                                 double min_bin_width, double min_bin_height, double min_derivative, nf_stream_t stream);
 /* Backward of the density-direction coupling transform (nf_rqs_coupling_bwd, mode NF_RQS_DENSITY) on cond / grad_cond rows
  * of 24 floats per transform feature (the layout above; 16-byte aligned).  float32, 8 bins, linear tails. */
+/* Alignment: cond24 and grad_cond24 16 bytes (NF_EINVAL otherwise).  x, grad_y, grad_x: with all three (and the parameter rows)
+ * 16-byte aligned the pipelined kernel runs, otherwise the wave kernel, which moves them element by element. */
 int nf_rqs_coupling_bwd_p24(const void *x, const void *grad_y, const void *grad_logdet, const void *cond24, const void *uw,
                             const void *uh, const void *ud, const int64_t *identity_idx, int nI, const int64_t *transform_idx,
                             int nT, int64_t B, int D, double tail_bound, double min_bin_width, double min_bin_height,
@@ -258,6 +278,8 @@ int nf_rqs_coupling_bwd_p24(const void *x, const void *grad_y, const void *grad_
  * cumulative-sum / softplus chain once: grad_uw, grad_uh (32, 8), grad_ud (32, 7), written.  D = 64, hidden = 128, K = 8, linear
  * tails, float32 (NF_ENOTSUP otherwise); any B. */
 int nf_final_bwd_partials(int64_t B);
+/* Alignment: x, grad_y, cond24, w_t, wpack, grad_x, grad_cond24 and grad_h 16 bytes (NF_EINVAL otherwise); grad_logdet and
+ * partials element type. */
 int nf_final_bwd(const void *x, const void *grad_y, const void *grad_logdet, const void *cond24, const void *w_t, const void *wpack,
                  void *grad_x, void *grad_cond24, void *grad_h, void *partials, int mask_parity, int64_t B, int D, int hidden,
                  int num_blocks, int K, double tail_bound, double min_bin_width, double min_bin_height, double min_derivative,
@@ -274,12 +296,14 @@ int nf_final_bwd_reduce(const void *partials, int n_partials, const void *uw, co
  */
 int64_t nf_rqs_fused_x3_pack_size(int nI, int nT, int hidden, int num_blocks, int K);
 int nf_rqs_fused_x3_pack(void *x3pack, const void *f32pack, int num_blocks, int has_lu, nf_stream_t stream);
+/* Alignment: x, y and x3pack 16 bytes (NF_EINVAL otherwise); logdet element type. */
 int nf_rqs_fused_x3(const void *x, void *y, void *logdet, const void *x3pack, int mask_parity, int fuse_lu,
                     int64_t B, int D, int hidden, int num_blocks, int K, double tail_bound, double min_bin_width,
                     double min_bin_height, double min_derivative, int direction, int acc, nf_stream_t stream);
 /* The split-bf16 counterpart of nf_rqs_fused_chain: up to 64 layers of one shape in ONE persistent launch (rows stay in
  * LDS between the layers, the weight stream runs through the layer boundaries).  x3packs (nf_rqs_fused_x3_pack) and
  * mask_parities in PROCESSING order. */
+/* Alignment: x, y and every x3packs[l] 16 bytes (NF_EINVAL otherwise); logdet element type. */
 int nf_rqs_fused_x3_chain(const void *x, void *y, void *logdet, const void *const *x3packs, const int *mask_parities,
                           int num_layers, int fuse_lu, int64_t B, int D, int hidden, int num_blocks, int K, double tail_bound,
                           double min_bin_width, double min_bin_height, double min_derivative, int direction, int acc,
@@ -307,6 +331,8 @@ int nf_lu_linear_permute(const void *x, void *y, void *logdet, const int64_t *pe
  *   direction 0 = forward:  y = b z + (1-b)(z e^{s} + t),   ld = +sum (1-b) s
  *   direction 1 = inverse:  y = b z + (1-b)(z - t) e^{-s},  ld = -sum (1-b) s
  */
+/* Alignment: element type; float32 with inner <= 256 and inner % 4 == 0 (the four-elements-per-lane path): z, b, s, t and y 16
+ * bytes (NF_EINVAL otherwise). */
 int nf_masked_affine(const void *z, const void *b, const void *s, const void *t, void *y, void *logdet,
                      int64_t B, int64_t inner, int direction, int acc, int dtype, nf_stream_t stream);
 
@@ -389,6 +415,8 @@ int nf_inv1x1_conv_t(const void *z, const void *W, void *y, int64_t B, int C, in
  *   z (B, d); loc, log_scale (d);  log_p[b] = -d/2 log(2 pi) - sum_j (log_scale_j + 0.5 ((z-loc)/e^{log_scale})^2)
  *   `log_scale_shift` is added to log_scale (temperature, base.py:95-98).  out (B) combined per `acc`.
  */
+/* Alignment: element type; float32 with d <= 256 and d % 4 == 0 (the four-elements-per-lane path): z, loc and log_scale 16 bytes
+ * (NF_EINVAL otherwise). */
 int nf_diag_gaussian_log_prob(const void *z, const void *loc, const void *log_scale, double log_scale_shift,
                               void *out, int64_t B, int64_t d, int acc, int dtype, nf_stream_t stream);
 
@@ -400,21 +428,26 @@ int nf_diag_gaussian_log_prob(const void *z, const void *loc, const void *log_sc
  *   a fixed order: results are run-to-run deterministic).
  */
 int64_t nf_linear_wgrad_scratch_floats(int64_t B, int M, int N);
+/* Alignment: with N % 4 == 0 (every kernel but the element-wise one): dY, X and scratch 16 bytes (NF_EINVAL otherwise).  dW and
+ * db: element type, any address -- views of a flat gradient buffer are written in place. */
 int nf_linear_wgrad(const void *dY, const void *X, void *dW, void *db, void *scratch, int64_t B, int M, int N,
                     int accumulate, nf_stream_t stream);
 /* Same with relu_x = 1: the second operand is relu(X), applied as the values are consumed (the caller keeps only the
  * pre-activation of the block, resnet.py:41-47). */
+/* Alignment: as nf_linear_wgrad. */
 int nf_linear_wgrad_act(const void *dY, const void *X, void *dW, void *db, void *scratch, int64_t B, int M, int N,
                         int accumulate, int relu_x, nf_stream_t stream);
 /* Same with pad rows: when skip_every > 1 (M % skip_every == 0), every skip_every-th row of dY (m % skip_every ==
  * skip_every - 1) is padding and has no output row -- dW is (M - M / skip_every, N), db (M - M / skip_every).  The 24-float
  * parameter rows of nf_rqs_fused_train_fwd / nf_rqs_coupling_bwd_p24 (23 parameters + 1 pad) against the reference's
  * 23-row final layer: the un-padding happens in the reduction, not as two strided copies. */
+/* Alignment: as nf_linear_wgrad. */
 int nf_linear_wgrad_skip(const void *dY, const void *X, void *dW, void *db, void *scratch, int64_t B, int M, int N,
                          int accumulate, int relu_x, int skip_every, nf_stream_t stream);
 /* Two problems of the same shape (B, M, N) in one partial launch and one reduction -- the two weight gradients of a
  * residual block (nets/resnet.py:37-50) become available together.  scratch: 2 x nf_linear_wgrad_scratch_floats(B, M, N);
  * db0 / db1 both given or both NULL; vector / tile paths only (N % 4 == 0), NF_ENOTSUP otherwise. */
+/* Alignment: as nf_linear_wgrad for both problems; besides, the two problems' tensors must sit a whole number of floats apart. */
 int nf_linear_wgrad_pair(const void *dY0, const void *X0, void *dW0, void *db0, const void *dY1, const void *X1, void *dW1,
                          void *db1, void *scratch, int64_t B, int M, int N, int accumulate, int relu_x, nf_stream_t stream);
 /* Backward of one residual block of the conditioner (nets/resnet.py:37-50; hidden H = 128) in ONE pass over the rows: the two
@@ -431,11 +464,14 @@ int nf_linear_wgrad_pair(const void *dY0, const void *X0, void *dW0, void *db0, 
  * (nf_lu_factors), u = the forward's intermediate (nf_rows_matvec2); nf_lu_param_grads turns (dL, dUp) into the packed
  * parameter gradients.  B a multiple of 64; scratch: nf_lu_bwd_scratch_floats(B) floats.  Deterministic. */
 int64_t nf_lu_bwd_scratch_floats(int64_t B);
+/* Alignment: gy, u, x and gx 16 bytes (NF_EINVAL otherwise: LDS-DMA tiles); the factors and the gradient destinations element
+ * type. */
 int nf_lu_bwd(const void *gy, const void *u, const void *x, const void *Lm, const void *Up, void *gx, void *dL, void *db, void *dUp,
               void *scratch, int64_t B, int D, nf_stream_t stream);
 /* ... and its forward on the same tiles: u (B, D) = U x[perm] per row (kept for the backward), y = L u + bias, logdet (op)=
  * ld_sign * *ld_const (acc = NF_LD_WRITE / ADD / SUB; logdet may be NULL).  UpT / LT: the transposed factor images of
  * nf_lu_factors.  D = 64, B a multiple of 64. */
+/* Alignment: x, u and y 16 bytes (NF_EINVAL otherwise); the factors, bias and logdet element type. */
 int nf_lu_fwd(const void *x, const void *UpT, const void *LT, const void *bias, void *u, void *y, void *logdet,
               const void *ld_const, double ld_sign, int acc, int64_t B, int D, nf_stream_t stream);
 /* Round 6: the LULinearPermute of a benchmark-shaped pair fused into the training forward, and its backward on the composed matrix.
@@ -452,12 +488,16 @@ int nf_lu_fwd(const void *x, const void *UpT, const void *LT, const void *bias, 
  *   diagonal through softplus' with gl_sum / diag (gld (B): the log-det cotangent, summed inside; may be NULL); Lm, Um: the dense
  *   factors of nf_lu_factors[_multi].  D = 64. */
 int nf_lu_pack_train_multi(const void *table, int n_layers, int num_blocks, int D, double eps, nf_stream_t stream);
+/* Alignment: x, xlu_out, y, cond_out, act_out and wpack 16 bytes (NF_EINVAL otherwise); logdet element type. */
 int nf_rqs_fused_train_pair_fwd(const void *x, void *xlu_out, void *y, void *logdet, void *cond_out, void *act_out, const void *wpack,
                                 int mask_parity, int64_t B, int D, int hidden, int num_blocks, int K, double tail_bound,
                                 double min_bin_width, double min_bin_height, double min_derivative, int acc, nf_stream_t stream);
 int64_t nf_lu_bwd_composed_scratch_floats(int64_t B);
+/* Alignment: g, x and gx 16 bytes (NF_EINVAL otherwise); Wd, dWd and db element type. */
 int nf_lu_bwd_composed(const void *g, const void *x, const void *Wd, void *gx, void *dWd, void *db, void *scratch, int64_t B, int D,
                        nf_stream_t stream);
+/* Alignment: element type.  gld: summed with 16-byte loads when it is 16-byte aligned, element by element otherwise (same order
+ * of additions per partial sum). */
 int nf_lu_param_grads_composed(const void *dWd, const void *Lm, const void *Um, const int64_t *perm, const void *gld, int64_t B,
                                const void *unconstrained_upper_diag, double eps, void *g_lower, void *g_upper, void *g_udiag, int D,
                                nf_stream_t stream);
@@ -467,9 +507,12 @@ int nf_lu_param_grads_composed(const void *dWd, const void *Lm, const void *Um, 
  * gradient, one reduction launch for the partial tiles of BOTH layers, nf_lu_param_grads_composed: seven launches.  Arguments as
  * the two calls it replaces; grad_x_in (B, 64) = the pair's input gradient; scratch: nf_pair_train_bwd_scratch_floats(B, num_blocks). */
 int nf_lu_bwd_composed_grid(int64_t B);
+/* Alignment: g, x and gx 16 bytes (NF_EINVAL otherwise). */
 int nf_lu_bwd_composed_partials(const void *g, const void *x, const void *Wd, void *gx, void *scratch, int64_t B, int D,
                                 nf_stream_t stream);
 int64_t nf_pair_train_bwd_scratch_floats(int64_t B, int num_blocks);
+/* Alignment: x_in, xlu, grad_y, cond24, acts, w_t, wpack, wfull_t, grad_x_in and scratch 16 bytes (NF_EINVAL before the first
+ * launch otherwise).  The weights, grad_logdet and every gradient destination: element type, any address. */
 int nf_pair_train_bwd(const void *x_in, const void *xlu, const void *grad_y, const void *grad_logdet, const void *cond24,
                       const void *acts, const void *w_t, const void *wpack, const void *wfull_t, const void *const *w_blocks,
                       const void *uw, const void *uh, const void *ud, const void *col_map, int n_cols, const void *Wd, const void *Lm,
@@ -486,6 +529,7 @@ int nf_pair_train_bwd(const void *x_in, const void *xlu, const void *grad_y, con
  * saved rows and every gradient destination stay in use until _tail's launches have run; a gradient may be read only on a stream
  * ordered behind them.  _head followed by _tail on one stream is exactly nf_pair_train_bwd (same seven launches, same bits). */
 #define NF_PAIR_TAIL_BYTES 2048
+/* Alignment: as nf_pair_train_bwd. */
 int nf_pair_train_bwd_head(const void *x_in, const void *xlu, const void *grad_y, const void *grad_logdet, const void *cond24,
                            const void *acts, const void *w_t, const void *wpack, const void *wfull_t, const void *const *w_blocks,
                            const void *uw, const void *uh, const void *ud, const void *col_map, int n_cols, const void *Wd,
@@ -496,6 +540,8 @@ int nf_pair_train_bwd_head(const void *x_in, const void *xlu, const void *grad_y
                            double min_bin_width, double min_bin_height, double min_derivative, void *tail, nf_stream_t stream);
 int nf_pair_train_bwd_tail(const void *tail, nf_stream_t stream);
 int64_t nf_resblock_bwd_scratch_floats(int64_t B, int with_init);
+/* Alignment: gh, t, h_in, x, gh_in, gx and wfull 16 bytes (NF_EINVAL otherwise: LDS-DMA tiles); W1, W2 and the gradient
+ * destinations element type. */
 int nf_resblock_bwd(const void *gh, const void *t, const void *h_in, const void *W1, const void *W2, void *gh_in, void *dW1,
                     void *db1, void *dW2, void *db2, const void *x, const void *wfull, void *gx, void *dW0, void *db0,
                     const void *col_map, int n_cols, void *scratch, int64_t B, int H, int D, nf_stream_t stream);
@@ -505,9 +551,11 @@ int nf_resblock_bwd(const void *gh, const void *t, const void *h_in, const void 
  *   nf_resblock_bwd_partials: scratch = [2][nf_resblock_bwd_grid(B)][128 * 128 + 128] ((dW2, db2) then (dW1, db1)), then with x
  *   the initial layer's [grid][128 * 64 + 128]; arguments as nf_resblock_bwd. */
 int nf_linear_wgrad_chunks(int64_t B, int M, int N);
+/* Alignment: as nf_linear_wgrad. */
 int nf_linear_wgrad_partials(const void *dY, const void *X, void *scratch, int64_t B, int M, int N, int relu_x, int want_bias,
                              nf_stream_t stream);
 int nf_resblock_bwd_grid(int64_t B);
+/* Alignment: as nf_resblock_bwd. */
 int nf_resblock_bwd_partials(const void *gh, const void *t, const void *h_in, const void *W1, const void *W2, void *gh_in,
                              const void *x, const void *wfull, void *gx, void *scratch, int64_t B, int H, int D,
                              nf_stream_t stream);
@@ -526,6 +574,8 @@ int nf_resblock_bwd_partials(const void *gh, const void *t, const void *h_in, co
  *   of one flat gradient buffer).  scratch: nf_coupling_train_bwd_scratch_floats(B, num_blocks) floats.
  *   D = 64, hidden = 128, K = 8, 1 <= num_blocks <= 5, B a multiple of 64, float32; NF_ENOTSUP otherwise. */
 int64_t nf_coupling_train_bwd_scratch_floats(int64_t B, int num_blocks);
+/* Alignment: x, grad_y, cond24, acts, w_t, wpack, wfull_t, grad_x and scratch 16 bytes (NF_EINVAL before the first launch
+ * otherwise).  The weights, grad_logdet and every gradient destination: element type, any address. */
 int nf_coupling_train_bwd(const void *x, const void *grad_y, const void *grad_logdet, const void *cond24, const void *acts,
                           const void *w_t, const void *wpack, const void *wfull_t, const void *const *w_blocks, const void *uw,
                           const void *uh, const void *ud, const void *col_map, int n_cols, void *grad_x, void *g_w0, void *g_b0,
@@ -614,12 +664,15 @@ int nf_maf_implicit_sweep(const void *x, const void *params, const void *gx, con
  */
 int nf_nsf_wide_tables(const void *uw, const void *uh, const void *ud, void *tabs, int n_identity, int K, double tail_bound,
                        double min_bin_width, double min_bin_height, double min_derivative, nf_stream_t stream);
+/* Alignment: with D % 4 == 0 x and y 16 bytes (NF_EINVAL otherwise: the tile moves as 16-byte vectors); with any other D the rows
+ * move element by element.  blob, tabs: as their pack functions allocate them (16 bytes). */
 int nf_nsf_wide(const void *x, void *y, void *logdet, const void *blob, const int32_t *table, const void *tabs,
                 const void *lu_logdet, int64_t B, int D, int hidden_padded, int direction, int acc, double tail_bound,
                 double min_bin_width, double min_bin_height, double min_derivative, nf_stream_t stream);
 /* the same with K = 4 | 8 | 16 bins (`num_bins` of wrapper.py:20-35; round 5): the pack (table[24] = K) and the tables
  * (nf_nsf_wide_tables with the same K: (n_identity, 3 (K + 1)) floats from widths / heights (n_identity, K), derivatives
  * (n_identity, K - 1)) are built for that K; a final-layer group then holds 8 / 4 / 2 transform features.  -ENOTSUP for other K. */
+/* Alignment: as nf_nsf_wide. */
 int nf_nsf_wide_k(const void *x, void *y, void *logdet, const void *blob, const int32_t *table, const void *tabs,
                   const void *lu_logdet, int64_t B, int D, int hidden_padded, int K, int direction, int acc, double tail_bound,
                   double min_bin_width, double min_bin_height, double min_derivative, nf_stream_t stream);
@@ -634,6 +687,7 @@ int nf_nsf_wide_k(const void *x, void *y, void *logdet, const void *blob, const 
  *   -EINVAL for B < 0, C < 1, ldc < 0 and nf_nsf_wide_k's cases; -ENOTSUP where the x tile's positions overflow
  *   (identity and transform features each rounded up to 32, + PC > 128: D <= 64 with C <= 64, D <= 96 with C <= 32), for
  *   hidden_padded 512 (not built: it spills registers) and for K outside 4 | 8 | 16; -EFAULT for a NULL pointer; B == 0: NF_OK. */
+/* Alignment: x, y as nf_nsf_wide; context element type, any row stride. */
 int nf_nsf_wide_ctx(const void *x, const void *context, void *y, void *logdet, const void *blob, const int32_t *table,
                     const void *tabs, int64_t B, int64_t ldc, int D, int C, int hidden_padded, int K, int direction, int acc,
                     double tail_bound, double min_bin_width, double min_bin_height, double min_derivative, nf_stream_t stream);
@@ -656,6 +710,7 @@ int nf_nsf_wide_ctx(const void *x, const void *context, void *y, void *logdet, c
 int nf_nsf_wide_tables_ft(const void *uw, const void *uh, const void *ud, const int32_t *tails_i, const void *bound_i, void *tabs,
                           int n_identity, int K, double min_bin_width, double min_bin_height, double min_derivative,
                           nf_stream_t stream);
+/* Alignment: as nf_nsf_wide. */
 int nf_nsf_wide_ft(const void *x, void *y, void *logdet, const void *blob, const int32_t *table, const void *ftable, const void *tabs,
                    int64_t B, int D, int hidden_padded, int K, int direction, int acc, double min_bin_width, double min_bin_height,
                    double min_derivative, nf_stream_t stream);
@@ -679,9 +734,11 @@ int64_t nf_resnet_ctx_save_floats(int64_t B, int nI, int C, int hidden, int num_
 int64_t nf_resnet_ctx_grad_floats(int64_t B, int hidden, int num_blocks);
 int nf_resnet_ctx_wgrad_chunks(int64_t B, int njobs);
 int64_t nf_resnet_ctx_scratch_floats(int64_t B, int njobs);
+/* Alignment: save and blob 16 bytes (NF_EINVAL otherwise); x, context and out element type. */
 int nf_resnet_ctx_forward_train(const void *x, int64_t ldx, const void *context, int64_t ldc, void *out, void *save, const void *blob,
                                 const int32_t *table, int64_t B, int nI, int C, int hidden, int out_features, int num_blocks,
                                 nf_stream_t stream);
+/* Alignment: save, G and blob 16 bytes (NF_EINVAL otherwise); g_out, g_x and g_context element type. */
 int nf_resnet_ctx_backward(const void *g_out, const void *save, void *G, void *g_x, void *g_context, const void *blob,
                            const int32_t *table, int64_t B, int nI, int C, int hidden, int out_features, int num_blocks,
                            nf_stream_t stream);
@@ -702,8 +759,10 @@ int nf_resnet_ctx_wgrad(const void *g_out, const void *save, const void *G, void
  *   nf_made_forward_affine: x, y (B, D), logdet (B) combined according to `acc`.
  *   nf_made_forward       : params (B, mult D), rows in the reference's order (mult f + p).
  */
+/* Alignment: with D % 4 == 0 x and y 16 bytes (NF_EINVAL otherwise); logdet element type. */
 int nf_made_forward_affine(const void *x, void *y, void *logdet, const void *blob, const int32_t *table, int64_t B, int D,
                            int hidden_padded, int acc, nf_stream_t stream);
+/* Alignment: params 16 bytes, and x with D % 4 == 0 (NF_EINVAL otherwise). */
 int nf_made_forward(const void *x, void *params, const void *blob, const int32_t *table, int64_t B, int D, int hidden_padded,
                     int mult, nf_stream_t stream);
 /* The autoregressive rational-quadratic spline layer's density direction in one launch: replaces
@@ -712,6 +771,7 @@ int nf_made_forward(const void *x, void *params, const void *blob, const int32_t
  * calls): MADE with 23 = 3 * 8 - 1 outputs per feature, then utils/splines.py:16-219 element-wise (8 bins, linear tails, no
  * 1 / sqrt(hidden) scaling: the reference's MADE has no `hidden_features`), row-summed log-det.
  *   blob, table : made_pack.pack_made_forward(made, 23, spline=True); x, y (B, D); logdet (B) combined according to `acc`. */
+/* Alignment: as nf_made_forward_affine. */
 int nf_made_forward_spline(const void *x, void *y, void *logdet, const void *blob, const int32_t *table, int64_t B, int D,
                            int hidden_padded, int acc, double tail_bound, double min_bin_width, double min_bin_height,
                            double min_derivative, nf_stream_t stream);
@@ -729,8 +789,10 @@ int nf_made_forward_spline(const void *x, void *y, void *logdet, const void *blo
  *                           `mask` (bytes, same layout) is non-zero -- the reference's weight.grad is zero under the mask too;
  *                           gp_pad / x_pad: g_params / x with Bp rows and the row length rounded up to 128 (zeros);
  *                           part: nf_made_wgrad_scratch_floats(B, ntiles) floats. */
+/* Alignment: params and save 16 bytes, and x with D % 4 == 0 (NF_EINVAL otherwise). */
 int nf_made_forward_train(const void *x, void *params, void *save, void *bits, const void *blob, const int32_t *table, int64_t B,
                           int D, int hidden_padded, int mult, nf_stream_t stream);
+/* Alignment: g_params and G 16 bytes, and g_x with D % 4 == 0 (NF_EINVAL otherwise). */
 int nf_made_backward(const void *g_params, const void *bits, void *g_x, void *G, const void *blob, const int32_t *table, int64_t B,
                      int D, int hidden_padded, int mult, nf_stream_t stream);
 /* nf_made_forward_train / nf_made_backward on 128-row tiles where a 256-slot network has <= 64 input features and the batch is a
@@ -739,6 +801,7 @@ int nf_made_backward(const void *g_params, const void *bits, void *g_x, void *G,
  * on (1, default) / off (0), returns the previous setting.  A forward and its backward must run under the same setting. */
 int nf_config_made_tr128(int on);
 int64_t nf_made_wgrad_scratch_floats(int64_t B, int ntiles);
+/* Alignment: gp_pad, x_pad, G, save and part 16 bytes (NF_EINVAL otherwise: LDS-DMA operands); grads element type. */
 int nf_made_wgrad(const void *gp_pad, const void *x_pad, const void *G, const void *save, void *grads, const void *mask, void *part,
                   const int32_t *wtable, const int32_t *stable, int ntiles, int64_t B, nf_stream_t stream);
 /* MADE under autograd for the autoregressive spline layers whose mask is permuted and / or whose circular coordinates pass the periodic
@@ -764,8 +827,10 @@ int nf_made_wgrad(const void *gp_pad, const void *x_pad, const void *G, const vo
  *                              part: 512 x 3 x n_circ floats of scratch (n_circ = 0: only the scatter-add runs, feed / g_weights /
  *                              part may be NULL).
  * -EINVAL for D < 2 or D > 128, -ENOTSUP for a hidden_padded other than 256 / 512, -EFAULT for a NULL operand, 0 at B = 0. */
+/* Alignment: params, save and x_pad 16 bytes (NF_EINVAL otherwise); x and x_pos element type. */
 int nf_made_forward_train_ft(const void *x, void *params, void *save, void *bits, void *x_pad, void *x_pos, const void *blob,
                              const int32_t *table, int64_t B, int D, int hidden_padded, int mult, nf_stream_t stream);
+/* Alignment: as nf_made_backward. */
 int nf_made_backward_t64(const void *g_params, const void *bits, void *g_x, void *G, const void *blob, const int32_t *table, int64_t B,
                          int D, int hidden_padded, int mult, nf_stream_t stream);
 int nf_made_feed_ft_bwd(const void *g_pre, const void *g_xpos, const void *x, const int32_t *ttable, const void *feed, void *g_x,
@@ -773,6 +838,7 @@ int nf_made_feed_ft_bwd(const void *g_pre, const void *g_xpos, const void *x, co
 /* The weight streams of a training step from the parameters as they are now: out[i] = flat[src[i]], flat = [0, every parameter of
  * the network flattened], src = the packer's stream with parameter positions in place of values (made_pack.train_structure) -- the
  * reference re-reads its nn.Parameters in every forward; a host-side repack per optimizer step would cost more than the step. */
+/* Alignment: src and out 16 bytes (NF_EINVAL otherwise); flat element type. */
 int nf_pack_gather(const void *flat, const int32_t *src, void *out, int64_t n, nf_stream_t stream);
 /* nf_pack_gather from the parameter tensors in place (round 6): params = n_params <= 16 host pointers to device float32 tensors of
  * numels[j] elements; the virtual flat vector is [0, params[0] ..., params[1] ..., ...] as above -- no concatenation per call. */
@@ -798,6 +864,7 @@ int nf_conv3x3_gather_sum(const void *P, const void *bias, void *out, int64_t B,
                           nf_stream_t stream);
 /* out (C) = sum over batch and pixels of g (B, C, H, W) (float32 NCHW): the bias gradient of the conditioner's last convolution
  * (nets/cnn.py:5-63 under loss.backward(); torch: conv2d's bias backward).  One block per channel, fixed order. */
+/* Alignment: with HW % 4 == 0 g 16 bytes (NF_EINVAL otherwise). */
 int nf_channel_sum(const void *g, void *out, int64_t B, int C, int64_t HW, nf_stream_t stream);
 /* ld (B) float32 = (((ld +- t_0) +- t_1) ...) for n per-sample log-det terms (terms: HOST array of n device pointers, negate[i] != 0:
  * subtracted), in order: what the chain of `log_q += log_det` / `log_q -= log_det` statements in core.py:600-611 / :193-195 computes
@@ -818,12 +885,14 @@ int nf_ld_fold_multi(void *ld, const void *const *terms, const int *negate, int 
  *   z, y (B, D) row-major; logdet (B) accumulated as `acc` says with -sum log(scale).
  */
 int64_t nf_maf_inverse_scratch_floats(int64_t B, int D, int hidden_padded);
+/* Alignment: blob and scratch 16 bytes (NF_EINVAL otherwise); z, y and logdet element type. */
 int nf_maf_inverse(const void *z, void *y, void *logdet, const void *blob, const int32_t *table, void *scratch,
                    int64_t B, int D, int hidden_padded, int acc, nf_stream_t stream);
 /* The same inverse on the second mapping (maf_inverse_h.hip): 32 samples per wave, the lane-halves share each sample's hidden
  * units, two waves per SIMD.  Same blob / table format, arguments and results as nf_maf_inverse, for MADE conditioners of
  * num_blocks = 1, 2 or 3 residual blocks (table[6]; nets/made.py:140-214); scratch: nf_maf_inverse_h_scratch_floats floats. */
 int64_t nf_maf_inverse_h_scratch_floats(int64_t B, int D, int hidden_padded, int num_blocks);
+/* Alignment: as nf_maf_inverse (likewise the _tri, _bits, _tri_bits and _train variants). */
 int nf_maf_inverse_h(const void *z, void *y, void *logdet, const void *blob, const int32_t *table, void *scratch,
                      int64_t B, int D, int hidden_padded, int num_blocks, int acc, nf_stream_t stream);
 /* The same kernel family for FORMAT-1 packs (maf_pack.pack_made(..., tri=True); table[7] == 1; round 5).  REGULAR tiles -- at most 8
@@ -834,6 +903,7 @@ int nf_maf_inverse_h(const void *z, void *y, void *logdet, const void *blob, con
  * runs of one kind and issues one launch per run (no device read-back, no host synchronisation); -EINVAL when table_host does not
  * describe this call (D, hidden_padded, num_blocks, format 1), -EFAULT when it is NULL.  Replaces the same reference lines as
  * nf_maf_inverse (affine/autoregressive.py:29-38, :114-128 over nets/made.py:217-304). */
+/* Alignment: as nf_maf_inverse: blob and scratch 16 bytes (NF_EINVAL otherwise). */
 int nf_maf_inverse_h_tri(const void *z, void *y, void *logdet, const void *blob, const int32_t *table, const int32_t *table_host,
                          void *scratch, int64_t B, int D, int hidden_padded, int num_blocks, int acc, nf_stream_t stream);
 
@@ -850,25 +920,30 @@ int nf_maf_inverse_h_tri(const void *z, void *y, void *logdet, const void *blob,
  *   nf_maf_solve_t        : x (B, D) the inverse's result, prm (B, 2 D) = MADE(x) (nf_made_forward_train), gx (B, D), gld (B) or NULL
  *                           -> v (B, D); blob / table from maf_pack.pack_made_transposed (format 2: table[7] == 2);
  *                           scratch: nf_maf_solve_t_scratch_floats floats, contents need not be initialised.  float32. */
+/* Alignment: as nf_maf_inverse: blob and scratch 16 bytes (NF_EINVAL otherwise). */
 int nf_maf_inverse_h_bits(const void *z, void *y, void *logdet, const void *blob, const int32_t *table, void *scratch, void *bits,
                           int64_t B, int D, int hidden_padded, int num_blocks, int acc, nf_stream_t stream);
 /* the same on a format-1 pack (table_host as in nf_maf_inverse_h_tri): the masks in that pack's positions, for a transposed pack
  * built with the same option (maf_pack.pack_made_transposed(tri=True)) -- the training forward then runs the fast inverse kernel */
+/* Alignment: as nf_maf_inverse: blob and scratch 16 bytes (NF_EINVAL otherwise). */
 int nf_maf_inverse_h_tri_bits(const void *z, void *y, void *logdet, const void *blob, const int32_t *table, const int32_t *table_host,
                               void *scratch, void *bits, int64_t B, int D, int hidden_padded, int num_blocks, int acc,
                               nf_stream_t stream);
 /* both in one entry point (table_host NULL: format-0 pack) that also writes prm (B, 2 D) float32 = MADE's output at the solution,
  * (unconstrained scale, shift) per feature as nets/made.py:296-304 returns it and affine/autoregressive.py:98-128 reads it: what
  * nf_maf_solve_t and nf_maf_affine_bwd take as `prm` -- no second evaluation of the final layer in the backward (round 6) */
+/* Alignment: as nf_maf_inverse: blob and scratch 16 bytes (NF_EINVAL otherwise). */
 int nf_maf_inverse_h_train(const void *z, void *y, void *logdet, const void *blob, const int32_t *table, const int32_t *table_host,
                            void *scratch, void *bits, void *prm, int64_t B, int D, int hidden_padded, int num_blocks, int acc,
                            nf_stream_t stream);
 int64_t nf_maf_solve_t_scratch_floats(int64_t B, int D, int hidden_padded, int num_blocks);
+/* Alignment: blob and scratch 16 bytes (NF_EINVAL otherwise); the rows element type (likewise nf_maf_solve_t_tri). */
 int nf_maf_solve_t(const void *x, const void *prm, const void *gx, const void *gld, const void *bits, void *v, const void *blob,
                    const int32_t *table, void *scratch, int64_t B, int D, int hidden_padded, int num_blocks, nf_stream_t stream);
 /* nf_maf_solve_t on a transposed pack over the format-1 forward positions (pack_made_transposed(tri=True)); table_host = the HOST copy
  * of `table`: the tiles it marks regular-8 (entry [21]) run a statically unrolled sequential part, launched per run of tiles of one
  * kind (round 6).  Bit for bit the results of nf_maf_solve_t on the same pack. */
+/* Alignment: as nf_maf_solve_t: blob and scratch 16 bytes (NF_EINVAL otherwise). */
 int nf_maf_solve_t_tri(const void *x, const void *prm, const void *gx, const void *gld, const void *bits, void *v, const void *blob,
                        const int32_t *table, const int32_t *table_host, void *scratch, int64_t B, int D, int hidden_padded,
                        int num_blocks, nf_stream_t stream);
@@ -878,6 +953,7 @@ int nf_maf_solve_t_tri(const void *x, const void *prm, const void *gx, const voi
  * out (2 num_blocks + 1, B rounded up to 64, ldo) row-major float32 -- what nf_made_wgrad reads as G (instead of another
  * nf_made_backward pass): column c = sign * position pos_of_col[c] of the scratch (ldo int32 on the device, < 0: zero column;
  * maf_pack.solve_t_gradient_columns), layer order reversed with reverse_layers, rows >= B zero.  hidden_padded: the pack's table[3]. */
+/* Alignment: scratch and out 16 bytes (NF_EINVAL otherwise). */
 int nf_maf_scratch_rows(const void *scratch, const int32_t *pos_of_col, void *out, int64_t B, int num_blocks, int hidden_padded, int ldo,
                         double sign, int reverse_layers, nf_stream_t stream);
 /* Round 6: the weight gradients of the same MaskedLinears (nets/made.py:73-81 under loss.backward(), reached from
@@ -889,9 +965,11 @@ int nf_maf_scratch_rows(const void *scratch, const int32_t *pos_of_col, void *ou
  * num_layers = 2 num_blocks + 1, positions = the packs' table[3].  B a multiple of 64 and positions a multiple of 128, else -ENOTSUP
  * (the caller then rearranges with nf_maf_scratch_rows).  nf_maf_scratch_layer: ONE layer of a scratch as out (Bp, ldo) row-major --
  * the inverse pass's last hidden tensor, from which MADE's output at the solution follows by one product. */
+/* Alignment: gp_pad, x_pad, gscratch, fscratch and part 16 bytes (NF_EINVAL otherwise); grads element type. */
 int nf_made_wgrad_pos(const void *gp_pad, const void *x_pad, const void *gscratch, const void *fscratch, void *grads, const void *mask,
                       void *part, const int32_t *wtable, const int32_t *stable, int ntiles, int64_t B, int num_layers, int positions,
                       nf_stream_t stream);
+/* Alignment: scratch and out 16 bytes (NF_EINVAL otherwise). */
 int nf_maf_scratch_layer(const void *scratch, const int32_t *pos_of_col, void *out, int64_t B, int num_blocks, int hidden_padded, int ldo,
                          int layer, nf_stream_t stream);
 
@@ -906,6 +984,7 @@ int nf_maf_scratch_layer(const void *scratch, const int32_t *pos_of_col, void *o
  *                 divided by sqrt(hidden) (the reference's MADE has no hidden_features attribute, :107-109).
  *   z, y (B, D) row-major; logdet (B) accumulated as `acc` says with the row sum of the inverse spline's logabsdet.
  */
+/* Alignment: as nf_maf_inverse. */
 int nf_arnsf_inverse(const void *z, void *y, void *logdet, const void *blob, const int32_t *table, void *scratch,
                      int64_t B, int D, int hidden_padded, int K, int tails, double tail_bound, double min_bin_width,
                      double min_bin_height, double min_derivative, int acc, nf_stream_t stream);
@@ -923,6 +1002,7 @@ int nf_arnsf_inverse(const void *z, void *y, void *logdet, const void *blob, con
  *                 NF_TAILS_NONE | _LINEAR | _CIRCULAR: that type for every feature, mult as for nf_arnsf_inverse.  The tail bound is
  *                 always the table's (per feature); mult <= 32, otherwise NF_ENOTSUP.
  *   scratch, z, y, logdet, acc, min_* : as nf_arnsf_inverse (scratch: nf_maf_inverse_scratch_floats). */
+/* Alignment: as nf_maf_inverse. */
 int nf_arnsf_inverse_ft(const void *z, void *y, void *logdet, const void *blob, const int32_t *table, const void *ftable,
                         void *scratch, int64_t B, int D, int hidden_padded, int K, int tails, double min_bin_width,
                         double min_bin_height, double min_derivative, int acc, nf_stream_t stream);
@@ -967,6 +1047,7 @@ int nf_glow_convnet_layout(int64_t B, int H, int W);
 int64_t nf_glow_convnet_pack_size(int Cin, int Cout, int hidden);
 int nf_glow_convnet_pack(void *wpack, const void *w1, const void *b1, const void *w2, const void *b2, const void *w3,
                          const void *b3, int Cin, int Cout, int hidden, int layout, nf_stream_t stream);
+/* Alignment: wpack 16 bytes (NF_EINVAL otherwise); x and out element type. */
 int nf_glow_convnet(const void *x, int64_t x_image_stride, void *out, const void *wpack, int64_t B, int Cin, int H,
                     int W, int Cout, int hidden, double leaky_slope, int layout, nf_stream_t stream);
 
@@ -995,6 +1076,8 @@ int nf_glow_convnet(const void *x, int64_t x_image_stride, void *out, const void
  * No input tensor may alias an output tensor.  Returns NF_ERANGE for nblocks outside 1..32, NF_ENOTSUP when
  * the level's working set does not fit one workgroup's LDS.
  */
+/* Alignment: the blobs named by block_table 16 bytes (not checked: the table is in device memory; nf_glow_convnet_pack's buffers
+ * are); images, mix matrices and logdet element type. */
 int nf_glow_level(const void *in0, const void *in1, int cin0, int in_squeezed, void *out0, void *out1, int cout0,
                   int out_squeezed, void *logdet, const void *block_table, int nblocks, int64_t B, int C, int H, int W,
                   int hidden, double leaky_slope, int scale_map, int direction, int acc, int layout, nf_stream_t stream);
@@ -1017,9 +1100,12 @@ int nf_affine_coupling_bwd(const void *z, const void *param, const void *gy, con
                            int64_t B, int C, int c1, int flip, int64_t HW, int scale_map, int direction, int dtype,
                            nf_stream_t stream);
 int64_t nf_actnorm_bwd_scratch_doubles(int64_t B, int C);   /* fp64 partial sums of nf_actnorm_bwd (caller-owned scratch) */
+/* Alignment: float32 with HW % 4 == 0: z, gy and gz 16 bytes (NF_EINVAL otherwise); element type in every other case. */
 int nf_actnorm_bwd(const void *z, const void *s, const void *t, const void *gy, const void *gld, void *gz, void *gs,
                    void *gt, void *scratch, int64_t B, int C, int64_t HW, int direction, int dtype, nf_stream_t stream);
 int64_t nf_inv1x1_wgrad_scratch_elems(int64_t B, int C);
+/* Alignment: element type.  Choice of kernel: float32 with HW % 16 == 0 and z, gy 16-byte aligned takes the MFMA kernel, anything
+ * else the element-wise one. */
 int nf_inv1x1_wgrad(const void *z, const void *gy, const void *gld, void *gW, void *gldu, void *scratch, int64_t B, int C,
                     int64_t HW, int dtype, nf_stream_t stream);
 
@@ -1029,13 +1115,16 @@ int nf_inv1x1_wgrad(const void *z, const void *gy, const void *gld, void *gW, vo
  * (mixing.py:535-563 under autograd: u = U x[perm], gu = L^T gy, gx = P U^T gu) with the permutation folded into W.
  * y must not alias x.
  */
+/* Alignment: with D = 64 or 128 x and y 16 bytes (NF_EINVAL otherwise); any other D moves element by element. */
 int nf_rows_matvec(const void *x, const void *W, void *y, int64_t B, int D, nf_stream_t stream);
 /* Same with a bias (D, may be NULL) and, when logdet != NULL, logdet[b] (acc) ld_sign * (*ld_const) for every row. */
+/* Alignment: as nf_rows_matvec; W, bias and logdet element type. */
 int nf_rows_matvec_affine(const void *x, const void *W, const void *bias, void *y, void *logdet, const void *ld_const,
                           double ld_sign, int acc, int64_t B, int D, nf_stream_t stream);
 /* Two chained products in one launch: u_b = W1 x_b (written when u != NULL), y_b = W2 u_b + bias (bias may be NULL), logdet as
  * nf_rows_matvec_affine.  LULinearPermute under autograd (mixing.py:535-563): forward u = U x[perm], y = L u + b; backward
  * gu = L^T gy, gx = P U^T gu -- u / gu are kept for the factor gradients and never leave the registers between the products. */
+/* Alignment: with D = 64 x, u and y 16 bytes (NF_EINVAL otherwise). */
 int nf_rows_matvec2(const void *x, const void *W1, const void *W2, const void *bias, void *u, void *y, void *logdet,
                     const void *ld_const, double ld_sign, int acc, int64_t B, int D, nf_stream_t stream);
 /* LULinearPermute (mixing.py:402-473, :535-563) composed into one dense matrix per direction (fp64 arithmetic in one
@@ -1053,6 +1142,7 @@ int nf_lu_factors(const int64_t *perm, const void *lower_entries, const void *up
 /* nf_lu_factors for n_layers layers of one width in ONE launch; table (device memory): n_layers rows of 5 pointers -- perm,
  * lower_entries, upper_entries, unconstrained_upper_diag, out. */
 int nf_lu_factors_multi(const void *table, int n_layers, double eps, int D, nf_stream_t stream);
+/* Alignment: element type.  gld: summed with 16-byte loads when 16-byte aligned, element by element otherwise. */
 int nf_lu_param_grads(const void *gL, const void *gU, const int64_t *perm, const void *gld, int64_t B,
                       const void *unconstrained_upper_diag, double eps, double sign, void *g_lower, void *g_upper, void *g_udiag,
                       int D, nf_stream_t stream);
@@ -1073,6 +1163,8 @@ int nf_lu_compose(const int64_t *perm, const void *lower_entries, const void *up
  * (transposed), mask2 = x -> out1 = gt, out2 = gx.  Both weight panels stay in LDS, out1 feeds the second product from
  * registers; per row one read of `in` and the mask sources, one write of out1 and out2.  Row pitches in floats, multiples
  * of 4; 16-byte aligned origins. */
+/* Alignment: in, out1, out2, c1, c2, mask1 and mask2 16 bytes and every row stride a multiple of 4 (NF_EINVAL otherwise).  M1 /
+ * M2: staged with 16-byte loads when 16-byte aligned with a row stride that is a multiple of 4, element by element otherwise. */
 int nf_rows_block(const void *in, int64_t ldi, const void *M1, int64_t ldw1, int trans1, const void *c1, const void *mask1,
                   int64_t ldm1, void *out1, int64_t ldo1, const void *M2, int64_t ldw2, int trans2, const void *c2,
                   const void *mask2, int64_t ldm2, void *out2, int64_t ldo2, int64_t B, int H, int relu1, int relu2,

@@ -358,6 +358,8 @@ extern "C" int nf_masked_affine(const void *z, const void *b, const void *s, con
     if (B < 0 || inner < 1 || (direction != 0 && direction != 1) || acc < NF_LD_SUB || acc > NF_LD_ADD) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!z || !b || !y || !logdet) return NF_EFAULT;
+    // the 4-elements-per-lane path reads z, b, s, t and writes y with 16-byte accesses
+    if (dtype == NF_F32 && inner <= 256 && (inner & 3) == 0 && nf_misaligned16(z, b, s, t, y)) return NF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     int grid = inner <= 64 ? grid_for(B * inner, 256 * 4) : grid_for(B, 1, 256 * 16);
     if (dtype == NF_F32 && inner <= 256 && (inner & 3) == 0) grid = grid_for(B * inner / 4, 256);
@@ -451,6 +453,8 @@ extern "C" int nf_diag_gaussian_log_prob(const void *z, const void *loc, const v
     if (B < 0 || d < 1 || acc < NF_LD_SUB || acc > NF_LD_ADD) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!z || !loc || !log_scale || !out) return NF_EFAULT;
+    // the 4-elements-per-lane path reads z, loc, log_scale with 16-byte loads
+    if (dtype == NF_F32 && d <= 256 && (d & 3) == 0 && nf_misaligned16(z, loc, log_scale)) return NF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const double cst = -0.5 * (double)d * log(2.0 * M_PI);  // base.py:99
     int grid = grid_for(B, 4);

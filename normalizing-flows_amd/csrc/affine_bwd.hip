@@ -535,6 +535,7 @@ extern "C" int nf_actnorm_bwd(const void *z, const void *s, const void *t, const
                               nf_stream_t stream) {
     if (B < 1 || C < 1 || HW < 1 || (direction != 0 && direction != 1)) return NF_EINVAL;
     if (!s || !t || !gs || !gt || !scratch || !z || !gy || !gz) return NF_EFAULT;
+    if (dtype == NF_F32 && (HW & 3) == 0 && nf_misaligned16(z, gy, gz)) return NF_EINVAL;   // 16-byte accesses on the planes
     hipStream_t st = (hipStream_t)stream;
     const int nsplit = actnorm_bwd_nsplit(B, C);
     NF_DISPATCH(dtype,

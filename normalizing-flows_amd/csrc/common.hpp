@@ -42,6 +42,13 @@
         if (e__ != hipSuccess) return NF_EIO;        \
     } while (0)
 
+// Host-side alignment test of caller pointers (NULL counts as aligned): true when any of them is off a 16-byte boundary.  Entry
+// points whose kernels make 16-byte vector accesses or LDS-DMA requests on a caller pointer return NF_EINVAL on it before any
+// launch (the table in INTEGRATION.md, "Pointer alignment").
+template <typename... P> static inline bool nf_misaligned16(P... p) {
+    return ((... | (uintptr_t)(const void *)p) & 15) != 0;
+}
+
 namespace nf {
 
 // ---- scalar math, precise variants (parity with the reference's fp32/fp64 CPU path, not fast-math) ----

@@ -459,6 +459,8 @@ extern "C" int nf_final_bwd(const void *x, const void *grad_y, const void *grad_
     if (min_bin_width * K > 1.0 || min_bin_height * K > 1.0) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!x || !grad_y || !grad_logdet || !cond24 || !w_t || !wpack || !grad_x || !grad_cond24 || !grad_h || !partials) return NF_EFAULT;
+    // rows and parameter rows move as 16-byte vectors / LDS-DMA requests (grad_logdet, partials: element by element)
+    if (nf_misaligned16(x, grad_y, cond24, w_t, wpack, grad_x, grad_cond24, grad_h)) return NF_EINVAL;
     FusedLayout lay;
     lay.nblk = num_blocks;
     FinalBwdArgs a;

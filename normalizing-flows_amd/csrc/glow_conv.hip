@@ -1372,6 +1372,7 @@ extern "C" int nf_glow_convnet(const void *x, int64_t x_image_stride, void *out,
     if (B < 0 || H < 1 || W < 1 || x_image_stride < (int64_t)Cin * H * W) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!x || !out || !wpack) return NF_EFAULT;
+    if (nf_misaligned16(wpack)) return NF_EINVAL;       // the weight stream: 16-byte loads / LDS-DMA (x, out: element by element)
     GlowLevel lv = {};
     return gc_launch(x, x_image_stride, out, wpack, gc_meta(Cin, Cout, leaky_slope), B, H, W, layout, lv, (hipStream_t)stream);
 }

@@ -523,6 +523,8 @@ extern "C" int nf_made_backward(const void *g_params, const void *bits, void *g_
     if (rc != NF_OK) return rc;
     if (B == 0) return NF_OK;
     if (!g_params || !bits || !g_x || !blob || !table) return NF_EFAULT;       // (G may be NULL: only g_x is wanted)
+    // g_params rows are read, g_x rows (D % 4 == 0) and G written as 16-byte vectors (g_params' row length is the device table's)
+    if (nf_misaligned16(g_params, G) || ((D & 3) == 0 && nf_misaligned16(g_x))) return NF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int dp = (D + 31) / 32 * 32;
     if (nf::mf_tr128(B, hidden_padded, dp)) return nf::made_bwd_launch<1, 128>(g_params, bits, g_x, G, blob, table, B, st, dp);    // (as the forward)
@@ -537,6 +539,7 @@ extern "C" int nf_made_backward_t64(const void *g_params, const void *bits, void
     if (rc != NF_OK) return rc;
     if (B == 0) return NF_OK;
     if (!g_params || !bits || !g_x || !blob || !table) return NF_EFAULT;
+    if (nf_misaligned16(g_params, G) || ((D & 3) == 0 && nf_misaligned16(g_x))) return NF_EINVAL;      // as nf_made_backward
     hipStream_t st = (hipStream_t)stream;
     const int dp = (D + 31) / 32 * 32;
     if (hidden_padded == 256) return nf::made_bwd_launch<1>(g_params, bits, g_x, G, blob, table, B, st, dp);
@@ -577,6 +580,7 @@ extern "C" int nf_made_wgrad(const void *gp_pad, const void *x_pad, const void *
     if (B < 0 || ntiles < 1) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!gp_pad || !x_pad || !G || !save || !grads || !mask || !part || !wtable || !stable) return NF_EFAULT;
+    if (nf_misaligned16(gp_pad, x_pad, G, save, part)) return NF_EINVAL;       // operands arrive by 16-byte LDS-DMA requests
     hipStream_t st = (hipStream_t)stream;
     const int64_t Bp = (B + 63) / 64 * 64;
     const int rows = made_wgrad_chunk_rows(Bp, ntiles);
@@ -607,6 +611,7 @@ extern "C" int nf_made_wgrad_pos(const void *gp_pad, const void *x_pad, const vo
     if (B % 64 || positions % 128) return NF_ENOTSUP;
     if (B == 0) return NF_OK;
     if (!gp_pad || !x_pad || !gscratch || !fscratch || !grads || !mask || !part || !wtable || !stable) return NF_EFAULT;
+    if (nf_misaligned16(gp_pad, x_pad, gscratch, fscratch, part)) return NF_EINVAL;       // as nf_made_wgrad
     hipStream_t st = (hipStream_t)stream;
     const int rows = made_wgrad_chunk_rows(B, ntiles);
     const int chunks = (int)((B + rows - 1) / rows);

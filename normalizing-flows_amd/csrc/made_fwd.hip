@@ -74,6 +74,7 @@ extern "C" int nf_made_forward_affine(const void *x, void *y, void *logdet, cons
     if (acc < NF_LD_SUB || acc > NF_LD_ADD) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!x || !y || !logdet || !blob || !table) return NF_EFAULT;
+    if ((D & 3) == 0 && nf_misaligned16(x, y)) return NF_EINVAL;        // rows a multiple of 4 floats long move as 16-byte vectors
     hipStream_t st = (hipStream_t)stream;
     if (hidden_padded == 256) return nf::made_fwd_launch<1, 0>(x, y, logdet, blob, table, B, acc, st);
     return nf::made_fwd_launch<2, 0>(x, y, logdet, blob, table, B, acc, st);
@@ -86,6 +87,9 @@ extern "C" int nf_made_forward(const void *x, void *params, const void *blob, co
     if (rc != NF_OK) return rc;
     if (B == 0) return NF_OK;
     if (!x || !params || !blob || !table) return NF_EFAULT;
+    // x rows a multiple of 4 floats long are read, parameter rows of such a length written, as 16-byte vectors (the row lengths
+    // are the device table's: params is held to the alignment whatever they are)
+    if (((D & 3) == 0 && nf_misaligned16(x)) || nf_misaligned16(params)) return NF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     if (hidden_padded == 256) return nf::made_fwd_launch<1, 1>(x, params, nullptr, blob, table, B, NF_LD_WRITE, st);
     return nf::made_fwd_launch<2, 1>(x, params, nullptr, blob, table, B, NF_LD_WRITE, st);
@@ -103,6 +107,7 @@ extern "C" int nf_made_forward_spline(const void *x, void *y, void *logdet, cons
     if (min_bin_width * nf::F_K > 1.0 || min_bin_height * nf::F_K > 1.0) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!x || !y || !logdet || !blob || !table) return NF_EFAULT;
+    if ((D & 3) == 0 && nf_misaligned16(x, y)) return NF_EINVAL;        // rows a multiple of 4 floats long move as 16-byte vectors
     auto p = nf::make_rqs_params<float>(nf::F_K, NF_TAILS_LINEAR, tail_bound, 0, 1, 0, 1, min_bin_width, min_bin_height, min_derivative, 1.0);
     hipStream_t st = (hipStream_t)stream;
     if (hidden_padded == 256) return nf::made_fwd_launch<1, 2>(x, y, logdet, blob, table, B, acc, st, p);
@@ -125,6 +130,7 @@ extern "C" int nf_made_forward_train(const void *x, void *params, void *save, vo
     if (rc != NF_OK) return rc;
     if (B == 0) return NF_OK;
     if (!x || !params || !save || !bits || !blob || !table) return NF_EFAULT;
+    if (((D & 3) == 0 && nf_misaligned16(x)) || nf_misaligned16(params, save)) return NF_EINVAL;   // as nf_made_forward; save: 16-byte stores
     hipStream_t st = (hipStream_t)stream;
     const int dp = (D + 31) / 32 * 32;
     if (nf::mf_tr128(B, hidden_padded, dp))      // (256 slots, <= 64 features, whole 128-row tiles: nf_made_backward decides the same way)

@@ -45,6 +45,7 @@ extern "C" int nf_made_forward_train_ft(const void *x, void *params, void *save,
     if (hidden_padded != 256 && hidden_padded != 512) return NF_ENOTSUP;
     if (B == 0) return NF_OK;
     if (!x || !params || !save || !bits || !x_pad || !x_pos || !blob || !table) return NF_EFAULT;
+    if (nf_misaligned16(params, save, x_pad)) return NF_EINVAL;       // written with 16-byte stores (x and x_pos: element by element)
     hipStream_t st = (hipStream_t)stream;
     if (hidden_padded == 256) return nf::made_fwd_train_ft_launch<1>(x, params, x_pos, blob, table, B, save, bits, x_pad, st);
     return nf::made_fwd_train_ft_launch<2>(x, params, x_pos, blob, table, B, save, bits, x_pad, st);

@@ -552,6 +552,7 @@ extern "C" int nf_maf_inverse(const void *z, void *y, void *logdet, const void *
     if (acc < NF_LD_SUB || acc > NF_LD_ADD) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!z || !y || !logdet || !blob || !table || !scratch) return NF_EFAULT;
+    if (nf_misaligned16(blob, scratch)) return NF_EINVAL;       // 16-byte loads / stores / LDS-DMA (the rows: element by element)
     hipStream_t st = (hipStream_t)stream;
     const int64_t nwt = (B + 63) / 64;
     const int64_t Dp = (D + 31) / 32 * 32;
@@ -588,6 +589,7 @@ extern "C" int nf_arnsf_inverse(const void *z, void *y, void *logdet, const void
     if (acc < NF_LD_SUB || acc > NF_LD_ADD) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!z || !y || !logdet || !blob || !table || !scratch) return NF_EFAULT;
+    if (nf_misaligned16(blob, scratch)) return NF_EINVAL;       // 16-byte loads / stores / LDS-DMA (the rows: element by element)
     hipStream_t st = (hipStream_t)stream;
     const int64_t nwt = (B + 63) / 64;
     const int64_t Dp = (D + 31) / 32 * 32;
@@ -619,6 +621,7 @@ extern "C" int nf_arnsf_inverse_ft(const void *z, void *y, void *logdet, const v
     if (acc < NF_LD_SUB || acc > NF_LD_ADD) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!z || !y || !logdet || !blob || !table || !ftable || !scratch) return NF_EFAULT;
+    if (nf_misaligned16(blob, scratch)) return NF_EINVAL;       // 16-byte loads / stores / LDS-DMA (the rows: element by element)
     hipStream_t st = (hipStream_t)stream;
     const int64_t nwt = (B + 63) / 64;
     const int64_t Dp = (D + 31) / 32 * 32;

@@ -1084,6 +1084,7 @@ static int maf_h_entry(const void *z, void *y, void *logdet, const void *blob, c
         return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!z || !y || !logdet || !blob || !table || !scratch) return NF_EFAULT;
+    if (nf_misaligned16(blob, scratch)) return NF_EINVAL;       // 16-byte loads / stores / LDS-DMA (the rows: element by element)
     hipStream_t st = (hipStream_t)stream;
     if (num_blocks == 1) return maf_h_launch<1>(z, y, logdet, blob, table, table_host, scratch, B, D, hidden_padded, acc, st, bits, prm);
     if (num_blocks == 2) return maf_h_launch<2>(z, y, logdet, blob, table, table_host, scratch, B, D, hidden_padded, acc, st, bits, prm);
@@ -1212,6 +1213,7 @@ extern "C" int nf_maf_scratch_rows(const void *scratch, const int32_t *pos_of_co
     if (B < 0 || num_blocks < 1 || num_blocks > 3 || hidden_padded < 32 || hidden_padded % 32 || ldo < 4 || ldo % 4) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!scratch || !pos_of_col || !out) return NF_EFAULT;
+    if (nf_misaligned16(scratch, out)) return NF_EINVAL;        // 16-byte loads of the scratch, 16-byte stores of the rows
     const int NL = 1 + 2 * num_blocks;
     const int64_t Bp = (B + 63) / 64 * 64;
     const size_t lds = (size_t)32 * (hidden_padded + 4) * sizeof(float);
@@ -1233,6 +1235,7 @@ extern "C" int nf_maf_scratch_layer(const void *scratch, const int32_t *pos_of_c
     if (layer < 0 || layer >= NL) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!scratch || !pos_of_col || !out) return NF_EFAULT;
+    if (nf_misaligned16(scratch, out)) return NF_EINVAL;        // 16-byte loads of the scratch, 16-byte stores of the rows
     const int64_t Bp = (B + 63) / 64 * 64;
     const size_t lds = (size_t)32 * (hidden_padded + 4) * sizeof(float);
     static nf::LdsOptIn opted = {};
@@ -1303,6 +1306,7 @@ extern "C" int nf_maf_solve_t(const void *x, const void *prm, const void *gx, co
     if (num_blocks < 1 || num_blocks > 3) return NF_ENOTSUP;
     if (B == 0) return NF_OK;
     if (!x || !prm || !gx || !bits || !v || !blob || !table || !scratch) return NF_EFAULT;
+    if (nf_misaligned16(blob, scratch)) return NF_EINVAL;       // 16-byte loads / stores / LDS-DMA (the rows: element by element)
     hipStream_t st = (hipStream_t)stream;
     if (num_blocks == 1) return maf_t_launch<1>(x, prm, gx, gld, bits, v, blob, table, nullptr, scratch, B, D, hidden_padded, st);
     if (num_blocks == 2) return maf_t_launch<2>(x, prm, gx, gld, bits, v, blob, table, nullptr, scratch, B, D, hidden_padded, st);
@@ -1324,6 +1328,7 @@ extern "C" int nf_maf_solve_t_tri(const void *x, const void *prm, const void *gx
         return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!x || !prm || !gx || !bits || !v || !blob || !table || !scratch) return NF_EFAULT;
+    if (nf_misaligned16(blob, scratch)) return NF_EINVAL;       // 16-byte loads / stores / LDS-DMA (the rows: element by element)
     hipStream_t st = (hipStream_t)stream;
     if (num_blocks == 1) return maf_t_launch<1>(x, prm, gx, gld, bits, v, blob, table, table_host, scratch, B, D, hidden_padded, st);
     if (num_blocks == 2) return maf_t_launch<2>(x, prm, gx, gld, bits, v, blob, table, table_host, scratch, B, D, hidden_padded, st);

@@ -168,6 +168,7 @@ extern "C" int nf_nsf_wide_ctx(const void *x, const void *context, void *y, void
     if (Dp + PC > 128) return NF_ENOTSUP;
     if (B == 0) return NF_OK;
     if (!x || !context || !y || !logdet || !blob || !table || !tabs) return NF_EFAULT;
+    if ((D & 3) == 0 && nf_misaligned16(x, y)) return NF_EINVAL;        // rows a multiple of 4 floats long move as 16-byte vectors
     auto p = nf::make_rqs_params<float>(K, NF_TAILS_LINEAR, tail_bound, 0, 1, 0, 1, min_bin_width, min_bin_height, min_derivative, 1.0);
     hipStream_t st = (hipStream_t)stream;
     if (direction == 0) return nf::nsf_ctx_dispatch<0>(x, context, y, logdet, blob, table, tabs, B, ldc, C, PC, Dp, hidden_padded, acc, p, st);

@@ -202,6 +202,7 @@ extern "C" int nf_nsf_wide_k(const void *x, void *y, void *logdet, const void *b
     if (min_bin_width * K > 1.0 || min_bin_height * K > 1.0) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!x || !y || !logdet || !blob || !table || !tabs) return NF_EFAULT;
+    if ((D & 3) == 0 && nf_misaligned16(x, y)) return NF_EINVAL;        // rows a multiple of 4 floats long move as 16-byte vectors
     auto p = nf::make_rqs_params<float>(K, NF_TAILS_LINEAR, tail_bound, 0, 1, 0, 1, min_bin_width, min_bin_height, min_derivative, 1.0);
     hipStream_t st = (hipStream_t)stream;
     const int Hp = hidden_padded;

@@ -448,7 +448,8 @@ extern "C" int nf_resblock_bwd_partials(const void *gh, const void *t, const voi
     if (init && D != BB_D) return NF_ENOTSUP;
     if (init && (!wfull || !gx)) return NF_EFAULT;
     if (!init && !gh_in) return NF_EFAULT;
-    if (((uintptr_t)gh | (uintptr_t)t | (uintptr_t)h_in | (uintptr_t)x | (uintptr_t)gh_in | (uintptr_t)gx) & 15) return NF_EINVAL;
+    // rows: 16-byte LDS-DMA requests / stores; wfull: 16-byte loads (W1, W2 and the gradient destinations: element by element)
+    if (nf_misaligned16(gh, t, h_in, x, gh_in, gx, wfull)) return NF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int grid = bb_grid(B);
     BlockBwdArgs a;

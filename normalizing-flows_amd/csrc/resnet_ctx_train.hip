@@ -529,6 +529,7 @@ extern "C" int nf_resnet_ctx_forward_train(const void *x, int64_t ldx, const voi
     if (ldx < nI || ldc < 0) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!x || !context || !out || !save || !blob || !table) return NF_EFAULT;
+    if (nf_misaligned16(save, blob)) return NF_EINVAL;       // 16-byte stores / loads (x, context, out: element by element)
     const int Hp = (hidden + 31) / 32 * 32, Kin = (nI + 31) / 32 * 32 + (C + 31) / 32 * 32;
     const int64_t Bp = (B + 63) / 64 * 64;
     const size_t lds = nf::rc_fwd_lds(Kin, Hp);
@@ -547,6 +548,7 @@ extern "C" int nf_resnet_ctx_backward(const void *g_out, const void *save, void 
     if (rc != NF_OK) return rc;
     if (B == 0) return NF_OK;
     if (!g_out || !save || !G || !g_x || !g_context || !blob || !table) return NF_EFAULT;
+    if (nf_misaligned16(save, G, blob)) return NF_EINVAL;    // 16-byte loads / stores (g_out, g_x, g_context: element by element)
     const int Hp = (hidden + 31) / 32 * 32;
     const int64_t Bp = (B + 63) / 64 * 64;
     const size_t lds = nf::rc_bwd_lds(Hp);

@@ -400,6 +400,7 @@ extern "C" int nf_rows_matvec_affine(const void *x, const void *W, const void *b
     if (D > 2 * RM_D) return NF_ENOTSUP;
     if (B == 0) return NF_OK;
     if (!x || !W || !y || (logdet && !ld_const)) return NF_EFAULT;
+    if ((D == RM_D || D == 2 * RM_D) && nf_misaligned16(x, y)) return NF_EINVAL;      // full rows move as 16-byte vectors
     const int64_t grid = (B + 32 * RM_NW - 1) / (32 * RM_NW);
     if (grid > 0x7fffffff) return NF_ERANGE;
     if (D > RM_D) {
@@ -425,6 +426,7 @@ extern "C" int nf_rows_matvec2(const void *x, const void *W1, const void *W2, co
     if (D > RM_D) return NF_ENOTSUP;
     if (B == 0) return NF_OK;
     if (!x || !W1 || !W2 || !y || (logdet && !ld_const)) return NF_EFAULT;
+    if (D == RM_D && nf_misaligned16(x, u, y)) return NF_EINVAL;      // full rows move as 16-byte vectors
     const int64_t grid = (B + 32 * RM_NW - 1) / (32 * RM_NW);
     if (grid > 0x7fffffff) return NF_ERANGE;
     hipLaunchKernelGGL(rows_matvec2_kernel, dim3((unsigned)grid), dim3(64 * RM_NW), 0, (hipStream_t)stream, (const float *)x,

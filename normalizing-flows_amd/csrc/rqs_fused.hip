@@ -1209,6 +1209,8 @@ extern "C" int nf_rqs_fused_train_full_fwd(const void *x, void *y, void *logdet,
     if (B < 0 || (mask_parity != 0 && mask_parity != 1) || acc < NF_LD_SUB || acc > NF_LD_ADD) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!x || !y || !logdet || !cond_out || !act_out || !wpack) return NF_EFAULT;
+    // 16-byte vector loads / stores on every row buffer, LDS-DMA on the blob (logdet: element by element)
+    if (nf_misaligned16(x, y, cond_out, act_out, wpack)) return NF_EINVAL;
     FlowArgs fa;
     fa.parity = mask_parity ? 1ull : 0ull;
     fa.nlayers = 1;
@@ -1233,6 +1235,8 @@ extern "C" int nf_rqs_fused_train_pair_fwd(const void *x, void *xlu_out, void *y
     if (B < 0 || (mask_parity != 0 && mask_parity != 1) || acc < NF_LD_SUB || acc > NF_LD_ADD) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!x || !xlu_out || !y || !logdet || !cond_out || !act_out || !wpack) return NF_EFAULT;
+    // 16-byte vector loads / stores on every row buffer, LDS-DMA on the blob (logdet: element by element)
+    if (nf_misaligned16(x, xlu_out, y, cond_out, act_out, wpack)) return NF_EINVAL;
     FlowArgs fa;
     fa.parity = mask_parity ? 1ull : 0ull;
     fa.nlayers = 1;
@@ -1453,6 +1457,8 @@ extern "C" int nf_rqs_fused_chain(const void *x, void *y, void *logdet, const vo
     if (acc < NF_LD_SUB || acc > NF_LD_ADD) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!x || !y || !logdet || !wpacks || !mask_parities) return NF_EFAULT;
+    // 16-byte vector loads / stores on every row buffer, LDS-DMA on the blob (logdet: element by element)
+    if (nf_misaligned16(x, y)) return NF_EINVAL;
     FlowArgs fa;
     fa.parity = 0ull;
     fa.nlayers = num_layers;
@@ -1461,6 +1467,7 @@ extern "C" int nf_rqs_fused_chain(const void *x, void *y, void *logdet, const vo
     for (int l = 0; l < num_layers; ++l) {
         if (!wpacks[l]) return NF_EFAULT;
         if (mask_parities[l] != 0 && mask_parities[l] != 1) return NF_EINVAL;
+        if (nf_misaligned16(wpacks[l])) return NF_EINVAL;
         fa.blob[l] = (const float *)wpacks[l];
         if (mask_parities[l]) fa.parity |= 1ull << l;
     }
@@ -1479,6 +1486,8 @@ extern "C" int nf_rqs_fused_train_fwd(const void *x, const void *h2, void *y, vo
     if (B < 0 || (mask_parity != 0 && mask_parity != 1) || acc < NF_LD_SUB || acc > NF_LD_ADD) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!x || !h2 || !y || !logdet || !cond_out || !wpack) return NF_EFAULT;
+    // 16-byte vector loads / stores on every row buffer, LDS-DMA on the blob (logdet: element by element)
+    if (nf_misaligned16(x, h2, y, cond_out, wpack)) return NF_EINVAL;
     FlowArgs fa;
     fa.parity = mask_parity ? 1ull : 0ull;
     fa.nlayers = 1;

@@ -670,6 +670,8 @@ static int x3_run(const void *x, void *y, void *logdet, const X3Args &xa, int fu
     if (acc < NF_LD_SUB || acc > NF_LD_ADD) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!x || !y || !logdet) return NF_EFAULT;
+    if (nf_misaligned16(x, y)) return NF_EINVAL;        // 16-byte row loads / stores (the blobs: LDS-DMA)
+    for (int l = 0; l < xa.nlayers; ++l) if (nf_misaligned16(xa.pack[l])) return NF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     X3Layout lay;
     lay.nblk = num_blocks;

@@ -139,6 +139,8 @@ static int coupling_bwd_core(const void *x, const void *grad_y, const void *grad
     const int nparts = nf_final_bwd_partials(B), chunks = nf_linear_wgrad_chunks(B, TB_MP, F_H), grid = nf_resblock_bwd_grid(B);
     if (nparts < 0 || chunks < 0 || grid < 0) return NF_ENOTSUP;
     if ((uintptr_t)scratch & 15) return NF_EINVAL;      // (every region below is a multiple of 4 floats: 16-byte reduction loads)
+    // what nf_final_bwd / nf_linear_wgrad_partials / nf_resblock_bwd_partials hold to 16 bytes, refused here: before the first launch
+    if (nf_misaligned16(x, grad_y, cond24, acts, w_t, wpack, wfull_t, grad_x)) return NF_EINVAL;
     float *s = (float *)scratch;
     float *gcond = s;                       s += B * (int64_t)TB_MP;
     float *ghA = s;                         s += B * (int64_t)F_H;
@@ -269,6 +271,7 @@ static int pair_train_bwd_head(const void *x_in, const void *xlu, const void *gr
         return NF_EFAULT;
     const int64_t n0 = nf_coupling_train_bwd_scratch_floats(B, num_blocks);
     if (n0 < 0) return (int)n0;
+    if (nf_misaligned16(x_in, grad_x_in, scratch)) return NF_EINVAL;       // nf_lu_bwd_composed_partials' rows, before any launch
     float *gxl = (float *)scratch + n0;                       // the coupling's input gradient = the LU's output gradient
     float *lu_part = gxl + B * (int64_t)F_D;
     const int lgrid = nf_lu_bwd_composed_grid(B);

@@ -557,7 +557,11 @@ static int wgrad_impl(const void *dY, const void *X, void *dW, void *db, void *s
     if (!dY || !X || !dW || !scratch) return NF_EFAULT;
     hipStream_t st = (hipStream_t)stream;
     const bool vec = N % 4 == 0;
-    const bool ring = wgrad_use_ring(B, M, N) && ((((uintptr_t)dY | (uintptr_t)X | (uintptr_t)dY1 | (uintptr_t)X1) & 15) == 0);
+    // every path but the element-wise one (N % 4 != 0) reads dY and X rows with 8- / 16-byte loads or 16-byte LDS-DMA requests and
+    // writes its partial tiles with 16-byte stores: the kernel the ring used to give way to on a misaligned operand (the tile
+    // kernel) makes the same 16-byte loads, so a misaligned operand is refused instead.  dW / db: element by element.
+    if (vec && nf_misaligned16(dY, X, dY1, X1, scratch)) return NF_EINVAL;
+    const bool ring = wgrad_use_ring(B, M, N);
     const bool tile = ring || wgrad_use_tile(M, N);
     const int rows = tile ? nf::wgrad_tile_chunk_rows(B, M) : nf::wgrad_chunk_rows(B, M, vec);
     const int chunks = (int)((B + rows - 1) / rows);

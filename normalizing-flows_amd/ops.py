@@ -20,6 +20,17 @@ def _ld_buffer(logdet, acc, B, like, want=True):
     return logdet, L.LD_ADD if acc is None else acc
 
 
+def _a16(t, vec=True):
+    """The tensor itself when its data pointer is 16-byte aligned (None stays None), otherwise a copy in a fresh allocation, which is.
+    Every entry point that refuses a misaligned pointer (the "Pointer alignment" table of INTEGRATION.md) gets its row operands through
+    this: a contiguous view that starts 4, 8 or 12 bytes into its storage -- a slice of a flat buffer, rows [i:] of a batch with
+    D % 4 != 0 -- is copied once instead of reaching a kernel that moves its rows as 16-byte vectors.  An integer test otherwise.
+    vec=False: the shape at hand takes the entry point's element-wise kernel, which reads the tensor where it is."""
+    if t is None or not vec or t.data_ptr() % 16 == 0:
+        return t
+    return torch.empty(t.shape, dtype=t.dtype, device=t.device).copy_(t)
+
+
 def _ld_acc(logdet, acc):
     """actnorm / inv1x1_conv: the per-sample `logdet` is optional and never allocated; LD_ADD when it is given without `acc`."""
     return (L.LD_ADD if logdet is not None and acc is None else acc) or 0
@@ -80,6 +91,7 @@ def rqs_coupling(x, cond, uw, uh, ud, identity_idx, transform_idx, K, mode, y=No
     L.require_device(x, cond, uw, uh, ud, identity_idx, transform_idx, tails_t, bound_t, tails_i, bound_i)
     B, D = x.shape
     x = x.contiguous()
+    cond = None if cond is None else cond.contiguous()
     if y is None:
         y = torch.empty_like(x)
     logdet, acc = _ld_buffer(logdet, acc, B, x)
@@ -118,10 +130,12 @@ def masked_affine(z, b, s, t, direction, logdet=None, acc=None):
     L.require_device(z, b, s, t)
     z = z.contiguous()
     B, inner, bb = _mask_rows(z, b)
+    vec = z.dtype == torch.float32 and inner <= 256 and inner % 4 == 0     # (the four-elements-per-lane kernel)
+    z, bb = _a16(z, vec), _a16(bb, vec)
     y = torch.empty_like(z)
     logdet, acc = _ld_buffer(logdet, acc, B, z)
-    s = None if s is None else s.contiguous()
-    t = None if t is None else t.contiguous()
+    s = None if s is None else _a16(s.contiguous(), vec)
+    t = None if t is None else _a16(t.contiguous(), vec)
     L.call("nf_masked_affine", ptr(z), ptr(bb), ptr(s), ptr(t), ptr(y), ptr(logdet), B, inner, direction, acc, L.dtype_code(z),
            L.stream())
     return y, logdet
@@ -315,6 +329,8 @@ def actnorm_bwd(z, s, t, gy, gld, direction):
     z, gy = z.contiguous(), gy.contiguous()
     B, Cc = z.shape[:2]
     HW = int(math.prod(z.shape[2:])) if z.dim() > 2 else 1
+    vec = z.dtype == torch.float32 and HW % 4 == 0
+    z, gy = _a16(z, vec), _a16(gy, vec)
     gz = torch.empty_like(z)
     gs = torch.empty(Cc, dtype=z.dtype, device=z.device)
     gt = torch.empty(Cc, dtype=z.dtype, device=z.device)
@@ -331,7 +347,7 @@ def rows_matvec(x, W):
     L.require_device(x, W)
     if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] > 128:
         raise NotImplementedError("rows_matvec: (B, D <= 128) float32")
-    x = x.contiguous()
+    x = _a16(x.contiguous(), x.shape[1] in (64, 128))
     y = torch.empty_like(x)
     L.call("nf_rows_matvec", ptr(x), ptr(W.to(torch.float32).contiguous()), ptr(y), x.shape[0], x.shape[1], L.stream())
     return y
@@ -341,14 +357,14 @@ def rows_block(x, M1, c1, M2, c2, trans=False, mask1=None, mask2=None, relu=True
     """(out1, out2) of nf_rows_block: out1 = mask1(M1 pre(x) + c1), out2 = x + mask2(M2 pre(out1) + c2); (B, H <= 128)
     float32.  trans: M1 / M2 are used transposed (the block's backward); relu: pre = ReLU on both products."""
     L.require_device(x, M1, c1, M2, c2, mask1, mask2)
-    x = x.contiguous()
+    x = _a16(x.contiguous())
     B, H = x.shape
     if x.dtype != torch.float32 or H > 128 or H % 4:
         raise NotImplementedError("rows_block: (B, H <= 128, H % 4 == 0) float32")
     M1, M2 = M1.contiguous(), M2.contiguous()
     assert tuple(M1.shape) == (H, H) and tuple(M2.shape) == (H, H)
     out1, out2 = torch.empty_like(x), torch.empty_like(x)
-    c = lambda t: None if t is None else t.contiguous()   # noqa: E731
+    c = lambda t: None if t is None else _a16(t.contiguous())   # noqa: E731
     L.call("nf_rows_block", ptr(x), H, ptr(M1), H, int(trans), ptr(c(c1)), ptr(c(mask1)), H, ptr(out1), H, ptr(M2), H, int(trans),
            ptr(c(c2)), ptr(c(mask2)), H, ptr(out2), H, B, H, int(relu), int(relu), L.stream())
     return out1, out2
@@ -425,7 +441,7 @@ def lu_param_grads(gL, gU, gld, unconstrained_upper_diag, n_tri, eps=1e-3, sign=
 def rows_matvec_affine(x, W, bias, ld_const=None, ld_sign=1.0, logdet=None, acc=None):
     """y_b = W x_b + bias and logdet[b] (acc) ld_sign * ld_const (nf_rows_matvec_affine); (B, D <= 128) float32."""
     L.require_device(x, W, bias, ld_const, logdet)
-    x = x.contiguous()
+    x = _a16(x.contiguous(), x.shape[1] in (64, 128))
     B, D = x.shape
     y = torch.empty_like(x)
     logdet, acc = _ld_buffer(logdet, acc, B, x, want=ld_const is not None)
@@ -437,7 +453,7 @@ def rows_matvec_affine(x, W, bias, ld_const=None, ld_sign=1.0, logdet=None, acc=
 def rows_matvec2(x, W1, W2, bias=None, ld_const=None, ld_sign=1.0, logdet=None, acc=None, want_u=True):
     """(u, y, logdet): u_b = W1 x_b, y_b = W2 u_b + bias in one launch (nf_rows_matvec2); (B, D <= 64) float32."""
     L.require_device(x, W1, W2, bias, ld_const, logdet)
-    x = x.contiguous()
+    x = _a16(x.contiguous(), x.shape[1] == 64)
     B, D = x.shape
     u = torch.empty_like(x) if want_u else None
     y = torch.empty_like(x)
@@ -470,8 +486,10 @@ def diag_gaussian_log_prob(z, loc, log_scale, log_scale_shift=0.0, out=None, acc
     z = z.contiguous()
     B = z.shape[0]
     d = int(math.prod(z.shape[1:]))
+    vec = z.dtype == torch.float32 and d <= 256 and d % 4 == 0      # (the four-elements-per-lane kernel)
+    z = _a16(z, vec)
     out, acc = _ld_buffer(out, acc, B, z)
-    L.call("nf_diag_gaussian_log_prob", ptr(z), ptr(loc.contiguous().view(-1)), ptr(log_scale.contiguous().view(-1)),
+    L.call("nf_diag_gaussian_log_prob", ptr(z), ptr(_a16(loc.contiguous(), vec).view(-1)), ptr(_a16(log_scale.contiguous(), vec).view(-1)),
            log_scale_shift, ptr(out), B, d, acc, L.dtype_code(z), L.stream())
     return out
 
@@ -531,7 +549,7 @@ def _rqs_fused_launch(name, x, blobs, parities, hidden, num_blocks, K, direction
     L.require_device(x, *(blobs if chain else [blobs]))
     if x.dtype != torch.float32:
         raise TypeError("%s is fp32 only" % name)
-    x = x.contiguous()
+    x = _a16(x.contiguous())
     B, D = x.shape
     y = torch.empty_like(x)
     logdet, acc = _ld_buffer(logdet, acc, B, x)
@@ -562,6 +580,7 @@ def rqs_coupling_bwd(x, grad_y, grad_logdet, cond, uw, uh, ud, identity_idx, tra
                      bound_i)
     B, D = x.shape
     x, grad_y, grad_logdet = x.contiguous(), grad_y.contiguous(), grad_logdet.contiguous()
+    cond = None if cond is None else cond.contiguous()
     # density mode owns (writes) every column of gx; the two sampling modes own one half and leave the rest zero
     gx = torch.empty_like(x) if mode == L.RQS_DENSITY else torch.zeros_like(x)
     gcond = torch.empty_like(cond) if cond is not None else None
@@ -613,7 +632,7 @@ def rqs_fused_train_fwd(x, h2, blob, mask_parity, num_blocks, tail_bound=3.0, mi
     """(y, logdet, cond24) of nf_rqs_fused_train_fwd: final Linear + density-direction coupling transform in one launch;
     cond24 (B, 32, 24) is the conditioner output kept for rqs_coupling_bwd_p24.  logdet given: folded into it per acc."""
     L.require_device(x, h2, blob)
-    return _train_fwd("nf_rqs_fused_train_fwd", x.contiguous(), h2.contiguous(), blob, mask_parity, num_blocks,
+    return _train_fwd("nf_rqs_fused_train_fwd", _a16(x.contiguous()), _a16(h2.contiguous()), blob, mask_parity, num_blocks,
                       (tail_bound, min_bin_width, min_bin_height, min_derivative), logdet, acc, with_acts=False)[:3]
 
 
@@ -634,7 +653,7 @@ def rqs_fused_train_full_fwd(x, blob, mask_parity, num_blocks, tail_bound=3.0, m
     """(y, logdet, cond24, acts) of nf_rqs_fused_train_full_fwd: the whole conditioner + coupling transform in one launch;
     acts (2 num_blocks + 1, B, 128) = h0, then (t, h) per residual block."""
     L.require_device(x, blob)
-    return _train_fwd("nf_rqs_fused_train_full_fwd", x.contiguous(), None, blob, mask_parity, num_blocks,
+    return _train_fwd("nf_rqs_fused_train_full_fwd", _a16(x.contiguous()), None, blob, mask_parity, num_blocks,
                       (tail_bound, min_bin_width, min_bin_height, min_derivative), logdet, acc)
 
 
@@ -651,6 +670,7 @@ def rqs_coupling_bwd_p24(x, grad_y, grad_logdet, cond24, uw, uh, ud, identity_id
     L.require_device(x, grad_y, grad_logdet, cond24, uw, uh, ud, identity_idx, transform_idx)
     B, D = x.shape
     x, grad_y, grad_logdet = x.contiguous(), grad_y.contiguous(), grad_logdet.contiguous()
+    cond24 = _a16(cond24.contiguous())      # (the parameter rows are refused when misaligned; x / grad_y only choose the kernel)
     gx = torch.empty_like(x)
     gcond = torch.empty_like(cond24)
     guw, guh, gud = _spline_grad_views(torch.zeros, uw, uh, ud)     # one zero fill for the three atomically-accumulated outputs
@@ -666,7 +686,8 @@ def final_bwd(x, grad_y, grad_logdet, cond24, w_t, blob, uw, uh, ud, mask_parity
     Linear's input gradient in one pass over the rows; the batch-shared parameters' gradients by a fixed-order reduction."""
     L.require_device(x, grad_y, grad_logdet, cond24, w_t, blob, uw, uh, ud)
     B = x.shape[0]
-    x, grad_y, grad_logdet = x.contiguous(), grad_y.contiguous(), grad_logdet.contiguous()
+    x, grad_y, grad_logdet = _a16(x.contiguous()), _a16(grad_y.contiguous()), grad_logdet.contiguous()
+    cond24, w_t = _a16(cond24.contiguous()), _a16(w_t.contiguous())
     gx = torch.empty_like(x)
     gcond = torch.empty_like(cond24)
     gh = torch.empty(B, 128, dtype=x.dtype, device=x.device)
@@ -711,7 +732,8 @@ def pair_train_bwd(x_in, xlu, grad_y, grad_logdet, cond24, acts, w_t, blob, wful
     L.require_device(x_in, xlu, grad_y, grad_logdet, cond24, acts, w_t, blob, wfull_t, uw, uh, ud, col_map, Wd, Lm, Um, perm, udiag,
                      *w_blocks)
     B = x_in.shape[0]
-    x_in, xlu, grad_y, grad_logdet = x_in.contiguous(), xlu.contiguous(), grad_y.contiguous(), grad_logdet.contiguous()
+    x_in, xlu, grad_y, grad_logdet = _a16(x_in.contiguous()), _a16(xlu.contiguous()), _a16(grad_y.contiguous()), grad_logdet.contiguous()
+    cond24, acts, w_t, wfull_t = (_a16(t.contiguous()) for t in (cond24, acts, w_t, wfull_t))
     scratch, wb, wp, gp = _train_bwd_operands("pair_train_bwd", B, num_blocks, w_blocks, dest, ("lower", "upper", "udiag", "lbias"),
                                               x_in.device)
     gx = torch.empty_like(x_in)
@@ -746,7 +768,7 @@ def rqs_fused_train_pair_fwd(x, blob, mask_parity, num_blocks, tail_bound=3.0, m
     """(xlu, y, logdet, cond24, acts) of nf_rqs_fused_train_pair_fwd: LULinearPermute.inverse + the whole coupling layer in one
     launch; xlu (B, 64) = the LU's output (the coupling's input), the rest as rqs_fused_train_full_fwd."""
     L.require_device(x, blob)
-    x = x.contiguous()
+    x = _a16(x.contiguous())
     xlu = torch.empty_like(x)
     return (xlu,) + _train_fwd("nf_rqs_fused_train_pair_fwd", x, xlu, blob, mask_parity, num_blocks,
                                (tail_bound, min_bin_width, min_bin_height, min_derivative), logdet, acc)
@@ -755,7 +777,7 @@ def rqs_fused_train_pair_fwd(x, blob, mask_parity, num_blocks, tail_bound=3.0, m
 def lu_bwd_composed(g, x, Wd, db_out=None):
     """(gx, dWd, db) of the composed LULinearPermute's backward, D = 64 (nf_lu_bwd_composed): gx = g Wd, dWd = g^T x, db = colsum(g)."""
     L.require_device(g, x, Wd, db_out)
-    g, x, Wd = g.contiguous(), x.contiguous(), Wd.contiguous()
+    g, x, Wd = _a16(g.contiguous()), _a16(x.contiguous()), Wd.contiguous()
     B, D = g.shape
     n = L.query("nf_lu_bwd_composed_scratch_floats", B)
     if n <= 0 or D != 64 or g.dtype != torch.float32:
@@ -801,7 +823,8 @@ def coupling_train_bwd(x, grad_y, grad_logdet, cond24, acts, w_t, blob, wfull_t,
     shapes (any addresses: fresh tensors or views of one flat gradient buffer).  Returns grad_x."""
     L.require_device(x, grad_y, grad_logdet, cond24, acts, w_t, blob, wfull_t, uw, uh, ud, col_map, *w_blocks)
     B = x.shape[0]
-    x, grad_y, grad_logdet = x.contiguous(), grad_y.contiguous(), grad_logdet.contiguous()
+    x, grad_y, grad_logdet = _a16(x.contiguous()), _a16(grad_y.contiguous()), grad_logdet.contiguous()
+    cond24, acts, w_t, wfull_t = (_a16(t.contiguous()) for t in (cond24, acts, w_t, wfull_t))
     scratch, wb, wp, gp = _train_bwd_operands("coupling_train_bwd", B, num_blocks, w_blocks, dest, (), x.device)
     gx = torch.empty_like(x)
     L.call("nf_coupling_train_bwd", ptr(x), ptr(grad_y), ptr(grad_logdet), ptr(cond24), ptr(acts), ptr(w_t), ptr(blob),
@@ -883,6 +906,7 @@ def channel_sum(g):
     if g.dtype != torch.float32 or g.dim() != 4:
         raise ValueError("channel_sum: a float32 (B, C, H, W) tensor")
     B, C, H, W = g.shape
+    g = _a16(g, (H * W) % 4 == 0)
     out = torch.empty(C, dtype=g.dtype, device=g.device)
     L.call("nf_channel_sum", ptr(g), ptr(out), B, C, H * W, L.stream())
     return out
@@ -945,7 +969,7 @@ def nsf_wide(x, blob, table, tabs, hidden_padded, direction, tail_bound, min_bin
     if x.dtype != torch.float32:
         raise NotImplementedError("nsf_wide: float32 only")
     B, D = x.shape
-    x = x.contiguous()
+    x = _a16(x.contiguous(), D % 4 == 0)
     y = torch.empty_like(x)
     logdet, acc = _ld_buffer(logdet, acc, B, x)
     L.call("nf_nsf_wide_k", ptr(x), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(tabs), ptr(lu_logdet), B, D, hidden_padded,
@@ -978,7 +1002,7 @@ def nsf_wide_ctx(x, context, blob, table, tabs, hidden_padded, direction, tail_b
     if table_host is not None and (int(table_host[25]) != C_ or int(table_host[26]) != (C_ + 31) // 32 * 32):
         raise ValueError("nsf_wide_ctx: the pack is for %d context features, the context has %d" % (int(table_host[25]), C_))
     context, ldc = _context_rows(context)
-    x = x.contiguous()
+    x = _a16(x.contiguous(), D % 4 == 0)
     y = torch.empty_like(x)
     logdet, acc = _ld_buffer(logdet, acc, B, x)
     L.call("nf_nsf_wide_ctx", ptr(x), ptr_any(context), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(tabs), B, ldc, D, C_,
@@ -1008,7 +1032,7 @@ def nsf_wide_ft(x, blob, table, ftable, tabs, hidden_padded, direction, min_bin_
     if x.dtype != torch.float32:
         raise NotImplementedError("nsf_wide_ft: float32 only")
     B, D = x.shape
-    x = x.contiguous()
+    x = _a16(x.contiguous(), D % 4 == 0)
     y = torch.empty_like(x)
     logdet, acc = _ld_buffer(logdet, acc, B, x)
     L.call("nf_nsf_wide_ft", ptr(x), ptr(y), ptr(logdet), ptr(blob), ptr(table), ptr(ftable), ptr(tabs), B, D, hidden_padded, int(K),
@@ -1076,7 +1100,7 @@ def made_forward_affine(x, blob, table, hidden_padded, logdet=None, acc=None):
     if x.dtype != torch.float32:
         raise NotImplementedError("made_forward_affine: float32 only")
     B, D = x.shape
-    x = x.contiguous()
+    x = _a16(x.contiguous(), D % 4 == 0)
     y = torch.empty_like(x)
     logdet, acc = _ld_buffer(logdet, acc, B, x)
     L.call("nf_made_forward_affine", ptr(x), ptr(y), ptr(logdet), ptr(blob), ptr(table), B, D, hidden_padded, acc, L.stream())
@@ -1091,7 +1115,7 @@ def made_forward_spline(x, blob, table, hidden_padded, tail_bound, min_bin_width
     if x.dtype != torch.float32:
         raise NotImplementedError("made_forward_spline: float32 only")
     B, D = x.shape
-    x = x.contiguous()
+    x = _a16(x.contiguous(), D % 4 == 0)
     y = torch.empty_like(x)
     logdet, acc = _ld_buffer(logdet, acc, B, x)
     L.call("nf_made_forward_spline", ptr(x), ptr(y), ptr(logdet), ptr(blob), ptr(table), B, D, hidden_padded, acc,
@@ -1125,7 +1149,7 @@ def made_forward(x, blob, table, hidden_padded, mult):
     if x.dtype != torch.float32:
         raise NotImplementedError("made_forward: float32 only")
     B, D = x.shape
-    x = x.contiguous()
+    x = _a16(x.contiguous(), D % 4 == 0)
     params = torch.empty(B, mult * D, dtype=x.dtype, device=x.device)
     L.call("nf_made_forward", ptr(x), ptr(params), ptr(blob), ptr(table), B, D, hidden_padded, mult, L.stream())
     return params
@@ -1181,7 +1205,7 @@ def made_forward_train(x, blob, table, hidden_padded, out_features, num_blocks, 
     B, D = x.shape
     if rows is not None:           # x is a padded buffer (rows >= B, row stride in the table's hdr[14]): the conv path
         B, D = rows, features
-    x = x.contiguous()
+    x = _a16(x.contiguous(), D % 4 == 0)
     Bp = (B + 63) // 64 * 64
     params = torch.empty(B, out_features, dtype=x.dtype, device=x.device)
     save = torch.empty(2 * num_blocks + 1, Bp, hidden_padded, dtype=x.dtype, device=x.device)
@@ -1237,7 +1261,7 @@ def made_backward(g_params, bits, blob, table, D, hidden_padded, num_blocks, row
     L.require_device(g_params, bits, blob, table)
     B = g_params.shape[0] if rows is None else rows
     md = g_params.shape[1] if out_features is None else out_features
-    g_params = g_params.contiguous()
+    g_params = _a16(g_params.contiguous())
     Bp = (B + 63) // 64 * 64
     gx = torch.empty(B, D if ld_out is None else ld_out, dtype=g_params.dtype, device=g_params.device)
     G = torch.empty(2 * num_blocks + 1, Bp, hidden_padded, dtype=g_params.dtype, device=g_params.device) if want_G else None
@@ -1248,7 +1272,7 @@ def made_backward(g_params, bits, blob, table, D, hidden_padded, num_blocks, row
 
 def _pad_rows_cols(t, rows, cols):
     if t.shape[0] == rows and t.shape[1] == cols:
-        return t.contiguous()
+        return _a16(t.contiguous())
     return torch.nn.functional.pad(t, (0, cols - t.shape[1], 0, rows - t.shape[0])).contiguous()
 
 
@@ -1266,7 +1290,7 @@ def made_wgrad(g_params, x, G, save, wtable, stable, mask, ntiles, nflat, Mp, Dx
     B = g_params.shape[0] if rows is None else rows          # (rows: the operands are already padded buffers)
     Bp = G.shape[1]
     gp_pad, x_pad, grads, part = _made_wgrad_operands(g_params, x, Bp, Mp, Dx, nflat, B, ntiles)
-    L.call("nf_made_wgrad", ptr(gp_pad), ptr(x_pad), ptr(G), ptr(save), ptr(grads), ptr(mask), ptr(part), ptr(wtable),
+    L.call("nf_made_wgrad", ptr(gp_pad), ptr(x_pad), ptr(_a16(G)), ptr(_a16(save)), ptr(grads), ptr(mask), ptr(part), ptr(wtable),
            ptr(stable), ntiles, B, L.stream())
     return grads
 
@@ -1281,7 +1305,7 @@ def made_wgrad_pos(g_params, x, gscratch, fscratch, wtable, stable, mask, ntiles
     if B % 64:
         raise NotImplementedError("made_wgrad_pos: a multiple of 64 rows")
     gp_pad, x_pad, grads, part = _made_wgrad_operands(g_params, x, B, Mp, Dx, nflat, B, ntiles)
-    L.call("nf_made_wgrad_pos", ptr(gp_pad), ptr(x_pad), ptr(gscratch), ptr(fscratch), ptr(grads), ptr(mask), ptr(part),
+    L.call("nf_made_wgrad_pos", ptr(gp_pad), ptr(x_pad), ptr(_a16(gscratch)), ptr(_a16(fscratch)), ptr(grads), ptr(mask), ptr(part),
            ptr(wtable), ptr(stable), ntiles, B, num_layers, positions, L.stream())
     return grads
 
@@ -1567,6 +1591,7 @@ def linear_wgrad(dy, x, want_bias=True, relu_x=False, skip_every=0):
     dy, x = dy.contiguous(), x.contiguous()
     B, M = dy.shape
     N = x.shape[1]
+    dy, x = _a16(dy, N % 4 == 0), _a16(x, N % 4 == 0)          # (N % 4 != 0: the element-wise kernel)
     Mo = M - M // skip_every if skip_every else M
     dW = torch.empty(Mo, N, dtype=torch.float32, device=dy.device)
     db = torch.empty(Mo, dtype=torch.float32, device=dy.device) if want_bias else None
@@ -1579,7 +1604,7 @@ def linear_wgrad(dy, x, want_bias=True, relu_x=False, skip_every=0):
 def linear_wgrad_pair(dy0, x0, dy1, x1, relu_x=False):
     """(dW0, db0, dW1, db1) of two same-shape Linear layers in one partial launch + one reduction (nf_linear_wgrad_pair)."""
     L.require_device(dy0, x0, dy1, x1)
-    dy0, x0, dy1, x1 = dy0.contiguous(), x0.contiguous(), dy1.contiguous(), x1.contiguous()
+    dy0, x0, dy1, x1 = (_a16(t.contiguous()) for t in (dy0, x0, dy1, x1))
     if dy0.shape != dy1.shape or x0.shape != x1.shape or any(t.dtype != torch.float32 for t in (dy0, x0, dy1, x1)):
         raise ValueError("linear_wgrad_pair: two float32 problems of the same shape")
     B, M = dy0.shape
@@ -1606,7 +1631,7 @@ def lu_fwd(x, UpT, LT, bias=None, ld_const=None, ld_sign=1.0, logdet=None, acc=N
     """(u, y, logdet): u = U x[perm], y = L u + bias per row with the constant log-det, D = 64, LDS-DMA tiles (nf_lu_fwd); the
     arguments of rows_matvec2 with the TRANSPOSED factor images (UpT, LT of lu_factors)."""
     L.require_device(x, UpT, LT, bias, ld_const, logdet)
-    x = x.contiguous()
+    x = _a16(x.contiguous())
     B, D = x.shape
     u, y = torch.empty_like(x), torch.empty_like(x)
     logdet, acc = _ld_buffer(logdet, acc, B, x, want=ld_const is not None)
@@ -1619,7 +1644,7 @@ def lu_bwd(gy, u, x, Lm, Up, db_out=None):
     """(gx, dL, db, dUp) of LULinearPermute's batch side in the density direction, D = 64, one pass over the rows (nf_lu_bwd);
     db_out: where the bias gradient (D floats) is written instead of a new tensor."""
     L.require_device(gy, u, x, Lm, Up)
-    gy, u, x, Lm, Up = gy.contiguous(), u.contiguous(), x.contiguous(), Lm.contiguous(), Up.contiguous()
+    gy, u, x, Lm, Up = _a16(gy.contiguous()), _a16(u.contiguous()), _a16(x.contiguous()), Lm.contiguous(), Up.contiguous()
     B, D = gy.shape
     n = L.query("nf_lu_bwd_scratch_floats", B)
     if n <= 0 or D != 64 or gy.dtype != torch.float32:
@@ -1644,7 +1669,7 @@ def resblock_bwd(gh, t, h_in, w1, w2, x=None, wfull=None, gx=None, col_map=None,
     (None, dW1, db1, dW2, db2, dW0 (128, 64), db0) is returned; col_map (64 int32, -1 = drop):
     dW0 is compacted to the (128, n_cols) columns it names."""
     L.require_device(gh, t, h_in, w1, w2, x, wfull, gx, col_map)
-    gh, t, h_in, w1, w2 = gh.contiguous(), t.contiguous(), h_in.contiguous(), w1.contiguous(), w2.contiguous()
+    gh, t, h_in, w1, w2 = _a16(gh.contiguous()), _a16(t.contiguous()), _a16(h_in.contiguous()), w1.contiguous(), w2.contiguous()
     if any(v.dtype != torch.float32 for v in (gh, t, h_in, w1, w2)):
         raise ValueError("resblock_bwd: float32 only")
     B, H = gh.shape
@@ -1659,6 +1684,9 @@ def resblock_bwd(gh, t, h_in, w1, w2, x=None, wfull=None, gx=None, col_map=None,
         if not (x.is_contiguous() and gx.is_contiguous() and wfull.is_contiguous()) or x.shape[1] != 64 or \
                 tuple(wfull.shape) != (64, 128):
             raise ValueError("resblock_bwd: contiguous x / gx (B, 64) and wfull (64, 128)")
+        if gx.data_ptr() % 16:          # (updated in place: a copy would not reach the caller)
+            raise ValueError("resblock_bwd: gx must be 16-byte aligned")
+        x, wfull = _a16(x), _a16(wfull)
         nc = int(n_cols) if col_map is not None else 64
         out0 = torch.empty(H * nc + H, dtype=torch.float32, device=gh.device)
         gh_in, w0g, b0g = None, out0[:H * nc], out0[H * nc:]

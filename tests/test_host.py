@@ -345,6 +345,146 @@ def test_c_abi_argument_validation_training_entry_points(nfa):
     assert wp(N=200) == -95 and wp(dY=null) == -14 and wp(wb=2) == -22 and wp(B=0) == -22
 
 
+def _abi_signatures(nfa):
+    """{entry point: [(parameter name, is a pointer)]} parsed from include/nf_mi355x.h (the declarations _lib.py binds)."""
+    import re
+    out = {}
+    for _, fn, params in re.findall(r"([A-Za-z_][\w \*]*?)\b(nf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", nfa._lib._header_text()):
+        out[fn] = [(re.findall(r"\w+", q)[-1], "*" in q) for q in params.split(",") if q.strip() != "void"]
+    return out
+
+
+def _abi_alignment_notes(nfa):
+    """{entry point: the text of the `Alignment:` line in front of its declaration}, `as nf_other` resolved to the other's text."""
+    import re
+    txt = open(os.path.join(nfa._lib.INCLUDE, "nf_mi355x.h")).read()
+    notes = {fn: " ".join(body.replace("\n *", " ").split())
+             for body, fn in re.findall(r"/\* Alignment:(.*?)\*/\n(?:int|int64_t) (nf_[a-z0-9_]+)\(", txt, flags=re.S)}
+
+    def resolve(fn, depth=0):
+        m = re.search(r"\bas (nf_[a-z0-9_]+)", notes[fn])
+        return notes[fn] + (" " + resolve(m.group(1), depth + 1) if m and m.group(1) in notes and depth < 4 else "")
+    return {fn: resolve(fn) for fn in notes}
+
+
+# The alignment contract of the C ABI (INTEGRATION.md, "Pointer alignment"): (entry point, its scalar arguments -- a shape the entry
+# point takes, so that nothing but the pointer under test is wrong --, the pointers it holds to 16 bytes).  Every other pointer is a
+# fake aligned address; host arrays (pointer lists, parities, the pair's tail record) are given by name.  ONLY rejecting entry
+# points: a call that is not refused would launch a kernel on fake addresses, and this file also runs on the GPU machine.
+_LIMITS = dict(tail_bound=3.0, min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3)
+_FUSED = dict(B=128, D=64, hidden=128, num_blocks=2, K=8, mask_parity=0, fuse_lu=0, direction=0, acc=1, **_LIMITS)
+_TRAIN = dict(B=128, D=64, hidden=128, num_blocks=1, K=8, mask_parity=0, n_cols=32, lu_eps=1e-3, **_LIMITS)
+_WIDE = dict(B=65, D=64, hidden_padded=256, K=8, direction=0, acc=1, C=16, ldc=16, **_LIMITS)
+_MADE = dict(B=65, D=64, hidden_padded=256, mult=2, acc=1, **_LIMITS)
+_MAF = dict(B=65, D=8, hidden_padded=64, num_blocks=1, acc=1, K=8, tails=1, **_LIMITS)
+_WG = dict(B=128, M=64, N=32, accumulate=0, relu_x=0, skip_every=0, want_bias=1)
+_ALIGNMENT_CONTRACT = [
+    ("nf_rqs_fused", _FUSED, ["x", "y", "wpack"]),
+    ("nf_rqs_fused_chain", dict(_FUSED, num_layers=2), ["x", "y", "wpacks[1]"]),
+    ("nf_rqs_fused_x3", _FUSED, ["x", "y", "x3pack"]),
+    ("nf_rqs_fused_x3_chain", dict(_FUSED, num_layers=2), ["x", "y", "x3packs[1]"]),
+    ("nf_rqs_fused_train_fwd", _FUSED, ["x", "h2", "y", "cond_out", "wpack"]),
+    ("nf_rqs_fused_train_full_fwd", _FUSED, ["x", "y", "cond_out", "act_out", "wpack"]),
+    ("nf_rqs_fused_train_pair_fwd", _FUSED, ["x", "xlu_out", "y", "cond_out", "act_out", "wpack"]),
+    ("nf_rqs_coupling_bwd_p24", dict(B=128, D=64, nI=32, nT=32, wh_div=1.0, **_LIMITS), ["cond24", "grad_cond24"]),
+    ("nf_final_bwd", _FUSED, ["x", "grad_y", "cond24", "w_t", "wpack", "grad_x", "grad_cond24", "grad_h"]),
+    ("nf_coupling_train_bwd", _TRAIN, ["x", "grad_y", "cond24", "acts", "w_t", "wpack", "wfull_t", "grad_x", "scratch"]),
+    ("nf_pair_train_bwd", _TRAIN, ["x_in", "xlu", "grad_y", "cond24", "acts", "w_t", "wpack", "wfull_t", "grad_x_in", "scratch"]),
+    ("nf_pair_train_bwd_head", _TRAIN, ["x_in", "xlu", "grad_y", "cond24", "acts", "w_t", "wpack", "wfull_t", "grad_x_in", "scratch"]),
+    ("nf_resblock_bwd", dict(B=128, H=128, D=64, n_cols=32), ["gh", "t", "h_in", "x", "gh_in", "gx", "wfull"]),
+    ("nf_resblock_bwd_partials", dict(B=128, H=128, D=64), ["gh", "t", "h_in", "x", "gh_in", "gx", "wfull"]),
+    ("nf_lu_fwd", dict(B=128, D=64, ld_sign=1.0, acc=1), ["x", "u", "y"]),
+    ("nf_lu_bwd", dict(B=128, D=64), ["gy", "u", "x", "gx"]),
+    ("nf_lu_bwd_composed", dict(B=128, D=64), ["g", "x", "gx"]),
+    ("nf_lu_bwd_composed_partials", dict(B=128, D=64), ["g", "x", "gx"]),
+    ("nf_linear_wgrad", _WG, ["dY", "X", "scratch"]),
+    ("nf_linear_wgrad_act", _WG, ["dY", "X", "scratch"]),
+    ("nf_linear_wgrad_skip", _WG, ["dY", "X", "scratch"]),
+    ("nf_linear_wgrad_partials", _WG, ["dY", "X", "scratch"]),
+    ("nf_linear_wgrad_pair", _WG, ["dY0", "X0", "dY1", "X1", "scratch"]),
+    ("nf_rows_block", dict(B=64, H=128, ldi=128, ldw1=128, ldw2=128, ldm1=128, ldm2=128, ldo1=128, ldo2=128, trans1=0, trans2=0,
+                           relu1=1, relu2=1), ["in", "out1", "out2", "c1", "c2", "mask1", "mask2"]),
+    ("nf_rows_matvec", dict(B=65, D=64), ["x", "y"]),
+    ("nf_rows_matvec_affine", dict(B=65, D=128, ld_sign=1.0, acc=1), ["x", "y"]),
+    ("nf_rows_matvec2", dict(B=65, D=64, ld_sign=1.0, acc=1), ["x", "u", "y"]),
+    ("nf_masked_affine", dict(B=8, inner=64, direction=0, acc=1, dtype=0), ["z", "b", "s", "t", "y"]),
+    ("nf_diag_gaussian_log_prob", dict(B=8, d=64, log_scale_shift=0.0, acc=1, dtype=0), ["z", "loc", "log_scale"]),
+    ("nf_actnorm_bwd", dict(B=2, C=3, HW=16, direction=0, dtype=0), ["z", "gy", "gz"]),
+    ("nf_channel_sum", dict(B=2, C=3, HW=16), ["g"]),
+    ("nf_nsf_wide", _WIDE, ["x", "y"]),
+    ("nf_nsf_wide_k", _WIDE, ["x", "y"]),
+    ("nf_nsf_wide_ctx", _WIDE, ["x", "y"]),
+    ("nf_nsf_wide_ft", _WIDE, ["x", "y"]),
+    ("nf_made_forward_affine", _MADE, ["x", "y"]),
+    ("nf_made_forward_spline", _MADE, ["x", "y"]),
+    ("nf_made_forward", _MADE, ["x", "params"]),
+    ("nf_made_forward_train", _MADE, ["x", "params", "save"]),
+    ("nf_made_forward_train_ft", _MADE, ["params", "save", "x_pad"]),
+    ("nf_made_backward", _MADE, ["g_params", "g_x", "G"]),
+    ("nf_made_backward_t64", _MADE, ["g_params", "g_x", "G"]),
+    ("nf_made_wgrad", dict(B=64, ntiles=1), ["gp_pad", "x_pad", "G", "save", "part"]),
+    ("nf_made_wgrad_pos", dict(B=64, ntiles=1, num_layers=1, positions=128), ["gp_pad", "x_pad", "gscratch", "fscratch", "part"]),
+    ("nf_pack_gather", dict(n=8), ["src", "out"]),
+    ("nf_resnet_ctx_forward_train", dict(B=65, nI=3, C=3, ldx=3, ldc=3, hidden=40, out_features=69, num_blocks=2), ["save", "blob"]),
+    ("nf_resnet_ctx_backward", dict(B=65, nI=3, C=3, hidden=40, out_features=69, num_blocks=2), ["save", "G", "blob"]),
+    ("nf_maf_inverse", _MAF, ["blob", "scratch"]),
+    ("nf_maf_inverse_h", _MAF, ["blob", "scratch"]),
+    ("nf_maf_inverse_h_tri", _MAF, ["blob", "scratch"]),
+    ("nf_maf_inverse_h_bits", _MAF, ["blob", "scratch"]),
+    ("nf_maf_inverse_h_tri_bits", _MAF, ["blob", "scratch"]),
+    ("nf_maf_inverse_h_train", _MAF, ["blob", "scratch"]),
+    ("nf_maf_solve_t_tri", _MAF, ["blob", "scratch"]),
+    ("nf_arnsf_inverse", _MAF, ["blob", "scratch"]),
+    ("nf_arnsf_inverse_ft", _MAF, ["blob", "scratch"]),
+    ("nf_maf_solve_t", _MAF, ["blob", "scratch"]),
+    ("nf_maf_scratch_rows", dict(B=65, num_blocks=1, hidden_padded=64, ldo=64, sign=1.0, reverse_layers=0), ["scratch", "out"]),
+    ("nf_maf_scratch_layer", dict(B=65, num_blocks=1, hidden_padded=64, ldo=64, layer=0), ["scratch", "out"]),
+    ("nf_glow_convnet", dict(B=2, Cin=2, H=4, W=4, Cout=4, hidden=256, leaky_slope=0.0, layout=0, x_image_stride=32), ["wpack"]),
+]
+
+
+def test_c_abi_rejects_misaligned_pointers_before_any_launch(nfa):
+    """Every pointer the alignment table of INTEGRATION.md lists under "rejects", set in turn to an address 4 bytes off a 16-byte
+    boundary with every other argument valid: NF_EINVAL, returned by the host-side checks (nothing is launched: the addresses are
+    fake).  The table names exactly the entry points whose `Alignment:` comment in the header promises NF_EINVAL."""
+    lib = nfa._lib.lib()
+    sigs = _abi_signatures(nfa)
+    vp = ctypes.c_void_p
+    good, off = 4096, 4096 + 4
+    th = np.zeros(8 + 24 * 2, dtype=np.int32)          # the host copy of a format-1 table that describes _MAF's call
+    th[:8] = [_MAF["D"], 32, 64, _MAF["hidden_padded"], _MAF["hidden_padded"] // 32, 2, _MAF["num_blocks"], 1]
+    host = {       # host-side arrays some entry points read before they launch
+        "table_host": lambda bad: vp(th.ctypes.data),
+        "wpacks": lambda bad: (vp * 2)(good, off if bad else good), "x3packs": lambda bad: (vp * 2)(good, off if bad else good),
+        "mask_parities": lambda bad: (ctypes.c_int * 2)(0, 1),
+        "w_blocks": lambda bad: (vp * 2)(good, good), "g_blocks": lambda bad: (vp * 4)(good, good, good, good),
+        "tail": lambda bad: ctypes.create_string_buffer(2048),
+    }
+    checked = 0
+    for fn, scalars, pointers in _ALIGNMENT_CONTRACT:
+        for bad in pointers:
+            args, keep = [], []
+            for name, is_ptr in sigs[fn]:
+                if name == "stream":
+                    args.append(None)
+                elif name in host:
+                    keep.append(host[name](bad == name + "[1]"))
+                    args.append(keep[-1])
+                elif is_ptr:
+                    args.append(vp(off if name == bad else good))
+                else:
+                    assert name in scalars, (fn, name)
+                    args.append(scalars[name])
+            assert bad.split("[")[0] in [n for n, _ in sigs[fn]], (fn, bad)
+            rc = getattr(lib, fn)(*args)
+            assert rc == -22, (fn, bad, rc)
+            checked += 1
+    assert checked > 150
+    notes = _abi_alignment_notes(nfa)
+    promised = sorted(fn for fn, text in notes.items() if "NF_EINVAL" in text)
+    assert promised == sorted(fn for fn, _, _ in _ALIGNMENT_CONTRACT), sorted(set(promised) ^ {fn for fn, _, _ in _ALIGNMENT_CONTRACT})
+
+
 def test_masks_bit_exact(nfa):
     m = nfa.utils.create_alternating_binary_mask(7, even=False)
     assert m.dtype == torch.uint8 and m.tolist() == [0, 1, 0, 1, 0, 1, 0]
