@@ -163,6 +163,25 @@ int nf_rqs_coupling_bwd_ft(const void *x, const void *grad_y, const void *grad_l
                            void *grad_ud, int dtype, const int32_t *tails_t, const void *bound_t,
                            const int32_t *tails_i, const void *bound_i, nf_stream_t stream);
 
+/* nf_rqs_coupling_bwd_ft for list tails (tails = NF_TAILS_FEATURE: cond / grad_cond rows of 3 K + 1 floats), K = 8, float32, on
+ * wave-private tiles (csrc/rqs_bwd_ft.hip; utils/splines.py:48-66 under nsf/coupling.py:71-128): a wave stages the conditioner
+ * rows, x and grad_y of its samples in its own LDS region with unit-stride accesses, the element runs in registers, the identity
+ * half's batch-shared parameter gradients are summed per lane, per workgroup (LDS atomics) and then globally (fp32 atomics: their
+ * summation order is not fixed; grad_x and grad_cond are deterministic).  Same arguments, same results up to float32 rounding, same
+ * zero-initialised grad_uw / grad_uh / grad_ud (and grad_x in the two sampling modes); nI = 0 and nT = 0 are allowed.  NF_ENOTSUP for
+ * any other K, tails or dtype and when its tile does not fit the LDS: nf_rqs_coupling_bwd_ft takes those.  NULL arguments as
+ * nf_rqs_coupling_bwd_ft (NF_EFAULT); a pointer off its element type's boundary is an invalid argument.
+ * nf_rqs_coupling_bwd_ft_wave_fits(nI, nT): 1 when the tile of that split fits the LDS, 0 when the entry point declines it. */
+int nf_rqs_coupling_bwd_ft_wave_fits(int nI, int nT);
+/* Alignment: as nf_rqs_coupling_bwd. */
+int nf_rqs_coupling_bwd_ft_wave(const void *x, const void *grad_y, const void *grad_logdet, const void *cond,
+                                const void *uw, const void *uh, const void *ud, const int64_t *identity_idx, int nI,
+                                const int64_t *transform_idx, int nT, int64_t B, int D, int K, int tails,
+                                double tail_bound, double min_bin_width, double min_bin_height, double min_derivative,
+                                double wh_div, int mode, void *grad_x, void *grad_cond, void *grad_uw, void *grad_uh,
+                                void *grad_ud, int dtype, const int32_t *tails_t, const void *bound_t,
+                                const int32_t *tails_i, const void *bound_i, nf_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fully fused NSF coupling layer: ResidualNet conditioner (fp32 MFMA) + spline epilogue, one launch.
  * Replaces the whole of CoupledRationalQuadraticSpline.forward/inverse

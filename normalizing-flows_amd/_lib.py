@@ -23,6 +23,7 @@ LD_WRITE, LD_ADD, LD_SUB = 0, 1, -1
 TAILS = {None: 0, "linear": 1, "circular": 2}
 SCALE = {"exp": 0, "sigmoid": 1, "sigmoid_inv": 2, None: 3}
 RQS_DENSITY, RQS_SAMPLE_IDENTITY, RQS_SAMPLE_TRANSFORM = 0, 1, 2
+ENOTSUP = -95          # NF_ENOTSUP: the entry point does not take this shape / dtype (check() raises NotImplementedError for it)
 
 _lib = None
 

@@ -147,7 +147,7 @@ def _rqs_backward(ctx, gy, gld):
     """(gx, gcond, guw, guh, gud) of SplineFn / CouplingDensityFn: one launch (nf_rqs_coupling_bwd)."""
     x, cond, uw, uh, ud, iidx, tidx = ctx.saved_tensors
     return ops.rqs_coupling_bwd(x, _gy_or_zeros(gy, x), _gld_or_zeros(gld, x), cond, uw, uh, ud, iidx, tidx, ctx.K, ctx.mode,
-                                **ctx.kw)
+                                ft_wave=ctx.ft_wave, **ctx.kw)
 
 
 class SplineFn(torch.autograd.Function):
@@ -158,7 +158,7 @@ class SplineFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, x, cond, uw, uh, ud, K, inverse, kw):
+    def forward(ctx, x, cond, uw, uh, ud, K, inverse, kw, ft_wave=False):
         B, D = x.shape
         idx = torch.arange(D, device=x.device)
         none = idx[:0]
@@ -170,12 +170,12 @@ class SplineFn(torch.autograd.Function):
             kw = dict(kw, wh_div=1.0)
             y, ld = ops.rqs_coupling(x, None, uw, uh, ud, ii, ti, K, mode, **kw)
         ctx.save_for_backward(x, cond, uw, uh, ud, ii, ti)
-        ctx.K, ctx.mode, ctx.kw = K, mode, kw
+        ctx.K, ctx.mode, ctx.kw, ctx.ft_wave = K, mode, kw, ft_wave
         return y, ld
 
     @staticmethod
     def backward(ctx, gy, gld):
-        return (*_rqs_backward(ctx, gy, gld), None, None, None)
+        return (*_rqs_backward(ctx, gy, gld), None, None, None, None)
 
 
 class CouplingDensityFn(torch.autograd.Function):
@@ -184,15 +184,15 @@ class CouplingDensityFn(torch.autograd.Function):
     unconditional spline (or copied), split / merge inside the kernels."""
 
     @staticmethod
-    def forward(ctx, x, cond, uw, uh, ud, iidx, tidx, K, kw):
+    def forward(ctx, x, cond, uw, uh, ud, iidx, tidx, K, kw, ft_wave=False):
         y, ld = ops.rqs_coupling(x, cond.contiguous(), uw, uh, ud, iidx, tidx, K, L.RQS_DENSITY, **kw)
         ctx.save_for_backward(x, cond, uw, uh, ud, iidx, tidx)
-        ctx.K, ctx.mode, ctx.kw = K, L.RQS_DENSITY, kw
+        ctx.K, ctx.mode, ctx.kw, ctx.ft_wave = K, L.RQS_DENSITY, kw, ft_wave
         return y, ld
 
     @staticmethod
     def backward(ctx, gy, gld):
-        return (*_rqs_backward(ctx, gy, gld), None, None, None, None)
+        return (*_rqs_backward(ctx, gy, gld), None, None, None, None, None)
 
 
 class FinalSplineDensityFn(torch.autograd.Function):
@@ -1047,6 +1047,20 @@ class MadeFtFn(torch.autograd.Function):
             periodic = [x.new_zeros(sh) for sh in ctx.pshapes]
         assert len(periodic) == len(ctx.pshapes)
         return (None, None, None, gx if ctx.needs_input_grad[3] else None) + tuple(grads) + tuple(periodic)
+
+
+class ResNetFtFn(MadeFtFn):
+    """MadeFtFn for a dense, periodically fed ResidualNet (flows/made_pack.resnet_train_structure_ft: the conditioner of the circular
+    coupling layer, nets/resnet.py:92-104 over utils/nn.py:64-129).  The same kernels on the same arguments; the pack's column map
+    is the identity, so x_pos is a copy of x that no caller reads: its cotangent stays None (no zero tensor is built for it, and
+    nf_made_feed_ft_bwd takes a NULL g_xpos)."""
+
+    @staticmethod
+    def forward(ctx, fwd, bwd, ft, x, *params):
+        ctx.set_materialize_grads(False)
+        out, x_pos = MadeFtFn.forward(ctx, fwd, bwd, ft, x, *params)
+        ctx.mark_non_differentiable(x_pos)
+        return out, x_pos
 
 
 class ResNetCtxFn(torch.autograd.Function):

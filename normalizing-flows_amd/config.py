@@ -358,6 +358,21 @@ def set_arnsf_train_ft(mode=True):
     arnsf_train_ft = bool(mode)
 
 
+# CircularCoupledRationalQuadraticSpline UNDER AUTOGRAD, both directions: the conditioner (a ResidualNet behind the periodic
+# preprocessing of the circular identity coordinates) on the MADE training kernels through a dense pack (autograd.ResNetFtFn:
+# nf_made_forward_train_ft, nf_made_backward, nf_made_feed_ft_bwd, nf_made_wgrad; flows/made_pack.resnet_train_structure_ft), and the
+# spline's backward of an 8-bin layer on wave-private tiles (nf_rqs_coupling_bwd_ft_wave, csrc/rqs_bwd_ft.hip); False = eager torch
+# modules (indexing, sin / cos, cat, one library GEMM per Linear) + nf_rqs_coupling_bwd_ft (A/B runs, differential tests).  The
+# conditioner route also follows made_train and made_fused, so inside higher_order_gradients() the torch modules run and double
+# backward keeps working.
+nsf_circular_train = True
+
+
+def set_nsf_circular_train(mode=True):
+    global nsf_circular_train
+    nsf_circular_train = bool(mode)
+
+
 # The GLU-gated conditioner of a conditional CoupledRationalQuadraticSpline (ResidualNet with context_features) under autograd on
 # HIP kernels (autograd.ResNetCtxFn, csrc/resnet_ctx_train.hip); False = the conditioner as eager torch modules.  The route also
 # follows made_train, so inside higher_order_gradients() the torch modules run and double backward keeps working.

@@ -209,6 +209,92 @@ __device__ __forceinline__ float rqs_regs_bwd(const RqsParams<float> &p, float x
     return inside ? gv[0] : gy_up;
 }
 
+// rqs_regs_bwd for PER-FEATURE tails (utils/splines.py:48-66: list tails and / or a tensor bound; the parametrisation of
+// rqs_element_bwd under rqs_feature_params with p.dfull = 1): the feature's own interval [-tb, tb] on both axes, K + 1 = 9 derivative
+// logits prm[16..24] per element.  A linear feature's end logits are the constant edge_logit (gradients 0); a circular feature's logit
+// K aliases logit 0, so its gradient is added to entry 0; g[24] is always 0.  Outside the interval the per-feature branch leaves
+// output and log-det 0, which do not depend on x or on the parameters: gx = 0 and every gradient 0.  prm[0..15] arrive multiplied by
+// log2(e) / wh_div as in rqs_regs_bwd; returns gx.
+constexpr int F_MFT = 3 * F_K + 1;   // 25 parameters per feature
+template <bool INVERSE>
+__device__ __forceinline__ float rqs_regs_bwd_ft(const RqsParams<float> &p, float tb, bool circular, float x, const float (&prm)[F_MFT],
+                                                 float gy_up, float gl_up, float (&g)[F_MFT], float inv_div) {
+    const float left = -tb, right = tb, bottom = -tb, top = tb;
+    const bool inside = x >= left && x <= right;
+    float mw = prm[0], mh = prm[F_K];
+#pragma unroll
+    for (int k = 1; k < F_K; ++k) {
+        mw = fmaxf(mw, prm[k]);
+        mh = fmaxf(mh, prm[F_K + k]);
+    }
+    float ew[F_K], eh[F_K], pw[F_K], ph[F_K];
+#pragma unroll
+    for (int k = 0; k < F_K; ++k) {
+        ew[k] = __builtin_amdgcn_exp2f(prm[k] - mw);
+        eh[k] = __builtin_amdgcn_exp2f(prm[F_K + k] - mh);
+        pw[k] = k == 0 ? ew[k] : pw[k - 1] + ew[k];
+        ph[k] = k == 0 ? eh[k] : ph[k - 1] + eh[k];
+    }
+    const float rsw = frcp(pw[F_K - 1]), rsh = frcp(ph[F_K - 1]);
+    const float cw = (right - left) * p.scale_w * rsw, ch = (top - bottom) * p.scale_h * rsh;
+    float kw[F_K + 1], kh[F_K + 1];
+    kw[0] = left; kh[0] = bottom; kw[F_K] = right; kh[F_K] = top;
+#pragma unroll
+    for (int k = 1; k < F_K; ++k) {
+        kw[k] = fmaf(pw[k - 1], cw, left + (right - left) * p.min_w * (float)k);
+        kh[k] = fmaf(ph[k - 1], ch, bottom + (top - bottom) * p.min_h * (float)k);
+    }
+    int bin = 0;
+    float xlo = kw[0], xhi = kw[1], ylo = kh[0], yhi = kh[1];
+    float Cw_lo = 0.0f, Cw_hi = pw[0] * rsw, Ch_lo = 0.0f, Ch_hi = ph[0] * rsh;
+#pragma unroll
+    for (int k = 1; k < F_K; ++k) {
+        const bool ge = x >= (INVERSE ? kh[k] : kw[k]);
+        bin = ge ? k : bin;
+        xlo = ge ? kw[k] : xlo; xhi = ge ? kw[k + 1] : xhi;
+        ylo = ge ? kh[k] : ylo; yhi = ge ? kh[k + 1] : yhi;
+        Cw_lo = ge ? pw[k - 1] * rsw : Cw_lo; Cw_hi = ge ? pw[k] * rsw : Cw_hi;
+        Ch_lo = ge ? ph[k - 1] * rsh : Ch_lo; Ch_hi = ge ? ph[k] * rsh : Ch_hi;
+    }
+    // logits 0 and K (common.hpp::rqs_dlogit, dfull): the constant of linear tails, the element's own logit 0 for a circular feature
+    const float end = circular ? prm[2 * F_K] : p.edge_logit;
+    float dl0 = end, dl1 = end;
+#pragma unroll
+    for (int k = 1; k < F_K; ++k) {
+        dl0 = (bin == k) ? prm[2 * F_K + k] : dl0;
+        dl1 = (bin + 1 == k) ? prm[2 * F_K + k] : dl1;
+    }
+    const float d0 = p.min_d + fsoftplus(dl0), d1 = p.min_d + fsoftplus(dl1);
+    float gv[7];
+    if constexpr (!INVERSE) {
+        rqs_eval_bin_vjp(x, xlo, xhi, ylo, yhi, d0, d1, gy_up, gl_up, gv);
+    } else {
+        float jy[7], jl[7];
+        rqs_eval_bin_dual<float>(x, xlo, xhi, ylo, yhi, d0, d1, true, jy, jl);
+#pragma unroll
+        for (int i = 0; i < 7; ++i) gv[i] = gy_up * jy[i] + gl_up * jl[i];
+    }
+    const float g_cw_lo = bin == 0 ? 0.0f : gv[1], g_cw_hi = bin == F_K - 1 ? 0.0f : gv[2];   // pinned end knots
+    const float g_ch_lo = bin == 0 ? 0.0f : gv[3], g_ch_hi = bin == F_K - 1 ? 0.0f : gv[4];
+    const float fw = (right - left) * p.scale_w * inv_div, fh = (top - bottom) * p.scale_h * inv_div;
+    const float base_w = g_cw_lo * Cw_lo + g_cw_hi * Cw_hi, base_h = g_ch_lo * Ch_lo + g_ch_hi * Ch_hi;
+#pragma unroll
+    for (int i = 0; i < F_K; ++i) {
+        const float tw = (i < bin ? g_cw_lo : 0.0f) + (i <= bin ? g_cw_hi : 0.0f) - base_w;
+        const float th = (i < bin ? g_ch_lo : 0.0f) + (i <= bin ? g_ch_hi : 0.0f) - base_h;
+        // (select, not multiply: NaN parameters of an element outside the interval must not leak into its zero gradient)
+        g[i] = inside ? fw * (ew[i] * rsw) * tw : 0.0f;
+        g[F_K + i] = inside ? fh * (eh[i] * rsh) * th : 0.0f;
+    }
+    const float s0 = dl0 > 20.0f ? 1.0f : sigmoid(dl0), s1 = dl1 > 20.0f ? 1.0f : sigmoid(dl1);
+    const float a0 = inside ? gv[5] * s0 : 0.0f, a1 = inside ? gv[6] * s1 : 0.0f;
+    g[2 * F_K] = circular ? (bin == 0 ? a0 : 0.0f) + (bin == F_K - 1 ? a1 : 0.0f) : 0.0f;
+#pragma unroll
+    for (int k = 1; k < F_K; ++k) g[2 * F_K + k] = (bin == k ? a0 : 0.0f) + (bin + 1 == k ? a1 : 0.0f);
+    g[3 * F_K] = 0.0f;
+    return inside ? gv[0] : 0.0f;
+}
+
 // Two elements at once (the two transform features a lane-half owns in a final-layer group): the same arithmetic as
 // rqs_regs_bwd<false>, statement by statement for both elements, so that the instruction stream of a wave that is alone on its SIMD
 // carries two independent dependency chains (a dependent v_fma issues every ~4 cycles, independent ones every ~2; transcendentals

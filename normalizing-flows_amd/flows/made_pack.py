@@ -172,9 +172,10 @@ def _slot_layers(made, mult, wb=None, ft=False):
                 layers=layers, masks=[l.mask.cpu().numpy() != 0 for l in lin + [fin]], col=col)
 
 
-def resnet_supported(net):
+def resnet_supported(net, preprocessing=False):
+    """preprocessing: the caller feeds the net's preprocessing itself (resnet_train_structure_ft)."""
     from .. import nets
-    if not isinstance(net, nets.ResidualNet) or not net.is_plain_relu():
+    if not isinstance(net, nets.ResidualNet) or not net.is_plain_relu(preprocessing=preprocessing):
         return False
     if len(net.blocks) < 1 or 2 * len(net.blocks) + 2 > MAX_LAYERS:
         return False
@@ -182,10 +183,11 @@ def resnet_supported(net):
     return 2 <= D <= MAX_D and 1 <= H <= 512 and MD >= 1 and net.initial_layer.weight.dtype == torch.float32
 
 
-def _dense_layers(net, wb=None):
+def _dense_layers(net, wb=None, preprocessing=False):
     """A ResidualNet (nets/resnet.py:53-104: the same layer structure as MADE without masks) as slot-space layers for the MADE
-    kernels: identity unit order, every mask all ones (no block is skipped), out_features = MD.  wb: as in _slot_layers."""
-    if not resnet_supported(net):
+    kernels: identity unit order, every mask all ones (no block is skipped), out_features = MD.  wb: as in _slot_layers;
+    preprocessing: as in resnet_supported."""
+    if not resnet_supported(net, preprocessing):
         return None
     D, H, MD = net.initial_layer.in_features, net.initial_layer.out_features, net.final_layer.out_features
     NB = len(net.blocks)
@@ -825,6 +827,66 @@ def resnet_train_structure(net):
         return None
     return _shared(("resnet", net.initial_layer.in_features, net.initial_layer.out_features, len(net.blocks),
                     net.final_layer.out_features), build)
+
+
+def resnet_supported_ft(net, table=True):
+    """What the dense, periodically fed training structure takes (resnet_train_structure_ft): resnet_supported with the preprocessing
+    left to the kernel's feed (a plain ReLU ResidualNet without a context, no batch norm, dropout off or in eval mode, within the MADE
+    training kernels' sizes), float32 throughout, behind a PeriodicFeaturesElementwise with an Identity activation that
+    train_feature_table can express.  table=False leaves that last, value-reading check to the structure's builder (the per-call
+    re-check of a net whose structure is cached: nothing is copied from the device)."""
+    from .. import nets
+    if not resnet_supported(net, preprocessing=True):
+        return False
+    pre = net.preprocessing
+    if not isinstance(pre, nets.PeriodicFeaturesElementwise) or not isinstance(pre.activation, torch.nn.Identity):
+        return False
+    if any(p.dtype != torch.float32 for p in net.parameters()):
+        return False
+    return not table or train_feature_table(net, np.arange(net.initial_layer.in_features)) is not None
+
+
+def resnet_train_structure_ft(net):
+    """made_train_structure_ft for a ResidualNet whose inputs pass a periodic preprocessing first (the conditioner of the circular
+    coupling layer, wrapper.py:88-185: nets/resnet.py:92-104 over utils/nn.py:64-129): _dense_layers (all masks ones) with the
+    identity column map, so position f IS input column f and nf_made_forward_train_ft's gather only feeds.  The same dict: `table`
+    followed by the training feature table (`tt_off`), `src` followed by the feed's gather indices (`feed_off` = table[9]), flat vector
+    = [0, the linears' weight / bias ..., preprocessing.weights, .bias], n_circ, has_bias.  None outside resnet_supported_ft."""
+    def build():
+        sl = _dense_layers(net, preprocessing=True)
+        if sl is None:
+            return None
+        D = sl["D"]
+        tt = train_feature_table(net, np.arange(D))
+        if tt is None:
+            return None
+        lins = [net.initial_layer] + [l for b in net.blocks for l in b.linear_layers] + [net.final_layer]
+        shapes = [tuple(l.weight.shape) for l in lins]
+        st = train_structure(sl, _dense_layers(net, wb=index_arrays(shapes), preprocessing=True))
+        pidx = tt[2]
+        n_circ = int((pidx >= 0).sum())
+        has_bias = bool(n_circ and net.preprocessing.apply_bias)
+        base = 1 + sum(o * i + o for o, i in shapes)          # flat position of preprocessing.weights[0, 0]
+        feed = np.zeros((3 * D + 63) // 64 * 64, dtype=np.int32)      # (padded: the backward streams that follow stay 16-byte aligned)
+        live = np.nonzero(pidx >= 0)[0]
+        feed[live] = base + 2 * pidx[live]
+        feed[D + live] = base + 2 * pidx[live] + 1
+        if has_bias:
+            feed[2 * D + live] = base + 2 * n_circ + pidx[live]
+        assert base + 3 * n_circ < 2 ** 24 and int(st["table"][9]) == st["src"].size
+        st["tt_off"], st["feed_off"] = int(st["table"].size), int(st["src"].size)
+        st["table"] = np.concatenate([st["table"], tt.reshape(-1)]).astype(np.int32)
+        st["src"] = np.concatenate([st["src"], feed]).astype(np.int32)
+        st.update(n_circ=n_circ, has_bias=has_bias)
+        return st
+    if not resnet_supported_ft(net):
+        return None
+    import hashlib
+    pre = net.preprocessing
+    sc = pre.scale.detach().cpu().numpy().tobytes() if torch.is_tensor(pre.scale) else float(pre.scale)
+    pkey = (hashlib.sha1(pre.ind.cpu().numpy().tobytes()).hexdigest(), sc, bool(pre.apply_bias), int(pre.ndim))
+    return _shared(("resnet_ft", net.initial_layer.in_features, net.initial_layer.out_features, len(net.blocks),
+                    net.final_layer.out_features, pkey), build)
 
 
 def convnet_train_structure(cin, hid, cout):

@@ -599,12 +599,14 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
                                                           wpad, ld, ld_sign(acc))
             return outputs, log_det      # log_det IS ld (updated inside the launch) when the caller passed its accumulator
         ident = inputs.index_select(1, self.identity_features)
+        # list tails, 8 bins: the spline's backward on wave-private tiles (nf_rqs_coupling_bwd_ft_wave); only this layer consents
+        wave = bool(_config.nsf_circular_train)
         if not sample:   # nsf/coupling.py:71-98 as one forward + one backward kernel on full rows
             cond = self.transform_net(ident, context)
             uw, uh, ud = (u.unnormalized_widths, u.unnormalized_heights, u.unnormalized_derivatives) if u is not None \
                 else (None, None, None)
             outputs, log_det = CouplingDensityFn.apply(inputs.contiguous(), cond, uw, uh, ud, self.identity_features,
-                                                       self.transform_features, self.num_bins, kw)
+                                                       self.transform_features, self.num_bins, kw, wave)
             return outputs, fold_logdet(ld, acc, log_det)
         trans = inputs.index_select(1, self.transform_features)
         ld_i = None
@@ -617,9 +619,9 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         else:            # nsf/coupling.py:100-128
             if u is not None:
                 ident, ld_i = SplineFn.apply(ident, None, u.unnormalized_widths, u.unnormalized_heights,
-                                             u.unnormalized_derivatives, self.num_bins, True, kw)
+                                             u.unnormalized_derivatives, self.num_bins, True, kw, wave)
             cond = self.transform_net(ident, context)
-            trans, ld_t = SplineFn.apply(trans, cond, None, None, None, self.num_bins, True, kw)
+            trans, ld_t = SplineFn.apply(trans, cond, None, None, None, self.num_bins, True, kw, wave)
         log_det = ld_t if ld_i is None else ld_t + ld_i
         outputs = torch.empty_like(inputs)
         outputs = outputs.index_copy(1, self.identity_features, ident).index_copy(1, self.transform_features, trans)

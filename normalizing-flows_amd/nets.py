@@ -161,7 +161,47 @@ class ResidualNet(nn.Module):
         return _train_packs_from(self, lambda: made_pack.resnet_train_structure(self), [t for l in lins for t in (l.weight, l.bias)],
                                  device)
 
+    def _train_packs_ft(self, device):
+        """(forward pack, backward pack, device tables, parameter list) of autograd.ResNetFtFn for a net behind a periodic
+        preprocessing, or None outside flows/made_pack.resnet_train_structure_ft.  As _train_packs: eligibility is re-checked on EVERY
+        call (dropout depends on the mode), the value-independent structure is built once per module and device, the weight streams
+        and the periodic parameters are gathered on the device from the parameters as they are in THIS call."""
+        from . import ops
+        from .flows import made_pack
+        if not made_pack.resnet_supported_ft(self, table=False):      # (the feature table is checked where the structure is built)
+            return None
+        lins = [self.initial_layer] + [l for b in self.blocks for l in b.linear_layers] + [self.final_layer]
+        plist = [t for l in lins for t in (l.weight, l.bias)] + made_pack.periodic_params(self)
+        if not all(p.is_cuda and p.device == device for p in plist):
+            return None
+        pre = self.preprocessing
+        sc = (pre.scale.data_ptr(), pre.scale._version) if torch.is_tensor(pre.scale) else float(pre.scale)
+        struct = _train_struct_for(self, lambda: made_pack.resnet_train_structure_ft(self), device,
+                                   ("ft", id(pre), bool(pre.apply_bias), pre.ind.data_ptr(), pre.ind._version, sc))
+        if struct is None:
+            return None
+        ft = struct.get("ft_dev")
+        if ft is None:
+            ft = struct["ft_dev"] = dict(ttable=struct["table"][struct["tt_off"]:], feed_off=struct["feed_off"],
+                                         n_circ=struct["n_circ"], has_bias=struct["has_bias"])
+        both = ops.pack_gather([p for p in plist if p.numel()], struct["src"])
+        bwd = dict(struct["bwd"])
+        bwd["blob"] = both[struct["nfwd"]:]
+        return (both[:struct["nfwd"]], struct["table"], struct["hp"]), bwd, ft, plist
+
     def forward(self, inputs, context=None):
+        # behind a periodic preprocessing (the conditioner of the circular coupling layer) under autograd: gather + feed, forward,
+        # input-gradient chain, the feed's backward and every weight gradient on the MADE training kernels through a dense pack
+        if (context is None and isinstance(self.preprocessing, PeriodicFeaturesElementwise) and inputs.dim() == 2 and inputs.is_cuda
+                and inputs.dtype == torch.float32 and inputs.shape[1] == self.initial_layer.in_features and torch.is_grad_enabled()
+                and (inputs.requires_grad or any(p.requires_grad for p in self.parameters()))):
+            from . import config
+            if config.nsf_circular_train and config.made_train and config.made_fused:
+                packs = self._train_packs_ft(inputs.device)
+                if packs is not None:
+                    from . import autograd
+                    fwd, bwd, ft, plist = packs
+                    return autograd.ResNetFtFn.apply(fwd, bwd, ft, inputs, *plist)[0]
         # hidden widths beyond the 128-column training kernels (ResidualBlockFn, autograd.linear) under autograd: the whole net's
         # forward, input-gradient chain and weight gradients on the MADE training kernels (csrc/made_bwd.hip; no mask = dense)
         if (context is None and self.hidden_features > 128 and inputs.dim() == 2 and inputs.is_cuda and inputs.dtype == torch.float32

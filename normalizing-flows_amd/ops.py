@@ -574,8 +574,15 @@ def rqs_fused(x, blob, mask_parity, hidden, num_blocks, K, direction, logdet=Non
 
 def rqs_coupling_bwd(x, grad_y, grad_logdet, cond, uw, uh, ud, identity_idx, transform_idx, K, mode, tails="linear",
                      tail_bound=3.0, min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3, wh_div=1.0,
-                     tails_t=None, bound_t=None, tails_i=None, bound_i=None):
-    """Vector-Jacobian product of rqs_coupling (nf_rqs_coupling_bwd[_ft]).  Returns (gx, gcond, guw, guh, gud)."""
+                     tails_t=None, bound_t=None, tails_i=None, bound_i=None, ft_wave=False):
+    """Vector-Jacobian product of rqs_coupling (nf_rqs_coupling_bwd[_ft]).  Returns (gx, gcond, guw, guh, gud).
+    ft_wave: the caller's consent (config.nsf_circular_train, passed by the circular coupling layer only) to the wave-private kernel
+    for list tails with conditioner rows, 8 bins, float32 (rqs_coupling_bwd_ft_wave); a tile beyond its LDS stays here."""
+    if ft_wave and tails == "feature" and K == 8 and x.dtype == torch.float32 and cond is not None:
+        out = rqs_coupling_bwd_ft_wave(x, grad_y, grad_logdet, cond, uw, uh, ud, identity_idx, transform_idx, K, mode, tail_bound,
+                                       min_bin_width, min_bin_height, min_derivative, wh_div, tails_t, bound_t, tails_i, bound_i)
+        if out is not None:
+            return out
     L.require_device(x, grad_y, grad_logdet, cond, uw, uh, ud, identity_idx, transform_idx, tails_t, bound_t, tails_i,
                      bound_i)
     B, D = x.shape
@@ -592,6 +599,46 @@ def rqs_coupling_bwd(x, grad_y, grad_logdet, cond, uw, uh, ud, identity_idx, tra
            ptr(identity_idx), identity_idx.numel(), ptr(transform_idx), transform_idx.numel(), B, D, K, code, bound,
            min_bin_width, min_bin_height, min_derivative, wh_div, mode, ptr(gx), ptr(gcond), ptr(guw), ptr(guh), ptr(gud),
            L.dtype_code(x), *map(ptr, feat), L.stream())
+    return gx, gcond, guw, guh, gud
+
+
+_FT_WAVE_FITS = {}
+
+
+def _ft_wave_fits(nI, nT):
+    """Whether nf_rqs_coupling_bwd_ft_wave's tile of this split fits the LDS (asked once per split)."""
+    key = (nI, nT)
+    if key not in _FT_WAVE_FITS:
+        _FT_WAVE_FITS[key] = L.query("nf_rqs_coupling_bwd_ft_wave_fits", nI, nT) == 1
+    return _FT_WAVE_FITS[key]
+
+
+def rqs_coupling_bwd_ft_wave(x, grad_y, grad_logdet, cond, uw, uh, ud, identity_idx, transform_idx, K, mode, tail_bound=3.0,
+                             min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3, wh_div=1.0, tails_t=None, bound_t=None,
+                             tails_i=None, bound_i=None):
+    """rqs_coupling_bwd for list tails (cond rows of 3 K + 1 floats), 8 bins, float32, on wave-private tiles
+    (nf_rqs_coupling_bwd_ft_wave, csrc/rqs_bwd_ft.hip): (gx, gcond, guw, guh, gud), or None when the kernel declines the shape (its
+    tile does not fit the LDS) -- nothing was allocated or launched then.  gx and gcond are deterministic, the batch-shared parameters' gradients
+    come through fp32 atomics."""
+    L.require_device(x, grad_y, grad_logdet, cond, uw, uh, ud, identity_idx, transform_idx, tails_t, bound_t, tails_i, bound_i)
+    B, D = x.shape
+    if not _ft_wave_fits(identity_idx.numel(), transform_idx.numel()):      # (decided before anything is allocated)
+        return None
+    x, grad_y, grad_logdet = x.contiguous(), grad_y.contiguous(), grad_logdet.contiguous()
+    cond = None if cond is None else cond.contiguous()
+    gx = torch.empty_like(x) if mode == L.RQS_DENSITY else torch.zeros_like(x)
+    gcond = torch.empty_like(cond) if cond is not None else None
+    guw = torch.zeros_like(uw) if uw is not None else None
+    guh = torch.zeros_like(uh) if uh is not None else None
+    gud = torch.zeros_like(ud) if ud is not None else None
+    _, code, bound, feat = _tails_args(x, "feature", tail_bound, tails_t, bound_t, tails_i, bound_i)
+    rc = L.lib().nf_rqs_coupling_bwd_ft_wave(
+        ptr(x), ptr(grad_y), ptr(grad_logdet), ptr(cond), ptr(uw), ptr(uh), ptr(ud), ptr(identity_idx), identity_idx.numel(),
+        ptr(transform_idx), transform_idx.numel(), B, D, K, code, bound, min_bin_width, min_bin_height, min_derivative, wh_div, mode,
+        ptr(gx), ptr(gcond), ptr(guw), ptr(guh), ptr(gud), L.dtype_code(x), *map(ptr, feat), L.stream())
+    if rc == L.ENOTSUP:
+        return None
+    L.check(rc, "nf_rqs_coupling_bwd_ft_wave")
     return gx, gcond, guw, guh, gud
 
 
