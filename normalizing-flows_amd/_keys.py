@@ -8,7 +8,15 @@ post-step hook records it by `data_ptr`): after an `optimizer.step()` the images
 rebuilt at their next use, whichever implementation the optimizer chose -- a frozen / EMA / teacher model in the same process keeps
 its packs and its recorded hipGraphs (round 4 advanced one process-wide epoch on any optimizer's step: ADVICE r04, _keys.py:31).
 `.data` updates stay the caller's business (`normflows_amd.invalidate_caches` -> `bump()`: the process-wide epoch, part of every
-key)."""
+key).
+
+Where the images live.  Every cached image sits in its owner's `__dict__` as `(key, value)`, or as a dict `sub -> (key, value)`,
+and is read and written through `cached` / `pcached` below -- nowhere else.  The slot's NAME says what it is:
+  * `*_cache`: derived from parameter VALUES.  `core.invalidate_caches` drops it (leaving None, or {} for a dict) and
+    `core._packed_blobs` keeps its tensors alive for the recorded hipGraphs that point at them.
+  * `*_struct`: a value-independent structure (tables, gather indices) keyed on masks, shapes or the device.  It survives
+    `invalidate_caches`; neither walk looks at it.
+Both consumers find their slots by that suffix, so `cached` refuses any other name."""
 _epoch = 0          # advanced by bump(): invalidates everything
 _steps = 0          # optimizer steps seen so far (any optimizer)
 _stepped = {}       # data_ptr -> number of the last optimizer step that updated the tensor at that address
@@ -76,6 +84,31 @@ def pkey(tensors):
         _note(ptr)
         out.append((ptr, t._version, _last_step(ptr)))
     return tuple(out) + (_epoch,)
+
+
+_NO_SUB = object()
+
+
+def cached(owner, slot, key, build, sub=_NO_SUB):
+    """The value stored under `key` in owner.__dict__[slot] == (key, value) -- or, with `sub`, in the dict
+    owner.__dict__[slot][sub] == (key, value); value = build() on a miss.  A slot that holds None, or anything but a dict where a
+    dict is expected (what invalidate_caches leaves), is a miss.  `owner` is a module, or the dict of a structure that carries
+    caches of its own.  The naming rule of `slot` is in the module docstring."""
+    assert slot.endswith(("_cache", "_struct")), slot
+    d = owner if type(owner) is dict else owner.__dict__
+    if sub is not _NO_SUB:
+        if type(d.get(slot)) is not dict:
+            d[slot] = {}
+        d, slot = d[slot], sub
+    ent = d.get(slot)
+    if type(ent) is not tuple or (ent[0] is not key and ent[0] != key):
+        ent = d[slot] = (key, build())
+    return ent[1]
+
+
+def pcached(owner, slot, tensors, extra, build, sub=_NO_SUB):
+    """`cached` under the parameter-version key of `tensors` followed by `extra` (device, mode, direction, ...)."""
+    return cached(owner, slot, pkey(tensors) + tuple(extra), build, sub)
 
 
 _class = {}         # (lo, hi) of a stepped tensor -> (len(_seen) when classified, kind): 0 plain parameter, 1 range, 2 unknown

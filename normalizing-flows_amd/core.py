@@ -30,7 +30,9 @@ def invalidate_caches(module):
     process-wide epoch that a global optimizer post-step hook advances (_keys.py: torch's FUSED optimizers do not bump
     `_version`).  Updates through `.data`
     (`p.data.add_(...)`, `p.data.copy_(...)`, hand-written SGD / EMA on .data) do NOT bump `_version`: call this afterwards, or
-    update `p` under torch.no_grad() instead."""
+    update `p` under torch.no_grad() instead.
+
+    Which attributes are caches is decided by their name alone: the `*_cache` / `*_struct` rule in _keys.py's docstring."""
     for m in module.modules():
         for k in list(m.__dict__.keys()):
             if k.endswith("_cache") and not k.startswith("__"):
@@ -156,19 +158,16 @@ def _pack_realnvp(run, d, device):
     return blob.to(device), hmax
 
 
-def _run_realnvp(run, cache, z, inverse, ld, acc):
+def _run_realnvp(run, z, inverse, ld, acc):
     from . import ops
     d = z.shape[1]
-    key = _keys.pkey(p for f in run for p in list(f.parameters()) + list(f.buffers())) + (str(z.device),)
-    ent = cache.get(id(run[0]))
-    if ent is None or ent[0] != key:
-        ent = (key,) + _pack_realnvp(run, d, z.device)
-        cache[id(run[0])] = ent
-    y, _ = ops.realnvp_chain(z, ent[1], d, ent[2], 1 if inverse else 0, logdet=ld, acc=acc)
+    blob, hmax = _keys.pcached(globals(), "_realnvp_cache", (p for f in run for p in list(f.parameters()) + list(f.buffers())),
+                               (str(z.device),), lambda: _pack_realnvp(run, d, z.device), sub=id(run[0]))
+    y, _ = ops.realnvp_chain(z, blob, d, hmax, 1 if inverse else 0, logdet=ld, acc=acc)
     return y
 
 
-_realnvp_cache = {}
+_realnvp_cache = {}       # id(first flow of a run) -> (key, (blob, hmax)): owned by this module, not by a layer
 
 
 class _frozen_parameters:
@@ -241,7 +240,7 @@ def _run_chain_impl(flows, z, inverse, ld, acc):
             if k2 - k >= 2:   # a run of at least two layers: one launch
                 z = flush(z)
                 idx = sorted(order[k:k2])
-                z = _run_realnvp([flows[q] for q in idx], _realnvp_cache, z, inverse, ld, acc)
+                z = _run_realnvp([flows[q] for q in idx], z, inverse, ld, acc)
                 k = k2
                 continue
         pair = None

@@ -148,19 +148,14 @@ class ClassCondDiagGaussian(BaseDistribution):
         self.loc = nn.Parameter(torch.zeros(*self.shape, num_classes))
         self.log_scale = nn.Parameter(torch.zeros(*self.shape, num_classes))
         self.temperature = None
-        self._rows_cache = None
 
     def _shift(self):
         return 0.0 if self.temperature is None else float(np.log(self.temperature))
 
     def _rows(self):
         """(num_classes, d) copies of loc / log_scale."""
-        key = _keys.pkey((self.loc, self.log_scale))
-        if self._rows_cache is None or self._rows_cache[0] != key:
-            d = int(self.d)
-            self._rows_cache = (key, self.loc.detach().reshape(d, self.num_classes).t().contiguous(),
-                                self.log_scale.detach().reshape(d, self.num_classes).t().contiguous())
-        return self._rows_cache[1], self._rows_cache[2]
+        rows = lambda p: p.detach().reshape(int(self.d), self.num_classes).t().contiguous()     # noqa: E731
+        return _keys.pcached(self, "_rows_cache", (self.loc, self.log_scale), (), lambda: (rows(self.loc), rows(self.log_scale)))
 
     def _select(self, y, num_samples):
         """Per-sample (loc, log_scale) rows and the row index the kernel should use."""

@@ -28,7 +28,7 @@ from torch.nn import functional as F
 
 from .. import autograd, nets, ops
 from . import maf_pack
-from .base import Flow
+from .base import Flow, upload
 
 
 class Autoregressive(Flow):
@@ -93,23 +93,21 @@ class MaskedAffineAutoregressive(Autoregressive):
         """Device copies of the incremental-inverse pack, rebuilt when any MADE parameter changes:
         (blob, table, hidden_padded, num_blocks, table_host); table_host = the host copy of a format-1 table, else None."""
         tri = self._tri()
-        key = _keys.pkey(self.autoregressive_net.parameters()) + (str(device), tri)
-        cache = getattr(self, "_maf_pack_cache", None)
-        if cache is None or cache[0] != key:
+
+        def build():
             if str(device) != "cpu":      # structure (shared by layers with these masks) + one gather on the device
                 st = self._inverse_struct(device)
-                packed = None
-                if st is not None:
-                    plist = [t for l in self.autoregressive_net._linears() for t in (l.weight, l.bias)]
-                    packed = (ops.pack_gather(plist, st[0]), st[1], st[2], st[3], st[4])
-            else:
-                packed = maf_pack.pack_made(self.autoregressive_net, blocks=(1, 2, 3), tri=tri)    # 1..3 residual blocks: nf_maf_inverse_h
-                if packed is not None:
-                    blob, table = packed
-                    packed = (torch.from_numpy(blob).to(device), torch.from_numpy(table).to(device), int(table[3]), int(table[6]),
-                              table if tri else None)
-            self._maf_pack_cache = cache = (key, packed)
-        return cache[1]
+                if st is None:
+                    return None
+                plist = [t for l in self.autoregressive_net._linears() for t in (l.weight, l.bias)]
+                return (ops.pack_gather(plist, st[0]),) + st[1:]
+            packed = maf_pack.pack_made(self.autoregressive_net, blocks=(1, 2, 3), tri=tri)    # 1..3 residual blocks: nf_maf_inverse_h
+            if packed is None:
+                return None
+            table = packed[1]
+            return upload(packed, device) + (int(table[3]), int(table[6]), table if tri else None)
+
+        return _keys.pcached(self, "_maf_pack_cache", self.autoregressive_net.parameters(), (str(device), tri), build)
 
     def _inverse_struct(self, device):
         """(gather indices, table, hidden_padded, num_blocks, table_host) of the one-pass inverse kernel's pack on the device;
@@ -117,15 +115,16 @@ class MaskedAffineAutoregressive(Autoregressive):
         from ..flows import made_pack
         net = self.autoregressive_net
         tri = self._tri()
-        skey = (str(device), tri) + tuple((l.mask.data_ptr(), l.mask._version) for l in net._linears())
-        st = self.__dict__.get("_inv_struct")
-        if st is None or st[0] != skey:
+
+        def build():
             struct = made_pack.maf_inverse_structure(net, tri=tri)
-            if struct is not None:
-                struct = (torch.from_numpy(struct[0]).to(device), torch.from_numpy(struct[1]).to(device), int(struct[1][3]),
-                          int(struct[1][6]), struct[1] if tri else None)
-            st = self.__dict__["_inv_struct"] = (skey, struct)
-        return st[1]
+            if struct is None:
+                return None
+            table = struct[1]
+            return upload(struct, device) + (int(table[3]), int(table[6]), table if tri else None)
+
+        skey = (str(device), tri) + tuple((l.mask.data_ptr(), l.mask._version) for l in net._linears())
+        return _keys.cached(self, "_inv_struct", skey, build)
 
     def forward(self, inputs, context=None):
         """autoregressive.py:24-27: one MADE pass + the element-wise affine map -- ONE launch (nf_made_forward_affine) for the
@@ -169,25 +168,25 @@ class MaskedAffineAutoregressive(Autoregressive):
             # round 5: the inverse on its FORMAT-0 pack (it leaves the ReLU masks in format-0 positions) + the transposed pack of the
             # one-pass solve (made_pack.maf_solve_t_structure), both gathered from the current parameters
             tri = self._tri()          # the forward on the format-1 pack (fast kernel) when available; the masks follow its positions
-            st = self.__dict__.get("_onepass_struct")
-            if st is None or st[0] != (str(device), tri) + skey:
+
+            def build():
                 s0 = made_pack.maf_inverse_structure(net, tri=tri)
                 s2 = made_pack.maf_solve_t_structure(net, tri=tri)
-                val = None
-                if s0 is not None and s2 is not None:
-                    dev = lambda a: torch.from_numpy(a).to(device)
-                    from . import maf_pack
-                    gc = maf_pack.solve_t_gradient_columns(net, tri=tri)
-                    fc = maf_pack.solve_t_gradient_columns(net, tri=tri, forward=True)
-                    pw = maf_pack.position_wgrad_tables(net, tri=tri)
-                    if pw is not None:
-                        pw = dict(pw, wtable=dev(pw["wtable"]), stable=dev(pw["stable"]))
-                    val = (dev(s0[0]), dev(s0[1]), int(s0[1][3]), int(s0[1][6]), int(s0[1][4]), dev(s2[0]), dev(s2[1]),
-                           s0[1] if tri else None, None if gc is None else dev(gc), None if fc is None else dev(fc),
-                           dev(maf_pack.final_layer_columns(net)), pw, s2[1] if tri else None)
-                st = self.__dict__["_onepass_struct"] = ((str(device), tri) + skey, val)
-            if st[1] is not None:
-                src0, table0, hp, nb, tiles, src2, table2, th, gcols, fcols, srcf, pw, tth = st[1]
+                if s0 is None or s2 is None:
+                    return None
+                dev = lambda a: torch.from_numpy(a).to(device)
+                gc = maf_pack.solve_t_gradient_columns(net, tri=tri)
+                fc = maf_pack.solve_t_gradient_columns(net, tri=tri, forward=True)
+                pw = maf_pack.position_wgrad_tables(net, tri=tri)
+                if pw is not None:
+                    pw = dict(pw, wtable=dev(pw["wtable"]), stable=dev(pw["stable"]))
+                return (dev(s0[0]), dev(s0[1]), int(s0[1][3]), int(s0[1][6]), int(s0[1][4]), dev(s2[0]), dev(s2[1]),
+                        s0[1] if tri else None, None if gc is None else dev(gc), None if fc is None else dev(fc),
+                        dev(maf_pack.final_layer_columns(net)), pw, s2[1] if tri else None)
+
+            st = _keys.cached(self, "_onepass_struct", (str(device), tri) + skey, build)
+            if st is not None:
+                src0, table0, hp, nb, tiles, src2, table2, th, gcols, fcols, srcf, pw, tth = st
                 inv = {"blob": ops.pack_gather(plist, src0), "table": table0, "hp": hp, "nb": nb, "tiles": tiles,
                        "tblob": ops.pack_gather(plist, src2), "ttable": table2, "table_host": th, "gcols": gcols, "fcols": fcols,
                        "wf_src": srcf if fcols is not None else None, "pw": pw, "ttable_host": tth}
@@ -264,58 +263,45 @@ class MaskedPiecewiseRationalQuadraticAutoregressive(Autoregressive):
 
     def _packed(self, device):
         """Device copies of the incremental-inverse pack (rows layout), rebuilt when any MADE parameter changes."""
-        key = _keys.pkey(self.autoregressive_net.parameters()) + (str(device),)
-        cache = getattr(self, "_arnsf_pack_cache", None)
-        if cache is None or cache[0] != key:
+        def build():
             packed = maf_pack.pack_made(self.autoregressive_net, mult=self._output_dim_multiplier(), rows=True)
-            if packed is not None:
-                blob, table = packed
-                packed = (torch.from_numpy(blob).to(device), torch.from_numpy(table).to(device), int(table[3]))
-            self._arnsf_pack_cache = cache = (key, packed)
-        return cache[1]
+            return None if packed is None else upload(packed, device) + (int(packed[1][3]),)
+
+        return _keys.pcached(self, "_arnsf_pack_cache", self.autoregressive_net.parameters(), (str(device),), build)
 
     def _permuted(self):
         """True when MADE's input degrees are not 1..D in column order (permute_mask; the final layer's degrees repeat them)."""
         fin = self.autoregressive_net.final_layer
-        key = (fin.degrees.data_ptr(), fin.degrees._version)
-        c = self.__dict__.get("_perm_cache")
-        if c is None or c[0] != key:
+
+        def build():
             deg = fin.degrees.cpu()
             mult = max(deg.numel() // self.features, 1)
-            c = self.__dict__["_perm_cache"] = (key, not torch.equal(deg[::mult], torch.arange(1, self.features + 1)))
-        return c[1]
+            return not torch.equal(deg[::mult], torch.arange(1, self.features + 1))
+
+        return _keys.cached(self, "_perm_cache", (fin.degrees.data_ptr(), fin.degrees._version), build)
+
+    def _ft_pack(self, slot, device, extra, pack):
+        """Device copies of a per-feature pack (blob, table, feature table) + hidden_padded, rebuilt when a MADE parameter (the
+        periodic weights are among them) or the tail bound changes; None outside the packer's structures."""
+        tb = self.tail_bound
+
+        def build():
+            packed = pack()
+            return None if packed is None else upload(packed, device) + (int(packed[1][3]),)
+
+        tensors = list(self.autoregressive_net.parameters()) + ([tb] if torch.is_tensor(tb) else [])
+        return _keys.pcached(self, slot, tensors, (str(device),) + extra, build)
 
     def _packed_ft(self, device):
-        """Device copies of the per-feature pack (rows layout + feature table, nf_arnsf_inverse_ft), rebuilt when a MADE parameter
-        (the periodic weights are among them) or the tail bound changes; None outside the kernel's structures."""
-        tb = self.tail_bound
-        key = _keys.pkey(list(self.autoregressive_net.parameters()) + ([tb] if torch.is_tensor(tb) else [])) + (str(device),)
-        cache = getattr(self, "_arnsf_ft_pack_cache", None)
-        if cache is None or cache[0] != key:
-            packed = maf_pack.pack_made(self.autoregressive_net, mult=self._output_dim_multiplier(), rows=True,
-                                        features=(self.tails, tb))
-            if packed is not None:
-                blob, table, ftable = packed
-                packed = (torch.from_numpy(blob).to(device), torch.from_numpy(table).to(device),
-                          torch.from_numpy(ftable).to(device), int(table[3]))
-            self._arnsf_ft_pack_cache = cache = (key, packed)
-        return cache[1]
+        """The sampling pack (rows layout + feature table, nf_arnsf_inverse_ft)."""
+        return self._ft_pack("_arnsf_ft_pack_cache", device, (), lambda: maf_pack.pack_made(
+            self.autoregressive_net, mult=self._output_dim_multiplier(), rows=True, features=(self.tails, self.tail_bound)))
 
     def _packed_fwd_ft(self, device):
-        """Device copies of the per-feature density pack (nf_made_forward_spline_ft), cached like _packed_ft: rebuilt when a MADE
-        parameter (the periodic weights are among them) or the tail bound changes; None outside the kernel's structures."""
+        """The density pack (nf_made_forward_spline_ft)."""
         from . import made_pack
-        tb = self.tail_bound
-        key = _keys.pkey(list(self.autoregressive_net.parameters()) + ([tb] if torch.is_tensor(tb) else [])) + (str(device), self.training)
-        cache = getattr(self, "_arnsf_fwd_ft_pack_cache", None)
-        if cache is None or cache[0] != key:
-            packed = made_pack.pack_made_forward_ft(self.autoregressive_net, self._output_dim_multiplier(), self.num_bins, self.tails, tb)
-            if packed is not None:
-                blob, table, ftable = packed
-                packed = (torch.from_numpy(blob).to(device), torch.from_numpy(table).to(device),
-                          torch.from_numpy(ftable).to(device), int(table[3]))
-            self._arnsf_fwd_ft_pack_cache = cache = (key, packed)
-        return cache[1]
+        return self._ft_pack("_arnsf_fwd_ft_pack_cache", device, (self.training,), lambda: made_pack.pack_made_forward_ft(
+            self.autoregressive_net, self._output_dim_multiplier(), self.num_bins, self.tails, self.tail_bound))
 
     def forward(self, inputs, context=None):
         """Density direction (autoregressive.py:24-27 + neural_spline/autoregressive.py:94-134): MADE + the element-wise spline as
@@ -396,11 +382,9 @@ class MaskedPiecewiseRationalQuadraticAutoregressive(Autoregressive):
         if isinstance(tails, (list, tuple)):
             tails = [tails[int(c)] for c in ft["col_host"]]
         if torch.is_tensor(tb) and tb.numel() > 1:
-            key = (tb.data_ptr(), tb._version, str(device))
-            c = ft.get("tb_pos")                  # (the caches live with the structure: a new permutation starts new ones)
-            if c is None or c[0] != key:
-                c = ft["tb_pos"] = (key, tb.reshape(-1).to(device).index_select(0, ft["col"]).contiguous())
-            tb = c[1]
+            bound = tb                            # (the caches live with the structure: a new permutation starts new ones)
+            tb = _keys.cached(ft, "tb_pos_cache", (tb.data_ptr(), tb._version, str(device)),
+                              lambda: bound.reshape(-1).to(device).index_select(0, ft["col"]).contiguous())
         return _tails_kwargs(tails, tb, "t", device, ft.setdefault("tcache", {}))
 
     def inverse(self, inputs, context=None):

@@ -31,6 +31,11 @@ def fold_logdet(ld, acc, log_det):
     return ld
 
 
+def upload(arrays, device):
+    """Device copies of a packer's numpy arrays (streams, tables, gather indices), as a tuple."""
+    return tuple(torch.from_numpy(a).to(device) for a in arrays)
+
+
 class Flow(nn.Module):
     """Generic flow layer (flows/base.py:5-24)."""
 

@@ -45,10 +45,7 @@ class GlowBlock(Flow):
             an._init_known = bool(an.data_dep_init_done.item() > 0.0)
         if not an._init_known:
             return None
-        params = [an.s, an.t] + ([conv.L, conv.U, conv.log_S] if conv.use_lu else [conv.W])
-        key = (inverse,) + _keys.pkey(params)
-        cache = getattr(self, "_mix_cache", None)
-        if cache is None or cache[0] != key:
+        def build():
             W, ldu = conv._weight(inverse)
             s_, t_ = an.s.detach().reshape(-1), an.t.detach().reshape(-1)
             if inverse:
@@ -59,9 +56,10 @@ class GlowBlock(Flow):
                 Wp = torch.exp(s_)[:, None] * W
                 bp = t_.clone()
                 ldp = ldu + s_.sum()
-            cache = (key, (Wp.contiguous(), bp.contiguous(), ldp))
-            self._mix_cache = cache
-        return cache[1]
+            return Wp.contiguous(), bp.contiguous(), ldp
+
+        params = [an.s, an.t] + ([conv.L, conv.U, conv.log_S] if conv.use_lu else [conv.W])
+        return _keys.pcached(self, "_mix_cache", params, (inverse,), build)
 
     def _whole_block(self, z):
         """(packed conditioner, layout, LeakyReLU slope, scale map) when the block runs as one launch for inputs like `z`
@@ -146,18 +144,17 @@ def run_level(blocks, entries, layout, slope, scale_map, in0, in1, in_squeezed, 
     device pointer table is cached on the first block per (direction, member tensors): building it is a host -> device copy,
     and a recorded hipGraph bakes its address in."""
     from .. import ops
-    first = blocks[0]
-    key = (inverse, layout) + tuple(t.data_ptr() for e in entries for t in e)
-    cache = first.__dict__.setdefault("_level_tbl_cache", {})
-    hit = cache.get((inverse, len(blocks)))
-    if hit is None or hit[0] != key:
+    def build():
         ents = [(b_, w_.contiguous(), bb_.contiguous(), l_.to(torch.float32).contiguous()) for b_, w_, bb_, l_ in entries]
-        hit = cache[(inverse, len(blocks))] = (key,) + ops.glow_block_table(ents, in0.device)
+        return ops.glow_block_table(ents, in0.device)
+
+    table = _keys.cached(blocks[0], "_level_tbl_cache", (inverse, layout) + tuple(t.data_ptr() for e in entries for t in e),
+                         build, sub=(inverse, len(blocks)))[0]
     if in_squeezed:
         C, H, W = in0.shape[1] * 4, in0.shape[2] // 2, in0.shape[3] // 2
     else:
         C, H, W = in0.shape[1] + (0 if in1 is None else in1.shape[1]), in0.shape[2], in0.shape[3]
-    out0, out1, _ = ops.glow_level(in0, in1, in_squeezed, C, H, W, hit[1], len(blocks), layout, slope, scale_map,
+    out0, out1, _ = ops.glow_level(in0, in1, in_squeezed, C, H, W, table, len(blocks), layout, slope, scale_map,
                                    1 if inverse else 0, cout0=cout0, out_squeezed=out_squeezed, logdet=ld, acc=acc)
     return out0, out1
 

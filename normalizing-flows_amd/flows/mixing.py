@@ -108,13 +108,9 @@ class Invertible1x1Conv(Flow):
         """W and the per-pixel log|det| (0-dim) for flow.inverse (inverse_dir=True) or flow.forward.  The assembled
         matrix is kept until a parameter changes: the reference re-assembles (and re-inverts) it on every call."""
         if self.use_lu:
-            key = (inverse_dir,) + _keys.pkey((self.L, self.U, self.log_S, self.P))
-            cache = getattr(self, "_w_cache", None)
-            if cache is None or cache[0] != key:
-                cache = (key, ops.inv1x1_assemble(self.P, self.L.detach(), self.U.detach(), self.sign_S,
-                                                  self.log_S.detach(), inverse=not inverse_dir))
-                self._w_cache = cache
-            return cache[1]
+            return _keys.pcached(self, "_w_cache", (self.L, self.U, self.log_S, self.P), (inverse_dir,),
+                                 lambda: ops.inv1x1_assemble(self.P, self.L.detach(), self.U.detach(), self.sign_S,
+                                                             self.log_S.detach(), inverse=not inverse_dir))
         W = self.W.detach()
         sld = torch.slogdet(W)[1]
         if inverse_dir:
@@ -194,10 +190,7 @@ class InvertibleAffine(Flow):
             self.W = nn.Parameter(Q)
 
     def _weight_t(self, inverse_dir):
-        params = (self.L, self.U, self.log_S, self.P) if self.use_lu else (self.W,)
-        key = (inverse_dir,) + _keys.pkey(params)
-        cache = getattr(self, "_w_cache", None)
-        if cache is None or cache[0] != key:
+        def build():
             if self.use_lu:
                 W, ldu = ops.inv1x1_assemble(self.P, self.L.detach(), self.U.detach(), self.sign_S, self.log_S.detach(),
                                              inverse=not inverse_dir)
@@ -207,9 +200,10 @@ class InvertibleAffine(Flow):
                 if not inverse_dir:
                     W = torch.inverse(W) if W.dtype == torch.float64 else torch.inverse(W.double()).type(W.dtype)
                     ldu = -ldu
-            cache = (key, (W.t().contiguous(), ldu))
-            self._w_cache = cache
-        return cache[1]
+            return W.t().contiguous(), ldu
+
+        params = (self.L, self.U, self.log_S, self.P) if self.use_lu else (self.W,)
+        return _keys.pcached(self, "_w_cache", params, (inverse_dir,), build)
 
     def _torch(self, z, inverse_dir):
         """Differentiable path (mixing.py:165-207 as torch ops), taken only when a gradient is asked for: the matrix is assembled
@@ -344,29 +338,11 @@ class LULinearPermute(Flow):
                                                  ld, ld_sign(acc), fout,
                                                  self.__dict__.setdefault("_img_holder", {}) if fout is not None else None)
             return y, log_det            # log_det IS ld (updated in place) when the caller passed its accumulator
-        if z.dtype == torch.float32 and z.is_cuda and 64 < lin.features <= 128 and self.use_dense:
-            # wider layers (round 3): the same ONE dense product on fp32 MFMA (nf_rows_matvec_affine takes D <= 128); the
-            # D x D matrices are composed in float64 by a handful of torch launches once per parameter version (the one-workgroup
-            # composer keeps four D x D fp64 matrices in LDS: 64 x 64 at most)
-            params = (lin.lower_entries, lin.upper_entries, lin.unconstrained_upper_diag, lin.bias)
-            key = _keys.pkey(params)
-            cache = self.__dict__.get("_dense_cache")
-            if cache is None or cache[0] != key:
-                cache = self._dense_cache = (key, self._compose_wide())
-            Wd, Ws, bd, bs, lad = cache[1]
-            if inverse:
-                return ops.rows_matvec_affine(z, Wd, bd, lad, +1.0, logdet=ld, acc=acc)
-            return ops.rows_matvec_affine(z, Ws, bs, lad, -1.0, logdet=ld, acc=acc)
-        if z.dtype == torch.float32 and z.is_cuda and lin.features <= 64 and self.use_dense:
-            # the layer as ONE dense D x D product on fp32 MFMA (nf_lu_compose once per parameter version + nf_rows_matvec_affine):
-            # HBM-bound, 5x the LDS-tile kernel below, which stays for D > 64 and float64
-            params = (lin.lower_entries, lin.upper_entries, lin.unconstrained_upper_diag, lin.bias)
-            key = _keys.pkey(params)
-            cache = self.__dict__.get("_dense_cache")
-            if cache is None or cache[0] != key:
-                cache = self._dense_cache = (key, ops.lu_compose(self.permutation._permutation, *[p_.detach() for p_ in params],
-                                                                 eps=lin.eps))
-            Wd, Ws, bd, bs, lad = cache[1]
+        if z.dtype == torch.float32 and z.is_cuda and lin.features <= 128 and self.use_dense:
+            # the layer as ONE dense D x D product on fp32 MFMA (nf_rows_matvec_affine takes D <= 128; the matrices are composed
+            # once per parameter version, _dense_matrices): HBM-bound, 5x the LDS-tile kernel below, which stays for D > 128 and
+            # float64
+            Wd, Ws, bd, bs, lad = self._dense_matrices()
             if inverse:
                 return ops.rows_matvec_affine(z, Wd, bd, lad, +1.0, logdet=ld, acc=acc)
             return ops.rows_matvec_affine(z, Ws, bs, lad, -1.0, logdet=ld, acc=acc)
@@ -380,15 +356,14 @@ class LULinearPermute(Flow):
         y = Ws x + bias_s (the dense form of mixing.py:402-473, :535-563 used by nf_rows_matvec_affine and by the fused pair kernels)."""
         lin = self.linear
         params = (lin.lower_entries, lin.upper_entries, lin.unconstrained_upper_diag, lin.bias)
-        key = _keys.pkey(params)
-        cache = self.__dict__.get("_dense_cache")
-        if cache is None or cache[0] != key:
+
+        def build():
+            # D <= 64: nf_lu_compose (one workgroup, four D x D fp64 matrices in LDS); wider: float64 torch launches on the device
             if lin.features <= 64:
-                val = ops.lu_compose(self.permutation._permutation, *[p_.detach() for p_ in params], eps=lin.eps)
-            else:
-                val = self._compose_wide()
-            cache = self._dense_cache = (key, val)
-        return cache[1]
+                return ops.lu_compose(self.permutation._permutation, *[p_.detach() for p_ in params], eps=lin.eps)
+            return self._compose_wide()
+
+        return _keys.pcached(self, "_dense_cache", params, (), build)
 
     def _compose_wide(self):
         """(Wd, Ws, bias_d, bias_s, log|det|) of mixing.py:402-473, :535-563 as dense matrices, float64 arithmetic on the device:

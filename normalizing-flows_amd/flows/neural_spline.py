@@ -25,7 +25,7 @@ from ..autograd import CouplingDensityFn, CouplingTrainFn, FinalSplineDensityFn,
 from ..nets import PeriodicFeaturesElementwise, ResidualNet
 from ..utils.masks import create_alternating_binary_mask
 from . import nsf_circ_pack, nsf_ctx_pack, nsf_wide_pack
-from .base import Flow, fold_logdet, ld_sign
+from .base import Flow, fold_logdet, ld_sign, upload
 
 DEFAULT_MIN_BIN_WIDTH = 1e-3
 DEFAULT_MIN_BIN_HEIGHT = 1e-3
@@ -77,6 +77,11 @@ def _image_rows(shape):
 
 
 FUSED_D, FUSED_H = 64, 128     # the shape of csrc/rqs_fused.hip (narrower layers are zero-padded into it)
+
+
+def _device_rows(t):
+    """2-D float32 rows on the device: what every one-launch route takes."""
+    return t.dim() == 2 and t.dtype == torch.float32 and t.is_cuda
 
 
 class PiecewiseRationalQuadraticCDF(Flow):
@@ -234,8 +239,6 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         self._per_feature = isinstance(self.tails, list) or torch.is_tensor(tail_bound)
         self._fused_ok = None      # lazily decided: shape handled by the fused MFMA kernel?
         self._fused_parity = 0
-        self._fused_cache = None   # (parameter-version key, packed weight blob)
-        self._fused_x3_cache = None  # (same key object, split-bf16 blob)
         self.use_fused = True      # set False to force the unfused (library GEMM + nf_rqs_coupling) path
         self.use_fused_train = True   # training: final Linear + coupling transform as one launch (FinalSplineDensityFn)
 
@@ -333,42 +336,45 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         return self._sample(inputs, context)
 
     # -- shapes beyond the benchmark kernel's (D <= 128, hidden <= 512): the whole layer as one launch (csrc/nsf_wide.hip) ---
+    def _pack_tensors(self):
+        """What every route's pack is built from: the conditioner's parameters and the batch-shared spline's."""
+        u = self.unconditional_transform
+        return list(self.transform_net.parameters()) + [u.unnormalized_widths, u.unnormalized_heights, u.unnormalized_derivatives]
+
+    def _resnet_rows(self, inputs, enabled):
+        """Shared by the one-launch routes: the switch is on, float32 device rows, a ResidualNet next to a batch-shared spline."""
+        return (self.use_fused and enabled and _device_rows(inputs) and self.unconditional_transform is not None
+                and isinstance(self.transform_net, ResidualNet))
+
     def _wide_pack(self, inputs, context, lu=None, direction=0):
         """Device copies of flows/nsf_wide_pack.py's streams + the batch-shared spline's knot tables, rebuilt when a parameter
         changes; None when the layer is outside nf_nsf_wide's structure (then: library GEMMs + nf_rqs_coupling).  With `lu` (the
         adjacent LULinearPermute, D <= 128) the pack carries its dense matrix for `direction` and the pair runs as one launch."""
-        if not (self.use_fused and _config.nsf_wide and context is None and inputs.dim() == 2 and inputs.dtype == torch.float32
-                and inputs.is_cuda):
+        if context is not None or not self._resnet_rows(inputs, _config.nsf_wide):
             return None
-        net, u = self.transform_net, self.unconditional_transform
-        if u is None or not isinstance(net, ResidualNet):
-            return None
-        tensors = list(net.parameters()) + [u.unnormalized_widths, u.unnormalized_heights, u.unnormalized_derivatives]
+        tensors = self._pack_tensors()
         if lu is not None:
             lin = lu.linear
-            tensors = tensors + [lin.lower_entries, lin.upper_entries, lin.unconstrained_upper_diag, lin.bias]
-        key = _keys.pkey(tensors) + (str(inputs.device),)
-        caches = self.__dict__.setdefault("_wide_cache", {})
-        slot = (id(lu), direction) if lu is not None else None
-        cache = caches.get(slot)
-        if cache is None or cache[0] != key:
+            tensors += [lin.lower_entries, lin.upper_entries, lin.unconstrained_upper_diag, lin.bias]
+
+        def build():
             lu_np = lad = None
             if lu is not None:
                 Wd, Ws, bd, bs, lad = lu._dense_matrices()
                 lu_np = (Wd.cpu().numpy(), bd.cpu().numpy()) if direction == 0 else (Ws.cpu().numpy(), bs.cpu().numpy())
-            packed = nsf_wide_pack.pack_nsf_wide(self, lu=lu_np, direction=direction)
-            cache = caches[slot] = (key, self._upload_pack(packed, inputs.device, lad))
-        return cache[1]
+            return self._upload_pack(nsf_wide_pack.pack_nsf_wide(self, lu=lu_np, direction=direction), inputs.device, lad)
+
+        return _keys.pcached(self, "_wide_cache", tensors, (str(inputs.device),), build,
+                             sub=(id(lu), direction) if lu is not None else None)
 
     def _upload_pack(self, packed, device, last):
         """(blob, table) of a packer -> (device blob, device table, knot tables of the batch-shared spline, Hp, last); None stays."""
         if packed is None:
             return None
-        blob, table = packed
         u = self.unconditional_transform
         tabs = ops.nsf_wide_tables(u.unnormalized_widths.detach(), u.unnormalized_heights.detach(), u.unnormalized_derivatives.detach(),
                                    self.num_bins, self.tail_bound, self.min_bin_width, self.min_bin_height, self.min_derivative)
-        return torch.from_numpy(blob).to(device), torch.from_numpy(table).to(device), tabs, int(table[3]), last
+        return upload(packed, device) + (tabs, int(packed[1][3]), last)
 
     def _wide(self, inputs, packed, direction, ld, acc):
         blob, table, tabs, hp, lad = packed
@@ -380,20 +386,17 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         """Device copies of flows/nsf_ctx_pack.py's streams + the batch-shared spline's knot tables, rebuilt when a parameter
         changes (the context_layer parameters are part of the net's); None when the layer or the call is outside nf_nsf_wide_ctx's
         structure (then: the conditioner as eager modules + nf_rqs_coupling)."""
-        if not (self.use_fused and _config.nsf_context and inputs.dim() == 2 and inputs.dtype == torch.float32 and inputs.is_cuda
-                and torch.is_tensor(context) and context.dim() == 2 and context.dtype == torch.float32 and context.is_cuda
-                and context.shape[0] == inputs.shape[0]):
+        net = self.transform_net
+        if not (self._resnet_rows(inputs, _config.nsf_context) and torch.is_tensor(context) and _device_rows(context)
+                and context.shape[0] == inputs.shape[0] and net.context_features is not None
+                and context.shape[1] == net.context_features):
             return None
-        net, u = self.transform_net, self.unconditional_transform
-        if u is None or not isinstance(net, ResidualNet) or net.context_features is None or context.shape[1] != net.context_features:
-            return None
-        tensors = list(net.parameters()) + [u.unnormalized_widths, u.unnormalized_heights, u.unnormalized_derivatives]
-        key = _keys.pkey(tensors) + (str(inputs.device), net.training)
-        cache = self.__dict__.get("_ctx_cache")
-        if cache is None or cache[0] != key:
+
+        def build():
             packed = nsf_ctx_pack.pack_nsf_ctx(self)
-            cache = self.__dict__["_ctx_cache"] = (key, self._upload_pack(packed, inputs.device, None if packed is None else packed[1]))
-        return cache[1]
+            return self._upload_pack(packed, inputs.device, None if packed is None else packed[1])
+
+        return _keys.pcached(self, "_ctx_cache", self._pack_tensors(), (str(inputs.device), net.training), build)
 
     def _wide_ctx(self, inputs, context, packed, direction, ld, acc):
         blob, table, tabs, hp, table_host = packed
@@ -405,27 +408,23 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         """Device copies of flows/nsf_circ_pack.py's streams and per-feature table + the batch-shared spline's knot tables, rebuilt
         when a parameter changes; None when the layer or the call is outside nf_nsf_wide_ft's structure (then: library GEMMs +
         nf_rqs_coupling_ft)."""
-        if not (self.use_fused and _config.nsf_circular and context is None and isinstance(self.tails, list) and inputs.dim() == 2
-                and inputs.dtype == torch.float32 and inputs.is_cuda):
+        if context is not None or not isinstance(self.tails, list) or not self._resnet_rows(inputs, _config.nsf_circular):
             return None
-        net, u = self.transform_net, self.unconditional_transform
-        if u is None or not isinstance(net, ResidualNet):
-            return None
-        tensors = list(net.parameters()) + [u.unnormalized_widths, u.unnormalized_heights, u.unnormalized_derivatives]
-        tensors += [b for b in (self.tail_bound, u.tail_bound) if torch.is_tensor(b)]
-        key = _keys.pkey(tensors) + (str(inputs.device), net.training)
-        cache = self.__dict__.get("_circ_cache")
-        if cache is None or cache[0] != key:
+        u = self.unconditional_transform
+
+        def build():
             packed = nsf_circ_pack.pack_nsf_circ(self)
-            if packed is not None:
-                blob, table, ftable = (torch.from_numpy(a).to(inputs.device) for a in packed)
-                nI = len(self.identity_features)
-                tabs = ops.nsf_wide_tables_ft(u.unnormalized_widths.detach(), u.unnormalized_heights.detach(),
-                                              u.unnormalized_derivatives.detach(), ftable[1, :nI].view(torch.int32), ftable[2, :nI],
-                                              self.num_bins, self.min_bin_width, self.min_bin_height, self.min_derivative)
-                packed = (blob, table, ftable, tabs, int(packed[1][3]))
-            cache = self.__dict__["_circ_cache"] = (key, packed)
-        return cache[1]
+            if packed is None:
+                return None
+            blob, table, ftable = upload(packed, inputs.device)
+            nI = len(self.identity_features)
+            tabs = ops.nsf_wide_tables_ft(u.unnormalized_widths.detach(), u.unnormalized_heights.detach(),
+                                          u.unnormalized_derivatives.detach(), ftable[1, :nI].view(torch.int32), ftable[2, :nI],
+                                          self.num_bins, self.min_bin_width, self.min_bin_height, self.min_derivative)
+            return blob, table, ftable, tabs, int(packed[1][3])
+
+        tensors = self._pack_tensors() + [b for b in (self.tail_bound, u.tail_bound) if torch.is_tensor(b)]
+        return _keys.pcached(self, "_circ_cache", tensors, (str(inputs.device), self.transform_net.training), build)
 
     def _wide_ft(self, inputs, packed, direction, ld, acc):
         blob, table, ftable, tabs, hp = packed
@@ -609,19 +608,12 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
                                                        self.transform_features, self.num_bins, kw, wave)
             return outputs, fold_logdet(ld, acc, log_det)
         trans = inputs.index_select(1, self.transform_features)
-        ld_i = None
-        if not sample:
-            cond = self.transform_net(ident, context)
-            trans, ld_t = SplineFn.apply(trans, cond, None, None, None, self.num_bins, False, kw)
-            if u is not None:
-                ident, ld_i = SplineFn.apply(ident, None, u.unnormalized_widths, u.unnormalized_heights,
-                                             u.unnormalized_derivatives, self.num_bins, False, kw)
-        else:            # nsf/coupling.py:100-128
-            if u is not None:
-                ident, ld_i = SplineFn.apply(ident, None, u.unnormalized_widths, u.unnormalized_heights,
-                                             u.unnormalized_derivatives, self.num_bins, True, kw, wave)
-            cond = self.transform_net(ident, context)
-            trans, ld_t = SplineFn.apply(trans, cond, None, None, None, self.num_bins, True, kw, wave)
+        ld_i = None      # nsf/coupling.py:100-128
+        if u is not None:
+            ident, ld_i = SplineFn.apply(ident, None, u.unnormalized_widths, u.unnormalized_heights,
+                                         u.unnormalized_derivatives, self.num_bins, True, kw, wave)
+        cond = self.transform_net(ident, context)
+        trans, ld_t = SplineFn.apply(trans, cond, None, None, None, self.num_bins, True, kw, wave)
         log_det = ld_t if ld_i is None else ld_t + ld_i
         outputs = torch.empty_like(inputs)
         outputs = outputs.index_copy(1, self.identity_features, ident).index_copy(1, self.transform_features, trans)
@@ -632,7 +624,7 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         net = self.transform_net
         if not (isinstance(net, ResidualNet) and net.is_plain_relu()):
             return False
-        if context is not None or inputs.dim() != 2 or inputs.dtype != torch.float32 or not inputs.is_cuda:
+        if context is not None or not _device_rows(inputs):
             return False
         if self.tails != "linear" or self._per_feature or self.unconditional_transform is None:
             return False
@@ -717,43 +709,41 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
 
     def _fused_blob(self, lu=None):
         net, u = self.transform_net, self.unconditional_transform
-        tensors = [net.initial_layer.weight, net.initial_layer.bias]
+        tensors = [net.initial_layer.weight, net.initial_layer.bias]        # (spelled out: `build` indexes this list by position)
         for b in net.blocks:
-            for lin in b.linear_layers:
-                tensors += [lin.weight, lin.bias]
+            for l in b.linear_layers:
+                tensors += [l.weight, l.bias]
         tensors += [net.final_layer.weight, net.final_layer.bias, u.unnormalized_widths, u.unnormalized_heights,
                     u.unnormalized_derivatives]
-        key = _keys.pkey(tensors)
+        lu_t, lin = [], None
         if lu is not None:
             lin = lu.linear
-            lu_t = [lu.permutation._permutation, lin.lower_entries, lin.upper_entries, lin.unconstrained_upper_diag,
-                    lin.bias]
-            key = key + _keys.pkey(lu_t) + (lin.eps,)
-        if self._fused_cache is None or self._fused_cache[0] != key:
-            d = [t.detach() for t in tensors]
+            lu_t = [lu.permutation._permutation, lin.lower_entries, lin.upper_entries, lin.unconstrained_upper_diag, lin.bias]
+
+        def build():
+            d, lt = [t.detach() for t in tensors], [t.detach() for t in lu_t]
             nb = len(net.blocks)
             if self._fused_padded():
-                d, lu_pad = self._padded_tensors(d, None if lu is None else [t.detach() for t in lu_t], lin.eps if lu is not None else 0.0)
+                d, lu_pad = self._padded_tensors(d, lt if lu is not None else None, lin.eps if lu is not None else 0.0)
                 if lu is not None:
-                    lu_t = list(lu_pad)
+                    lt = list(lu_pad)
             wb = [d[2 + 2 * i] for i in range(2 * nb)]
             bb = [d[3 + 2 * i] for i in range(2 * nb)]
             o = 2 + 4 * nb
             blob = ops.rqs_fused_pack(d[0], d[1], wb, bb, d[o], d[o + 1], d[o + 2], d[o + 3], d[o + 4], self.num_bins,
                                       self.tail_bound, self.min_bin_width, self.min_bin_height, self.min_derivative)
             if lu is not None:
-                ops.rqs_fused_pack_lu(blob, nb, lu_t[0], lu_t[1].detach(), lu_t[2].detach(), lu_t[3].detach(),
-                                      lu_t[4].detach(), eps=lin.eps, K=self.num_bins)
-            self._fused_cache = (key, blob)
-        return self._fused_cache[1]
+                ops.rqs_fused_pack_lu(blob, nb, *lt, eps=lin.eps, K=self.num_bins)
+            return blob
+
+        return _keys.pcached(self, "_fused_cache", tensors + lu_t, (lin.eps,) if lu is not None else (), build)
 
     def _fused_x3_blob(self, lu):
-        """Split-bf16 blob of this layer (+ its LU), derived from the fp32 blob once per parameter version."""
+        """Split-bf16 blob of this layer (+ its LU), derived from the fp32 blob once per parameter version: the slot follows the
+        key OBJECT of `_fused_cache`."""
         blob = self._fused_blob(lu)
-        key = self._fused_cache[0]
-        if self._fused_x3_cache is None or self._fused_x3_cache[0] is not key:
-            self._fused_x3_cache = (key, ops.rqs_fused_x3_pack(blob, len(self.transform_net.blocks), lu is not None))
-        return self._fused_x3_cache[1]
+        return _keys.cached(self, "_fused_x3_cache", self.__dict__["_fused_cache"][0],
+                            lambda: ops.rqs_fused_x3_pack(blob, len(self.transform_net.blocks), lu is not None))
 
     def _fused(self, inputs, direction, ld=None, acc=None, lu=None):
         self._check(inputs)
@@ -764,8 +754,7 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
 
     def _fused_run(self, inputs, direction, ld=None, acc=None, lu=None):
         net = self.transform_net
-        from .. import config
-        if config.fused_gemm == "bf16x3" and self.num_bins == 8:      # the split-bf16 kernel is instantiated for 8 bins only
+        if _config.fused_gemm == "bf16x3" and self.num_bins == 8:      # the split-bf16 kernel is instantiated for 8 bins only
             return ops.rqs_fused_x3(inputs, self._fused_x3_blob(lu), self._fused_parity, FUSED_H,
                                     len(net.blocks), self.num_bins, direction, logdet=ld, acc=acc,
                                     tail_bound=self.tail_bound, min_bin_width=self.min_bin_width,

@@ -111,9 +111,7 @@ def clear_prefetched_packs(convnets):
 
 def _train_struct_for(module, build, device, skey=()):
     """The module's value-independent pack structure with device copies of its tables and gather indices (built once)."""
-    st = module.__dict__.get("_train_struct")
-    skey = (str(device),) + tuple(skey)             # (skey: what the structure itself depends on, e.g. MADE's mask buffers)
-    if st is None or st[0] != skey:
+    def on_device():
         struct = build()
         if struct is not None:
             bwd = struct["bwd"]
@@ -123,8 +121,11 @@ def _train_struct_for(module, build, device, skey=()):
             struct["table"] = torch.from_numpy(struct["table"]).to(device)
             struct["nfwd"] = int(struct["src"].size)             # one gather for both streams: [forward | backward]
             struct["src"] = torch.cat([torch.from_numpy(struct["src"]), bwd["src"].cpu()]).to(device)
-        st = module.__dict__["_train_struct"] = (skey, struct)
-    return st[1]
+        return struct
+
+    # (skey: what the structure itself depends on, e.g. MADE's mask buffers; callers test their mode-dependent eligibility BEFORE
+    # they come here, so a None verdict of theirs never replaces a cached structure)
+    return _keys.cached(module, "_train_struct", (str(device),) + tuple(skey), on_device)
 
 
 class ResidualNet(nn.Module):
@@ -248,14 +249,12 @@ class ResidualNet(nn.Module):
             return None
         if not all(p.is_cuda and p.device == inputs.device and p.is_contiguous() for p in params):
             return None
-        key = (str(inputs.device),) + tuple(tuple(p.shape) for p in params)
-        cached = self.__dict__.get("_ctx_train_struct")
-        if cached is None or cached[0] != key:
+        def build():
             st = ctx_train_pack.structure_for(self)
-            dev = inputs.device
-            cached = self.__dict__["_ctx_train_struct"] = (key, st, torch.from_numpy(st["src"]).to(dev),
-                                                           torch.from_numpy(st["table"]).to(dev), torch.from_numpy(st["jobs"]).to(dev))
-        _, st, src, table, jobs = cached
+            return (st,) + tuple(torch.from_numpy(st[k]).to(inputs.device) for k in ("src", "table", "jobs"))
+
+        st, src, table, jobs = _keys.cached(self, "_ctx_train_struct",
+                                            (str(inputs.device),) + tuple(tuple(p.shape) for p in params), build)
         from . import ops
         blob = ops.pack_gather([p.detach() for p in params], src)
         return blob, table, jobs, st
@@ -491,10 +490,7 @@ class ConvNet2d(nn.Module):
         if layout is None or (layout == ops.GLOW_CONV_WIDE and B * H * W < self.FUSED_WIDE_MIN_PIXELS):
             return None
         params = [c1.weight, c1.bias, c2.weight, c2.bias, c3.weight, c3.bias]
-        key = _keys.pkey(params)
-        cache = self.__dict__.setdefault("_gc_cache", {})
-        hit = cache.get(layout)
-        if hit is None or hit[0] != key:
+        def build():
             ws = [p_.detach() for p_ in params]
             if hid != 256:   # zero hidden channels stay zero through the bias-free LeakyReLU: pad up to the kernels' 256
                 w1, b1, w2, b2, w3, b3 = ws
@@ -509,8 +505,10 @@ class ConvNet2d(nn.Module):
                 W3 = w3.new_zeros(w3.shape[0], 256, 3, 3)
                 W3[:, :hid] = w3
                 ws = [W1, B1, W2, B2, W3, b3]
-            hit = cache[layout] = (key, ops.glow_convnet_pack(*ws, layout=layout))
-        return None if hit[1] is None else (hit[1], layout)
+            return ops.glow_convnet_pack(*ws, layout=layout)
+
+        pack = _keys.pcached(self, "_gc_cache", params, (), build, sub=layout)
+        return None if pack is None else (pack, layout)
 
     def forward_split(self, x):
         """(output without the last convolution's bias, that bias) for callers that fold the bias into their own kernel
@@ -567,7 +565,6 @@ class MaskedLinear(nn.Linear):
                                                    out_degrees_=out_degrees_)
         self.register_buffer("mask", mask)
         self.register_buffer("degrees", degrees)
-        self._masked_cache = None
 
     @classmethod
     def _get_mask_and_degrees(cls, in_degrees, out_features, autoregressive_features, random_mask, is_output,
@@ -593,10 +590,8 @@ class MaskedLinear(nn.Linear):
     def masked_weight(self):
         if torch.is_grad_enabled() and self.weight.requires_grad:
             return self.weight * self.mask
-        key = _keys.pkey((self.weight,)) + (self.mask.data_ptr(),)
-        if self._masked_cache is None or self._masked_cache[0] != key:
-            self._masked_cache = (key, (self.weight.detach() * self.mask).contiguous())
-        return self._masked_cache[1]
+        return _keys.pcached(self, "_masked_cache", (self.weight,), (self.mask.data_ptr(),),
+                             lambda: (self.weight.detach() * self.mask).contiguous())
 
     def forward(self, x):
         return F.linear(x, self.masked_weight(), self.bias)
@@ -710,12 +705,8 @@ class MADE(nn.Module):
         from . import config
         if not config.made_fused:
             return None
-        key = _keys.pkey(self.parameters()) + (str(device),)
-        caches = self.__dict__.setdefault("_fwd_pack_cache", {})
-        if not isinstance(caches, dict):
-            caches = self.__dict__["_fwd_pack_cache"] = {}
-        cache = caches.get(bool(spline))
-        if cache is None or cache[0] != key:
+        def build():
+            from . import ops
             from .flows import made_pack
             mult = self.final_layer.out_features // self.initial_layer.in_features
             if not spline and str(device) != "cpu":
@@ -724,17 +715,14 @@ class MADE(nn.Module):
                 plist = [t for l in self._linears() for t in (l.weight, l.bias)]
                 st = _train_struct_for(self, lambda: made_pack.made_train_structure(self, mult), device,
                                        skey=tuple((l.mask.data_ptr(), l.mask._version) for l in self._linears()))
-                packed = None
-                if st is not None:
-                    from . import ops
-                    packed = (ops.pack_gather(plist, st["src"][:st["nfwd"]]), st["table"], st["hp"], mult)
-            else:
-                packed = made_pack.pack_made_forward(self, mult, spline=bool(spline))
-                if packed is not None:
-                    blob, table = packed
-                    packed = (torch.from_numpy(blob).to(device), torch.from_numpy(table).to(device), int(table[3]), mult)
-            cache = caches[bool(spline)] = (key, packed)
-        return cache[1]
+                return None if st is None else (ops.pack_gather(plist, st["src"][:st["nfwd"]]), st["table"], st["hp"], mult)
+            packed = made_pack.pack_made_forward(self, mult, spline=bool(spline))
+            if packed is None:
+                return None
+            blob, table = packed
+            return torch.from_numpy(blob).to(device), torch.from_numpy(table).to(device), int(table[3]), mult
+
+        return _keys.pcached(self, "_fwd_pack_cache", self.parameters(), (str(device),), build, sub=bool(spline))
 
     def _linears(self):
         return [self.initial_layer] + [l for b in self.blocks for l in b.linear_layers] + [self.final_layer]
