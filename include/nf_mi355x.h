@@ -52,6 +52,9 @@ const char *nf_strerror(int code);
 int nf_mfma_clock_probe(void *out2_u64, void *sink_f32, int iters, nf_stream_t stream);
 /* Largest number of spline bins the compiled kernels accept. */
 int nf_max_bins(void);
+/* Workgroups of a persistent tile-engine launch (nf_made_forward*, nf_made_backward, nf_nsf_wide*, nf_resnet_ctx_*): grid = min(tiles,
+ * this) and every workgroup walks tile, tile + grid, ...: a workgroup starts a second tile beyond this many tiles' rows. */
+int nf_persistent_workgroups(void);
 
 /* ------------------------------------------------------------------------------------------------
  * Rational-quadratic spline, element-wise.
@@ -819,6 +822,9 @@ int nf_made_backward(const void *g_params, const void *bits, void *g_x, void *G,
  * spans two sample blocks like the 512-slot kernels; same bits as 64-row tiles):
  * on (1, default) / off (0), returns the previous setting.  A forward and its backward must run under the same setting. */
 int nf_config_made_tr128(int on);
+/* Rows per tile nf_made_forward_train / nf_made_backward run a batch of B rows on under the current setting: 128 or 64.  B <= 0: the
+ * 64-row tile of every other MADE entry point (nf_made_forward*, nf_made_forward_train_ft, nf_made_backward_t64). */
+int nf_made_tile_rows(int64_t B, int D, int hidden_padded);
 int64_t nf_made_wgrad_scratch_floats(int64_t B, int ntiles);
 /* Alignment: gp_pad, x_pad, G, save and part 16 bytes (NF_EINVAL otherwise: LDS-DMA operands); grads element type. */
 int nf_made_wgrad(const void *gp_pad, const void *x_pad, const void *G, const void *save, void *grads, const void *mask, void *part,

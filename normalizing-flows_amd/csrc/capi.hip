@@ -6,6 +6,8 @@ extern "C" const char *nf_version(void) { return "nf_mi355x 0.1.0 (gfx950)"; }
 
 extern "C" int nf_max_bins(void) { return NF_MAX_BINS; }
 
+extern "C" int nf_persistent_workgroups(void) { return nf::NF_PERSISTENT_WORKGROUPS; }
+
 extern "C" const char *nf_strerror(int code) {
     switch (code) {
         case NF_OK: return "ok";

@@ -386,6 +386,14 @@ static inline int grid_for(int64_t work_items, int per_block, int max_blocks = 2
     return (int)g;
 }
 
+// The persistent tile-engine kernels (made_fwd*, made_bwd, nsf_wide / _ctx / _circ, resnet_ctx_train) launch at most this many
+// workgroups -- one per CU -- and each walks `for (tile = blockIdx.x; tile < ntiles; tile += gridDim.x)`: a workgroup starts a second
+// tile only when the batch exceeds NF_PERSISTENT_WORKGROUPS x tile rows.  Exported as nf_persistent_workgroups() (capi.hip).
+constexpr int NF_PERSISTENT_WORKGROUPS = 256;
+static inline int persistent_grid(int64_t ntiles) {
+    return (int)(ntiles < NF_PERSISTENT_WORKGROUPS ? ntiles : NF_PERSISTENT_WORKGROUPS);
+}
+
 // Dynamic LDS above 64 KB needs a per-kernel opt-in.  hipFuncSetAttribute is a slow, synchronising host call (measured
 // in milliseconds when it lands between launches), so each launch site remembers, per device, the largest size it has
 // opted in (the attribute belongs to the kernel image of the CURRENT device).

@@ -193,7 +193,7 @@ template <int NSB, int TR = MF_ROWS>
 static int made_bwd_launch(const void *gp, const void *bits, void *gx, void *G, const void *blob, const int32_t *table, int64_t B,
                            hipStream_t st, int dp) {
     const int64_t ntiles = (B + TR - 1) / TR;
-    const int grid = (int)(ntiles < 256 ? ntiles : 256);
+    const int grid = persistent_grid(ntiles);
     const size_t lds = sizeof(float) * ((size_t)8 * NSB * 4 * 8 * TR + (dp > 128 ? 2 * MF_XFLOATS : MF_XFLOATS));
     static LdsOptIn opted;
     if (opt_in_lds(reinterpret_cast<const void *>(&made_bwd_kernel<NSB, TR>), lds, opted) != NF_OK) return NF_ENOTSUP;

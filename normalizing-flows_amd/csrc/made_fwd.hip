@@ -46,7 +46,7 @@ template <int NSB, int EPI, int TR = MF_ROWS>
 static int made_fwd_launch(const void *x, void *y, void *logdet, const void *blob, const int32_t *table, int64_t B, int acc, hipStream_t st,
                            const RqsParams<float> &p = RqsParams<float>(), void *save = nullptr, void *bits = nullptr, int table_dp = 128) {
     const int64_t ntiles = (B + TR - 1) / TR;
-    const int grid = (int)(ntiles < 256 ? ntiles : 256);        // persistent: one workgroup per CU (160 KB of LDS at Hp = 512)
+    const int grid = persistent_grid(ntiles);        // persistent: one workgroup per CU (160 KB of LDS at Hp = 512)
     const int xfloats = table_dp > 128 ? 2 * MF_XFLOATS : MF_XFLOATS;       // x tile: 64 rows x Dp (<= 256 next to 256 hidden slots)
     const size_t lds = sizeof(float) * ((size_t)8 * NSB * 4 * 8 * TR + xfloats);       // (TR = 128: 128 rows x Dp <= 64 = the same 32 KB)
     static LdsOptIn opted;
@@ -120,6 +120,12 @@ extern "C" int nf_config_made_tr128(int on) {
     const int prev = nf::mf_tr128_switch();
     nf::mf_tr128_switch() = on ? 1 : 0;
     return prev;
+}
+
+// Rows per tile of nf_made_forward_train / nf_made_backward at this batch under the current setting (mf_tr128 decides for both); every
+// other MADE entry point runs MF_ROWS-row tiles, which is also the answer for B <= 0.
+extern "C" int nf_made_tile_rows(int64_t B, int D, int hidden_padded) {
+    return nf::mf_tr128(B, hidden_padded, (D + 31) / 32 * 32) ? 128 : nf::MF_ROWS;
 }
 
 // MADE.forward under autograd: nf_made_forward + the operands of nf_made_backward / nf_made_wgrad (csrc/made_bwd.hip).  Bp = B rounded

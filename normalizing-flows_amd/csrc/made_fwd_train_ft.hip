@@ -25,7 +25,7 @@ template <int NSB>
 static int made_fwd_train_ft_launch(const void *x, void *params, void *x_pos, const void *blob, const int32_t *table, int64_t B, void *save,
                                     void *bits, void *x_pad, hipStream_t st) {
     const int64_t ntiles = (B + MF_ROWS - 1) / MF_ROWS;
-    const int grid = (int)(ntiles < 256 ? ntiles : 256);        // persistent: one workgroup per CU
+    const int grid = persistent_grid(ntiles);        // persistent: one workgroup per CU
     const size_t lds = sizeof(float) * ((size_t)8 * NSB * 4 * 8 * MF_ROWS + MF_XFLOATS);
     static LdsOptIn opted;
     if (opt_in_lds(reinterpret_cast<const void *>(&made_fwd_train_ft_kernel<NSB>), lds, opted) != NF_OK) return NF_ENOTSUP;

@@ -29,7 +29,8 @@ inline bool mf_tr128(int64_t B, int hidden_padded, int dp) {
     // The kernels are persistent over min(tiles, 256) workgroups: a launch lasts ceil(tiles / 256) rounds, a 128-row tile about 15/8 of
     // a 64-row tile (measured at 65 536 rows: -6.5 %).  128-row tiles only where the rounds come out shorter -- 32 768 rows: 1 round
     // against 2, 65 536: 2 against 4; NOT 49 152: 2 long rounds against 3 short ones.
-    const int64_t r128 = (B / 128 + 255) / 256, r64 = (B / 64 + 255) / 256;
+    constexpr int64_t WG = NF_PERSISTENT_WORKGROUPS;
+    const int64_t r128 = (B / 128 + WG - 1) / WG, r64 = (B / 64 + WG - 1) / WG;
     return 15 * r128 < 8 * r64;
 }
 

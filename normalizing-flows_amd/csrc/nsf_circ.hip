@@ -173,7 +173,7 @@ template <int NHI, int NS, int DIR, int TR, int KB>
 static int nsf_circ_launch(const void *x, void *y, void *logdet, const void *blob, const int32_t *table, const void *ftable,
                            const void *tabs, int64_t B, int Hp, int acc, const RqsParams<float> &p, hipStream_t st) {
     const int64_t ntiles = (B + TR - 1) / TR;
-    const int grid = (int)(ntiles < 256 ? ntiles : 256);
+    const int grid = persistent_grid(ntiles);
     const size_t act_floats = (size_t)(Hp / 8) * 8 * TR;
     const size_t lds = sizeof(float) * (act_floats + (size_t)16 * 8 * TR + 8 * NSF_FT_STRIDE);
     static LdsOptIn opted;

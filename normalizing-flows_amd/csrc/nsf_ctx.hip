@@ -118,7 +118,7 @@ template <int NHI, int NS, int DIR, int TR, int KB>
 static int nsf_ctx_launch(const void *x, const void *ctx, void *y, void *logdet, const void *blob, const int32_t *table, const void *tabs,
                           int64_t B, int64_t ldc, int C, int PC, int Dp, int Hp, int acc, const RqsParams<float> &p, hipStream_t st) {
     const int64_t ntiles = (B + TR - 1) / TR;
-    const int grid = (int)(ntiles < 256 ? ntiles : 256);
+    const int grid = persistent_grid(ntiles);
     const size_t act_floats = (size_t)(Hp / 8) * 8 * TR;
     const size_t lds = sizeof(float) * (act_floats + (size_t)16 * 8 * TR);      // x tile: 128 positions (Dp + PC <= 128)
     static LdsOptIn opted;

@@ -475,7 +475,7 @@ static size_t rc_fwd_lds(int Kin, int Hp) { return sizeof(float) * (size_t)RC_RO
 static size_t rc_bwd_lds(int Hp) { return sizeof(float) * (size_t)RC_ROWS * 2 * ((Hp > 128 ? Hp : 128) + 4); }
 static int rc_grid(int64_t Bp) {
     const int64_t nt = Bp / RC_ROWS;
-    return (int)(nt < 256 ? nt : 256);        // persistent: one workgroup per CU
+    return persistent_grid(nt);        // persistent: one workgroup per CU
 }
 
 }  // namespace nf

@@ -152,3 +152,133 @@ def emulate_forward_spline(blob, table, x):
         assert np.array_equal(blob[pos[w]:pos[w] + RING * 256], np.resize(blob[start[w]:pos[w]], RING * 256)), w
         assert pos[w] + RING * 256 == (int(table[16 + w + 1]) if w < 7 else total)
     return prm[:, :D]
+
+
+# ---- the register weight ring over two tiles of one persistent workgroup (csrc/mlp_tile.hpp MfRing) ---------------------------------
+class RingWalk:
+    """One wave's MfRing on stream-entry INDICES (an entry = 256 floats: one 16-byte load per lane), exactly as mlp_tile.hpp moves it:
+    mf_ring_start requests entries 0..7 once; every consumed entry is re-requested 8 entries ahead of the item's own position
+    (`ap + e + 8`); items with an even number of 4-entry groups swap the ring halves; the tile loop only resets `ap` -- nothing is
+    reloaded between tiles.  Every value the kernel multiplies with is checked to BE the stream entry the schedule means (by index, or --
+    behind the wrap -- by content), and no request may leave the wave's stream."""
+
+    def __init__(self, blob, start, end):
+        assert (end - start) % 256 == 0 and 0 <= start < end <= blob.size
+        self.e = blob[start:end].reshape(-1, 256)
+        self.a = list(range(8))                              # mf_ring_start
+        assert len(self.e) >= 8
+        self.ap, self.last, self.consumed = 0, 7, 0
+
+    def _take(self, idx, e):                                 # mf_take / the bias and A reads of mf_item, mf_group
+        held, want = self.a[idx], self.ap + e
+        assert held == want or np.array_equal(self.e[held], self.e[want]), (
+            "ring register %d holds stream entry %d where the item reads entry %d" % (idx, held, want))
+        nxt = self.ap + e + 8
+        assert nxt < len(self.e), "request of entry %d behind the wave's stream of %d entries" % (nxt, len(self.e))
+        self.a[idx] = nxt
+        self.last = max(self.last, nxt)
+        self.consumed += 1
+
+    def _swap(self):
+        self.a = self.a[4:] + self.a[:4]
+
+    def item(self, nkg):                                     # mf_item: 4 bias entries + nkg A entries
+        assert nkg % 4 == 0
+        for q in range(4):
+            self._take(q, q)
+        kg = 0
+        while kg + 8 <= nkg:
+            for j in range(4):
+                self._take(4 + j, 4 + kg + j)
+            for j in range(4):
+                self._take(j, 8 + kg + j)
+            kg += 8
+        if kg < nkg:
+            for j in range(4):
+                self._take(4 + j, 4 + kg + j)
+        else:
+            self._swap()
+        self.ap += 4 + nkg
+
+    def final_item(self, nkg):                               # mf_final_item: 12 bias entries + 3 nkg A entries, compile-time phases
+        assert nkg % 4 == 0
+        for e in range(12):
+            self._take(e & 7, e)
+        kg = 0
+        while kg + 8 <= nkg:
+            for k in range(8):
+                for r3 in range(3):
+                    self._take((4 + 3 * k + r3) & 7, 12 + 3 * kg + 3 * k + r3)
+            kg += 8
+        if kg < nkg:
+            for k in range(4):
+                for r3 in range(3):
+                    self._take((4 + 3 * k + r3) & 7, 12 + 3 * kg + 3 * k + r3)
+        else:
+            self._swap()
+        self.ap += 12 + 3 * nkg
+
+    def next_tile(self):                                     # `ring.ap = stream + lane * 4` at the top of the persistent loop
+        """The ring must hold stream entries 0..7 (the packer's wrap copy behind the stream); returns the entries one tile consumed."""
+        n = self.ap
+        assert self.a == list(range(n, n + 8)), ("ring phase at the end of a tile", self.a, n)
+        for j in range(8):
+            assert np.array_equal(self.e[self.a[j]], self.e[j]), "ring register %d does not hold stream entry %d at the start of the next tile" % (j, j)
+        assert len(self.e) == n + 8, "the stream is %d entries, a tile consumes %d (+ 8 of the wrap)" % (len(self.e), n)
+        self.ap = 0
+        return n
+
+
+def two_tile_ring_walk(blob, table, entry=2):
+    """Two tiles of a persistent workgroup of made_fwd_kernel / made_fwd_ft_kernel / made_fwd_train*_kernel over every wave's stream:
+    hidden items through mf_item, the final items through mf_item (`entry` = 2: [nkg, rb | feature]; nf_made_forward, _ft, _train) or
+    mf_final_item (spline groups, hdr[11] = 1); entries with a negative id are skipped and consume nothing.  Returns the number of
+    4-entry groups each wave consumes per tile."""
+    NB, nitems = int(table[5]), int(table[10])
+    groups_final = int(table[11]) == 1
+    nh = 2 * (1 + 2 * NB)
+    tab = table[HDR:HDR + 8 * nitems * entry].reshape(8, nitems, entry)
+    total = int(table[9])                                    # (a training pack's periodic feed follows the streams)
+    assert total <= blob.size
+    out = []
+    for w in range(8):
+        ring = RingWalk(blob, int(table[16 + w]), int(table[16 + w + 1]) if w < 7 else total)
+        per_tile = []
+        for tile in range(2):
+            for i in range(nitems):
+                nkg, ident = int(tab[w, i, 0]), int(tab[w, i, 1])
+                if ident < 0:
+                    assert nkg == 0
+                    continue
+                if i >= nh and groups_final:
+                    ring.final_item(nkg)
+                else:
+                    ring.item(nkg)
+            per_tile.append(ring.next_tile())
+        assert per_tile[0] == per_tile[1] and per_tile[0] % 4 == 0 and ring.last < len(ring.e)
+        out.append(per_tile[0] // 4)
+    return out
+
+
+def two_tile_ring_walk_backward(blob, table):
+    """two_tile_ring_walk for made_bwd_kernel (flows/made_pack._pack_backward_from: entries [nkg, rb, kg0, -]): the 2 NC chunk items of
+    Wf^T and the 4 NB block items always run; only a round of the last product W0^T skips (rb < 0) and consumes nothing."""
+    NB, NC, nitems, total = int(table[5]), int(table[7]), int(table[10]), int(table[9])
+    tab = table[HDR:HDR + 8 * nitems * 4].reshape(8, nitems, 4)
+    nh = 2 * NC + 4 * NB
+    assert total <= blob.size and nitems == nh + max(int(table[8]), 1)
+    out = []
+    for w in range(8):
+        ring = RingWalk(blob, int(table[16 + w]), int(table[16 + w + 1]) if w < 7 else total)
+        per_tile = []
+        for tile in range(2):
+            for i in range(nitems):
+                nkg, rb = int(tab[w, i, 0]), int(tab[w, i, 1])
+                if rb < 0:                                   # (also the plain-MLP mode's absent second linear)
+                    assert nkg == 0 and (i >= nh or int(table[13]))
+                    continue
+                ring.item(nkg)
+            per_tile.append(ring.next_tile())
+        assert per_tile[0] == per_tile[1] and per_tile[0] % 4 == 0 and ring.last < len(ring.e)
+        out.append(per_tile[0] // 4)
+    return out

@@ -106,3 +106,14 @@ def emulate_forward_ft(blob, table, ftable, x, element):
         for f in range(D):
             y[row0:row0 + nrows, col[f]] = yt[:nrows, f]
     return y, ld
+
+
+def two_tile_ring_walk(blob, table):
+    """Two tiles of a persistent workgroup of made_fwd_ft_kernel over every wave's stream (made_fwd_emulator.RingWalk = mlp_tile.hpp's
+    MfRing on entry indices): 2 (1 + 2 NB) hidden items, then nfi final items [nkg, feature], all through mf_item -- four bias entries +
+    nkg A entries each; `if (f < 0) continue;` consumes nothing.  At the start of the second tile the ring must hold stream entries
+    0..7 (it is not reloaded) and no request may have left the wave's stream.  Returns the number of 4-entry groups each wave consumes
+    per tile."""
+    from made_fwd_emulator import two_tile_ring_walk as walk
+    assert int(table[11]) == 2
+    return walk(blob, table)

@@ -69,3 +69,35 @@ def emulate_layer(oracle, blob, table, ftable, uncond, x, direction, min_derivat
     out[:, par_i::2] = tile[:, :nI]
     out[:, par_t::2] = tile[:, PI:PI + nT]
     return out, ld, prm
+
+
+def two_tile_ring_walk(blob, table):
+    """Two tiles of a persistent workgroup of nsf_circ_kernel over every wave's stream (made_fwd_emulator.RingWalk = mlp_tile.hpp's
+    MfRing on entry indices): (1 + 2 NB) nhi hidden items through mf_item, nfi final items [nkg, group, sample block] through
+    mf_final_item with its compile-time ring phases; an entry with group < 0 is skipped and consumes nothing.  At the start of the
+    second tile the ring must hold stream entries 0..7 and no request may have left the wave's stream.  Returns the number of 4-entry
+    groups each wave consumes per tile."""
+    from made_fwd_emulator import RingWalk
+    HDR = 32
+    NB, nfi, total, nhi, has_lu = int(table[4]), int(table[10]), int(table[11]), int(table[12]), int(table[13])
+    assert has_lu == 0 and total == blob.size
+    nh = (1 + 2 * NB) * nhi
+    tab = table[HDR:HDR + 8 * (nh + nfi) * 3].reshape(8, nh + nfi, 3)
+    out = []
+    for w in range(8):
+        ring = RingWalk(blob, int(table[16 + w]), int(table[16 + w + 1]) if w < 7 else total)
+        per_tile = []
+        for tile in range(2):
+            for i in range(nh + nfi):
+                nkg, ident = int(tab[w, i, 0]), int(tab[w, i, 1])
+                if i < nh:
+                    assert ident >= 0
+                    ring.item(nkg)
+                elif ident >= 0:
+                    ring.final_item(nkg)
+                else:
+                    assert nkg == 0
+            per_tile.append(ring.next_tile())
+        assert per_tile[0] == per_tile[1] and per_tile[0] % 4 == 0 and ring.last < len(ring.e)
+        out.append(per_tile[0] // 4)
+    return out

@@ -30,6 +30,7 @@ def test_library_loads_and_exports_every_declared_symbol(nfa):
     assert not missing, missing
     assert b"gfx950" in lib.nf_version()
     assert lib.nf_max_bins() >= 16
+    assert lib.nf_persistent_workgroups() == 256       # one workgroup per CU (csrc/common.hpp NF_PERSISTENT_WORKGROUPS)
     assert lib.nf_strerror(-22) == b"invalid argument"
 
 
@@ -1404,6 +1405,51 @@ def test_made_forward_pack_matches_dense_made(D, H, NB, mult):
         assert work_fraction(table) < 0.56          # BASELINE configs[4]: 54 % of the dense MFMA work ...
         wpw = work_per_wave(table)
         assert wpw.max() == wpw.min()               # ... and every wave of the workgroup gets the same share of it
+
+
+def test_weight_ring_over_two_tiles_of_the_made_kernels(nfa):
+    """made_fwd_kernel, made_fwd_train_ft's kernel and made_bwd_kernel load their register ring once per launch and only reset `ap`
+    between tiles: every wave's stream of the shapes tests/test_gpu_tile_rounds.py runs past 256 tiles walked twice
+    (tests/made_fwd_emulator.RingWalk = mlp_tile.hpp's MfRing on entry indices: four bias entries + nkg A entries per mf_item, twelve +
+    3 nkg per mf_final_item of the spline groups, absent entries consume nothing, every entry re-requested 8 ahead).  Each multiplied
+    value is the stream entry the schedule means, the ring holds entries 0..7 again at the start of the second tile, no request leaves
+    the wave's stream; both parities of the number of 4-entry groups per wave occur, and a wrap copy of zeros is noticed."""
+    from normflows_amd.flows import made_pack
+    from made_fwd_emulator import two_tile_ring_walk, two_tile_ring_walk_backward
+    F = nfa.flows
+    torch.manual_seed(7)
+    packs = {}
+    for D, H in ((33, 96), (128, 512)):                       # nf_made_forward_spline: linear-tails AR-NSF density
+        made = F.AutoregressiveRationalQuadraticSpline(D, 2, H, num_bins=8, tail_bound=3, init_identity=False).mprqat.autoregressive_net
+        packs["spline d%d" % D] = made_pack.pack_made_forward(made, 23, spline=True)
+    made = F.AutoregressiveRationalQuadraticSpline(32, 2, 64, num_bins=8, tail_bound=3, init_identity=False).mprqat.autoregressive_net
+    sl = made_pack._slot_layers(made, 23)                     # MadeFn: nf_made_forward_train / nf_made_backward, 23 rows per feature
+    packs["train d32"], bwd = made_pack._pack_forward_from(sl), {"train d32": made_pack._pack_backward_from(sl)}
+    for name, t in (("ft d33 h300", F.CircularAutoregressiveRationalQuadraticSpline(33, 2, 300, ind_circ=[0, 7, 32], num_bins=8, tail_bound=3.0,
+                                                                                      permute_mask=True, init_identity=False).mprqat),
+                    ("ft d24 h40", F.CircularAutoregressiveRationalQuadraticSpline(24, 2, 40, ind_circ=[2, 9, 13, 23], num_bins=8, tail_bound=3.0,
+                                                                                     permute_mask=True, init_identity=False).mprqat)):
+        sl = made_pack._slot_layers(t.autoregressive_net, t._output_dim_multiplier(), ft=True)      # MadeFtFn: the degree-order pack
+        packs[name], bwd[name] = made_pack._pack_forward_from(sl), made_pack._pack_backward_from(sl)
+    net = F.CircularCoupledRationalQuadraticSpline(64, 2, 256, ind_circ=list(range(0, 64, 3)), num_bins=8, tail_bound=3.0,
+                                                   init_identity=False).prqct.transform_net
+    sl = made_pack._dense_layers(net, preprocessing=True)      # ResNetFtFn: the dense pack
+    packs["resnet d64 h256"], bwd["resnet d64 h256"] = made_pack._pack_forward_from(sl), made_pack._pack_backward_from(sl)
+    parities = {}
+    for name, pk in packs.items():
+        assert pk is not None, name
+        for g in two_tile_ring_walk(pk[0], pk[1]):
+            parities.setdefault(g % 2, name)
+    for name, pk in bwd.items():
+        for g in two_tile_ring_walk_backward(pk["blob"], pk["table"]):
+            parities.setdefault(g % 2, name + " backward")
+    print("4-entry groups per wave: odd in %s, even in %s" % (parities.get(1), parities.get(0)))
+    assert set(parities) == {0, 1}, parities
+    for blob, table in (packs["spline d33"], packs["train d32"]):
+        blob = blob.copy()
+        blob[int(table[17]) - 8 * 256:int(table[17])] = 0.0
+        with pytest.raises(AssertionError):
+            two_tile_ring_walk(blob, table)
 
 
 @pytest.mark.parametrize("D,H,NB,mult,B", [(128, 512, 2, 2, 3), (20, 40, 2, 2, 7), (6, 16, 2, 23, 7), (33, 300, 1, 3, 5), (5, 7, 3, 2, 4)])

@@ -188,6 +188,54 @@ def test_full_block_k11_scalar_linear_schedule(nfa):
     assert z[2, 1] == 9.0
 
 
+def _cpu_case(nfa, monkeypatch, case):
+    """tests/test_gpu_made_fwd_ft.build_case with the layer left on the CPU."""
+    import test_gpu_made_fwd_ft as gpu_cases
+    monkeypatch.setattr(gpu_cases, "DEV", "cpu")
+    return gpu_cases.build_case(nfa, case)
+
+
+RING_CASES = ["d2_h4_k4", "d33_h24_k6", "d128_h300_k10", "all_circular", "none_circular", "scalar_linear_permuted",
+              "scalar_linear_k11_permuted", "scalar_linear_tensor_bound", "scalar_circular_tensor_bound"]
+
+
+def test_weight_ring_over_two_tiles_of_a_persistent_workgroup(nfa, monkeypatch):
+    """The register ring is loaded once per launch and only `ap` is reset between tiles: walking every wave's stream of every GPU-test
+    shape twice (tests/made_fwd_ft_emulator.two_tile_ring_walk: four bias entries + nkg A entries per item, `f < 0` entries consume
+    nothing, every entry re-requested 8 ahead), each multiplied value is the stream entry the schedule means, the ring holds entries
+    0..7 again at the start of the second tile and no request leaves the wave's stream.  Both parities of the number of 4-entry groups
+    per wave occur (odd: the last item ends in ring half 0 without a swap; even: through the swap)."""
+    from made_fwd_ft_emulator import two_tile_ring_walk
+    parities = {}
+    for case in RING_CASES:
+        blob, table, _ = pack(_cpu_case(nfa, monkeypatch, case))
+        groups = two_tile_ring_walk(blob, table)
+        assert len(groups) == 8 and min(groups) >= 1
+        for g in groups:
+            parities.setdefault(g % 2, case)
+    print("4-entry groups per wave: odd in %s, even in %s" % (parities.get(1), parities.get(0)))
+    assert set(parities) == {0, 1}, parities
+
+
+@pytest.mark.parametrize("what", ["zero_wrap", "short_item", "skipped_item_with_entries"])
+def test_ring_walk_notices_a_stream_the_kernel_would_misread(nfa, monkeypatch, what):
+    """The walk fails on a wrap copy of zeros, on an item whose A entries are fewer than its table entry says, and on a skipped entry
+    (feature < 0) that still owns stream entries."""
+    from made_fwd_ft_emulator import two_tile_ring_walk
+    blob, table, _ = pack(_cpu_case(nfa, monkeypatch, "d33_h24_k6"))
+    blob, table = blob.copy(), table.copy()
+    nitems = int(table[10])
+    if what == "zero_wrap":
+        blob[int(table[17]) - 8 * 256:int(table[17])] = 0.0
+    elif what == "short_item":
+        table[32 + 2 * 2] += 4                                   # wave 0, third item: four k-groups more than its stream holds
+    else:
+        table[32 + 2 * (nitems - 1) + 1] = -1                    # wave 0's last feature item marked absent, its entries still there
+        table[32 + 2 * (nitems - 1)] = 0
+    with pytest.raises(AssertionError):
+        two_tile_ring_walk(blob, table)
+
+
 def test_packer_eligibility(nfa):
     from normflows_amd import nets
     from normflows_amd.flows import made_pack, maf_pack

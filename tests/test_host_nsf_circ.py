@@ -83,6 +83,31 @@ def test_feature_table_in_position_order(nfa):
     assert ft[FT_SCALE][2] == np.float32(np.pi) / np.float32(cw.TB_A[2])
 
 
+def test_weight_ring_over_two_tiles_of_a_persistent_workgroup(nfa):
+    """nsf_circ_kernel loads its register ring once per launch and only resets `ap` between tiles: every wave's stream of the seven
+    fixture layers (Hp 128 on 128-row tiles and Hp 256 on 64-row tiles; 4, 8 and 16 bins: 8 / 4 / 2 transform features per final
+    group) walked twice (tests/nsf_circ_emulator.two_tile_ring_walk: hidden items through mf_item, final groups through
+    mf_final_item's compile-time ring phases, `g < 0` entries consume nothing).  Each multiplied value is the stream entry the schedule
+    means, the ring holds entries 0..7 again at the start of the second tile, no request leaves the wave's stream; both parities of
+    the number of 4-entry groups per wave occur, and a wrap copy of zeros is noticed."""
+    from normflows_amd.flows import nsf_circ_pack
+    from nsf_circ_emulator import two_tile_ring_walk
+    parities = {}
+    for name in sorted(cw.LAYERS):
+        blob, table, _ = nsf_circ_pack.pack_nsf_circ(cw.layer(nfa, name).prqct)
+        groups = two_tile_ring_walk(blob, table)
+        assert len(groups) == 8 and min(groups) >= 1
+        for g in groups:
+            parities.setdefault(g % 2, name)
+    print("4-entry groups per wave: odd in layer %s, even in layer %s" % (parities.get(1), parities.get(0)))
+    assert set(parities) == {0, 1}, parities
+    blob, table, _ = nsf_circ_pack.pack_nsf_circ(cw.layer(nfa, "c").prqct)
+    blob = blob.copy()
+    blob[int(table[17]) - 8 * 256:int(table[17])] = 0.0
+    with pytest.raises(AssertionError):
+        two_tile_ring_walk(blob, table)
+
+
 def test_packer_rejections_keep_the_layerwise_path(nfa):
     """What nf_nsf_wide_ft does not cover is declined by the packer (None): the route then never enters the new branch.  That the five
     layers of circ_wide_cases.DECLINED still evaluate needs a device (the package has no CPU path):
