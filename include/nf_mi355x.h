@@ -648,6 +648,31 @@ int nf_diag_gaussian_log_prob_rows(const void *z, const void *loc_rows, const vo
 int nf_realnvp_chain(const void *z, void *y, void *logdet, const void *blob, int64_t B, int d, int hmax, int direction,
                      int acc, nf_stream_t stream);
 
+/* The training twin of nf_realnvp_chain (csrc/realnvp_train.hip): the same run of records, the same blob layout, under
+ * autograd.  Replaces what PyTorch autograd records and replays over normflows/flows/affine/coupling.py:38-54 (AffineConstFlow /
+ * ActNorm), :209-229 (MaskedAffineFlow) and nets/mlp.py:5-58 (one GEMM + one LeakyReLU launch per Linear, forward and backward).
+ *   act_floats = max over the run's MLPs of sum(sizes[:-1]) (the inputs of every Linear of one MLP), at least d; hmax >= d.
+ *   nf_realnvp_train_rows: rows (lanes) per workgroup the launches use -- 256, 128 or 64, the largest for which
+ *     (act_floats + 2 hmax) (rows + 1) floats of LDS fit in 160 KB; NF_ENOTSUP when 64 rows do not fit or hmax > 64.
+ *   nf_realnvp_train_scratch_floats: size of `slabs` = workgroups x blob_floats.  The grid is min(row tiles,
+ *     nf_persistent_workgroups()), lowered so that the slabs stay within 2^24 floats (64 MiB).
+ *   nf_realnvp_chain_train_fwd: y (B, d), logdet (B) WRITTEN (not accumulated), save (nrec, B, d): save[q, r, :] = the input of the
+ *     q-th executed record for row r.  Non-finite s / t -> NaN as in nf_realnvp_chain.
+ *   nf_realnvp_chain_bwd: gy (B, d) / gld (B) cotangents of y / logdet (NULL = zeros); gz (B, d) or NULL (not wanted); wmask bit
+ *     2 r: the s-net (ActNorm: s) of record r needs its gradient, bit 2 r + 1: the t-net (t) -- at most 32 records; grads
+ *     (blob_floats) = the parameter gradients in the LAYOUT OF THE BLOB (positions of records without a set bit and of
+ *     non-parameters hold 0 or partial sums nobody reads: slice by the parameters' offsets).  Two launches (backward, fixed-order
+ *     reduction of the workgroups' slabs); one when wmask == 0.  No atomics: bit-identical from run to run.
+ *     LeakyReLU slopes must be >= 0 (the derivative is taken from the sign of the activation).
+ */
+int nf_realnvp_train_rows(int hmax, int act_floats);
+int64_t nf_realnvp_train_scratch_floats(int64_t B, int hmax, int act_floats, int64_t blob_floats);
+int nf_realnvp_chain_train_fwd(const void *z, void *y, void *logdet, void *save, const void *blob, int64_t B, int d, int hmax,
+                               int act_floats, int direction, nf_stream_t stream);
+int nf_realnvp_chain_bwd(const void *save, const void *gy, const void *gld, void *gz, const void *blob, void *slabs, void *grads,
+                         int64_t B, int d, int hmax, int act_floats, int64_t blob_floats, int direction, int64_t wmask,
+                         nf_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * MaskedAffineAutoregressive element-wise transform (MAF).  Replaces
  * normflows/flows/affine/autoregressive.py:98-128 (_elementwise_forward / _elementwise_inverse).

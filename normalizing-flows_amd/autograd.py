@@ -1407,3 +1407,33 @@ class MafAffineFn(torch.autograd.Function):
         x, params = ctx.saved_tensors
         gx, gp = ops.maf_affine_bwd(x, params, gy, gld, ctx.direction)
         return gx, gp, None
+
+
+class RealNVPChainFn(torch.autograd.Function):
+    """A run of MaskedAffineFlow(MLP s, MLP t) / ActNorm / AffineConstFlow layers (coupling.py:38-54, :209-229, nets/mlp.py:5-58)
+    as one forward and one backward launch (csrc/realnvp_train.hip).  `st` = flows/realnvp_pack.structure on the device,
+    `tensors` = realnvp_pack.tensors(run): the blob is gathered from them as they are in THIS call.  Returns (y, per-row log-det).
+
+    The backward hands autograd one fresh tensor per parameter that requires grad -- views of the gradient blob this call reduced
+    into -- and autograd accumulates: no kernel ever writes a buffer that a p.grad aliases."""
+
+    @staticmethod
+    def forward(ctx, z, st, direction, *tensors):
+        blob = ops.pack_gather([st["static"]] + [t.detach() for t in tensors], st["src"])
+        y, ld, save = ops.realnvp_chain_train_fwd(z, blob, st["nrec"], st["d"], st["hmax"], st["act"], direction)
+        ctx.save_for_backward(save, blob)
+        ctx.st, ctx.direction = st, direction
+        ctx.set_materialize_grads(False)
+        return y, ld
+
+    @staticmethod
+    @once_differentiable          # (the backward is a set of kernels, not a differentiable graph: double backward raises)
+    def backward(ctx, gy, gld):
+        from .flows import realnvp_pack
+        save, blob = ctx.saved_tensors
+        st, needs = ctx.st, ctx.needs_input_grad[3:]
+        wmask = realnvp_pack.grad_mask(st, needs)
+        gz, grads = ops.realnvp_chain_bwd(save, gy, gld, blob, st["d"], st["hmax"], st["act"], ctx.direction, wmask,
+                                          ctx.needs_input_grad[0])
+        return (gz, None, None) + tuple(realnvp_pack.carve(st, grads, k) if need and st["sides"][k][1] is not None else None
+                                        for k, need in enumerate(needs))

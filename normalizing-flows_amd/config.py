@@ -384,6 +384,25 @@ def set_nsf_context_train(mode=True):
     nsf_context_train = bool(mode)
 
 
+# Runs of MaskedAffineFlow(MLP s, MLP t) / ActNorm / AffineConstFlow layers (the inference kernel nf_realnvp_chain's records) under
+# autograd as one forward and one backward launch (autograd.RealNVPChainFn, csrc/realnvp_train.hip: nf_realnvp_chain_train_fwd /
+# nf_realnvp_chain_bwd); False = layer by layer: library GEMMs + LeakyReLU launches for the MLPs, MaskedAffineFn / ActNormFn on top
+# (A/B runs, differential tests).  The Function is once-differentiable: inside higher_order_gradients() the route is not taken.
+realnvp_train = True
+# While a stream is being CAPTURED (torch.cuda.graph) the route is taken from this many rows on.  Replayed from a graph the
+# layer-by-layer route has no launch overhead left, and below this size its many small kernels finish sooner than the two long
+# ones (profiles/realnvp_train_bench.json: `capture_min_batch`, tools/realnvp_train_bench.py).  Eager steps take the route at every
+# batch size (2.4x faster or more at 1024 and at 65 536 rows).
+realnvp_train_capture_min_batch = 4096
+
+
+def set_realnvp_train(mode=True, capture_min_batch=None):
+    global realnvp_train, realnvp_train_capture_min_batch
+    realnvp_train = bool(mode)
+    if capture_min_batch is not None:
+        realnvp_train_capture_min_batch = int(capture_min_batch)
+
+
 # Debug mode of the element-wise spline API (utils.splines): after every call a check launch (nf_rqs_spline_check)
 # sets device-side flags and the shim reads them back -- a host synchronisation per call, which is why it is off by default -- and
 # raises what the reference raises: AssertionError for a negative discriminant in the inverse direction (utils/splines.py:181),

@@ -170,6 +170,52 @@ def _run_realnvp(run, z, inverse, ld, acc):
 _realnvp_cache = {}       # id(first flow of a run) -> (key, (blob, hmax)): owned by this module, not by a layer
 
 
+# ---- the same runs under autograd: one forward, one backward launch (csrc/realnvp_train.hip, autograd.RealNVPChainFn) ----
+def _realnvp_train_enabled():
+    """The switch of the training route: config.realnvp_train, and not inside config.higher_order_gradients() (the Function is
+    once-differentiable)."""
+    return bool(_config.realnvp_train) and not _config.torch_elementwise
+
+
+def _realnvp_train_record_ok(f, d):
+    """_realnvp_record_ok plus what the training kernels need: float32 tensors, LeakyReLU slopes >= 0 (the backward takes the
+    derivative from the sign of the activation) and one MLP's Linear inputs + two gradient columns of the widest layer the kernels
+    take (64) within the LDS budget at 64 lanes per workgroup (nf_realnvp_train_rows)."""
+    from . import ops
+    from .flows import realnvp_pack
+    from .flows.affine import MaskedAffineFlow
+    if d > 16 or not _realnvp_record_ok(f, d):
+        return False
+    if isinstance(f, MaskedAffineFlow):
+        if f.b.dtype != torch.float32:
+            return False
+        for net in (f.s, f.t):
+            if net is None:
+                continue
+            lin, slope = _plain_mlp(net)
+            if slope < 0.0 or any(l.weight.dtype != torch.float32 for l in lin):
+                return False
+            if ops.realnvp_rows(64, realnvp_pack.mlp_footprint(lin, d)[1]) == 0:
+                return False
+        return True
+    return f.s.dtype == torch.float32 and f.t.dtype == torch.float32
+
+
+def _run_realnvp_train(run, z, inverse, ld, acc):
+    from .autograd import RealNVPChainFn
+    from .flows import realnvp_pack
+    from .flows.affine import _fold_ld
+    d = z.shape[1]
+    st = _keys.cached(globals(), "_realnvp_train_struct", (realnvp_pack.signature(run, d), str(z.device)),
+                      lambda: realnvp_pack.to_device(realnvp_pack.structure(run, d), z.device), sub=id(run[0]))
+    y, log_det = RealNVPChainFn.apply(z.contiguous(), st, 1 if inverse else 0, *[t for t, _, _ in realnvp_pack.tensors(run)])
+    _fold_ld(ld, acc, log_det)
+    return y
+
+
+_realnvp_train_struct = {}     # id(first flow of a run) -> (structure signature, structure on the device): no parameter value in it
+
+
 class _frozen_parameters:
     """requires_grad switched off on every parameter of `module` for the `with` body and ALWAYS restored (a layer without a
     differentiable path raises mid-loop: the model must not stay frozen).  reverse_kld(score_fn=False), core.py:353-363."""
@@ -230,9 +276,30 @@ def _run_chain_impl(flows, z, inverse, ld, acc):
     rn_ok = (z.dim() == 2 and z.dtype == torch.float32 and z.is_cuda and z.shape[1] <= 16
              and not (torch.is_grad_enabled() and (z.requires_grad
                                                    or any(p.requires_grad for f_ in flows for p in f_.parameters()))))
+    rn_train = (z.dim() == 2 and z.dtype == torch.float32 and z.is_cuda and z.shape[1] <= 16 and torch.is_grad_enabled()
+                and _realnvp_train_enabled())
+    if rn_train:      # an ActNorm whose data-dependent initialisation is pending: this whole call goes layer by layer
+        from .flows.normalization import ActNorm
+        rn_train = all(f_.initialised() for f_ in flows if isinstance(f_, ActNorm))
+    if rn_train and z.shape[0] < _config.realnvp_train_capture_min_batch:
+        rn_train = not torch.cuda.is_current_stream_capturing()      # (replayed, small batches are faster layer by layer)
     while k < n:
         i = order[k]
         f = flows[i]
+        if rn_train and _realnvp_train_record_ok(f, z.shape[1]):
+            from .flows import realnvp_pack
+            from .flows.affine import MaskedAffineFlow
+            k2 = k
+            while k2 < n and k2 - k < realnvp_pack.MAX_RECORDS and _realnvp_train_record_ok(flows[order[k2]], z.shape[1]):
+                k2 += 1
+            run = [flows[q] for q in sorted(order[k:k2])]
+            # gradients are needed (the input's, or of a parameter of the run) and there is an MLP-conditioned layer to fuse
+            if (any(isinstance(f_, MaskedAffineFlow) for f_ in run) and z.shape[0] > 0
+                    and (z.requires_grad or any(p.requires_grad for f_ in run for p in f_.parameters()))):
+                z = flush(z)
+                z = _run_realnvp_train(run, z, inverse, ld, acc)
+                k = k2
+                continue
         if rn_ok and _realnvp_record_ok(f, z.shape[1]):
             k2 = k
             while k2 < n and _realnvp_record_ok(flows[order[k2]], z.shape[1]):

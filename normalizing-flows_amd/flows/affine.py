@@ -9,6 +9,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from .. import config as _config
 from .. import ops
 from ..autograd import ActNormFn, AffineCouplingFn, MaskedAffineFn, needs_grad
 from .base import Flow, fold_logdet, run_flow
@@ -96,6 +97,17 @@ class AffineConstFlow(Flow):
         return self._geometry(z), s.reshape(-1), t.reshape(-1)
 
     def _apply_kernel(self, z, inverse, ld=None, acc=None, want_scalar=True):
+        if _config.torch_elementwise and needs_grad(z, self.s, self.t):
+            # config.higher_order_gradients(): coupling.py:38-54 in torch ops, differentiable to any order (ActNormFn's backward is a
+            # kernel: first order only)
+            n = float(np.prod([z.shape[i] for i in self.batch_dims[1:]]))
+            if inverse:
+                y, log_det = (z - self.t) * torch.exp(-self.s), -n * torch.sum(self.s)
+            else:
+                y, log_det = z * torch.exp(self.s) + self.t, n * torch.sum(self.s)
+            if ld is None and want_scalar:
+                return y, log_det
+            return y, _fold_ld(ld, acc, log_det.expand(z.shape[0]))
         if needs_grad(z, self.s, self.t):   # training: HIP forward through ActNormFn, per-sample log-det
             zz, sv, tv = self._operands(z, False)
             y, log_det = ActNormFn.apply(zz.contiguous(), sv, tv, 1 if inverse else 0)
@@ -222,6 +234,19 @@ class MaskedAffineFlow(Flow):
         z_masked = self.b * z if need_net else None
         scale = self.s(z_masked) if self.s is not None else None
         trans = self.t(z_masked) if self.t is not None else None
+        if _config.torch_elementwise and needs_grad(z, scale, trans):
+            # config.higher_order_gradients(): coupling.py:209-229 in torch ops, differentiable to any order (MaskedAffineFn's backward
+            # is a kernel: first order only)
+            nan = torch.tensor(float("nan"), dtype=z.dtype, device=z.device)
+            sc = torch.zeros_like(z) if scale is None else torch.where(torch.isfinite(scale), scale, nan)
+            tr = torch.zeros_like(z) if trans is None else torch.where(torch.isfinite(trans), trans, nan)
+            zm = self.b * z
+            dims = list(range(1, self.b.dim()))
+            if inverse:
+                y, log_det = zm + (1 - self.b) * (z - tr) * torch.exp(-sc), -torch.sum((1 - self.b) * sc, dim=dims)
+            else:
+                y, log_det = zm + (1 - self.b) * (z * torch.exp(sc) + tr), torch.sum((1 - self.b) * sc, dim=dims)
+            return y, _fold_ld(ld, acc, log_det)
         if needs_grad(z, scale, trans):
             y, log_det = MaskedAffineFn.apply(z.contiguous(), self.b, scale, trans, 1 if inverse else 0)
             return y, _fold_ld(ld, acc, log_det)

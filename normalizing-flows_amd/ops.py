@@ -1768,3 +1768,40 @@ def realnvp_chain(z, blob, d, hmax, direction, logdet=None, acc=None):
     logdet, acc = _ld_buffer(logdet, acc, B, z)
     L.call("nf_realnvp_chain", ptr(z), ptr(y), ptr(logdet), ptr(blob), B, d, hmax, direction, acc, L.stream())
     return y, logdet
+
+
+def realnvp_rows(hmax, act):
+    """Rows per workgroup of the RealNVP training kernels for this LDS footprint (nf_realnvp_train_rows); 0 = does not fit."""
+    rows = L.query("nf_realnvp_train_rows", int(hmax), int(act))
+    if rows == L.ENOTSUP:
+        return 0
+    if rows < 0:
+        L.check(rows, "nf_realnvp_train_rows")
+    return rows
+
+
+def realnvp_chain_train_fwd(z, blob, nrec, d, hmax, act, direction):
+    """nf_realnvp_chain_train_fwd: (y, per-row log-det, save (nrec, B, d) = every executed record's input)."""
+    L.require_device(z, blob)
+    if z.dtype != torch.float32 or not z.is_contiguous():
+        raise NotImplementedError("realnvp_chain_train_fwd: contiguous float32 only")
+    B = z.shape[0]
+    y = torch.empty_like(z)
+    logdet = torch.empty(B, dtype=z.dtype, device=z.device)
+    save = torch.empty(nrec, B, d, dtype=z.dtype, device=z.device)
+    L.call("nf_realnvp_chain_train_fwd", ptr(z), ptr(y), ptr(logdet), ptr(save), ptr(blob), B, d, hmax, act, direction, L.stream())
+    return y, logdet, save
+
+
+def realnvp_chain_bwd(save, gy, gld, blob, d, hmax, act, direction, wmask, want_gz):
+    """nf_realnvp_chain_bwd: (gz or None, the parameter gradients in the blob's layout or None when wmask == 0)."""
+    L.require_device(save, gy, gld, blob)
+    B, nblob = save.shape[1], blob.numel()
+    gz = torch.empty(B, d, dtype=save.dtype, device=save.device) if want_gz else None
+    slabs = grads = None
+    if wmask:
+        slabs = torch.empty(L.size("nf_realnvp_train_scratch_floats", B, hmax, act, nblob), dtype=save.dtype, device=save.device)
+        grads = torch.empty(nblob, dtype=save.dtype, device=save.device)
+    L.call("nf_realnvp_chain_bwd", ptr(save), _cptr(gy), _cptr(gld), ptr(gz), ptr(blob), ptr(slabs), ptr(grads), B, d, hmax, act,
+           nblob, direction, wmask, L.stream())
+    return gz, grads
