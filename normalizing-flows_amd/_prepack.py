@@ -98,7 +98,14 @@ def _plan(flows, z, sig):
     from .flows.mixing import LULinearPermute
     from .flows.neural_spline import CoupledRationalQuadraticSpline
     groups, packed = {}, set()
+    # a module that is in the list more than once (shared weights) packs for itself at every use: its images are layer-owned, one
+    # token covers one use, and the second use's own pack would rewrite the blob the first use's pair backward still reads
+    seen, twice = set(), set()
     for f in flows:
+        (twice if id(f) in seen else seen).add(id(f))
+    for f in flows:
+        if id(f) in twice:
+            continue
         if isinstance(f, CoupledRationalQuadraticSpline):
             c = f.prqct
             if c._train_full_ok(z, None, False) and all(p.requires_grad for p in c.parameters()):

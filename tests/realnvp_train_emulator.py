@@ -1,5 +1,5 @@
 """The formulas of a RealNVP-style stack restated in plain torch (any device, any dtype; float64 on the CPU pins the fixtures):
-MaskedAffineFlow (coupling.py:209-229), AffineConstFlow / ActNorm once initialised (coupling.py:38-54), nets.MLP (mlp.py:5-58:
+MaskedAffineFlow (coupling.py:209-229), AffineConstFlow / ActNorm once initialised (coupling.py:38-54), Permute (mixing.py:9-54), nets.MLP (mlp.py:5-58:
 Linear + LeakyReLU).  Reads the tensors of the given flow modules and runs no method of theirs, so autograd differentiates
 exactly what is written here."""
 import torch
@@ -31,6 +31,12 @@ def chain(flows, x, inverse):
             else:
                 x = zm + (1 - f.b) * (x * torch.exp(s) + t)
                 ld = ld + ((1 - f.b) * s).sum(1)
+        elif hasattr(f, "mode"):            # Permute (mixing.py:9-54): data movement, log-det 0
+            if f.mode == "shuffle":
+                x = x[:, f.inv_perm if inverse else f.perm]
+            else:
+                cut = (x.shape[1] + 1) // 2 if inverse else x.shape[1] // 2
+                x = torch.cat([x[:, cut:], x[:, :cut]], dim=1)
         else:
             if inverse:
                 x = (x - f.t) * torch.exp(-f.s)

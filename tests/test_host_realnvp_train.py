@@ -191,3 +191,76 @@ def test_fixtures_equal_the_float64_restatement(nfa, name):
     for k in ("z_fwd", "ld_inv", "gx_inv"):
         assert np.abs(g[k] - g[k + "_f64"]).max() < 1e-3 * max(1.0, np.abs(g[k + "_f64"]).max()), k
     assert g["sd__flows__%d__data_dep_init_done" % (len(flows) - 1)] > 0
+
+
+# ---- the limit of 32 records ------------------------------------------------------------------------------------------------------
+def _records(nfa, n, d=2):
+    """n records alternating MaskedAffineFlow(MLP [d, 4, d] s and t) / ActNorm (initialised), every parameter random, on the CPU."""
+    g = torch.Generator().manual_seed(n)
+    b = torch.tensor([1.0, 0.0] * ((d + 1) // 2))[:d]
+    flows = []
+    for i in range(n):
+        if i % 2 == 0:
+            flows.append(nfa.flows.MaskedAffineFlow(b if i % 4 == 0 else 1 - b, nfa.nets.MLP([d, 4, d]), nfa.nets.MLP([d, 4, d], leaky=0.05)))
+        else:
+            flows.append(nfa.flows.ActNorm(d))
+            flows[-1].data_dep_init_done.fill_(1.0)
+    with torch.no_grad():
+        for f in flows:
+            for p in f.parameters():
+                p.copy_(0.3 * torch.randn(p.shape, generator=g))
+    return flows
+
+
+def test_structure_mask_and_slices_at_32_records(nfa):
+    """MAX_RECORDS records: the gather map still reproduces the host blob; bit 2 * 31 + 1 alone (the t of the last record, an ActNorm)
+    is the int64 -(1 << 63), all 64 bits are -1, bit 62 alone stays positive; the last record's tensors are the last slices of the blob."""
+    from normflows_amd import core
+    from normflows_amd.flows import realnvp_pack as rp
+    assert rp.MAX_RECORDS == 32
+    run = _records(nfa, 32)
+    st = rp.structure(run, 2)
+    tl = rp.tensors(run)
+    assert st["nrec"] == 32 and len(tl) == len(st["sides"]) == len(st["slices"])
+    blob = rp.gather_reference(st, [t for t, _, _ in tl])
+    ref, hmax = core._pack_realnvp(run, 2, "cpu")
+    assert torch.equal(blob, ref) and hmax == st["hmax"]
+    sides = st["sides"]
+    assert sides[-2:] == [(31, 0), (31, 1)] and {r for r, _ in sides} == set(range(32))
+    assert rp.grad_mask(st, [rs == (31, 1) for rs in sides]) == -(1 << 63)
+    assert rp.grad_mask(st, [rs == (31, 0) for rs in sides]) == 1 << 62
+    assert rp.grad_mask(st, [r == 31 for r, _ in sides]) == -(1 << 63) + (1 << 62)
+    assert rp.grad_mask(st, [True] * len(sides)) == -1                     # every record has an s side and a t side
+    assert rp.grad_mask(st, [r == 0 for r, _ in sides]) == 3
+    for m in (rp.grad_mask(st, [True] * len(sides)), rp.grad_mask(st, [rs == (31, 1) for rs in sides])):
+        assert ctypes.c_int64(m).value == m                                # representable as the C side's int64_t
+    # carve: the last record's s and t are the last 2 d floats of a gradient blob, in that order
+    grads = torch.arange(st["nblob"], dtype=torch.float32)
+    k = len(tl) - 2
+    assert torch.equal(rp.carve(st, grads, k).reshape(-1), grads[-4:-2]) and torch.equal(rp.carve(st, grads, k + 1).reshape(-1), grads[-2:])
+    assert rp.carve(st, grads, k).shape == run[31].s.shape and rp.carve(st, grads, k + 1).shape == run[31].t.shape
+    assert torch.equal(rp.carve(st, blob, k), run[31].s.detach()) and torch.equal(rp.carve(st, blob, k + 1), run[31].t.detach())
+    # ... and the first tensor with a gradient of the last MaskedAffineFlow (record 30) lies where its offset says
+    k30 = min(i for i, (r, s) in enumerate(sides) if r == 30 and s is not None)
+    assert torch.equal(rp.carve(st, blob, k30), tl[k30][0].detach())
+
+
+def test_the_two_directions_of_a_40_record_stack_share_a_slot_with_two_signatures(nfa):
+    """core cuts a run after 32 records in processing order: the forward pass fuses records [0, 32) and [32, 40), the inverse pass
+    [8, 40) and [0, 8).  [0, 32) and [0, 8) start with the same flow, which names their cache slot (sub=id(run[0])): the slot's key
+    -- signature(run, d) -- must tell them apart, and the structures must differ."""
+    from normflows_amd import _keys
+    from normflows_amd.flows import realnvp_pack as rp
+    flows = _records(nfa, 40)
+    fwd, inv = flows[:32], flows[:8]
+    assert fwd[0] is inv[0]
+    assert rp.signature(fwd, 2) != rp.signature(inv, 2) and rp.signature(fwd, 2)[:9] == rp.signature(inv, 2)
+    assert rp.signature(flows[8:40], 2) == rp.signature(fwd, 2)            # same kinds and shapes, other flows: another slot
+    assert rp.structure(fwd, 2)["nblob"] != rp.structure(inv, 2)["nblob"]
+    holder, built = {"run_struct": {}}, []
+
+    def get(run):
+        return _keys.cached(holder, "run_struct", (rp.signature(run, 2), "cpu"), lambda: built.append(len(run)) or rp.structure(run, 2),
+                            sub=id(run[0]))
+    assert get(fwd)["nrec"] == 32 and get(inv)["nrec"] == 8 and get(fwd)["nrec"] == 32 and get(fwd)["nrec"] == 32
+    assert built == [32, 8, 32]                                            # one slot: rebuilt on every change of direction, never stale
