@@ -644,6 +644,13 @@ int nf_diag_gaussian_log_prob_rows(const void *z, const void *loc_rows, const vo
  *   z, y (B, d) float32, d <= 16; blob: host-packed parameters of the stack (normflows_amd/core.py documents the
  *   layout); hmax = widest MLP layer; direction 0 applies the records in order with the forward formulas,
  *   1 in reverse order with the inverse formulas; logdet (B) combined according to `acc`.
+ * A third record kind, "coupling block", stands for one AffineCouplingBlock (coupling.py:117-171, 232-267; split modes channel /
+ * channel_inv, reshape.py:30-34, 59-64; scale maps exp / sigmoid / sigmoid_inv or scale=False) whose param_map is such an MLP
+ * (c1 inputs, c2 or 2 c2 outputs, c1 + c2 = d) together with the Permute (mixing.py:32-54, shuffle or swap) that stands directly
+ * behind it: [3, c1, flip + 2 scale_map, has_perm, pf[d], pi[d], mlp], pf / pi = the permutation's index maps of the forward /
+ * inverse direction (y[i] = x[p[i]]), each a permutation of 0 .. d - 1 (the caller's duty: they address LDS columns).  Direction 0
+ * runs the block, then the permutation; direction 1 the inverse permutation, then the block's inverse.  No non-finite -> NaN
+ * substitution in this record (that rule is MaskedAffineFlow's).
  */
 int nf_realnvp_chain(const void *z, void *y, void *logdet, const void *blob, int64_t B, int d, int hmax, int direction,
                      int acc, nf_stream_t stream);
@@ -664,6 +671,9 @@ int nf_realnvp_chain(const void *z, void *y, void *logdet, const void *blob, int
  *     non-parameters hold 0 or partial sums nobody reads: slice by the parameters' offsets).  Two launches (backward, fixed-order
  *     reduction of the workgroups' slabs); one when wmask == 0.  No atomics: bit-identical from run to run.
  *     LeakyReLU slopes must be >= 0 (the derivative is taken from the sign of the activation).
+ *   A coupling block record (above) is saved like the others (its input, in the inverse direction the one in front of the
+ *   permutation); its single MLP is side 0, bit 2 r of wmask, and bit 2 r + 1 is unused.  The backward recomputes the MLP, applies
+ *   the coupling's derivative (nf_affine_coupling_bwd's formulas) and the permutation's transpose to the cotangent.
  */
 int nf_realnvp_train_rows(int hmax, int act_floats);
 int64_t nf_realnvp_train_scratch_floats(int64_t B, int hmax, int act_floats, int64_t blob_floats);

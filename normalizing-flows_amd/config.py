@@ -403,6 +403,22 @@ def set_realnvp_train(mode=True, capture_min_batch=None):
         realnvp_train_capture_min_batch = int(capture_min_batch)
 
 
+# AffineCouplingBlock(MLP) layers, each with the Permute directly behind it, as "coupling block" records of those same runs -- at
+# inference (nf_realnvp_chain) and under autograd (RealNVPChainFn): the reference's quick-start model, 32 x [AffineCouplingBlock(MLP),
+# Permute(2, 'swap')], is one launch / one forward and one backward launch.  False = the record kind is never formed: every block runs
+# its own conditioner modules + nf_affine_coupling and every Permute its torch indexing, as before the record existed (A/B runs,
+# differential tests).  Under autograd the record follows realnvp_train and realnvp_train_capture_min_batch like the other kinds.
+realnvp_blocks = True
+# At inference the record is formed at every batch size, captured or not.  lane = sample: a launch lasts as long as one lane needs
+# for all the MLPs of the run, so replayed from a graph -- where the layer-by-layer kernels have no launch overhead left -- a small
+# batch is faster with the switch off (profiles/realnvp_block_bench.json: `log_prob_graph`, `inference_graph_not_slower_from`).
+
+
+def set_realnvp_blocks(mode=True):
+    global realnvp_blocks
+    realnvp_blocks = bool(mode)
+
+
 # Debug mode of the element-wise spline API (utils.splines): after every call a check launch (nf_rqs_spline_check)
 # sets device-side flags and the shim reads them back -- a host synchronisation per call, which is why it is off by default -- and
 # raises what the reference raises: AssertionError for a negative discriminant in the inverse direction (utils/splines.py:181),

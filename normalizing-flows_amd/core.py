@@ -81,7 +81,8 @@ def _run_pairs_impl(pairs, z, inverse, ld, acc):
     return z[:, :feats].contiguous() if narrow else z
 
 
-# ---- RealNVP-style runs: MaskedAffineFlow(MLP, MLP) / ActNorm stacks as one launch (csrc/realnvp_chain.hip) --------------
+# ---- RealNVP-style runs: MaskedAffineFlow(MLP, MLP) / ActNorm / AffineCouplingBlock(MLP) + Permute stacks as one launch
+# (csrc/realnvp_chain.hip) ------------------------------------------------------------------------------------------------
 def _plain_mlp(net):
     """(linears, slope) if `net` is a nets.MLP made of Linear + LeakyReLU only (mlp.py:5-58 without output_fn/dropout)."""
     from . import nets
@@ -103,10 +104,53 @@ def _plain_mlp(net):
     return lin, slope
 
 
+def _block_net(f, d):
+    """(linears, slope) of an AffineCouplingBlock that can be a coupling block record on (B, d) inputs (csrc/realnvp_block.hpp):
+    split mode channel / channel_inv, a plain MLP with biases from the c1 columns of z1 to c2 (scale=False) or 2 c2 parameters,
+    no layer wider than 64; None otherwise, and whenever config.realnvp_blocks is off."""
+    from .flows import realnvp_pack
+    from .flows.affine import AffineCoupling, AffineCouplingBlock
+    if not (_config.realnvp_blocks and isinstance(f, AffineCouplingBlock) and f.split_mode in ("channel", "channel_inv")
+            and 2 <= d <= 16 and len(f.flows) == 3 and isinstance(f.flows[1], AffineCoupling)):
+        return None
+    pm = _plain_mlp(f.flows[1].param_map)
+    c1 = realnvp_pack.block_split(f, d)[0]
+    if pm is None or pm[0][0].in_features != c1 or pm[0][-1].out_features != (d - c1) * (2 if f.flows[1].scale else 1):
+        return None
+    if any(l.out_features > 64 or l.bias is None for l in pm[0]):
+        return None
+    return pm
+
+
+def _permute_joins(p, d):
+    """True when `p` is a Permute that a coupling block record on (B, d) inputs can carry: exactly Permute, shuffle or swap over d
+    channels, both index maps permutations of 0 .. d - 1 (the kernels address a lane's LDS columns with them)."""
+    from .flows.mixing import Permute
+    if type(p) is not Permute or p.num_channels != d:
+        return False
+    maps = p._index_maps()
+    return maps is not None and all(sorted(m) == list(range(d)) for m in maps)
+
+
+def _realnvp_take(flows, order, k, d, inverse, ok):
+    """How many flows the record that starts at position k of the processing order takes: 2 = an eligible AffineCouplingBlock and
+    the Permute directly behind it in LIST order (processed behind it going forward, in front of it going backward), 1 = any
+    other eligible flow, 0 = none.  A Permute anywhere else ends a run."""
+    from .flows.affine import AffineCouplingBlock
+    f = flows[order[k]]
+    if k + 1 < len(order):
+        blk, perm = (flows[order[k + 1]], f) if inverse else (f, flows[order[k + 1]])
+        if isinstance(blk, AffineCouplingBlock) and ok(blk, d) and _permute_joins(perm, d):
+            return 2
+    return 1 if ok(f, d) else 0
+
+
 def _realnvp_record_ok(f, d):
     """True when flow `f` can be a record of the RealNVP chain kernel for (B, d) inputs."""
-    from .flows.affine import AffineConstFlow, MaskedAffineFlow
+    from .flows.affine import AffineConstFlow, AffineCouplingBlock, MaskedAffineFlow
     from .flows.normalization import ActNorm
+    if isinstance(f, AffineCouplingBlock):
+        return _block_net(f, d) is not None
     if isinstance(f, MaskedAffineFlow):
         if f.b.numel() != d:
             return False
@@ -132,10 +176,19 @@ def _realnvp_record_ok(f, d):
 
 def _pack_realnvp(run, d, device):
     """Blob of csrc/realnvp_chain.hip for the flows `run` (stored in forward order)."""
-    from .flows.affine import MaskedAffineFlow
+    from .flows import realnvp_pack
+    from .flows.affine import AffineCouplingBlock, MaskedAffineFlow
     recs, hmax = [], d
-    for f in run:
-        if isinstance(f, MaskedAffineFlow):
+    for f, perm in realnvp_pack.records(run):
+        if isinstance(f, AffineCouplingBlock):
+            lin, slope = _block_net(f, d)
+            sizes = [lin[0].in_features] + [l.out_features for l in lin]
+            hmax = max(hmax, max(sizes))
+            r = [torch.tensor(realnvp_pack.block_header(f, perm, d) + [float(len(lin)), slope] + [float(v) for v in sizes])]
+            for l in lin:
+                r += [l.weight.detach().reshape(-1).float().cpu(), l.bias.detach().reshape(-1).float().cpu()]
+            recs.append(torch.cat(r))
+        elif isinstance(f, MaskedAffineFlow):
             r = [torch.tensor([2.0, float(f.s is not None), float(f.t is not None), 0.0]), f.b.detach().reshape(-1).float().cpu()]
             for net in (f.s, f.t):
                 if net is None:
@@ -183,9 +236,13 @@ def _realnvp_train_record_ok(f, d):
     take (64) within the LDS budget at 64 lanes per workgroup (nf_realnvp_train_rows)."""
     from . import ops
     from .flows import realnvp_pack
-    from .flows.affine import MaskedAffineFlow
+    from .flows.affine import AffineCouplingBlock, MaskedAffineFlow
     if d > 16 or not _realnvp_record_ok(f, d):
         return False
+    if isinstance(f, AffineCouplingBlock):
+        lin, slope = _block_net(f, d)
+        return (slope >= 0.0 and all(l.weight.dtype == torch.float32 and l.bias.dtype == torch.float32 for l in lin)
+                and ops.realnvp_rows(64, realnvp_pack.mlp_footprint(lin, d)[1]) != 0)
     if isinstance(f, MaskedAffineFlow):
         if f.b.dtype != torch.float32:
             return False
@@ -199,6 +256,21 @@ def _realnvp_train_record_ok(f, d):
                 return False
         return True
     return f.s.dtype == torch.float32 and f.t.dtype == torch.float32
+
+
+def _realnvp_run_end(flows, order, k, d, inverse, train):
+    """The position behind the run of chain records that starts at position k of the processing order (k itself: no record starts
+    there).  Under autograd (`train`) a run is cut after realnvp_pack.MAX_RECORDS RECORDS: a block and its Permute are one, so the
+    cut never falls between them."""
+    from .flows import realnvp_pack
+    ok = _realnvp_train_record_ok if train else _realnvp_record_ok
+    k2, nrec = k, 0
+    while k2 < len(order) and not (train and nrec == realnvp_pack.MAX_RECORDS):
+        take = _realnvp_take(flows, order, k2, d, inverse, ok)
+        if take == 0:
+            break
+        k2, nrec = k2 + take, nrec + 1
+    return k2
 
 
 def _run_realnvp_train(run, z, inverse, ld, acc):
@@ -286,30 +358,24 @@ def _run_chain_impl(flows, z, inverse, ld, acc):
     while k < n:
         i = order[k]
         f = flows[i]
-        if rn_train and _realnvp_train_record_ok(f, z.shape[1]):
-            from .flows import realnvp_pack
-            from .flows.affine import MaskedAffineFlow
-            k2 = k
-            while k2 < n and k2 - k < realnvp_pack.MAX_RECORDS and _realnvp_train_record_ok(flows[order[k2]], z.shape[1]):
-                k2 += 1
+        k2 = _realnvp_run_end(flows, order, k, z.shape[1], inverse, True) if rn_train else k
+        if k2 > k:
+            from .flows.affine import AffineCouplingBlock, MaskedAffineFlow
             run = [flows[q] for q in sorted(order[k:k2])]
             # gradients are needed (the input's, or of a parameter of the run) and there is an MLP-conditioned layer to fuse
-            if (any(isinstance(f_, MaskedAffineFlow) for f_ in run) and z.shape[0] > 0
+            if (any(isinstance(f_, (MaskedAffineFlow, AffineCouplingBlock)) for f_ in run) and z.shape[0] > 0
                     and (z.requires_grad or any(p.requires_grad for f_ in run for p in f_.parameters()))):
                 z = flush(z)
                 z = _run_realnvp_train(run, z, inverse, ld, acc)
                 k = k2
                 continue
-        if rn_ok and _realnvp_record_ok(f, z.shape[1]):
-            k2 = k
-            while k2 < n and _realnvp_record_ok(flows[order[k2]], z.shape[1]):
-                k2 += 1
-            if k2 - k >= 2:   # a run of at least two layers: one launch
-                z = flush(z)
-                idx = sorted(order[k:k2])
-                z = _run_realnvp([flows[q] for q in idx], z, inverse, ld, acc)
-                k = k2
-                continue
+        k2 = _realnvp_run_end(flows, order, k, z.shape[1], inverse, False) if rn_ok else k
+        if k2 - k >= 2:   # a run of at least two layers: one launch
+            z = flush(z)
+            idx = sorted(order[k:k2])
+            z = _run_realnvp([flows[q] for q in idx], z, inverse, ld, acc)
+            k = k2
+            continue
         pair = None
         if k + 1 < n:
             j = order[k + 1]

@@ -13,8 +13,11 @@
 //   [nrec, d, hmax, 0, off_0 .. off_{nrec-1}, records]     (all float32; small integers stored exactly)
 //   record ActNorm      : [1, 0, 0, 0, s[d], t[d]]
 //   record MaskedAffine : [2, has_s, has_t, 0, b[d], mlp_s?, mlp_t?]
+//   record CouplingBlock: [3, c1, flip + 2 scale_map, has_perm, pf[d], pi[d], mlp]      (realnvp_block.hpp: an AffineCouplingBlock
+//                         with a plain-MLP param_map and the Permute directly behind it, coupling.py:117-171, 232-267)
 //   mlp                 : [nlin, slope, n_0 .. n_nlin, then per linear: W (n_{k+1} x n_k row-major), bias (n_{k+1})]
 #include "common.hpp"
+#include "realnvp_block.hpp"
 
 namespace nf {
 
@@ -79,6 +82,38 @@ realnvp_chain_kernel(const float *__restrict__ z, float *__restrict__ y, float *
                         else { v[i] = (v[i] - t[i]) * M<float>::exp(-s[i]); ld -= s[i]; }
                     }
                 }
+            } else if (type == 3) {
+                // Split -> AffineCoupling -> Merge, the Permute behind it (inverse: in front).  c1, flip and the index maps are
+                // run-time values: columns move through the lane's LDS columns, never through a computed register index.
+                const RbRecord k = rb_decode(rec, d);
+                if (direction == 1 && k.has_perm) rb_gather(v, buf, bs, d, k.pi);
+                float x[RN_DMAX], z2[RB_CMAX], par[RN_DMAX];
+#pragma unroll
+                for (int i = 0; i < RN_DMAX; ++i)
+                    if (i < d) buf[(size_t)i * bs] = v[i];
+#pragma unroll
+                for (int i = 0; i < RN_DMAX; ++i) x[i] = i < k.c1 ? buf[(size_t)(k.o1 + i) * bs] : 0.0f;
+#pragma unroll
+                for (int i = 0; i < RB_CMAX; ++i) z2[i] = i < k.c2 ? buf[(size_t)(k.o2 + i) * bs] : 0.0f;
+#pragma unroll
+                for (int i = 0; i < RN_DMAX; ++i)
+                    if (i < k.c1) buf[(size_t)i * bs] = x[i];          // z1 in the MLP's input columns
+                rb_mlp_lds(k.mlp, par, buf, bs, hmax);
+#pragma unroll
+                for (int i = 0; i < RN_DMAX; ++i)
+                    if (i < d) buf[(size_t)i * bs] = v[i];
+#pragma unroll
+                for (int i = 0; i < RB_CMAX; ++i) {
+                    if (i < k.c2) {
+                        const float sh = k.smap == NF_SCALE_NONE ? par[i] : par[2 * i];
+                        const float sc = k.smap == NF_SCALE_NONE ? 0.0f : par[2 * i + 1];
+                        buf[(size_t)(k.o2 + i) * bs] = rb_apply(z2[i], sh, sc, k.smap, direction, ld);
+                    }
+                }
+                const bool move = direction == 0 && k.has_perm;
+#pragma unroll
+                for (int i = 0; i < RN_DMAX; ++i)
+                    if (i < d) v[i] = buf[(size_t)(move ? (int)k.pf[i] : i) * bs];
             } else {
                 const bool has_s = rec[1] != 0.0f, has_t = rec[2] != 0.0f;
                 const float *b = rec + 4;

@@ -1,5 +1,5 @@
 // realnvp_train.hip -- the training twin of realnvp_chain.hip for gfx950: a run of MaskedAffineFlow(MLP s, MLP t) / ActNorm /
-// AffineConstFlow records under autograd as THREE launches per step (forward with saves, backward, slab reduction) where the
+// AffineConstFlow / AffineCouplingBlock(MLP) + Permute records under autograd as THREE launches per step (forward with saves, backward, slab reduction) where the
 // layer-by-layer route runs one library GEMM + one LeakyReLU launch per Linear, MaskedAffineFn and a log-det fold per layer, and
 // autograd replays all of it (BASELINE configs[0]: several dozen launches per layer and direction on an 8 KB problem).
 //
@@ -28,6 +28,7 @@
 // atomics: gradients are bit-identical from run to run.  Scratch bound: grid x blob floats <= 2^24 floats (64 MiB); the grid is
 // lowered below NF_PERSISTENT_WORKGROUPS where the blob is larger than 64 K floats.
 #include "common.hpp"
+#include "realnvp_block.hpp"
 #include "train_reduce.hpp"
 
 namespace nf {
@@ -174,6 +175,32 @@ realnvp_train_fwd_kernel(const float *__restrict__ z, float *__restrict__ y, flo
                         else { v[i] = (v[i] - t[i]) * M<float>::exp(-s[i]); ld -= s[i]; }
                     }
                 }
+            } else if ((int)rec[0] == 3) {
+                // the coupling block record (realnvp_block.hpp): columns move through the lane's G columns (>= d of them, free
+                // between MLP passes), the MLP reads z1 from the first c1 columns of A
+                const RbRecord k = rb_decode(rec, d);
+                if (direction == 1 && k.has_perm) rb_gather(v, G, cs, d, k.pi);
+                float z2[RB_CMAX], par[RT_DMAX];
+                rt_store_cols(v, G, cs, d);
+#pragma unroll
+                for (int i = 0; i < RT_DMAX; ++i)
+                    if (i < k.c1) A[(size_t)i * cs] = G[(size_t)(k.o1 + i) * cs];
+#pragma unroll
+                for (int i = 0; i < RB_CMAX; ++i) z2[i] = i < k.c2 ? G[(size_t)(k.o2 + i) * cs] : 0.0f;
+                rt_mlp_fwd(k.mlp, par, A, G, cs);
+                rt_store_cols(v, G, cs, d);
+#pragma unroll
+                for (int i = 0; i < RB_CMAX; ++i) {
+                    if (i < k.c2) {
+                        const float sh = k.smap == NF_SCALE_NONE ? par[i] : par[2 * i];
+                        const float sc = k.smap == NF_SCALE_NONE ? 0.0f : par[2 * i + 1];
+                        G[(size_t)(k.o2 + i) * cs] = rb_apply(z2[i], sh, sc, k.smap, direction, ld);
+                    }
+                }
+                const bool move = direction == 0 && k.has_perm;
+#pragma unroll
+                for (int i = 0; i < RT_DMAX; ++i)
+                    if (i < d) v[i] = G[(size_t)(move ? (int)k.pf[i] : i) * cs];
             } else {
                 const bool has_s = rec[1] != 0.0f, has_t = rec[2] != 0.0f;
                 const float *b = rec + 4;
@@ -284,7 +311,8 @@ __device__ __forceinline__ void rt_mlp_bwd(const float *__restrict__ rec, const 
         if (i < din) gin[i] += gcur[(size_t)i * cs];
 }
 
-// wmask: bit 2 ri = the s-net (ActNorm: s) of record ri needs its gradient, bit 2 ri + 1 = the t-net (ActNorm: t).
+// wmask: bit 2 ri = the s-net (ActNorm: s; coupling block: its one MLP) of record ri needs its gradient, bit 2 ri + 1 = the t-net
+// (ActNorm: t; unused for a coupling block).
 __global__ void __launch_bounds__(256)
 realnvp_train_bwd_kernel(const float *__restrict__ save, const float *__restrict__ gy, const float *__restrict__ gld,
                          float *__restrict__ gz, const float *__restrict__ blob, float *__restrict__ slabs, int64_t B, int direction,
@@ -343,6 +371,61 @@ realnvp_train_bwd_kernel(const float *__restrict__ save, const float *__restrict
                         slab[roff + 4 + tid] += (s0 + s1) + (s2 + s3);
                     }
                     __syncthreads();
+                }
+            } else if ((int)rec[0] == 3) {
+                // the coupling block record (realnvp_block.hpp); its one MLP is side 0 (bit 2 ri).  Forward direction: the Permute
+                // ran behind the block, so its transpose meets the cotangent first; inverse direction: it ran in front of the
+                // block, so the block's input is recomputed from the saved one and the transpose comes last.
+                const RbRecord k = rb_decode(rec, d);
+                if (k.has_perm) {
+                    if (direction == 0) rb_scatter(g, G, cs, d, k.pf);
+                    else rb_gather(v, G, cs, d, k.pi);
+                }
+                float z2[RB_CMAX], g2[RB_CMAX], gz2[RB_CMAX], par[RT_DMAX], gp[RT_DMAX], gin[RT_DMAX];
+                rt_store_cols(v, G, cs, d);
+#pragma unroll
+                for (int i = 0; i < RT_DMAX; ++i)
+                    if (i < k.c1) A[(size_t)i * cs] = G[(size_t)(k.o1 + i) * cs];
+#pragma unroll
+                for (int i = 0; i < RB_CMAX; ++i) z2[i] = i < k.c2 ? G[(size_t)(k.o2 + i) * cs] : 0.0f;
+                rt_store_cols(g, G, cs, d);
+#pragma unroll
+                for (int i = 0; i < RB_CMAX; ++i) g2[i] = i < k.c2 ? G[(size_t)(k.o2 + i) * cs] : 0.0f;
+                rt_mlp_fwd(k.mlp, par, A, G, cs);
+#pragma unroll
+                for (int i = 0; i < RT_DMAX; ++i) { gp[i] = 0.0f; gin[i] = 0.0f; }
+#pragma unroll
+                for (int i = 0; i < RB_CMAX; ++i) {
+                    gz2[i] = 0.0f;
+                    if (i < k.c2) {
+                        const float sh = k.smap == NF_SCALE_NONE ? par[i] : par[2 * i];
+                        const float sc = k.smap == NF_SCALE_NONE ? 0.0f : par[2 * i + 1];
+                        float gsh, gsc;
+                        rb_apply_bwd(z2[i], sh, sc, g2[i], gl, k.smap, direction, gz2[i], gsh, gsc);
+                        if (!valid) { gsh = 0.0f; gsc = 0.0f; }      // (0 * e^s is NaN for an overflowing s of the zero row)
+                        if (k.smap == NF_SCALE_NONE) gp[i] = gsh;
+                        else { gp[2 * i] = gsh; gp[2 * i + 1] = gsc; }
+                    }
+                }
+                if (q > 0 || gz != nullptr || (wbits & 1))      // somebody reads the cotangent of this record's input, or the MLP's
+                    rt_mlp_bwd(k.mlp, gp, gin, A, G, cs, hmax, slab + roff + (int)(k.mlp - rec), (wbits & 1) != 0);
+                // merge: the identity half keeps its cotangent and gains the MLP's, the transformed half takes the coupling's
+                rt_store_cols(g, G, cs, d);
+#pragma unroll
+                for (int i = 0; i < RT_DMAX; ++i)
+                    if (i < k.c1) G[(size_t)(k.o1 + i) * cs] += gin[i];
+#pragma unroll
+                for (int i = 0; i < RB_CMAX; ++i)
+                    if (i < k.c2) G[(size_t)(k.o2 + i) * cs] = gz2[i];
+                if (direction == 1 && k.has_perm) {            // u[i] = x[pi[i]]: gx[pi[i]] = gu[i]
+#pragma unroll
+                    for (int i = 0; i < RT_DMAX; ++i)
+                        if (i < d) g[i] = G[(size_t)i * cs];
+                    rb_scatter(g, G, cs, d, k.pi);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < RT_DMAX; ++i)
+                        if (i < d) g[i] = G[(size_t)i * cs];
                 }
             } else {
                 const bool has_s = rec[1] != 0.0f, has_t = rec[2] != 0.0f;

@@ -40,6 +40,19 @@ class Permute(Flow):
             return torch.cat([z[:, cut:, ...], z[:, :cut, ...]], dim=1)
         raise NotImplementedError("The mode " + self.mode + " is not implemented.")
 
+    def _index_maps(self):
+        """(forward, inverse) index maps as tuples of ints on the host, y[:, i] = z[:, map[i]] -- what `_move` computes; None for
+        any other mode.  The shuffle buffers are read from the device ONCE per version of them (`_keys.pcached`: load_state_dict
+        and every other in-place update bump it): the RealNVP chain records that carry the maps (flows/realnvp_pack.py) ask in
+        every forward, and a read per call would be a host synchronisation."""
+        n = self.num_channels
+        if self.mode == "swap":
+            return tuple((i + n // 2) % n for i in range(n)), tuple((i + (n + 1) // 2) % n for i in range(n))
+        if self.mode != "shuffle":
+            return None
+        return _keys.pcached(self, "_maps_cache", (self.perm, self.inv_perm), (),
+                             lambda: (tuple(self.perm.tolist()), tuple(self.inv_perm.tolist())))
+
     def forward(self, z, context=None):
         return self._move(z, False), torch.zeros(len(z), device=z.device)
 

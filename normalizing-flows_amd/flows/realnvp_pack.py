@@ -4,6 +4,7 @@ The blob has the layout of core._pack_realnvp (the inference kernel's host-packe
     [nrec, d, hmax, 0, off_0 .. off_{nrec-1}, records]
     record ActNorm / AffineConst : [1, 0, 0, 0, s[d], t[d]]
     record MaskedAffine          : [2, has_s, has_t, 0, b[d], mlp_s?, mlp_t?]
+    record CouplingBlock         : [3, c1, flip + 2 scale_map, has_perm, pf[d], pi[d], mlp]     (csrc/realnvp_block.hpp)
     mlp                          : [nlin, slope, n_0 .. n_nlin, then per linear: W (n_{k+1} x n_k row-major), bias (n_{k+1})]
 Under autograd the parameters change every step, so the value-independent part is built once per run structure (`structure`):
 `static` = the blob with zeros in place of every tensor value, `src` = for every blob position its position in
@@ -11,6 +12,11 @@ Under autograd the parameters change every step, so the value-independent part i
 and every forward gathers blob = flat[src] on the device (ops.pack_gather) from `tensors(run)` as they are in that call -- the
 masks `b` included.  `slices[k]` = (offset, shape) of tensor k inside the blob: the gradient blob of nf_realnvp_chain_bwd has the
 same layout, so tensor k's gradient is that slice of it.
+
+A coupling block record is ONE AffineCouplingBlock whose param_map is a plain MLP together with the Permute that stands directly
+behind it in `run` (`records`): two flows, one record -- the 64 layers of 32 x [block, Permute] are 32 records.  Its header and the
+permutation's index maps are value-independent structure (`static`, `signature`): the maps come from Permute._index_maps, a host
+copy cached on the buffers' versions, so no forward reads the device for them.
 """
 import math
 
@@ -21,17 +27,50 @@ MAX_RECORDS = 32        # one bit pair per record in nf_realnvp_chain_bwd's 64-b
 
 def _nets(f):
     from ..core import _plain_mlp
+    from .affine import AffineCouplingBlock
+    if isinstance(f, AffineCouplingBlock):
+        return [(_plain_mlp(f.flows[1].param_map), 0)]
     return [(_plain_mlp(net), side) for net, side in ((f.s, 0), (f.t, 1)) if net is not None]
 
 
-def tensors(run):
-    """The live tensors of the flows `run` (forward order) in blob order, each with (record, side): side 0 = the s-net (ActNorm: s),
-    1 = the t-net (t), None = the mask buffer b (no gradient)."""
-    from .affine import MaskedAffineFlow
+def records(run):
+    """[(flow, Permute or None)] of the flows `run` (forward order), one entry per record: a Permute belongs to the record of the
+    AffineCouplingBlock directly in front of it (core._run_chain_impl lets no other Permute into a run)."""
+    from .affine import AffineCouplingBlock
+    from .mixing import Permute
     out = []
-    for r, f in enumerate(run):
-        if isinstance(f, MaskedAffineFlow):
-            out.append((f.b, r, None))
+    for f in run:
+        if isinstance(f, Permute):
+            assert out and isinstance(out[-1][0], AffineCouplingBlock) and out[-1][1] is None, "a Permute joins a run behind a block only"
+            out[-1] = (out[-1][0], f)
+        else:
+            out.append((f, None))
+    return out
+
+
+def block_split(f, d):
+    """(c1, flip) of an AffineCouplingBlock on (B, d) inputs: AffineCouplingBlock._fused's convention (reshape.py:30-34)."""
+    return ((d + 1) // 2, 0) if f.split_mode == "channel" else (d // 2, 1)
+
+
+def block_header(f, perm, d):
+    """The value-independent floats of a coupling block record: [3, c1, flip + 2 scale_map, has_perm, pf[d], pi[d]]."""
+    from .._lib import SCALE
+    c1, flip = block_split(f, d)
+    pf, pi = perm._index_maps() if perm is not None else (tuple(range(d)),) * 2
+    assert len(pf) == len(pi) == d
+    return [3.0, float(c1), float(flip + 2 * SCALE[f.flows[1]._smap()]), float(perm is not None)] + [float(v) for v in pf + pi]
+
+
+def tensors(run):
+    """The live tensors of the flows `run` (forward order) in blob order, each with (record, side): side 0 = the s-net (ActNorm: s;
+    coupling block: its MLP), 1 = the t-net (t), None = the mask buffer b (no gradient)."""
+    from .affine import AffineCouplingBlock, MaskedAffineFlow
+    out = []
+    for r, (f, _) in enumerate(records(run)):
+        if isinstance(f, (MaskedAffineFlow, AffineCouplingBlock)):
+            if isinstance(f, MaskedAffineFlow):
+                out.append((f.b, r, None))
             for (lin, _), side in _nets(f):
                 for l in lin:
                     out += [(l.weight, r, side), (l.bias, r, side)]
@@ -41,13 +80,17 @@ def tensors(run):
 
 
 def signature(run, d):
-    """What `structure` depends on: record kinds, layer sizes and slopes -- no parameter value."""
-    from .affine import MaskedAffineFlow
+    """What `structure` depends on: record kinds, layer sizes, slopes and a coupling block's header with its Permute's index maps
+    (their cached host copy) -- no parameter value."""
+    from .affine import AffineCouplingBlock, MaskedAffineFlow
     sig = [d]
-    for f in run:
+    for f, perm in records(run):
+        nets = tuple((side, slope) + tuple(tuple(l.weight.shape) for l in lin) for (lin, slope), side in _nets(f)) \
+            if isinstance(f, (MaskedAffineFlow, AffineCouplingBlock)) else ()
         if isinstance(f, MaskedAffineFlow):
-            sig.append((2, f.s is not None, f.t is not None)
-                       + tuple((side, slope) + tuple(tuple(l.weight.shape) for l in lin) for (lin, slope), side in _nets(f)))
+            sig.append((2, f.s is not None, f.t is not None) + nets)
+        elif isinstance(f, AffineCouplingBlock):
+            sig.append(tuple(block_header(f, perm, d)) + nets)
         else:
             sig.append((1,))
     return tuple(sig)
@@ -61,11 +104,14 @@ def mlp_footprint(lin, d):
 
 def structure(run, d):
     """dict(static, src: CPU tensors; slices, sides, hmax, act, nblob, nrec) of the flows `run` (forward order) on (B, d) inputs."""
-    from .affine import MaskedAffineFlow
+    from .affine import AffineCouplingBlock, MaskedAffineFlow
     recs, hmax, act = [], d, d          # a record = list of floats (constants) and ("t", numel) placeholders
-    for f in run:
-        if isinstance(f, MaskedAffineFlow):
-            r = [2.0, float(f.s is not None), float(f.t is not None), 0.0, ("t", d)]
+    for f, perm in records(run):
+        if isinstance(f, (MaskedAffineFlow, AffineCouplingBlock)):
+            if isinstance(f, MaskedAffineFlow):
+                r = [2.0, float(f.s is not None), float(f.t is not None), 0.0, ("t", d)]
+            else:
+                r = block_header(f, perm, d)
             for (lin, slope), _ in _nets(f):
                 sizes = [lin[0].in_features] + [l.out_features for l in lin]
                 h, a = mlp_footprint(lin, d)

@@ -1758,7 +1758,7 @@ def bias_leaky_relu_(y, bias, negative_slope):
 
 
 def realnvp_chain(z, blob, d, hmax, direction, logdet=None, acc=None):
-    """A stack of MaskedAffineFlow(MLP s, MLP t) / ActNorm layers in one launch (nf_realnvp_chain)."""
+    """A stack of MaskedAffineFlow(MLP s, MLP t) / ActNorm / AffineCouplingBlock(MLP) + Permute layers in one launch (nf_realnvp_chain)."""
     L.require_device(z, blob)
     if z.dtype != torch.float32:
         raise NotImplementedError("realnvp_chain: float32 only")
