@@ -7,8 +7,10 @@ current HIP stream.
 """
 import ctypes as C
 import glob
+import math
 import os
 import subprocess
+import sys
 
 import torch
 
@@ -179,7 +181,13 @@ def lib():
 
 def call(name, *args):
     """Call the entry point `name` (returns an errno-style code) and raise on failure under that same name."""
-    check(getattr(lib(), name)(*args), name)
+    check(call_rc(name, *args), name)
+
+
+def call_rc(name, *args):
+    """The raw return code of the entry point `name`, for the callers that read NF_ENOTSUP as "this shape is declined" (every C-ABI
+    call goes through here: one place to observe them)."""
+    return getattr(lib(), name)(*args)
 
 
 def query(name, *args):
@@ -214,7 +222,87 @@ def dtype_code(t):
     raise TypeError("nf_mi355x kernels support float32/float64 tensors, got %s" % t.dtype)
 
 
-def require_device(*tensors):
+KERNEL_DTYPES = (torch.float32, torch.float64)
+
+
+def check_operands(entry, tensors, dtype=None):
+    """The dtype contract of one C-ABI call ("Operand dtypes and shapes"): every floating-point tensor among `tensors`
+    has ONE dtype, float32 or float64, and that is `dtype` when one is given (an entry point without a `dtype` parameter reads
+    float32).  Integer / bool tensors (index tables, pointer tables, ReLU bits) and None are not looked at.  The C side sees
+    `const void *`: a kernel instantiated for one element type would read another's bytes, past the end of the narrower buffer.
+    Attribute reads only: no synchronisation, no allocation, any device (safe under stream capture).  Returns the common dtype (None
+    when no floating tensor is among the operands)."""
+    ref, ref_i = dtype, None
+    for i, t in enumerate(tensors):
+        if t is None or not t.dtype.is_floating_point:
+            continue
+        if ref is None:
+            ref, ref_i = t.dtype, i
+        if t.dtype != ref or ref not in KERNEL_DTYPES:
+            if ref not in KERNEL_DTYPES:
+                raise TypeError("%s: operand %d is %s; the kernels take float32 / float64 tensors only" % (entry, i, t.dtype))
+            raise TypeError("%s: operand %d is %s but %s: one call takes tensors of one floating-point dtype (nothing is converted "
+                            "silently; cast the input or the module)"
+                            % (entry, i, t.dtype, "this entry point reads %s" % ref if ref_i is None else "operand %d is %s" % (ref_i, ref)))
+    return ref
+
+
+def check_count(entry, name, t, want, why):
+    """ValueError unless the tensor `t` (None passes) holds exactly `want` elements (`why`: the formula, for the message): the kernels
+    index an operand by the call's scalar arguments, whatever its size."""
+    if t is not None and t.numel() != want:
+        raise ValueError("%s: %s has %d elements (shape %s), the call reads %d (%s)" % (entry, name, t.numel(), tuple(t.shape), want, why))
+
+
+def tri_count(D):
+    """Entries of a strict triangle of a D x D matrix (LULinearPermute's lower_entries / upper_entries)."""
+    return D * (D - 1) // 2
+
+
+def coupling_param_channels(C, c1, scale_map):
+    """P of nf_affine_coupling[_pb|_bwd]: channels of `param` for z (B, C, HW) with c1 identity channels -- (shift, scale) interleaved per
+    transformed channel, or the shift alone without a scale map."""
+    return (C - c1) * (1 if scale_map is None else 2)
+
+
+def rqs_derivative_count(K, tails_code):
+    """Derivative logits per element that nf_rqs_coupling reads behind the 2 K widths and heights: K - 1 (linear tails), K (circular),
+    K + 1 (no tails, or per-feature tails)."""
+    return {TAILS["linear"]: K - 1, TAILS["circular"]: K}.get(tails_code, K + 1)
+
+
+def rqs_derivative_ok(K, n):
+    """nf_rqs_spline takes (K-1 | K | K+1) derivative logits per element (linear | circular | no tails)."""
+    return n in (K - 1, K, K + 1)
+
+
+def rows_ok(n_loc, n_log_scale, d, B, indexed):
+    """nf_diag_gaussian_log_prob_rows: both parameter blocks are the same whole number of rows of d elements -- one per sample unless the
+    rows are picked by an index (class labels)."""
+    if n_loc != n_log_scale or (n_loc % d if d else n_loc):
+        return False
+    return indexed or d == 0 or n_loc // d == B
+
+
+def leading_shape_ok(x_shape, p_shape):
+    """A per-element parameter block (..., K) of nf_rqs_spline has one row per input element (the leading shape itself may be the
+    inputs' flattened: the kernel sees N rows)."""
+    return len(p_shape) >= 1 and math.prod(p_shape[:-1]) == math.prod(x_shape)
+
+
+def require_device(*tensors, dtype=None, entry=None, also=()):
+    """Every tensor operand of a wrapper: on the current HIP device, and (check_operands) of one kernel dtype -- `dtype` when the entry
+    point is float32-only.  `also`: operands the wrapper converts itself (a mask, a label matrix) -- device check only.  `entry`: the
+    name for the message (default: the calling function's)."""
+    _require_device(tensors)
+    if also:
+        _require_device(also)
+    if entry is None:
+        entry = sys._getframe(1).f_code.co_name
+    return check_operands(entry, tensors, dtype)
+
+
+def _require_device(tensors):
     cur = None
     for t in tensors:
         if t is None:

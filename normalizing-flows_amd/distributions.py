@@ -194,6 +194,8 @@ class ClassCondDiagGaussian(BaseDistribution):
         return z, log_p
 
     def log_prob(self, z, y):
+        if tuple(z.shape[1:]) != tuple(self.shape):   # (num_classes rows of d elements can be a whole number of rows of another width)
+            raise ValueError("ClassCondDiagGaussian: samples of shape %s expected, got %s" % (tuple(self.shape), tuple(z.shape[1:])))
         if needs_grad(z, self.loc, self.log_scale):   # training: differentiable row tables, HIP forward
             d = int(self.d)
             loc_r = self.loc.reshape(d, self.num_classes).t()

@@ -60,6 +60,32 @@ def _fold_ld(ld, acc, log_det):
     return fold_logdet(ld, acc, log_det)
 
 
+def conditioner_output(who, out, z, full_shape=None):
+    """What a caller-supplied module (`s`, `t`, `param_map`) returned, as the kernel beside `z` reads it ("Operand
+    dtypes and shapes").  The reference computes z * exp(out) + ...: torch promotes and broadcasts there.  A NARROWER dtype
+    (bfloat16 / float16 under torch.autocast, float32 beside a float64 z) is cast to z's -- the promotion's result, and the gradient
+    flows back through the cast; a WIDER one would promote z and is refused (TypeError).  full_shape (MaskedAffineFlow): an output
+    that broadcasts to it -- (B, 1), (inner,) -- is expanded as a view; any other shape is refused (ValueError) like the reference's
+    broadcast.  Attribute reads only."""
+    if out is None:
+        return None
+    if out.dtype != z.dtype:
+        if torch.promote_types(out.dtype, z.dtype) != z.dtype:
+            raise TypeError("%s returned %s for a %s input: a wider output would promote the input (cast the input or the module; "
+                            "nothing is converted silently)" % (who, out.dtype, z.dtype))
+        out = out.to(z.dtype)
+    if full_shape is not None and tuple(out.shape) != tuple(full_shape):
+        try:
+            ok = tuple(torch.broadcast_shapes(tuple(out.shape), tuple(full_shape))) == tuple(full_shape)
+        except RuntimeError:
+            ok = False
+        if not ok:
+            raise ValueError("%s returned shape %s, which does not broadcast to the input's %s"
+                             % (who, tuple(out.shape), tuple(full_shape)))
+        out = out.expand(tuple(full_shape))
+    return out
+
+
 class AffineConstFlow(Flow):
     """Per-dimension learned scale and shift (coupling.py:9-54); base class of ActNorm."""
 
@@ -195,7 +221,7 @@ class AffineCoupling(Flow):
 
     def _transform(self, z, inverse, ld=None, acc=None):
         z1, z2 = z
-        param = self.param_map(z1)
+        param = conditioner_output("AffineCoupling.param_map", self.param_map(z1), z2)
         if needs_grad(z1, z2, param):
             y2, log_det = AffineCouplingFn.apply(z2.contiguous(), param, 0, False, self._smap(), 1 if inverse else 0)
             return [z1, y2], _fold_ld(ld, acc, log_det)
@@ -232,8 +258,8 @@ class MaskedAffineFlow(Flow):
     def _transform(self, z, inverse, ld=None, acc=None):
         need_net = self.s is not None or self.t is not None
         z_masked = self.b * z if need_net else None
-        scale = self.s(z_masked) if self.s is not None else None
-        trans = self.t(z_masked) if self.t is not None else None
+        scale = conditioner_output("MaskedAffineFlow.s", self.s(z_masked), z, z.shape) if self.s is not None else None
+        trans = conditioner_output("MaskedAffineFlow.t", self.t(z_masked), z, z.shape) if self.t is not None else None
         if _config.torch_elementwise and needs_grad(z, scale, trans):
             # config.higher_order_gradients(): coupling.py:209-229 in torch ops, differentiable to any order (MaskedAffineFn's backward
             # is a kernel: first order only)
@@ -291,9 +317,9 @@ class AffineCouplingBlock(Flow):
             z1 = z[:, C - c1:]
         split = coupling.param_map.forward_split(z1) if hasattr(coupling.param_map, "forward_split") else None
         if split is not None:   # inference: the last convolution's bias is added inside the coupling kernel
-            return ops.affine_coupling(z, split[0], c1, flip, coupling._smap(), 1 if inverse else 0, logdet=ld, acc=acc,
-                                       param_bias=split[1])
-        param = coupling.param_map(z1)
+            return ops.affine_coupling(z, conditioner_output("AffineCouplingBlock.param_map", split[0], z), c1, flip, coupling._smap(),
+                                       1 if inverse else 0, logdet=ld, acc=acc, param_bias=conditioner_output("AffineCouplingBlock.param_map", split[1], z))
+        param = conditioner_output("AffineCouplingBlock.param_map", coupling.param_map(z1), z)
         if needs_grad(z, param):
             y, log_det = AffineCouplingFn.apply(z.contiguous(), param, c1, flip, coupling._smap(), 1 if inverse else 0)
             return y, _fold_ld(ld, acc, log_det)

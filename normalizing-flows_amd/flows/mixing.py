@@ -246,7 +246,7 @@ class InvertibleAffine(Flow):
                 ld.add_(l, alpha=float(acc))
             return y, l
         Wt, ldu = self._weight_t(inverse_dir)
-        y, lds = ops.inv1x1_conv(z.reshape(z.shape[0], -1, 1, 1), Wt, ldu, logdet=ld, acc=acc, want_scalar=want_scalar)
+        y, lds = ops.inv1x1_conv(z.reshape(z.shape[0], z.shape[1], 1, 1), Wt, ldu, logdet=ld, acc=acc, want_scalar=want_scalar)
         return y.view(z.shape), lds
 
     def forward(self, z, context=None):
@@ -351,10 +351,10 @@ class LULinearPermute(Flow):
                                                  ld, ld_sign(acc), fout,
                                                  self.__dict__.setdefault("_img_holder", {}) if fout is not None else None)
             return y, log_det            # log_det IS ld (updated in place) when the caller passed its accumulator
-        if z.dtype == torch.float32 and z.is_cuda and lin.features <= 128 and self.use_dense:
+        if z.dtype == torch.float32 and lin.bias.dtype == torch.float32 and z.is_cuda and lin.features <= 128 and self.use_dense:
             # the layer as ONE dense D x D product on fp32 MFMA (nf_rows_matvec_affine takes D <= 128; the matrices are composed
             # once per parameter version, _dense_matrices): HBM-bound, 5x the LDS-tile kernel below, which stays for D > 128 and
-            # float64
+            # float64 (and for float32 rows beside float64 parameters, which it refuses: the composition would convert them unasked)
             Wd, Ws, bd, bs, lad = self._dense_matrices()
             if inverse:
                 return ops.rows_matvec_affine(z, Wd, bd, lad, +1.0, logdet=ld, acc=acc)
@@ -405,7 +405,8 @@ class LULinearPermute(Flow):
 
     def _train_factors_ok(self, z):
         """The density direction under autograd assembles its factors with nf_lu_factors (LULinearPermuteFn.forward)."""
-        return z.is_cuda and z.dtype == torch.float32 and z.dim() == 2 and 2 <= self.linear.features <= 64 \
+        return z.is_cuda and z.dtype == torch.float32 and self.linear.bias.dtype == torch.float32 and z.dim() == 2 \
+            and 2 <= self.linear.features <= 64 \
             and z.shape[1] == self.linear.features
 
     def _factors_buffer(self, device):

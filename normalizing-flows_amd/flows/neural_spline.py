@@ -342,9 +342,10 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
         return list(self.transform_net.parameters()) + [u.unnormalized_widths, u.unnormalized_heights, u.unnormalized_derivatives]
 
     def _resnet_rows(self, inputs, enabled):
-        """Shared by the one-launch routes: the switch is on, float32 device rows, a ResidualNet next to a batch-shared spline."""
+        """Shared by the one-launch routes: the switch is on, float32 device rows, a ResidualNet with float32 weights (the packers
+        convert on the host: a .double() / .half() module would otherwise run in float32 without a word) next to a batch-shared spline."""
         return (self.use_fused and enabled and _device_rows(inputs) and self.unconditional_transform is not None
-                and isinstance(self.transform_net, ResidualNet))
+                and isinstance(self.transform_net, ResidualNet) and self.transform_net.initial_layer.weight.dtype == torch.float32)
 
     def _wide_pack(self, inputs, context, lu=None, direction=0):
         """Device copies of flows/nsf_wide_pack.py's streams + the batch-shared spline's knot tables, rebuilt when a parameter
@@ -626,6 +627,8 @@ class PiecewiseRationalQuadraticCoupling(Coupling):
             return False
         if context is not None or not _device_rows(inputs):
             return False
+        if net.initial_layer.weight.dtype != torch.float32:     # (read per call: .double() / .half() come after the cached decision)
+            return False       # a float32 kernel on float32 rows needs float32 weights; the layer-wise path refuses the mix loudly
         if self.tails != "linear" or self._per_feature or self.unconditional_transform is None:
             return False
         if self._fused_ok is None:

@@ -42,6 +42,11 @@ def rqs_spline(x, w, h, d, inverse=False, tails="linear", tail_bound=1.0, left=0
     parameter block are accepted (row stride taken from .stride(-2))."""
     L.require_device(x, w, h, d)
     K = w.shape[-1]
+    for name, a in (("widths", w), ("heights", h), ("derivatives", d)):
+        if not L.leading_shape_ok(x.shape, a.shape):
+            raise ValueError("rqs_spline: %s %s do not belong to inputs %s (one parameter row per element)" % (name, tuple(a.shape), tuple(x.shape)))
+    if h.shape[-1] != K or not L.rqs_derivative_ok(K, d.shape[-1]):
+        raise ValueError("rqs_spline: %d widths, %d heights, %d derivatives per element (K, K, K-1 | K | K+1 expected)" % (K, h.shape[-1], d.shape[-1]))
     xs = x.contiguous().view(-1)
     N = xs.numel()
 
@@ -82,13 +87,26 @@ def _tails_args(x, tails, tail_bound, tails_t, bound_t, tails_i, bound_i):
     return "_ft", code, scalar_bound, [fix(tails_t, torch.int32), fix(bound_t, x.dtype), fix(tails_i, torch.int32), fix(bound_i, x.dtype)]
 
 
+def _rqs_coupling_counts(entry, B, D, K, code, cond, uw, uh, ud, identity_idx, transform_idx, y=None, logdet=None):
+    """Element counts of nf_rqs_coupling[_ft|_bwd]: cond (B, nT, M) with M = 2 K + derivatives, the batch-shared rows (nI, K | K | M - 2 K)."""
+    nI, nT = identity_idx.numel(), transform_idx.numel()
+    nd = L.rqs_derivative_count(K, code)
+    L.check_count(entry, "cond", cond, B * nT * (2 * K + nd), "B * nT * (2 K + %d)" % nd)
+    L.check_count(entry, "unnormalized_widths", uw, nI * K, "nI * K")
+    L.check_count(entry, "unnormalized_heights", uh, nI * K, "nI * K")
+    L.check_count(entry, "unnormalized_derivatives", ud, nI * nd, "nI * %d" % nd)
+    L.check_count(entry, "y", y, B * D, "B * D")
+    L.check_count(entry, "logdet", logdet, B, "B")
+
+
 def rqs_coupling(x, cond, uw, uh, ud, identity_idx, transform_idx, K, mode, y=None, logdet=None, acc=None,
                  tails="linear", tail_bound=3.0, min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3,
                  wh_div=1.0, tails_t=None, bound_t=None, tails_i=None, bound_i=None):
     """nsf/coupling.py:71-128 given the conditioner output `cond` (B, nT*M) or (B, nT, M).  tails="feature" with
     int32 tensors tails_t / tails_i (1 linear, 2 circular) and / or per-feature bound tensors bound_t / bound_i select
     the per-feature variant (nf_rqs_coupling_ft, utils/splines.py:48-66)."""
-    L.require_device(x, cond, uw, uh, ud, identity_idx, transform_idx, tails_t, bound_t, tails_i, bound_i)
+    # (tails_* / bound_*: converted to int32 / x.dtype by _tails_args)
+    L.require_device(x, cond, uw, uh, ud, y, logdet, also=(identity_idx, transform_idx, tails_t, bound_t, tails_i, bound_i))
     B, D = x.shape
     x = x.contiguous()
     cond = None if cond is None else cond.contiguous()
@@ -96,6 +114,7 @@ def rqs_coupling(x, cond, uw, uh, ud, identity_idx, transform_idx, K, mode, y=No
         y = torch.empty_like(x)
     logdet, acc = _ld_buffer(logdet, acc, B, x)
     ft, code, bound, feat = _tails_args(x, tails, tail_bound, tails_t, bound_t, tails_i, bound_i)
+    _rqs_coupling_counts("rqs_coupling", B, D, K, code, cond, uw, uh, ud, identity_idx, transform_idx, y, logdet)
     L.call("nf_rqs_coupling" + ft, ptr(x), ptr(y), ptr(logdet), ptr(cond), ptr(uw), ptr(uh), ptr(ud), ptr(identity_idx),
            identity_idx.numel(), ptr(transform_idx), transform_idx.numel(), B, D, K, code, bound, min_bin_width, min_bin_height,
            min_derivative, wh_div, mode, acc, L.dtype_code(x), *map(ptr, feat), L.stream())
@@ -105,13 +124,19 @@ def rqs_coupling(x, cond, uw, uh, ud, identity_idx, transform_idx, K, mode, y=No
 def lu_linear_permute(x, perm, lower_entries, upper_entries, unconstrained_upper_diag, bias, direction, eps=1e-3,
                       logdet=None, acc=None):
     """mixing.py:535-563.  direction 0 = density (LULinearPermute.inverse), 1 = sample (.forward)."""
-    L.require_device(x, perm, lower_entries, upper_entries, unconstrained_upper_diag, bias)
+    L.require_device(x, perm, lower_entries, upper_entries, unconstrained_upper_diag, bias, logdet)
     B, D = x.shape
+    if perm.dtype != torch.int64:
+        raise TypeError("lu_linear_permute: perm is %s, the kernel reads int64" % perm.dtype)
+    for name, a, n in (("perm", perm, D), ("unconstrained_upper_diag", unconstrained_upper_diag, D), ("bias", bias, D),
+                       ("lower_entries", lower_entries, L.tri_count(D)), ("upper_entries", upper_entries, L.tri_count(D)),
+                       ("logdet", logdet, B)):
+        L.check_count("lu_linear_permute", name, a, n, "D = %d: D | D (D - 1) / 2; logdet: B" % D)
     x = x.contiguous()
     y = torch.empty_like(x)
     logdet, acc = _ld_buffer(logdet, acc, B, x)
-    L.call("nf_lu_linear_permute", ptr(x), ptr(y), ptr(logdet), ptr(perm), ptr(lower_entries), ptr(upper_entries),
-           ptr(unconstrained_upper_diag), ptr(bias), B, D, eps, direction, acc, L.dtype_code(x), L.stream())
+    L.call("nf_lu_linear_permute", ptr(x), ptr(y), ptr(logdet), ptr(perm.contiguous()), _cptr(lower_entries), _cptr(upper_entries),
+           _cptr(unconstrained_upper_diag), _cptr(bias), B, D, eps, direction, acc, L.dtype_code(x), L.stream())
     return y, logdet
 
 
@@ -125,11 +150,19 @@ def _mask_rows(z, b):
     return B, inner, bb.contiguous().view(-1)
 
 
+def _masked_affine_counts(entry, B, inner, bb, s, t, gy=None, logdet=None):
+    L.check_count(entry, "b", bb, inner, "elements of one sample")
+    for name, a in (("s", s), ("t", t), ("gy", gy)):
+        L.check_count(entry, name, a, B * inner, "B * inner = %d * %d: the shape of z" % (B, inner))
+    L.check_count(entry, "logdet", logdet, B, "B")
+
+
 def masked_affine(z, b, s, t, direction, logdet=None, acc=None):
     """affine/coupling.py:209-229.  b broadcastable to z.shape[1:]; s, t same shape as z or None."""
-    L.require_device(z, b, s, t)
+    L.require_device(z, s, t, logdet, also=(b,))      # (b: converted to z.dtype by _mask_rows)
     z = z.contiguous()
     B, inner, bb = _mask_rows(z, b)
+    _masked_affine_counts("masked_affine", B, inner, bb, s, t, logdet=logdet)
     vec = z.dtype == torch.float32 and inner <= 256 and inner % 4 == 0     # (the four-elements-per-lane kernel)
     z, bb = _a16(z, vec), _a16(bb, vec)
     y = torch.empty_like(z)
@@ -141,14 +174,23 @@ def masked_affine(z, b, s, t, direction, logdet=None, acc=None):
     return y, logdet
 
 
+def _affine_coupling_counts(entry, B, Cc, c1, HW, scale_map, param, param_bias=None, gy=None, logdet=None):
+    P = L.coupling_param_channels(Cc, c1, scale_map)
+    L.check_count(entry, "param", param, B * P * HW, "B * P * HW = %d * %d * %d, P from C = %d, c1 = %d, scale_map = %r" % (B, P, HW, Cc, c1, scale_map))
+    L.check_count(entry, "param_bias", param_bias, P, "P")
+    L.check_count(entry, "gy", gy, B * Cc * HW, "B * C * HW")
+    L.check_count(entry, "logdet", logdet, B, "B")
+
+
 def affine_coupling(z, param, c1, flip, scale_map, direction, logdet=None, acc=None, param_bias=None):
     """affine/coupling.py:117-171 + channel Split/Merge.  z (B, C, *spatial), param (B, P, *spatial); param_bias (P)
     is added to param inside the kernel (bias of a bias-free last convolution)."""
-    L.require_device(z, param, param_bias)
+    L.require_device(z, param, param_bias, logdet)
     z = z.contiguous()
     param = param.contiguous()
     B, Cc = z.shape[:2]
     HW = int(math.prod(z.shape[2:])) if z.dim() > 2 else 1
+    _affine_coupling_counts("affine_coupling", B, Cc, c1, HW, scale_map, param, param_bias, logdet=logdet)
     y = torch.empty_like(z)
     logdet, acc = _ld_buffer(logdet, acc, B, z)
     L.call("nf_affine_coupling_pb", ptr(z), ptr(param), _cptr(param_bias), ptr(y), ptr(logdet), B, Cc, c1, int(flip), HW,
@@ -156,12 +198,20 @@ def affine_coupling(z, param, c1, flip, scale_map, direction, logdet=None, acc=N
     return y, logdet
 
 
+def _actnorm_counts(entry, B, Cc, s, t, gy=None, n_gy=0, logdet=None):
+    L.check_count(entry, "s", s, Cc, "C: one per channel")
+    L.check_count(entry, "t", t, Cc, "C: one per channel")
+    L.check_count(entry, "gy", gy, n_gy, "B * C * HW")
+    L.check_count(entry, "logdet", logdet, B, "B")
+
+
 def actnorm(z, s, t, direction, logdet=None, acc=None, want_scalar=True):
     """affine/coupling.py:38-54 with s, t of C elements (shape (1,C,1,..,1) flattened)."""
-    L.require_device(z, s, t)
+    L.require_device(z, s, t, logdet)
     z = z.contiguous()
     B, Cc = z.shape[:2]
     HW = int(math.prod(z.shape[2:])) if z.dim() > 2 else 1
+    _actnorm_counts("actnorm", B, Cc, s, t, logdet=logdet)
     y = torch.empty_like(z)
     lds = torch.empty((), dtype=z.dtype, device=z.device) if want_scalar else None
     L.call("nf_actnorm", ptr(z), ptr(s.contiguous().view(-1)), ptr(t.contiguous().view(-1)), ptr(y), ptr(lds), ptr(logdet), B, Cc,
@@ -182,6 +232,12 @@ def actnorm_stats(z):
 
 def actnorm_init(mean, std, s_out, t_out, direction):
     L.require_device(mean, std, s_out, t_out)
+    Cc = mean.numel()
+    for name, a in (("std", std), ("s_out", s_out), ("t_out", t_out)):
+        L.check_count("actnorm_init", name, a, Cc, "C = mean.numel()")
+    if not (s_out.is_contiguous() and t_out.is_contiguous()):
+        raise ValueError("actnorm_init: s_out / t_out are written in place: contiguous tensors")
+    mean, std = mean.contiguous(), std.contiguous()
     L.call("nf_actnorm_init", ptr(mean), ptr(std), ptr(s_out), ptr(t_out), mean.numel(), direction, L.dtype_code(mean),
            L.stream())
 
@@ -226,7 +282,7 @@ def _ptr_array(tensors):
 
 def ld_fold_multi(ld, terms, negate):
     """nf_ld_fold_multi: ld (B) float32 updated IN PLACE with the (B) terms in order (negate[i]: subtracted)."""
-    L.require_device(ld, *terms)
+    L.require_device(ld, *terms, dtype=torch.float32)
     if ld.dtype != torch.float32 or not ld.is_contiguous() or any(t.dtype != torch.float32 or t.shape != ld.shape for t in terms):
         raise NotImplementedError("ld_fold_multi: contiguous float32 vectors of one length")
     terms = [t.contiguous() for t in terms]
@@ -241,7 +297,7 @@ def inv1x1_assemble_multi(layers):
     n = len(layers)
     Cc = layers[0][1].shape[0]
     for tup in layers:
-        L.require_device(*tup)
+        L.require_device(*tup, dtype=torch.float32)
         if tup[1].shape != (Cc, Cc) or tup[1].dtype != torch.float32:
             raise NotImplementedError("inv1x1_assemble_multi: float32 layers of one size")
     dev = layers[0][1].device
@@ -263,7 +319,7 @@ def inv1x1_lu_grads_multi(layers, gWs, gls):
     cols = [[t.contiguous() for t in tup] for tup in layers]
     gWs = [g.contiguous() for g in gWs]
     gls = [None if g is None else g.contiguous() for g in gls]
-    L.require_device(*gWs)
+    L.require_device(*gWs, *gls, *[t for c in cols for t in c], dtype=torch.float32)
     gL = torch.empty(n, Cc, Cc, dtype=torch.float32, device=dev)
     gU = torch.empty(n, Cc, Cc, dtype=torch.float32, device=dev)
     gs = torch.empty(n, Cc, dtype=torch.float32, device=dev)
@@ -274,11 +330,19 @@ def inv1x1_lu_grads_multi(layers, gWs, gls):
     return list(zip(gLs, gUs, gss))
 
 
+def _inv1x1_counts(entry, B, Cc, W, bias=None, logdet_unit=None, logdet=None):
+    L.check_count(entry, "W", W, Cc * Cc, "C x C")
+    L.check_count(entry, "bias", bias, Cc, "C")
+    L.check_count(entry, "logdet_unit", logdet_unit, 1, "one value: log|det W| per pixel")
+    L.check_count(entry, "logdet", logdet, B, "B")
+
+
 def inv1x1_conv(z, W, logdet_unit, logdet=None, acc=None, want_scalar=True, bias=None):
-    L.require_device(z, W, logdet_unit, bias)
+    L.require_device(z, W, logdet_unit, bias, logdet)
     z = z.contiguous()
     B, Cc = z.shape[:2]
     HW = int(math.prod(z.shape[2:]))
+    _inv1x1_counts("inv1x1_conv", B, Cc, W, bias, logdet_unit, logdet)
     y = torch.empty_like(z)
     lds = torch.empty((), dtype=z.dtype, device=z.device) if want_scalar else None
     L.call("nf_inv1x1_conv_affine", ptr(z), ptr(W.contiguous()), _cptr(bias), ptr(logdet_unit), ptr(y), ptr(lds), ptr(logdet), B,
@@ -292,6 +356,7 @@ def inv1x1_conv_t(z, W):
     z = z.contiguous()
     B, Cc = z.shape[:2]
     HW = int(math.prod(z.shape[2:]))
+    _inv1x1_counts("inv1x1_conv_t", B, Cc, W)
     y = torch.empty_like(z)
     L.call("nf_inv1x1_conv_t", ptr(z), ptr(W.contiguous()), ptr(y), B, Cc, HW, L.dtype_code(z), L.stream())
     return y
@@ -300,9 +365,10 @@ def inv1x1_conv_t(z, W):
 # ---- backward of the affine family (csrc/affine_bwd.hip): closed-form vector-Jacobian products ------------------------
 def masked_affine_bwd(z, b, s, t, gy, gld, direction):
     """(gz, gs, gt) of nf_masked_affine for cotangents gy (like z) and gld (B) -- coupling.py:209-229 under autograd."""
-    L.require_device(z, b, s, t, gy, gld)
+    L.require_device(z, s, t, gy, gld, also=(b,))     # (b: converted to z.dtype by _mask_rows)
     z, gy = z.contiguous(), gy.contiguous()
     B, inner, bb = _mask_rows(z, b)
+    _masked_affine_counts("masked_affine_bwd", B, inner, bb, s, t, gy=gy, logdet=gld)
     gz = torch.empty_like(z)
     gs = None if s is None else torch.empty_like(z)
     gt = None if t is None else torch.empty_like(z)
@@ -317,6 +383,7 @@ def affine_coupling_bwd(z, param, gy, gld, c1, flip, scale_map, direction):
     z, param, gy = z.contiguous(), param.contiguous(), gy.contiguous()
     B, Cc = z.shape[:2]
     HW = int(math.prod(z.shape[2:])) if z.dim() > 2 else 1
+    _affine_coupling_counts("affine_coupling_bwd", B, Cc, c1, HW, scale_map, param, gy=gy, logdet=gld)
     gz, gp = torch.empty_like(z), torch.empty_like(param)
     L.call("nf_affine_coupling_bwd", ptr(z), ptr(param), ptr(gy), _cptr(gld), ptr(gz), ptr(gp), B, Cc, c1, int(flip), HW,
            L.SCALE[scale_map], direction, L.dtype_code(z), L.stream())
@@ -329,6 +396,7 @@ def actnorm_bwd(z, s, t, gy, gld, direction):
     z, gy = z.contiguous(), gy.contiguous()
     B, Cc = z.shape[:2]
     HW = int(math.prod(z.shape[2:])) if z.dim() > 2 else 1
+    _actnorm_counts("actnorm_bwd", B, Cc, s, t, gy=gy, n_gy=z.numel(), logdet=gld)
     vec = z.dtype == torch.float32 and HW % 4 == 0
     z, gy = _a16(z, vec), _a16(gy, vec)
     gz = torch.empty_like(z)
@@ -344,7 +412,7 @@ def actnorm_bwd(z, s, t, gy, gld, direction):
 
 def rows_matvec(x, W):
     """y_b = W x_b for every row of x (B, D) float32, D <= 128 (nf_rows_matvec, csrc/rows_matvec.hip)."""
-    L.require_device(x, W)
+    L.require_device(x, dtype=torch.float32, also=(W,))      # (W: converted to float32 below)
     if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] > 128:
         raise NotImplementedError("rows_matvec: (B, D <= 128) float32")
     x = _a16(x.contiguous(), x.shape[1] in (64, 128))
@@ -356,7 +424,7 @@ def rows_matvec(x, W):
 def rows_block(x, M1, c1, M2, c2, trans=False, mask1=None, mask2=None, relu=True):
     """(out1, out2) of nf_rows_block: out1 = mask1(M1 pre(x) + c1), out2 = x + mask2(M2 pre(out1) + c2); (B, H <= 128)
     float32.  trans: M1 / M2 are used transposed (the block's backward); relu: pre = ReLU on both products."""
-    L.require_device(x, M1, c1, M2, c2, mask1, mask2)
+    L.require_device(x, M1, c1, M2, c2, mask1, mask2, dtype=torch.float32)
     x = _a16(x.contiguous())
     B, H = x.shape
     if x.dtype != torch.float32 or H > 128 or H % 4:
@@ -373,7 +441,7 @@ def rows_block(x, M1, c1, M2, c2, trans=False, mask1=None, mask2=None, relu=True
 def lu_compose(perm, lower_entries, upper_entries, unconstrained_upper_diag, bias, eps=1e-3):
     """LULinearPermute as dense matrices (nf_lu_compose): (Wd, Ws, bias_d, bias_s, log|det| (1-element)) views of one
     buffer; float32, D <= 64."""
-    L.require_device(perm, lower_entries, upper_entries, unconstrained_upper_diag, bias)
+    L.require_device(perm, lower_entries, upper_entries, unconstrained_upper_diag, bias, dtype=torch.float32)
     D = bias.numel()
     out = torch.empty(2 * D * D + 2 * D + 1, dtype=torch.float32, device=bias.device)
     L.call("nf_lu_compose", ptr(perm), ptr(lower_entries.contiguous()), ptr(upper_entries.contiguous()),
@@ -384,7 +452,7 @@ def lu_compose(perm, lower_entries, upper_entries, unconstrained_upper_diag, bia
 
 def lu_factors(perm, lower_entries, upper_entries, unconstrained_upper_diag, eps=1e-3):
     """(L, U, Up, diag, log|det| (1-element), L^T, Up^T) of LULinearPermute's factors in one launch (nf_lu_factors); float32."""
-    L.require_device(perm, lower_entries, upper_entries, unconstrained_upper_diag)
+    L.require_device(perm, lower_entries, upper_entries, unconstrained_upper_diag, dtype=torch.float32)
     D = unconstrained_upper_diag.numel()
     out = torch.empty(5 * D * D + D + 1, dtype=torch.float32, device=unconstrained_upper_diag.device)
     L.call("nf_lu_factors", ptr(perm), ptr(lower_entries.contiguous()), ptr(upper_entries.contiguous()),
@@ -402,14 +470,14 @@ def lu_factors_views(out, D):
 
 def lu_factors_multi(table, n_layers, eps, D):
     """nf_lu_factors for n_layers layers in one launch; table: (n_layers x 5) int64 device pointers (perm, lower, upper, udiag, out)."""
-    L.require_device(table)
+    L.require_device(table, dtype=torch.float32)
     L.call("nf_lu_factors_multi", ptr(table), n_layers, eps, D, L.stream())
 
 
 def rqs_fused_pack_all_multi(table, n_layers, num_blocks, tail_bound=3.0, min_bin_width=1e-3, min_bin_height=1e-3,
                              min_derivative=1e-3):
     """nf_rqs_fused_pack_all for n_layers layers in one launch; table: (n_layers x (11 + 4 num_blocks)) int64 device pointers."""
-    L.require_device(table)
+    L.require_device(table, dtype=torch.float32)
     L.call("nf_rqs_fused_pack_all_multi", ptr(table), n_layers, 128, num_blocks, 8, tail_bound, min_bin_width, min_bin_height,
            min_derivative, L.stream())
 
@@ -418,7 +486,7 @@ def lu_param_grads(gL, gU, gld, unconstrained_upper_diag, n_tri, eps=1e-3, sign=
     """(g_lower, g_upper, g_udiag) from the dense factor gradients (nf_lu_param_grads); float32.  gld: the (B) log-det
     cotangent (summed inside the launch) or None; perm: gU's columns are read through it (gU = (gu^T x)[:, perm]);
     out: (g_lower, g_upper, g_udiag) destinations written in place (contiguous float32) instead of new tensors."""
-    L.require_device(gL, gU, gld, unconstrained_upper_diag, perm)
+    L.require_device(gL, gU, gld, unconstrained_upper_diag, perm, dtype=torch.float32)
     if gld is not None:
         gld = gld.contiguous()
     D = unconstrained_upper_diag.numel()
@@ -440,7 +508,7 @@ def lu_param_grads(gL, gU, gld, unconstrained_upper_diag, n_tri, eps=1e-3, sign=
 
 def rows_matvec_affine(x, W, bias, ld_const=None, ld_sign=1.0, logdet=None, acc=None):
     """y_b = W x_b + bias and logdet[b] (acc) ld_sign * ld_const (nf_rows_matvec_affine); (B, D <= 128) float32."""
-    L.require_device(x, W, bias, ld_const, logdet)
+    L.require_device(x, W, bias, ld_const, logdet, dtype=torch.float32)
     x = _a16(x.contiguous(), x.shape[1] in (64, 128))
     B, D = x.shape
     y = torch.empty_like(x)
@@ -452,7 +520,7 @@ def rows_matvec_affine(x, W, bias, ld_const=None, ld_sign=1.0, logdet=None, acc=
 
 def rows_matvec2(x, W1, W2, bias=None, ld_const=None, ld_sign=1.0, logdet=None, acc=None, want_u=True):
     """(u, y, logdet): u_b = W1 x_b, y_b = W2 u_b + bias in one launch (nf_rows_matvec2); (B, D <= 64) float32."""
-    L.require_device(x, W1, W2, bias, ld_const, logdet)
+    L.require_device(x, W1, W2, bias, ld_const, logdet, dtype=torch.float32)
     x = _a16(x.contiguous(), x.shape[1] == 64)
     B, D = x.shape
     u = torch.empty_like(x) if want_u else None
@@ -482,10 +550,12 @@ def inv1x1_wgrad(z, gy, gld):
 
 def diag_gaussian_log_prob(z, loc, log_scale, log_scale_shift=0.0, out=None, acc=None):
     """distributions/base.py:94-103."""
-    L.require_device(z, loc, log_scale)
+    L.require_device(z, loc, log_scale, out)
     z = z.contiguous()
     B = z.shape[0]
     d = int(math.prod(z.shape[1:]))
+    for name, a, n in (("loc", loc, d), ("log_scale", log_scale, d), ("out", out, B)):
+        L.check_count("diag_gaussian_log_prob", name, a, n, "d = %d elements per sample of z %s; out: B" % (d, tuple(z.shape)))
     vec = z.dtype == torch.float32 and d <= 256 and d % 4 == 0      # (the four-elements-per-lane kernel)
     z = _a16(z, vec)
     out, acc = _ld_buffer(out, acc, B, z)
@@ -513,7 +583,7 @@ def rqs_fused_supported(nI, nT, hidden, num_blocks, K):
 def rqs_fused_pack(w_init, b_init, w_blocks, b_blocks, w_final, b_final, uw, uh, ud, K, tail_bound, min_bin_width,
                    min_bin_height, min_derivative):
     """Re-lay-out one layer's weights in MFMA operand order (nf_rqs_fused_pack).  Returns the packed device blob."""
-    L.require_device(w_init, b_init, w_final, b_final, uw, uh, ud, *w_blocks, *b_blocks)
+    L.require_device(w_init, b_init, w_final, b_final, uw, uh, ud, *w_blocks, *b_blocks, dtype=torch.float32)
     hidden, nI = w_init.shape
     nT = uw.shape[0]
     nb = len(w_blocks) // 2
@@ -533,7 +603,7 @@ def rqs_fused_pack(w_init, b_init, w_blocks, b_blocks, w_final, b_final, uw, uh,
 
 def rqs_fused_pack_lu(blob, num_blocks, perm, lower_entries, upper_entries, unconstrained_upper_diag, bias, eps=1e-3, K=8):
     """Add the layer's LULinearPermute (composed dense 64 x 64 matrices, both directions) to a packed blob of K bins."""
-    L.require_device(blob, perm, lower_entries, upper_entries, unconstrained_upper_diag, bias)
+    L.require_device(blob, perm, lower_entries, upper_entries, unconstrained_upper_diag, bias, dtype=torch.float32)
     D = bias.numel()
     L.call("nf_rqs_fused_pack_lu", ptr(blob), num_blocks, ptr(perm), ptr(lower_entries.contiguous()),
            ptr(upper_entries.contiguous()), ptr(unconstrained_upper_diag.contiguous()), ptr(bias.contiguous()), D, eps, K,
@@ -546,7 +616,7 @@ def _rqs_fused_launch(name, x, blobs, parities, hidden, num_blocks, K, direction
     """The shared body of rqs_fused[_x3][_chain], `name` the entry point: one layer (blobs a tensor, parities its mask parity) or a chain
     (lists of both, in processing order); padded_rows: rows must have 64 columns, of which live_d are in use."""
     chain = not torch.is_tensor(blobs)
-    L.require_device(x, *(blobs if chain else [blobs]))
+    L.require_device(x, *(blobs if chain else [blobs]), dtype=torch.float32)
     if x.dtype != torch.float32:
         raise TypeError("%s is fp32 only" % name)
     x = _a16(x.contiguous())
@@ -583,8 +653,8 @@ def rqs_coupling_bwd(x, grad_y, grad_logdet, cond, uw, uh, ud, identity_idx, tra
                                        min_bin_width, min_bin_height, min_derivative, wh_div, tails_t, bound_t, tails_i, bound_i)
         if out is not None:
             return out
-    L.require_device(x, grad_y, grad_logdet, cond, uw, uh, ud, identity_idx, transform_idx, tails_t, bound_t, tails_i,
-                     bound_i)
+    # (tails_* / bound_*: converted to int32 / x.dtype by _tails_args)
+    L.require_device(x, grad_y, grad_logdet, cond, uw, uh, ud, also=(identity_idx, transform_idx, tails_t, bound_t, tails_i, bound_i))
     B, D = x.shape
     x, grad_y, grad_logdet = x.contiguous(), grad_y.contiguous(), grad_logdet.contiguous()
     cond = None if cond is None else cond.contiguous()
@@ -595,6 +665,7 @@ def rqs_coupling_bwd(x, grad_y, grad_logdet, cond, uw, uh, ud, identity_idx, tra
     guh = torch.zeros_like(uh) if uh is not None else None
     gud = torch.zeros_like(ud) if ud is not None else None
     ft, code, bound, feat = _tails_args(x, tails, tail_bound, tails_t, bound_t, tails_i, bound_i)
+    _rqs_coupling_counts("rqs_coupling_bwd", B, D, K, code, cond, uw, uh, ud, identity_idx, transform_idx, grad_y, grad_logdet)
     L.call("nf_rqs_coupling_bwd" + ft, ptr(x), ptr(grad_y), ptr(grad_logdet), ptr(cond), ptr(uw), ptr(uh), ptr(ud),
            ptr(identity_idx), identity_idx.numel(), ptr(transform_idx), transform_idx.numel(), B, D, K, code, bound,
            min_bin_width, min_bin_height, min_derivative, wh_div, mode, ptr(gx), ptr(gcond), ptr(guw), ptr(guh), ptr(gud),
@@ -620,8 +691,10 @@ def rqs_coupling_bwd_ft_wave(x, grad_y, grad_logdet, cond, uw, uh, ud, identity_
     (nf_rqs_coupling_bwd_ft_wave, csrc/rqs_bwd_ft.hip): (gx, gcond, guw, guh, gud), or None when the kernel declines the shape (its
     tile does not fit the LDS) -- nothing was allocated or launched then.  gx and gcond are deterministic, the batch-shared parameters' gradients
     come through fp32 atomics."""
-    L.require_device(x, grad_y, grad_logdet, cond, uw, uh, ud, identity_idx, transform_idx, tails_t, bound_t, tails_i, bound_i)
+    # (tails_* / bound_*: converted to int32 / x.dtype by _tails_args)
+    L.require_device(x, grad_y, grad_logdet, cond, uw, uh, ud, also=(identity_idx, transform_idx, tails_t, bound_t, tails_i, bound_i))
     B, D = x.shape
+    _rqs_coupling_counts("rqs_coupling_bwd_ft_wave", B, D, K, 3, cond, uw, uh, ud, identity_idx, transform_idx, grad_y, grad_logdet)
     if not _ft_wave_fits(identity_idx.numel(), transform_idx.numel()):      # (decided before anything is allocated)
         return None
     x, grad_y, grad_logdet = x.contiguous(), grad_y.contiguous(), grad_logdet.contiguous()
@@ -632,8 +705,8 @@ def rqs_coupling_bwd_ft_wave(x, grad_y, grad_logdet, cond, uw, uh, ud, identity_
     guh = torch.zeros_like(uh) if uh is not None else None
     gud = torch.zeros_like(ud) if ud is not None else None
     _, code, bound, feat = _tails_args(x, "feature", tail_bound, tails_t, bound_t, tails_i, bound_i)
-    rc = L.lib().nf_rqs_coupling_bwd_ft_wave(
-        ptr(x), ptr(grad_y), ptr(grad_logdet), ptr(cond), ptr(uw), ptr(uh), ptr(ud), ptr(identity_idx), identity_idx.numel(),
+    rc = L.call_rc(
+        "nf_rqs_coupling_bwd_ft_wave", ptr(x), ptr(grad_y), ptr(grad_logdet), ptr(cond), ptr(uw), ptr(uh), ptr(ud), ptr(identity_idx), identity_idx.numel(),
         ptr(transform_idx), transform_idx.numel(), B, D, K, code, bound, min_bin_width, min_bin_height, min_derivative, wh_div, mode,
         ptr(gx), ptr(gcond), ptr(guw), ptr(guh), ptr(gud), L.dtype_code(x), *map(ptr, feat), L.stream())
     if rc == L.ENOTSUP:
@@ -653,7 +726,7 @@ def rqs_fused_train_blob(num_blocks, device):
 
 def rqs_fused_pack_final(blob, w_final, b_final, uw, uh, ud, num_blocks, tail_bound=3.0, min_bin_width=1e-3,
                          min_bin_height=1e-3, min_derivative=1e-3):
-    L.require_device(blob, w_final, b_final, uw, uh, ud)
+    L.require_device(blob, w_final, b_final, uw, uh, ud, dtype=torch.float32)
     L.call("nf_rqs_fused_pack_final", ptr(blob), ptr(w_final.contiguous()), ptr(b_final.contiguous()), ptr(uw.contiguous()),
            ptr(uh.contiguous()), ptr(ud.contiguous()), 128, num_blocks, 8, tail_bound, min_bin_width, min_bin_height,
            min_derivative, L.stream())
@@ -686,7 +759,7 @@ def rqs_fused_train_fwd(x, h2, blob, mask_parity, num_blocks, tail_bound=3.0, mi
 def rqs_fused_pack_all(blob, w_init, b_init, w_blocks, b_blocks, w_final, b_final, uw, uh, ud, tail_bound=3.0, min_bin_width=1e-3,
                        min_bin_height=1e-3, min_derivative=1e-3, wfull=None, wpad=None, identity_idx=None):
     """The whole layer's blob (no LU) in one launch (nf_rqs_fused_pack_all); hidden 128, 8 bins."""
-    L.require_device(blob, w_init, b_init, w_final, b_final, uw, uh, ud, wfull, wpad, identity_idx, *w_blocks, *b_blocks)
+    L.require_device(blob, w_init, b_init, w_final, b_final, uw, uh, ud, wfull, wpad, identity_idx, *w_blocks, *b_blocks, dtype=torch.float32)
     n = len(w_blocks)
     wp, bp = _ptr_array(w_blocks), _ptr_array(b_blocks)
     L.call("nf_rqs_fused_pack_all", ptr(blob), ptr(w_init), ptr(b_init), wp, bp, ptr(w_final), ptr(b_final), ptr(uw), ptr(uh),
@@ -714,7 +787,7 @@ def _spline_grad_views(alloc, uw, uh, ud):
 def rqs_coupling_bwd_p24(x, grad_y, grad_logdet, cond24, uw, uh, ud, identity_idx, transform_idx, tail_bound=3.0,
                          min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3, wh_div=1.0):
     """rqs_coupling_bwd (density direction) on the 24-float rows of rqs_fused_train_fwd.  Returns (gx, gcond24, guw, guh, gud)."""
-    L.require_device(x, grad_y, grad_logdet, cond24, uw, uh, ud, identity_idx, transform_idx)
+    L.require_device(x, grad_y, grad_logdet, cond24, uw, uh, ud, identity_idx, transform_idx, dtype=torch.float32)
     B, D = x.shape
     x, grad_y, grad_logdet = x.contiguous(), grad_y.contiguous(), grad_logdet.contiguous()
     cond24 = _a16(cond24.contiguous())      # (the parameter rows are refused when misaligned; x / grad_y only choose the kernel)
@@ -731,7 +804,7 @@ def final_bwd(x, grad_y, grad_logdet, cond24, w_t, blob, uw, uh, ud, mask_parity
               min_bin_height=1e-3, min_derivative=1e-3):
     """(gx, gcond24, gh, guw, guh, gud) of nf_final_bwd + nf_final_bwd_reduce: the coupling transform's backward and the final
     Linear's input gradient in one pass over the rows; the batch-shared parameters' gradients by a fixed-order reduction."""
-    L.require_device(x, grad_y, grad_logdet, cond24, w_t, blob, uw, uh, ud)
+    L.require_device(x, grad_y, grad_logdet, cond24, w_t, blob, uw, uh, ud, dtype=torch.float32)
     B = x.shape[0]
     x, grad_y, grad_logdet = _a16(x.contiguous()), _a16(grad_y.contiguous()), grad_logdet.contiguous()
     cond24, w_t = _a16(cond24.contiguous()), _a16(w_t.contiguous())
@@ -759,7 +832,7 @@ def _train_bwd_operands(who, B, num_blocks, w_blocks, dest, more_keys, device):
     tensors = [dest[k] for k in ("w0", "b0", "wf", "bf", "uw", "uh", "ud") + tuple(more_keys)] + list(dest["blocks"])
     if len(w_blocks) != 2 * num_blocks or len(dest["blocks"]) != 4 * num_blocks:
         raise ValueError("%s: 2 weights and 4 gradient destinations per residual block" % who)
-    L.require_device(*tensors)
+    L.require_device(*tensors, dtype=torch.float32)
     if any(t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
         raise ValueError("%s: gradient destinations must be contiguous float32" % who)
     scratch = torch.empty(n, dtype=torch.float32, device=device)
@@ -777,7 +850,7 @@ def pair_train_bwd(x_in, xlu, grad_y, grad_logdet, cond24, acts, w_t, blob, wful
     run under whatever the current stream does next.  The CALLER joins (`current_stream().wait_stream(side)`) before a gradient in
     `dest` is read; the scratch and the tensors the tail reads are kept from reuse through record_stream."""
     L.require_device(x_in, xlu, grad_y, grad_logdet, cond24, acts, w_t, blob, wfull_t, uw, uh, ud, col_map, Wd, Lm, Um, perm, udiag,
-                     *w_blocks)
+                     *w_blocks, dtype=torch.float32)
     B = x_in.shape[0]
     x_in, xlu, grad_y, grad_logdet = _a16(x_in.contiguous()), _a16(xlu.contiguous()), _a16(grad_y.contiguous()), grad_logdet.contiguous()
     cond24, acts, w_t, wfull_t = (_a16(t.contiguous()) for t in (cond24, acts, w_t, wfull_t))
@@ -807,6 +880,7 @@ def pair_train_bwd(x_in, xlu, grad_y, grad_logdet, cond24, acts, w_t, blob, wful
 
 def lu_pack_train_multi(table, n_layers, num_blocks, eps, D=64):
     """The LU stage of n training blobs + the composed matrices for the backward in one launch (nf_lu_pack_train_multi)."""
+    L.require_device(table, dtype=torch.float32)
     L.call("nf_lu_pack_train_multi", ptr(table), n_layers, num_blocks, D, eps, L.stream())
 
 
@@ -823,7 +897,7 @@ def rqs_fused_train_pair_fwd(x, blob, mask_parity, num_blocks, tail_bound=3.0, m
 
 def lu_bwd_composed(g, x, Wd, db_out=None):
     """(gx, dWd, db) of the composed LULinearPermute's backward, D = 64 (nf_lu_bwd_composed): gx = g Wd, dWd = g^T x, db = colsum(g)."""
-    L.require_device(g, x, Wd, db_out)
+    L.require_device(g, x, Wd, db_out, dtype=torch.float32)
     g, x, Wd = _a16(g.contiguous()), _a16(x.contiguous()), Wd.contiguous()
     B, D = g.shape
     n = L.query("nf_lu_bwd_composed_scratch_floats", B)
@@ -842,7 +916,7 @@ def lu_bwd_composed(g, x, Wd, db_out=None):
 
 def lu_param_grads_composed(dWd, Lm, Um, perm, gld, unconstrained_upper_diag, n_tri, eps=1e-3, out=None):
     """(g_lower, g_upper, g_udiag) from the composed matrix's gradient (nf_lu_param_grads_composed); out: destinations."""
-    L.require_device(dWd, Lm, Um, perm, gld, unconstrained_upper_diag)
+    L.require_device(dWd, Lm, Um, perm, gld, unconstrained_upper_diag, dtype=torch.float32)
     D = unconstrained_upper_diag.numel()
     dev = dWd.device
     if gld is not None:
@@ -868,7 +942,7 @@ def coupling_train_bwd(x, grad_y, grad_logdet, cond24, acts, w_t, blob, wfull_t,
     and ONE reduction launch.  w_blocks: [W1, W2] per residual block; dest: the gradient destinations, written in place --
     dict(w0, b0, wf, bf, uw, uh, ud, blocks=[gW1, gb1, gW2, gb2 per block]) of contiguous float32 tensors of the parameters'
     shapes (any addresses: fresh tensors or views of one flat gradient buffer).  Returns grad_x."""
-    L.require_device(x, grad_y, grad_logdet, cond24, acts, w_t, blob, wfull_t, uw, uh, ud, col_map, *w_blocks)
+    L.require_device(x, grad_y, grad_logdet, cond24, acts, w_t, blob, wfull_t, uw, uh, ud, col_map, *w_blocks, dtype=torch.float32)
     B = x.shape[0]
     x, grad_y, grad_logdet = _a16(x.contiguous()), _a16(grad_y.contiguous()), grad_logdet.contiguous()
     cond24, acts, w_t, wfull_t = (_a16(t.contiguous()) for t in (cond24, acts, w_t, wfull_t))
@@ -885,7 +959,7 @@ def coupling_train_bwd(x, grad_y, grad_logdet, cond24, acts, w_t, blob, wfull_t,
 # ---- bf16x3 (error-compensated split-bf16 MFMA) variant of the fused layer ----------------------------------------
 def rqs_fused_x3_pack(f32_blob, num_blocks, has_lu, nI=32, nT=32, hidden=128, K=8):
     """Derive the split-bf16 weight blob from an rqs_fused_pack blob of the same layer (nf_rqs_fused_x3_pack)."""
-    L.require_device(f32_blob)
+    L.require_device(f32_blob, dtype=torch.float32)
     size = L.query("nf_rqs_fused_x3_pack_size", nI, nT, hidden, num_blocks, K)
     if size <= 0:
         raise NotImplementedError("nf_rqs_fused_x3: shape not supported")
@@ -916,7 +990,7 @@ def conv3x3_gather(x, flip=False, ld=None):
     """col (B H W, 9 C) of an NCHW float32 tensor: col[r][tap C + c] = x[b][c][y + dy][x + dx] (nf_conv3x3_gather); flip negates the
     offsets.  ld: row length of the returned buffer (>= 9 C; rows rounded up to 64: the layout the MADE training kernels' weight
     gradients read directly) -- columns beyond 9 C are not written, rows beyond B H W are zero."""
-    L.require_device(x)
+    L.require_device(x, dtype=torch.float32)
     if x.dtype != torch.float32 or x.dim() != 4:
         raise NotImplementedError("conv3x3_gather: (B, C, H, W) float32")
     B, C, H, W = x.shape
@@ -936,7 +1010,7 @@ def conv3x3_gather(x, flip=False, ld=None):
 def conv3x3_gather_sum(P, bias, shape, flip=False):
     """(B, C, H, W) from per-pixel tap products P (B H W, 9 C): out[b][c][y][x] = bias[c] + sum_tap P[(b, y + dy, x + dx)][tap C + c]
     (nf_conv3x3_gather_sum); flip negates the offsets."""
-    L.require_device(P, bias)
+    L.require_device(P, bias, dtype=torch.float32)
     B, C, H, W = shape
     P = P.contiguous()
     if P.dtype != torch.float32 or P.dim() != 2 or P.shape[0] < B * H * W or P.shape[1] < 9 * C:
@@ -948,7 +1022,7 @@ def conv3x3_gather_sum(P, bias, shape, flip=False):
 
 def channel_sum(g):
     """(C) = g (B, C, H, W).sum((0, 2, 3)) in one launch with a fixed summation order (nf_channel_sum)."""
-    L.require_device(g)
+    L.require_device(g, dtype=torch.float32)
     g = g.contiguous()
     if g.dtype != torch.float32 or g.dim() != 4:
         raise ValueError("channel_sum: a float32 (B, C, H, W) tensor")
@@ -1000,7 +1074,7 @@ def rqs_fused_x3_chain(x, blobs, parities, hidden, num_blocks, K, direction, log
 
 def nsf_wide_tables(uw, uh, ud, K, tail_bound, min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3):
     """Knot tables (n_identity, 3 (K + 1)) of the batch-shared spline for nf_nsf_wide (nsf/coupling.py:170-259)."""
-    L.require_device(uw, uh, ud)
+    L.require_device(uw, uh, ud, dtype=torch.float32)
     tabs = torch.empty(uw.shape[0], 3 * (K + 1), dtype=torch.float32, device=uw.device)
     L.call("nf_nsf_wide_tables", ptr(uw.contiguous()), ptr(uh.contiguous()), ptr(ud.contiguous()), ptr(tabs), uw.shape[0], K,
            float(tail_bound), min_bin_width, min_bin_height, min_derivative, L.stream())
@@ -1012,7 +1086,7 @@ def nsf_wide(x, blob, table, tabs, hidden_padded, direction, tail_bound, min_bin
     """CoupledRationalQuadraticSpline beyond the benchmark kernel's shapes as one launch (nf_nsf_wide_k); blob / table from
     flows/nsf_wide_pack.pack_nsf_wide, tabs from nsf_wide_tables (both for K bins: 4 | 8 | 16); lu_logdet: device scalar of the
     LULinearPermute packed with it."""
-    L.require_device(x, blob, table, tabs, lu_logdet)
+    L.require_device(x, blob, table, tabs, lu_logdet, dtype=torch.float32)
     if x.dtype != torch.float32:
         raise NotImplementedError("nsf_wide: float32 only")
     B, D = x.shape
@@ -1039,7 +1113,7 @@ def nsf_wide_ctx(x, context, blob, table, tabs, hidden_padded, direction, tail_b
     flows/nsf_ctx_pack.pack_nsf_ctx (table_host: its host copy, checked against the context's width), tabs from nsf_wide_tables.
     context (B, C) float32: a row stride is passed as it is when the inner stride is 1 (0 for context.expand(B, C)), otherwise the
     context is made contiguous."""
-    L.require_device(x, context, blob, table, tabs)
+    L.require_device(x, context, blob, table, tabs, dtype=torch.float32)
     if x.dtype != torch.float32:
         raise NotImplementedError("nsf_wide_ctx: float32 only")
     B, D = x.shape
@@ -1060,7 +1134,7 @@ def nsf_wide_ctx(x, context, blob, table, tabs, hidden_padded, direction, tail_b
 def nsf_wide_tables_ft(uw, uh, ud, tails_i, bound_i, K, min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3):
     """Knot tables (n_identity, 3 (K + 1)) of the batch-shared spline under list tails for nf_nsf_wide_ft: derivatives
     (n_identity, K + 1), tails_i int32 / bound_i float32 (n_identity,) per identity feature (utils/splines.py:48-66)."""
-    L.require_device(uw, uh, ud, tails_i, bound_i)
+    L.require_device(uw, uh, ud, tails_i, bound_i, dtype=torch.float32)
     nI = uw.shape[0]
     if tuple(ud.shape) != (nI, K + 1) or tails_i.numel() != nI or bound_i.numel() != nI:
         raise ValueError("nsf_wide_tables_ft: derivatives (%d, %d), tails_i and bound_i (%d,) expected" % (nI, K + 1, nI))
@@ -1075,7 +1149,7 @@ def nsf_wide_ft(x, blob, table, ftable, tabs, hidden_padded, direction, min_bin_
     """CircularCoupledRationalQuadraticSpline as one launch (nf_nsf_wide_ft); blob / table / ftable from
     flows/nsf_circ_pack.pack_nsf_circ (ftable (8, Dp): tails, bounds and periodic features by tile position), tabs from
     nsf_wide_tables_ft."""
-    L.require_device(x, blob, table, ftable, tabs)
+    L.require_device(x, blob, table, ftable, tabs, dtype=torch.float32)
     if x.dtype != torch.float32:
         raise NotImplementedError("nsf_wide_ft: float32 only")
     B, D = x.shape
@@ -1091,7 +1165,7 @@ def resnet_ctx_forward_train(x, context, blob, table, st):
     """The GLU-gated ResidualNet under autograd (nf_resnet_ctx_forward_train): (out (B, O), save) -- save holds what
     resnet_ctx_backward / resnet_ctx_wgrad read.  st: flows/ctx_train_pack.structure; context (B, C) float32 with unit inner stride
     is passed with its row stride (0 for context.expand(B, C))."""
-    L.require_device(x, context, blob, table)
+    L.require_device(x, context, blob, table, dtype=torch.float32)
     if x.dtype != torch.float32 or context.dtype != torch.float32:
         raise NotImplementedError("resnet_ctx_forward_train: float32 only")
     B = x.shape[0]
@@ -1111,7 +1185,7 @@ def resnet_ctx_forward_train(x, context, blob, table, st):
 def resnet_ctx_backward(g_out, save, blob, table, st):
     """Input-gradient chain of the gated ResidualNet (nf_resnet_ctx_backward): (g_x (B, nI), g_context (B, C), G) -- G holds every
     layer's output gradient for resnet_ctx_wgrad."""
-    L.require_device(g_out, save, blob, table)
+    L.require_device(g_out, save, blob, table, dtype=torch.float32)
     B = g_out.shape[0]
     g_out = g_out.contiguous()
     n = L.size("nf_resnet_ctx_grad_floats", B, st["H"], st["NB"])
@@ -1126,7 +1200,7 @@ def resnet_ctx_backward(g_out, save, blob, table, st):
 def resnet_ctx_wgrad(g_out, save, G, table, jobs, st):
     """Every weight / bias gradient of the gated ResidualNet (nf_resnet_ctx_wgrad: one launch over 64 x 64 tiles and row chunks + a
     fixed-order reduction): the flat buffer in the parameter order of flows/ctx_train_pack.params_of."""
-    L.require_device(g_out, save, G, table, jobs)
+    L.require_device(g_out, save, G, table, jobs, dtype=torch.float32)
     B = g_out.shape[0]
     g_out = g_out.contiguous()
     if B == 0:                  # (nothing to reduce: the kernels launch nothing, the gradients are zero)
@@ -1143,7 +1217,7 @@ def resnet_ctx_wgrad(g_out, save, G, table, jobs, st):
 def made_forward_affine(x, blob, table, hidden_padded, logdet=None, acc=None):
     """MaskedAffineAutoregressive.forward (autoregressive.py:24-27, :101-110 over nets/made.py:296-304) as one launch
     (nf_made_forward_affine); blob / table from flows/made_pack.pack_made_forward."""
-    L.require_device(x, blob, table)
+    L.require_device(x, blob, table, dtype=torch.float32)
     if x.dtype != torch.float32:
         raise NotImplementedError("made_forward_affine: float32 only")
     B, D = x.shape
@@ -1158,7 +1232,7 @@ def made_forward_spline(x, blob, table, hidden_padded, tail_bound, min_bin_width
                         logdet=None, acc=None):
     """neural_spline/autoregressive.py:94-134 density direction (MADE + 8-bin spline with linear tails) as one launch
     (nf_made_forward_spline); blob / table from flows/made_pack.pack_made_forward(made, 23, spline=True)."""
-    L.require_device(x, blob, table)
+    L.require_device(x, blob, table, dtype=torch.float32)
     if x.dtype != torch.float32:
         raise NotImplementedError("made_forward_spline: float32 only")
     B, D = x.shape
@@ -1176,7 +1250,7 @@ def made_forward_spline_ft(x, blob, table, ftable, hidden_padded, K, tails, min_
     samples -- permuted masks, per-feature tails ("feature") and bounds, the periodic preprocessing of circular coordinates
     (neural_spline/autoregressive.py:44-55, :94-134; utils/splines.py:48-66; utils/nn.py:64-129); blob / table / ftable from
     flows/made_pack.pack_made_forward_ft."""
-    L.require_device(x, blob, table, ftable)
+    L.require_device(x, blob, table, ftable, dtype=torch.float32)
     if x.dtype != torch.float32:
         raise NotImplementedError("made_forward_spline_ft: float32 only")
     B, D = x.shape
@@ -1192,7 +1266,7 @@ def made_forward_spline_ft(x, blob, table, ftable, hidden_padded, K, tails, min_
 
 def made_forward(x, blob, table, hidden_padded, mult):
     """MADE.forward (nets/made.py:296-304) as one launch (nf_made_forward): (B, mult D) parameters."""
-    L.require_device(x, blob, table)
+    L.require_device(x, blob, table, dtype=torch.float32)
     if x.dtype != torch.float32:
         raise NotImplementedError("made_forward: float32 only")
     B, D = x.shape
@@ -1207,7 +1281,7 @@ _ZERO1 = {}
 
 def pack_gather(params, src):
     """The packed weight streams from the current parameters (nf_pack_gather): flat = [0, params flattened ...], out = flat[src]."""
-    L.require_device(src, *params)
+    L.require_device(src, *params, dtype=torch.float32)
     zero = _ZERO1.get(src.device)
     if zero is None:
         zero = _ZERO1[src.device] = torch.zeros(1, dtype=torch.float32, device=src.device)
@@ -1226,7 +1300,7 @@ def pack_gather(params, src):
 def pack_gather_batch(param_lists, src):
     """nf_pack_gather_batch: [flat_m[src]] for modules m of ONE structure (param_lists[m] = its <= 8 contiguous float32 parameter
     tensors, the same shapes for every module) -- one launch per 32 modules."""
-    L.require_device(src, *[p for pl in param_lists for p in pl])
+    L.require_device(src, *[p for pl in param_lists for p in pl], dtype=torch.float32)
     n_mod, n_par = len(param_lists), len(param_lists[0])
     if n_par > 8 or any(len(pl) != n_par for pl in param_lists):
         raise NotImplementedError("pack_gather_batch: <= 8 parameters per module, the same number for all")
@@ -1246,7 +1320,7 @@ def made_forward_train(x, blob, table, hidden_padded, out_features, num_blocks, 
     """MADE.forward / ResidualNet.forward under autograd (nf_made_forward_train): (params (B, out_features), save (2 NB + 1, Bp, Hp)
     pre-activations, bits (Bp / 64, 2 NB, 2, 512) ReLU signs), Bp = B rounded up to 64 -- the operands of made_backward / made_wgrad.
     out_features = mult D for a MADE (the table's hdr[12])."""
-    L.require_device(x, blob, table)
+    L.require_device(x, blob, table, dtype=torch.float32)
     if x.dtype != torch.float32:
         raise NotImplementedError("made_forward_train: float32 only")
     B, D = x.shape
@@ -1267,7 +1341,7 @@ def made_forward_train_ft(x, blob, table, hidden_padded, out_features, num_block
     gathered through the feature table behind `table` and fed with the periodic features whose live parameters end `blob`): (params
     (B, out_features) in position order, save, bits, x_pad (Bp, 128): the fed inputs as made_wgrad takes them, x_pos (B, D): the raw
     inputs in position order).  64-row tiles: its chain is made_backward(..., tile64=True)."""
-    L.require_device(x, blob, table)
+    L.require_device(x, blob, table, dtype=torch.float32)
     if x.dtype != torch.float32:
         raise NotImplementedError("made_forward_train_ft: float32 only")
     B, D = x.shape
@@ -1287,7 +1361,7 @@ def made_feed_ft_bwd(g_pre, g_xpos, x, ttable, feed, n_circ, has_bias):
     """The backward of made_forward_train_ft's gather + periodic feed (nf_made_feed_ft_bwd): (g_x (B, D) in column order =
     g_pre d + g_xpos scattered through the table, g_weights (n_circ, 2), g_bias (n_circ) or None); g_xpos may be None.  Deterministic:
     per-workgroup partials, fixed-order reduction."""
-    L.require_device(g_pre, g_xpos, x, ttable, feed)
+    L.require_device(g_pre, g_xpos, x, ttable, feed, dtype=torch.float32)
     B, D = x.shape
     g_pre = g_pre.contiguous()
     g_xpos = None if g_xpos is None else g_xpos.contiguous()
@@ -1305,7 +1379,7 @@ def made_backward(g_params, bits, blob, table, D, hidden_padded, num_blocks, row
     """The input-gradient chain of MADE (nf_made_backward): g_x (B, D) and every layer's output gradient G (2 NB + 1, Bp, Hp).
     rows / out_features / ld_out: g_params is a padded buffer (row strides in the table's hdr[14], hdr[15]) and so is the returned
     g_x (rows, ld_out): the conv path.  tile64: nf_made_backward_t64 (the chain of made_forward_train_ft, which has no 128-row tile)."""
-    L.require_device(g_params, bits, blob, table)
+    L.require_device(g_params, bits, blob, table, dtype=torch.float32)
     B = g_params.shape[0] if rows is None else rows
     md = g_params.shape[1] if out_features is None else out_features
     g_params = _a16(g_params.contiguous())
@@ -1333,7 +1407,7 @@ def _made_wgrad_operands(g_params, x, Bp, Mp, Dx, nflat, B, ntiles):
 def made_wgrad(g_params, x, G, save, wtable, stable, mask, ntiles, nflat, Mp, Dx, rows=None):
     """Every weight / bias gradient of the MADE (nf_made_wgrad): the flat vector in flows/made_pack.pack_made_backward's layout,
     masked entries zero."""
-    L.require_device(g_params, x, G, save, wtable, stable, mask)
+    L.require_device(g_params, x, G, save, wtable, stable, mask, dtype=torch.float32)
     B = g_params.shape[0] if rows is None else rows          # (rows: the operands are already padded buffers)
     Bp = G.shape[1]
     gp_pad, x_pad, grads, part = _made_wgrad_operands(g_params, x, Bp, Mp, Dx, nflat, B, ntiles)
@@ -1347,7 +1421,7 @@ def made_wgrad_pos(g_params, x, gscratch, fscratch, wtable, stable, mask, ntiles
     gscratch from maf_solve_t(return_scratch=True), fscratch from maf_inverse_bits(return_scratch=True); tables from
     flows/maf_pack.position_wgrad_tables; mask / nflat / Mp / Dx of the MADE's ordinary backward pack (same flat layout).  The batch must
     be a multiple of 64 rows."""
-    L.require_device(g_params, x, gscratch, fscratch, wtable, stable, mask)
+    L.require_device(g_params, x, gscratch, fscratch, wtable, stable, mask, dtype=torch.float32)
     B = g_params.shape[0]
     if B % 64:
         raise NotImplementedError("made_wgrad_pos: a multiple of 64 rows")
@@ -1368,7 +1442,7 @@ def maf_inverse(z, blob, table, hidden_padded, logdet=None, acc=None, num_blocks
     nf_maf_inverse_h (32 samples per wave, 1..3 residual blocks); otherwise round 2's nf_maf_inverse (two blocks only).
     `table_host`: the host (numpy int32) copy of a FORMAT-1 table (pack_made(tri=True)) -> nf_maf_inverse_h_tri; a format-1 pack
     must come with it (the format-0 entry points cannot read its regular tiles)."""
-    L.require_device(z, blob, table)
+    L.require_device(z, blob, table, dtype=torch.float32)
     if z.dtype != torch.float32:
         raise NotImplementedError("maf_inverse: float32 only")
     from . import config
@@ -1400,7 +1474,7 @@ def maf_inverse_bits(z, blob, table, hidden_padded, num_blocks, tiles, table_hos
     leaves the pass's ReLU masks (uint32 words per 32-row wave, tile and lane, in the pack's positions) for maf_solve_t on a
     transposed pack of the same format.  Returns (y, logdet, bits [, scratch]); want_params (round 6, nf_maf_inverse_h_train): MADE's
     output at the solution, (B, 2 D), is appended."""
-    L.require_device(z, blob, table)
+    L.require_device(z, blob, table, dtype=torch.float32)
     if z.dtype != torch.float32:
         raise NotImplementedError("maf_inverse_bits: float32 only")
     B, D = z.shape
@@ -1430,7 +1504,7 @@ def maf_solve_t(x, params, gx, gld, bits, blob, table, hidden_padded, num_blocks
     """nf_maf_solve_t: v with  v s + J^T g_p(v, g_ld) = g_x  in one pass (the implicit backward of the MAF inverse);
     blob / table from flows/maf_pack.pack_made_transposed.  return_scratch: (v, scratch) -- the activation scratch for
     maf_scratch_rows."""
-    L.require_device(x, params, gx, gld, bits, blob, table)
+    L.require_device(x, params, gx, gld, bits, blob, table, dtype=torch.float32)
     if x.dtype != torch.float32:
         raise NotImplementedError("maf_solve_t: float32 only")
     B, D = x.shape
@@ -1450,7 +1524,7 @@ def maf_solve_t(x, params, gx, gld, bits, blob, table, hidden_padded, num_blocks
 
 def maf_scratch_rows(scratch, pos_of_col, B, num_blocks, hidden_padded, sign=1.0, reverse_layers=False):
     """nf_maf_scratch_rows: the one-pass kernels' activation scratch as (2 num_blocks + 1, Bp, len(pos_of_col)) row-major tensors."""
-    L.require_device(scratch, pos_of_col)
+    L.require_device(scratch, pos_of_col, dtype=torch.float32)
     ldo = pos_of_col.numel()
     Bp = (B + 63) // 64 * 64
     out = torch.empty(2 * num_blocks + 1, Bp, ldo, dtype=torch.float32, device=scratch.device)
@@ -1461,7 +1535,7 @@ def maf_scratch_rows(scratch, pos_of_col, B, num_blocks, hidden_padded, sign=1.0
 
 def maf_scratch_layer(scratch, pos_of_col, B, num_blocks, hidden_padded, layer):
     """nf_maf_scratch_layer: ONE layer of a one-pass kernel's activation scratch as a (Bp, len(pos_of_col)) row-major tensor."""
-    L.require_device(scratch, pos_of_col)
+    L.require_device(scratch, pos_of_col, dtype=torch.float32)
     ldo = pos_of_col.numel()
     Bp = (B + 63) // 64 * 64
     out = torch.empty(Bp, ldo, dtype=torch.float32, device=scratch.device)
@@ -1473,7 +1547,7 @@ def arnsf_inverse(z, blob, table, hidden_padded, K, tails, tail_bound, min_bin_w
                   min_derivative=1e-3, logdet=None, acc=None):
     """neural_spline/autoregressive.py:94-134 inverse over affine/autoregressive.py:29-38 in one pass
     (nf_arnsf_inverse); blob/table from flows/maf_pack.pack_made(made, mult, rows=True)."""
-    L.require_device(z, blob, table)
+    L.require_device(z, blob, table, dtype=torch.float32)
     if z.dtype != torch.float32:
         raise NotImplementedError("arnsf_inverse: float32 only")
     B, D = z.shape
@@ -1491,7 +1565,7 @@ def arnsf_inverse_ft(z, blob, table, ftable, hidden_padded, K, tails, min_bin_wi
     """arnsf_inverse with a per-feature table (nf_arnsf_inverse_ft): permuted masks, per-feature tails ("feature") and bounds and the
     periodic preprocessing of circular coordinates (neural_spline/autoregressive.py:44-55, :94-134; utils/splines.py:48-66;
     utils/nn.py:64-129); blob/table/ftable from flows/maf_pack.pack_made(made, mult, rows=True, features=(tails, tail_bound))."""
-    L.require_device(z, blob, table, ftable)
+    L.require_device(z, blob, table, ftable, dtype=torch.float32)
     if z.dtype != torch.float32:
         raise NotImplementedError("arnsf_inverse_ft: float32 only")
     B, D = z.shape
@@ -1517,7 +1591,7 @@ def glow_convnet_layout(B, H, W):
 
 def glow_convnet_pack(w1, b1, w2, b2, w3, b3, layout=GLOW_CONV_WIDE):
     """Packed weights of a GlowBlock conditioner for glow_convnet (nf_glow_convnet_pack); None for unsupported shapes."""
-    L.require_device(w1, b1, w2, b2, w3, b3)
+    L.require_device(w1, b1, w2, b2, w3, b3, dtype=torch.float32)
     Cin, Cout, hidden = w1.shape[1], w3.shape[0], w1.shape[0]
     size = L.query("nf_glow_convnet_pack_size", Cin, Cout, hidden)
     if size <= 0 or (layout == GLOW_CONV_SMALL and Cout > 48):
@@ -1531,7 +1605,7 @@ def glow_convnet_pack(w1, b1, w2, b2, w3, b3, layout=GLOW_CONV_WIDE):
 def glow_convnet(x, blob, Cout, slope, layout=GLOW_CONV_WIDE, hidden=256):
     """cnn.py:5-63 for the GlowBlock network in one launch (nf_glow_convnet).  x: (B, Cin, H, W), possibly a channel
     slice of a contiguous NCHW tensor (planes contiguous, arbitrary image stride); blob packed for the same layout."""
-    L.require_device(x, blob)
+    L.require_device(x, blob, dtype=torch.float32)
     B, Cin, H, W = x.shape
     if x.dtype != torch.float32 or x.stride(3) != 1 or x.stride(2) != W or x.stride(1) != H * W:
         raise NotImplementedError("glow_convnet: float32 with contiguous (H, W) planes")
@@ -1562,7 +1636,7 @@ def glow_level(in0, in1, in_squeezed, C, H, W, table, nblocks, layout, slope, sc
     in1 (B, C - cin0, H, W) (in1 None: in0 has all C channels).  Output: out_squeezed -> (B, C/4, 2H, 2W) through
     Squeeze.forward; cout0 < C -> two tensors split after cout0 channels; else one (B, C, H, W) tensor.
     Returns (out0, out1 or None, logdet)."""
-    L.require_device(in0, in1, table)
+    L.require_device(in0, in1, table, dtype=torch.float32)
     if in0.dtype != torch.float32 or (in1 is not None and in1.dtype != torch.float32):
         raise NotImplementedError("glow_level: float32 only")
     in0 = in0.contiguous()
@@ -1615,13 +1689,21 @@ def logit(z, alpha, direction, logdet=None, acc=None):
 
 def diag_gaussian_log_prob_rows(z, loc_rows, log_scale_rows, row_idx=None, ls_shift=0.0, out=None, acc=None):
     """distributions/base.py:326-345: one (loc, log_scale) row per sample, picked by `row_idx` (class labels) or row b."""
-    L.require_device(z, loc_rows, log_scale_rows, row_idx)
+    L.require_device(z, loc_rows, log_scale_rows, row_idx, out)
     B = z.shape[0]
     z = z.contiguous()
     d = z[0].numel() if B else int(math.prod(z.shape[1:]))
+    if not L.rows_ok(loc_rows.numel(), log_scale_rows.numel(), d, B, row_idx is not None):
+        raise ValueError("diag_gaussian_log_prob_rows: loc rows (%d elements) and log_scale rows (%d) must be equally many rows of d = %d "
+                         "elements (z %s)%s" % (loc_rows.numel(), log_scale_rows.numel(), d, tuple(z.shape),
+                                                "" if row_idx is not None else ", one row per sample"))
+    L.check_count("diag_gaussian_log_prob_rows", "row_idx", row_idx, B, "B")
+    L.check_count("diag_gaussian_log_prob_rows", "out", out, B, "B")
     loc_rows = loc_rows.contiguous().view(-1, d)
     log_scale_rows = log_scale_rows.contiguous().view(-1, d)
     out, acc = _ld_buffer(out, acc, B, z)
+    if B == 0:          # (an empty batch of blended rows has no row at all, which the entry point refuses: nothing to compute)
+        return out
     if row_idx is not None:
         row_idx = row_idx.to(torch.long).contiguous()
     L.call("nf_diag_gaussian_log_prob_rows", ptr(z), ptr(loc_rows), ptr(log_scale_rows), ptr(row_idx), loc_rows.shape[0],
@@ -1632,7 +1714,7 @@ def diag_gaussian_log_prob_rows(z, loc_rows, log_scale_rows, row_idx=None, ls_sh
 def linear_wgrad(dy, x, want_bias=True, relu_x=False, skip_every=0):
     """dW = dy^T x (x -> relu(x) with relu_x), db = dy.sum(0) for a Linear layer (nf_linear_wgrad[_act|_skip], split-K fp32
     MFMA, deterministic reduction).  skip_every > 1: every skip_every-th column of dy is padding and has no output row."""
-    L.require_device(dy, x)
+    L.require_device(dy, x, dtype=torch.float32)
     if dy.dtype != torch.float32 or x.dtype != torch.float32:
         raise NotImplementedError("linear_wgrad: float32 only")
     dy, x = dy.contiguous(), x.contiguous()
@@ -1650,7 +1732,7 @@ def linear_wgrad(dy, x, want_bias=True, relu_x=False, skip_every=0):
 
 def linear_wgrad_pair(dy0, x0, dy1, x1, relu_x=False):
     """(dW0, db0, dW1, db1) of two same-shape Linear layers in one partial launch + one reduction (nf_linear_wgrad_pair)."""
-    L.require_device(dy0, x0, dy1, x1)
+    L.require_device(dy0, x0, dy1, x1, dtype=torch.float32)
     dy0, x0, dy1, x1 = (_a16(t.contiguous()) for t in (dy0, x0, dy1, x1))
     if dy0.shape != dy1.shape or x0.shape != x1.shape or any(t.dtype != torch.float32 for t in (dy0, x0, dy1, x1)):
         raise ValueError("linear_wgrad_pair: two float32 problems of the same shape")
@@ -1677,7 +1759,7 @@ def mfma_clock_mhz(device, iters=20000):
 def lu_fwd(x, UpT, LT, bias=None, ld_const=None, ld_sign=1.0, logdet=None, acc=None):
     """(u, y, logdet): u = U x[perm], y = L u + bias per row with the constant log-det, D = 64, LDS-DMA tiles (nf_lu_fwd); the
     arguments of rows_matvec2 with the TRANSPOSED factor images (UpT, LT of lu_factors)."""
-    L.require_device(x, UpT, LT, bias, ld_const, logdet)
+    L.require_device(x, UpT, LT, bias, ld_const, logdet, dtype=torch.float32)
     x = _a16(x.contiguous())
     B, D = x.shape
     u, y = torch.empty_like(x), torch.empty_like(x)
@@ -1690,7 +1772,7 @@ def lu_fwd(x, UpT, LT, bias=None, ld_const=None, ld_sign=1.0, logdet=None, acc=N
 def lu_bwd(gy, u, x, Lm, Up, db_out=None):
     """(gx, dL, db, dUp) of LULinearPermute's batch side in the density direction, D = 64, one pass over the rows (nf_lu_bwd);
     db_out: where the bias gradient (D floats) is written instead of a new tensor."""
-    L.require_device(gy, u, x, Lm, Up)
+    L.require_device(gy, u, x, Lm, Up, dtype=torch.float32)
     gy, u, x, Lm, Up = _a16(gy.contiguous()), _a16(u.contiguous()), _a16(x.contiguous()), Lm.contiguous(), Up.contiguous()
     B, D = gy.shape
     n = L.query("nf_lu_bwd_scratch_floats", B)
@@ -1715,7 +1797,7 @@ def resblock_bwd(gh, t, h_in, w1, w2, x=None, wfull=None, gx=None, col_map=None,
     gx += gh_in @ wfull.t() in place (wfull (64, 128): the layer's weight transposed on full rows), and
     (None, dW1, db1, dW2, db2, dW0 (128, 64), db0) is returned; col_map (64 int32, -1 = drop):
     dW0 is compacted to the (128, n_cols) columns it names."""
-    L.require_device(gh, t, h_in, w1, w2, x, wfull, gx, col_map)
+    L.require_device(gh, t, h_in, w1, w2, x, wfull, gx, col_map, dtype=torch.float32)
     gh, t, h_in, w1, w2 = _a16(gh.contiguous()), _a16(t.contiguous()), _a16(h_in.contiguous()), w1.contiguous(), w2.contiguous()
     if any(v.dtype != torch.float32 for v in (gh, t, h_in, w1, w2)):
         raise ValueError("resblock_bwd: float32 only")
@@ -1759,7 +1841,7 @@ def bias_leaky_relu_(y, bias, negative_slope):
 
 def realnvp_chain(z, blob, d, hmax, direction, logdet=None, acc=None):
     """A stack of MaskedAffineFlow(MLP s, MLP t) / ActNorm / AffineCouplingBlock(MLP) + Permute layers in one launch (nf_realnvp_chain)."""
-    L.require_device(z, blob)
+    L.require_device(z, blob, dtype=torch.float32)
     if z.dtype != torch.float32:
         raise NotImplementedError("realnvp_chain: float32 only")
     z = z.contiguous()
@@ -1782,7 +1864,7 @@ def realnvp_rows(hmax, act):
 
 def realnvp_chain_train_fwd(z, blob, nrec, d, hmax, act, direction):
     """nf_realnvp_chain_train_fwd: (y, per-row log-det, save (nrec, B, d) = every executed record's input)."""
-    L.require_device(z, blob)
+    L.require_device(z, blob, dtype=torch.float32)
     if z.dtype != torch.float32 or not z.is_contiguous():
         raise NotImplementedError("realnvp_chain_train_fwd: contiguous float32 only")
     B = z.shape[0]
@@ -1795,7 +1877,7 @@ def realnvp_chain_train_fwd(z, blob, nrec, d, hmax, act, direction):
 
 def realnvp_chain_bwd(save, gy, gld, blob, d, hmax, act, direction, wmask, want_gz):
     """nf_realnvp_chain_bwd: (gz or None, the parameter gradients in the blob's layout or None when wmask == 0)."""
-    L.require_device(save, gy, gld, blob)
+    L.require_device(save, gy, gld, blob, dtype=torch.float32)
     B, nblob = save.shape[1], blob.numel()
     gz = torch.empty(B, d, dtype=save.dtype, device=save.device) if want_gz else None
     slabs = grads = None
