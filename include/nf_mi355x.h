@@ -199,6 +199,9 @@ int nf_rqs_coupling_bwd_ft_wave(const void *x, const void *grad_y, const void *g
  * Likewise D = 16 | 32 | 48: rows are still 64 floats wide, columns >= D are the caller's padding (values outside the splines'
  * interval, identity block in the packed LU): the final-layer groups of the all-padding 16-column chunks are skipped.
  *   mask_parity 0: reverse_mask = False (identity = even columns, transform = odd), 1: the opposite.
+ * nf_rqs_fused_pack with K = 8 also writes the COMPACT final section (21 stages behind the two LU stages + 672 bias floats at the
+ * end of the small section: nf_rqs_fused_compact_row below), which is what the 8-bin inference launches stream for the final layer;
+ * the 24 final stages stay in the blob for the training forward and nf_rqs_fused_x3_pack.  nf_rqs_fused_pack_size counts both.
  * `wpack` is the layer's weights re-laid-out in MFMA operand order by nf_rqs_fused_pack() (device
  * buffer of nf_rqs_fused_pack_size() bytes, 16-byte aligned); weights are torch nn.Linear layout
  * (out, in); w_blocks/b_blocks are HOST arrays of 2*num_blocks DEVICE pointers
@@ -208,6 +211,14 @@ int nf_rqs_coupling_bwd_ft_wave(const void *x, const void *grad_y, const void *g
 /* Row order of the packed final layer (host-side, for tests and tools): the row of the reference's (32 (3 K - 1), hidden)
  * final-layer weight that MFMA row rho (0..31) of row-block rb (0..2) of group g (0 .. K - 1) holds, or -1 for a padding row. */
 int nf_rqs_fused_final_row(int K, int g, int rb, int rho);
+/* The COMPACT final section of an 8-bin blob (what the 8-bin inference kernels stream; the 24 stages above stay for the training
+ * forward and the split-bf16 packer): a softmax is unchanged by a common shift of its logits, so width / height logit 0 is
+ * subtracted from logits 1..7 at pack time and is the constant 0 in the kernel -- 7 + 7 + 7 = 21 rows per transform feature,
+ * 21 row-blocks of 32 with no padding.  Returns the weight row held by MFMA row rho (0..31) of compact row-block rb (0..20), with
+ * NF_RQS_COMPACT_DIFF set where it is stored minus row tf * 23 (widths) / tf * 23 + 8 (heights); NF_ENOTSUP unless K = 8.  Lane-half
+ * hh's slots 16 rb + reg (rho = 8 (reg / 4) + 4 hh + reg % 4) list its 16 features' 21 values in the pair order of the groups above. */
+#define NF_RQS_COMPACT_DIFF (1 << 16)
+int nf_rqs_fused_compact_row(int K, int rb, int rho);
 int64_t nf_rqs_fused_pack_size(int nI, int nT, int hidden, int num_blocks, int K);
 int nf_rqs_fused_pack(void *wpack, const void *w_init, const void *b_init, const void *const *w_blocks,
                       const void *const *b_blocks, const void *w_final, const void *b_final, const void *uw,
@@ -247,7 +258,8 @@ int nf_rqs_fused_small_batch(int enable);
  * activations h2 (B, 128) -- the output of the residual blocks, computed by the autograd-tracked trunk -- read from HBM.
  * x, y (B, 64); logdet (B) per `acc`; cond_out (B, 32, 24): the conditioner output kept for the backward, 23 parameters + 1
  * pad per transform feature, raw scale (nf_rqs_coupling_bwd_p24 reads this layout).  wpack: nf_rqs_fused_pack, or
- * nf_rqs_fused_pack_final (header + final-layer stages + knot tables only: what this entry point reads).
+ * nf_rqs_fused_pack_final (header + the 24 final-layer stages + knot tables only: what this entry point reads; NOT the compact
+ * final section -- a blob packed by it alone must not go to nf_rqs_fused / nf_rqs_fused_chain).
  * Shape: D = 64, hidden = 128, K = 8, linear tails (NF_ENOTSUP otherwise). */
 int nf_rqs_fused_pack_final(void *wpack, const void *w_final, const void *b_final, const void *uw, const void *uh,
                             const void *ud, int hidden, int num_blocks, int K, double tail_bound, double min_bin_width,
@@ -259,7 +271,7 @@ int nf_rqs_fused_train_fwd(const void *x, const void *h2, void *y, void *logdet,
 /* Training forward of the WHOLE layer in one launch (the inference kernel + what the backward needs): act_out
  * (2 num_blocks + 1, B, 128) = h0 (initial layer's output), then per residual block its pre-activation t and its output h
  * (nets/resnet.py:37-50, :92-104); cond_out (B, 32, 24) as above.  wpack: nf_rqs_fused_pack_all (one launch; same layout as
- * nf_rqs_fused_pack without the LU).  D = 64, hidden = 128, K = 8, linear tails.  wfull / wpad / identity_idx (all or none): the
+ * nf_rqs_fused_pack without the LU, the compact final section of the inference kernels included).  D = 64, hidden = 128, K = 8, linear tails.  wfull / wpad / identity_idx (all or none): the
  * same launch also leaves the initial weight transposed on full rows (64, hidden; the identity features' rows written, the caller
  * keeps the rest zero) and, in `wpad` (32 x 24 x hidden floats), the final weight as the 24 A-operand stages nf_final_bwd streams
  * (w_t: stage 3 g + rb = [k-step vv (8)][unit-block quad uq (2)][lane (64)][4]: lane (m = lane & 15, hq = lane >> 4) holds

@@ -27,7 +27,14 @@ constexpr int F_HDR = 64;          // header floats
 //     bias_final  [8 groups][3 rowblocks][2][16]                     768
 //     tables      [32 identity features][27]                         864
 //     bias_lu     [2 directions][2 rowblocks][2][16]                 128
-//   stages (16 KB each, 16-byte aligned): init | hidden (8 per block) | final (24) | lu density | lu sample
+//     bias_compact [21 rowblocks][2][16]  (8 bins only)              672   (2 blocks: 2400 + 672 = 3072 = the padded size before)
+//   stages (16 KB each, 16-byte aligned): init | hidden (8 per block) | final (24) | lu density | lu sample | compact final (21,
+//   8 bins only)
+// The COMPACT final section (8 bins; what the inference kernels stream instead of the 24 legacy stages, which the training
+// forward, the backward's packers and the split-bf16 packer keep reading): a softmax does not change when a common value is taken
+// off its logits, so width / height logit 0 is subtracted from logits 1..7 at pack time (W'_k = (W_k - W_0) wh_scale, b'_k
+// likewise: compact_value) and logit 0 is the constant 0 in the epilogue.  A feature then needs 7 + 7 + 7 = 21 rows, a
+// lane-half's 16 features 336 = 21 x 16 accumulator slots: 21 row-blocks with no padding (compact_row below).
 struct FusedLayout {
     int nblk;
     int K = F_K;    // bins: 4 | 8 | 16 (exact-fp32 kernel; the split-bf16 and training variants are K = 8 only).  A transform
@@ -37,17 +44,23 @@ struct FusedLayout {
     __host__ __device__ int nfinal() const { return 3 * K; }
     __host__ __device__ int tabw() const { return 3 * (K + 1); }
     __host__ __device__ int bias_final_floats() const { return 96 * K; }
-    __host__ __device__ int small_floats() const { return 128 + 256 * nblk + bias_final_floats() + F_NI * tabw() + 128; }
+    __host__ __device__ int small_floats() const { return 128 + 256 * nblk + bias_final_floats() + F_NI * tabw() + 128; }  // without bias_compact
+    __host__ __device__ int ncompact() const { return K == 8 ? 21 : 0; }               // stages of the compact final section
+    __host__ __device__ int bias_compact_floats() const { return 32 * ncompact(); }
+    __host__ __device__ int off_bias_compact() const { return small_floats(); }
+    __host__ __device__ int compact_stage(int rb) const { return 1 + 8 * nblk + nfinal() + 2 + rb; }
     __host__ __device__ int off_bias_init() const { return 0; }
     __host__ __device__ int off_bias_hidden(int lin) const { return 128 + 128 * lin; }
     __host__ __device__ int off_bias_final() const { return 128 + 256 * nblk; }
     __host__ __device__ int off_tables() const { return off_bias_final() + bias_final_floats(); }
     __host__ __device__ int off_bias_lu(int dir) const { return off_tables() + F_NI * tabw() + 64 * dir; }
     __host__ __device__ int lu_stage(int dir) const { return 1 + 8 * nblk + nfinal() + dir; }
-    __host__ __device__ int small_padded() const { return (small_floats() + 1023) / 1024 * 1024; }
+    __host__ __device__ int small_padded() const { return (small_floats() + bias_compact_floats() + 1023) / 1024 * 1024; }
+    // what a kernel that never reads bias_compact copies to LDS (the training forwards: their LDS budget is what it was)
+    __host__ __device__ int small_padded_legacy() const { return (small_floats() + 1023) / 1024 * 1024; }
     __host__ __device__ int off_stages() const { return F_HDR + small_padded(); }  // multiple of 4 floats
     __host__ __device__ int nstages(bool lu) const { return 1 + 8 * nblk + nfinal() + (lu ? 1 : 0); }
-    __host__ __device__ int64_t total_floats() const { return (int64_t)off_stages() + (int64_t)(nstages(false) + 2) * F_STAGE; }
+    __host__ __device__ int64_t total_floats() const { return (int64_t)off_stages() + (int64_t)(nstages(false) + 2 + ncompact()) * F_STAGE; }
 };
 
 // Row of the final layer (0 .. 32 (3 K - 1) - 1) held by MFMA row `rho` (0..31) of row-block rb (0..2) of group g (0 .. K - 1),
@@ -64,6 +77,31 @@ __host__ __device__ inline int final_row_k(int g, int rb, int rho) {
     return tf * M + prm;
 }
 __host__ __device__ inline int final_row(int g, int rb, int rho) { return final_row_k<F_K>(g, rb, rho); }
+
+// Compact final section (8 bins): what MFMA row `rho` (0..31) of row-block rb (0..20) holds.  Lane-half hh's 336 slots v = 16 rb + reg
+// are the 21-value lists of its 16 features in the pair order of the legacy groups: pair j = v / 42 is legacy group j (features
+// tf = 8 (j / 2) + 4 hh + 2 (j % 2) + {0, 1}), value c = v % 21: 0..6 width logit c + 1 MINUS width logit 0, 7..13 height logit
+// c - 6 MINUS height logit 0, 14..20 derivative logit c - 14.  Returns the row of the (32 * 23, hidden) weight, with F_COMPACT_DIFF
+// set where row tf * 23 (widths) / tf * 23 + 8 (heights) is subtracted from it.
+constexpr int F_COMPACT_DIFF = 1 << 16;
+constexpr int F_NCOMPACT = 21;     // row-blocks; pair j's 42 values are complete after (42 (j + 1) + 15) / 16 of them
+__host__ __device__ inline int compact_row(int rb, int rho) {
+    const int q = rho >> 3, hh = (rho >> 2) & 1, r = rho & 3;
+    const int v = 16 * rb + 4 * q + r;       // 0..335
+    const int j = v / 42, f = (v % 42) / 21, c = v % 21;
+    const int tf = 8 * (j >> 1) + 4 * hh + 2 * (j & 1) + f;
+    if (c < 7) return (tf * F_M + 1 + c) | F_COMPACT_DIFF;
+    if (c < 14) return (tf * F_M + F_K + 1 + (c - 7)) | F_COMPACT_DIFF;
+    return tf * F_M + 2 * F_K + (c - 14);
+}
+// value of the compact section for weight / bias accessor `at(row)`: differences in fp32, widths / heights then scaled
+template <class At>
+__host__ __device__ inline float compact_value(int rb, int rho, float wh_scale, At at) {
+    const int cr = compact_row(rb, rho), row = cr & (F_COMPACT_DIFF - 1);
+    if (!(cr & F_COMPACT_DIFF)) return at(row);
+    const int prm = row % F_M, row0 = row - prm + (prm < F_K ? 0 : F_K);
+    return (at(row) - at(row0)) * wh_scale;
+}
 
 // nf_final_bwd (final_bwd.hip): final-layer row (of the (32 * 23, hidden) weight) that k-entry hq (0..3) of k-step v (0..23) of
 // group g (0..7) contracts over on v_mfma_f32_16x16x4_f32 -- the four transform features of the group, parameter v; -1: the pad
@@ -203,6 +241,17 @@ __device__ __forceinline__ f32x2e pk_fma(f32x2e a, f32x2e b, f32x2e c) { return 
 __device__ __forceinline__ f32x2e pk_rcp(f32x2e a) { return f32x2e{frcp(a[0]), frcp(a[1])}; }
 __device__ __forceinline__ f32x2e pk_log(f32x2e a) { return f32x2e{flog(a[0]), flog(a[1])}; }
 __device__ __forceinline__ f32x2e pk_bc(float a) { return f32x2e{a, a}; }
+// v_rcp_f32 (1 ulp) with one Newton step on packed arithmetic (two v_pk_fma_f32 per pair): r + r (1 - a r).  FINE: the compact
+// final layer's epilogue (rqs_regs2<.., Z0>), whose width / height logits come from DIFFERENCE rows and so carry about sqrt(2) of a
+// single row's rounding through the products: the four reciprocals of the bin evaluation (slope, position in the bin, the quotient)
+// give that back.  Long chains (64 pairs) then stay within the suite's bars against float64 where the plain reciprocals did not
+// (tests/test_gpu_mixed_stacks.py, I2); no measurable cost (8 packed instructions per element pair of ~300).
+template <bool FINE>
+__device__ __forceinline__ f32x2e pk_rcp_t(f32x2e a) {
+    f32x2e r = pk_rcp(a);
+    if constexpr (FINE) r = pk_fma(r, pk_fma(-a, r, pk_bc(1.0f)), r);
+    return r;
+}
 
 // descent over N bins: s = search knots, o = the other axis' knots, d = padded derivative logits (N + 1 candidates each)
 template <int N>
@@ -224,25 +273,25 @@ __device__ __forceinline__ void rqs_descend2(f32x2e x, const f32x2e (&s)[N + 1],
     }
 }
 
-template <bool INVERSE>
+template <bool INVERSE, bool FINE = false>
 __device__ __forceinline__ void rqs_eval_bin_fast2(f32x2e x, f32x2e cw, f32x2e bw, f32x2e ch, f32x2e bh, f32x2e d0, f32x2e d1,
                                                    f32x2e &y, f32x2e &lad) {
-    const f32x2e delta = bh * pk_rcp(bw);
+    const f32x2e delta = bh * pk_rcp_t<FINE>(bw);
     const f32x2e dsum = d0 + d1 - 2.0f * delta;
     f32x2e theta, den;
     if (!INVERSE) {
-        theta = (x - cw) * pk_rcp(bw);
+        theta = (x - cw) * pk_rcp_t<FINE>(bw);
         const f32x2e t1mt = theta * (1.0f - theta);
         const f32x2e num = bh * (delta * theta * theta + d0 * t1mt);
         den = delta + dsum * t1mt;
-        y = ch + num * pk_rcp(den);
+        y = ch + num * pk_rcp_t<FINE>(den);
     } else {
         const f32x2e dy = x - ch;
         const f32x2e a = dy * dsum + bh * (delta - d0);
         const f32x2e b = bh * d0 - dy * dsum;
         const f32x2e c = -delta * dy;
         const f32x2e disc = b * b - 4.0f * a * c;
-        theta = (2.0f * c) * pk_rcp(-b - f32x2e{fsqrt(disc[0]), fsqrt(disc[1])});
+        theta = (2.0f * c) * pk_rcp_t<FINE>(-b - f32x2e{fsqrt(disc[0]), fsqrt(disc[1])});
         y = theta * bw + cw;
         den = delta + dsum * (theta * (1.0f - theta));
     }
@@ -252,18 +301,48 @@ __device__ __forceinline__ void rqs_eval_bin_fast2(f32x2e x, f32x2e cw, f32x2e b
     lad = INVERSE ? -l : l;
 }
 
+// max on values that come straight from MFMA accumulators: fmaxf makes the compiler canonicalise such an operand first (v_max x, x:
+// one more instruction per operand); the instruction itself does not need it.  Same value as fmaxf for every input (a NaN operand
+// loses against a number).
+__device__ __forceinline__ float fmax3_raw(float a, float b, float c) {
+    float r;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+__device__ __forceinline__ float fmax3_raw0(float b, float c) {      // max(0, b, c)
+    float r;
+    asm("v_max3_f32 %0, 0, %1, %2" : "=v"(r) : "v"(b), "v"(c));
+    return r;
+}
+__device__ __forceinline__ float fmax_raw(float a, float b) {
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
 // elements (x0, prm0) and (x1, prm1); prm as in rqs_regs.  KB a power of two.
-template <bool INVERSE, int KB = F_K>
+// Z0 (the compact final section of the 8-bin inference kernels): prm[0] and prm[KB], logit 0 of the two softmaxes, are the constant 0
+// (the packer subtracted them from the other logits); maximum, subtraction and exp2 stay, so large logits behave as before; the bin
+// evaluation refines its reciprocals (pk_rcp_t).
+template <bool INVERSE, int KB = F_K, bool Z0 = false>
 __device__ __forceinline__ void rqs_regs2(const RqsParams<float> &p, float x0, float x1, const float (&prm0)[3 * KB],
                                           const float (&prm1)[3 * KB], float &y0, float &y1, float &lad0, float &lad1) {
     static_assert((KB & (KB - 1)) == 0, "binary descent");
     const f32x2e x = {x0, x1};
     const i32x2e inside = (x >= p.left) & (x <= p.right);          // false for NaN (utils/splines.py:28)
     f32x2e mw = {prm0[0], prm1[0]}, mh = {prm0[KB], prm1[KB]};
+    if constexpr (Z0) {
+        static_assert(KB == 8, "the compact final section");
+#define NF_MAX8(q, o) fmax_raw(fmax3_raw(fmax3_raw(fmax3_raw0(q[o + 1], q[o + 2]), q[o + 3], q[o + 4]), q[o + 5], q[o + 6]), q[o + 7])
+        mw = f32x2e{NF_MAX8(prm0, 0), NF_MAX8(prm1, 0)};      // max(0, logits 1..7)
+        mh = f32x2e{NF_MAX8(prm0, KB), NF_MAX8(prm1, KB)};
+#undef NF_MAX8
+    } else {
 #pragma unroll
-    for (int k = 1; k < KB; ++k) {
-        mw = f32x2e{fmaxf(mw[0], prm0[k]), fmaxf(mw[1], prm1[k])};
-        mh = f32x2e{fmaxf(mh[0], prm0[KB + k]), fmaxf(mh[1], prm1[KB + k])};
+        for (int k = 1; k < KB; ++k) {
+            mw = f32x2e{fmaxf(mw[0], prm0[k]), fmaxf(mw[1], prm1[k])};
+            mh = f32x2e{fmaxf(mh[0], prm0[KB + k]), fmaxf(mh[1], prm1[KB + k])};
+        }
     }
     f32x2e pw[KB], ph[KB];
 #pragma unroll
@@ -297,9 +376,9 @@ __device__ __forceinline__ void rqs_regs2(const RqsParams<float> &p, float x0, f
     const f32x2e d1 = p.min_d + f32x2e{fsoftplus(dl1[0]), fsoftplus(dl1[1])};
     f32x2e yy, ll;
     if (!INVERSE)
-        rqs_eval_bin_fast2<false>(x, slo, shi - slo, olo, ohi - olo, d0, d1, yy, ll);
+        rqs_eval_bin_fast2<false, Z0>(x, slo, shi - slo, olo, ohi - olo, d0, d1, yy, ll);
     else
-        rqs_eval_bin_fast2<true>(x, olo, ohi - olo, slo, shi - slo, d0, d1, yy, ll);
+        rqs_eval_bin_fast2<true, Z0>(x, olo, ohi - olo, slo, shi - slo, d0, d1, yy, ll);
     const f32x2e yr = inside ? yy : x;       // linear tails: identity outside, also for NaN / +-inf (utils/splines.py:40-41)
     const f32x2e lr = inside ? ll : pk_bc(0.0f);
     y0 = yr[0]; y1 = yr[1]; lad0 = lr[0]; lad1 = lr[1];

@@ -19,6 +19,10 @@
 //   The final layer's 736 rows are re-ordered (and padded to 768) at pack time so that after three 32-row blocks a
 //   lane holds the complete 23-parameter sets of two (sample, feature) spline elements: the conditioner output is
 //   never materialised (2944 B/sample/layer of HBM traffic in the unfused path -> 0).
+//   8 bins, inference: the COMPACT form of the same rows -- logit 0 of the width and of the height softmax subtracted from
+//   the other seven at pack time (a softmax ignores a common shift), 21 rows per feature, 672 rows = 21 row-blocks with
+//   no padding; pair j of features is complete after ceil(42 (j + 1) / 16) row-blocks.  The 768-row form stays in the blob
+//   for the training forwards (the backward wants the raw 23 rows), K = 4 / 16 and the split-bf16 packer.
 //
 // Weight stream
 //   The layer's weights are packed once (nf_rqs_fused_pack) into MFMA A-operand order: 16 KB "stages", each a
@@ -28,8 +32,10 @@
 //   stage s+1 lands.  One barrier per stage (per 64 MFMAs = 4096 SIMD cycles).
 //
 // HBM traffic per sample: 256 B in + 256 B out + 8 B log-det (the 0.66 MB of weights per layer are read from L2).
-// Arithmetic: 2 * 167 936 MAC per sample (768-row padded final layer) at the fp32 MFMA rate.
+// Arithmetic: 2 * 167 936 MAC per sample with the 768-row padded final layer (2624 MFMAs per layer-wave, 2688 with the LU);
+// 2 * 155 648 with the 672-row compact one (2432 / 2496), at the fp32 MFMA rate.
 #include "fused_common.hpp"
+#include <type_traits>
 
 // Rows the training variants write for the backward (386 MB per launch) are not read again by this launch: non-temporal stores
 // (measured 29.7-29.8 vs 29.9-30.0 ms per training step, three alternating runs; -DNF_TRAIN_TEMPORAL_STORES: ordinary stores).
@@ -102,6 +108,26 @@ __global__ void pack_final_kernel(const float *__restrict__ W /* 32 (3 KB - 1) x
         const float sc = (row >= 0 && (row % M) < 2 * KB) ? wh_scale : 1.0f;
         bias_dst[i] = row >= 0 ? b[row] * sc : 0.0f;
     }
+}
+
+// The compact final section (8 bins, fused_common.hpp compact_row): 21 stages + 672 bias floats, what the inference kernels stream.
+// Any grid: element i of the section by thread i modulo the grid (also called from pack_all_body).
+__device__ __forceinline__ void pack_compact_body(const float *__restrict__ W /* 736 x 128 */, const float *__restrict__ b,
+                                                  float *__restrict__ stages /* 21 stages */, float *__restrict__ bias_dst,
+                                                  float wh_scale, int64_t tid0, int64_t nth) {
+    for (int64_t i = tid0; i < (int64_t)F_NCOMPACT * F_STAGE; i += nth) {
+        const int r4 = i & 3, lane = (i >> 2) & 63, s = (i >> 8) & 15, rb = (int)(i >> 12);
+        const int k = 8 * s + 4 * (lane >> 5) + r4;
+        stages[i] = compact_value(rb, lane & 31, wh_scale, [=](int row) { return W[row * F_H + k]; });
+    }
+    for (int64_t i = tid0; i < 32 * F_NCOMPACT; i += nth) {
+        const int reg = i & 15, hh = (i >> 4) & 1, rb = (int)(i >> 5);
+        bias_dst[i] = compact_value(rb, 8 * (reg >> 2) + 4 * hh + (reg & 3), wh_scale, [=](int row) { return b[row]; });
+    }
+}
+__global__ void pack_compact_kernel(const float *__restrict__ W, const float *__restrict__ b, float *__restrict__ stages,
+                                    float *__restrict__ bias_dst, float wh_scale) {
+    pack_compact_body(W, b, stages, bias_dst, wh_scale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
 __global__ void pack_tables_kernel(const float *__restrict__ uw, const float *__restrict__ uh, const float *__restrict__ ud,
@@ -445,6 +471,9 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
     static_assert(!TRAIN || (KB == F_K && DIR == 0 && (!LU || TRAIN == 2)),
                   "the training variants: 8 bins, density direction; the fused LU only with the whole-layer forward (TRAIN = 2)");
     static_assert(HB == 4 || ((HB == 2 || HB == 1) && !TRAIN), "hidden row-blocks");
+    // 8 bins, inference: the final layer streams the blob's COMPACT section (21 rows per feature, logit 0 of each softmax == 0:
+    // fused_common.hpp) -- 21 row-blocks instead of 24
+    constexpr bool COMPACT = KB == 8 && TRAIN == 0;
     constexpr int MP = 3 * KB, FPL = 16 / KB, GQ = KB / 4, TABW = 3 * (KB + 1);   // slots per feature, features per lane-half and
                                                                                  // group, groups per 16-column chunk, table row
     FusedLayout lay;
@@ -453,19 +482,23 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
     float *ring = smem;                       // 2 x 4096
     float *stash = ring + 2 * F_STAGE;        // F_NW waves x 32 x 64
     float *small2 = stash + F_NW * 32 * 64;   // 2 x small_padded: biases + tables of the current / next layer
-    const int small_pitch = lay.small_padded();
+    const int small_pitch = TRAIN ? lay.small_padded_legacy() : lay.small_padded();
     const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar: LDS-DMA bases are wave-uniform
     const int64_t row = (int64_t)blockIdx.x * F_ROWS + wid * 32 + (lane & 31);
     const bool valid = row < B;
-    // logical stages of a layer: init | 2 nblk x HB hidden row-blocks | 3 KB final | (LU)
+    // logical stages of a layer: init | 2 nblk x HB hidden row-blocks | 3 KB final (compact: the 21 or fewer row-blocks that hold
+    // the first ngrp pairs' 42 ngrp values) | (LU)
     const int nhid = 2 * nblk * HB;
     const int ngrp = TRAIN ? KB : fa.ngroups;
-    const int nbase = 1 + nhid + 3 * ngrp;
+    const int nbase = 1 + nhid + (COMPACT ? (42 * ngrp + 15) >> 4 : 3 * ngrp);
     const int nstages = TRAIN == 1 ? 24 : nbase + (LU ? 1 : 0);
     const int total_stages = nstages * fa.nlayers;
     // base stage (without the LU) -> stage of the blob, which always holds four row-blocks per hidden Linear
     auto phys_base = [&](int b) -> int {
+        if constexpr (COMPACT) {
+            if (b > nhid) return lay.compact_stage(b - 1 - nhid);
+        }
         if (HB == 4 || b == 0) return b;
         if (b <= nhid) return 1 + 4 * ((b - 1) / HB) + (b - 1) % HB;
         return 1 + 8 * nblk + (b - 1 - nhid);
@@ -835,6 +868,7 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
         }
     };
 #ifdef NF_F32_SWPIPE
+    static_assert(!COMPACT, "the software-pipelined order streams the 24 legacy stages");
     static_assert(KB == F_K && HB == 4, "the software-pipelined order is written for 8 bins, 128 hidden units");
     {   // group 0: MFMAs only
         const float *bsrc = small + lay.off_bias_final() + hh * 16;
@@ -874,6 +908,63 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
     // The exact-fp32 MFMA shares the vector ALU (tools/ubench/overlap.py): there is nothing to hide the epilogue
     // behind, so each group's spline elements are evaluated straight from its accumulators (no parameter copies, lower
     // register pressure); the software-pipelined order (NF_F32_SWPIPE) only pays on the bf16 matrix pipe.
+    if constexpr (COMPACT) {
+        // 21 row-blocks, no padding: the lane's accumulator slots v = 16 rb + reg list 21 values per feature, pair j (= group j of
+        // the legacy order: same features, same stash slots) owns slots [42 j, 42 j + 42) and is complete after row-block
+        // (42 (j + 1) + 15) / 16 - 1: 3, 6, 8, 11, 14, 16, 19, 21 row-blocks.  The start offsets 42 j mod 16 all differ, so the eight
+        // bodies are distinct (static unroll); a pair's last row-block holds up to 14 values of the NEXT pair and is carried
+        // along.  Narrow layers leave after their ngrp pairs (wave-uniform).
+        const float *bfin = small + lay.off_bias_compact() + hh * 16;
+        f32x16 C = {};      // a pair's last row-block: its tail belongs to the next pair
+        auto pair = [&](auto jc) __attribute__((always_inline)) {      // (not inlined, its captures go through memory)
+            constexpr int J = decltype(jc)::value;
+            constexpr int S0 = 42 * J, RN = (S0 + 15) / 16, RE = (S0 + 42 + 15) / 16, NNEW = RE - RN;   // new row-blocks [RN, RE)
+            static_assert(NNEW == 2 || NNEW == 3, "row-blocks per pair");
+            f32x16 A0 = load_bias16(bfin + RN * 32), A1 = load_bias16(bfin + (RN + 1) * 32), A2 = A1;
+            mm128<false, HB, LA>(acquire(), lane, A0, H0, H1, H2, H3);
+            mm128<false, HB, LA>(acquire(), lane, A1, H0, H1, H2, H3);
+            if constexpr (NNEW == 3) {
+                A2 = load_bias16(bfin + (RN + 2) * 32);
+                mm128<false, HB, LA>(acquire(), lane, A2, H0, H1, H2, H3);
+            }
+            // rqs_regs2's lists: 7 width, 7 height, 7 derivative values per feature; logit 0 of the widths and of the heights is the
+            // constant 0 (subtracted from the others at pack time).  Slot indices are constants once the loop is unrolled.
+            auto val = [&](int slot) -> float {
+                const int rb = slot >> 4, e = slot & 15;
+                return rb < RN ? C[e] : (rb == RN ? A0[e] : (rb == RN + 1 ? A1[e] : A2[e]));
+            };
+            float p0[MP], p1[MP];
+#pragma unroll
+            for (int v = 0; v < MP; ++v) {
+                const int c = v < KB ? v - 1 : v - 2;      // which of the feature's 21 values (list entries 0 and KB are the constants)
+                const bool zero = v == 0 || v == KB || v == MP - 1;
+                p0[v] = zero ? 0.0f : val(S0 + c);
+                p1[v] = zero ? 0.0f : val(S0 + 21 + c);
+            }
+            C = NNEW == 3 ? A2 : A1;
+#ifdef NF_ABL_NOEPI
+#pragma unroll
+            for (int v = 0; v < MP; ++v) asm volatile("" ::"v"(p0[v]), "v"(p1[v]));
+#else
+            const int s0 = 8 * (J / 2) + 4 * (J % 2) + par_t, s1 = s0 + 2;
+            float y0, y1, l0, l1;
+            rqs_regs2<DIR == 1, KB, true>(p, st[s0 * 64], st[s1 * 64], p0, p1, y0, y1, l0, l1);
+            st[s0 * 64] = y0;
+            st[s1 * 64] = y1;
+            ld += l0;
+            ld += l1;
+#endif
+            if (DIR == 0) uncond_group(J);
+        };
+        pair(std::integral_constant<int, 0>{});
+        if (ngrp > 1) pair(std::integral_constant<int, 1>{});
+        if (ngrp > 2) pair(std::integral_constant<int, 2>{});
+        if (ngrp > 3) pair(std::integral_constant<int, 3>{});
+        if (ngrp > 4) pair(std::integral_constant<int, 4>{});
+        if (ngrp > 5) pair(std::integral_constant<int, 5>{});
+        if (ngrp > 6) pair(std::integral_constant<int, 6>{});
+        if (ngrp > 7) pair(std::integral_constant<int, 7>{});
+    } else
     for (int g = 0; g < ngrp; ++g) {   // (up to) KB groups of 3 row-blocks
         const float *bsrc = small + lay.off_bias_final() + (g * 3) * 32 + hh * 16;
         f32x16 A0 = load_bias16(bsrc), A1 = load_bias16(bsrc + 32), A2 = load_bias16(bsrc + 64);
@@ -992,7 +1083,8 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
 }
 
 #ifndef NF_FUSED_SECONDARY
-// The whole blob of a layer (without the LU) in ONE launch: what nf_rqs_fused_pack does with 4 + 2 nblk launches.  The training
+// The whole blob of a layer (without the LU, with the compact final section) in ONE launch: what nf_rqs_fused_pack does with
+// 5 + 2 nblk launches.  The training
 // step re-packs every layer's weights once per step, so the launches count (8 bins only: the training variants' shape).
 struct PackAllArgs {
     const float *w_init, *b_init, *w_final, *b_final, *uw, *uh, *ud;
@@ -1057,6 +1149,9 @@ __device__ __forceinline__ void pack_all_body(const PackAllArgs &a, float *__res
         }
         small[i] = v;       // bias_init | bias_hidden | bias_final are contiguous at the start of the small section
     }
+    // the compact final section the inference kernels stream (a blob packed here can go to nf_rqs_fused_chain)
+    pack_compact_body(a.w_final, a.b_final, stages + (size_t)lay.compact_stage(0) * F_STAGE, small + lay.off_bias_compact(), wh_scale,
+                      tid0, nth);
     if (blockIdx.x == gridDim.x - 1) {
         const int j = threadIdx.x;
         if (j == 0) {
@@ -1114,7 +1209,7 @@ static int train_fwd_launch(const void *x, void *xlu_out, void *y, void *logdet,
                             int64_t B, int hidden, int num_blocks, const RqsParams<float> &p, int acc, hipStream_t st) {
     FusedLayout lay;
     lay.nblk = num_blocks;
-    const size_t lds = (size_t)(2 * F_STAGE + F_NW * 32 * 64 + lay.small_padded() + F_NW * 1536) * sizeof(float);
+    const size_t lds = (size_t)(2 * F_STAGE + F_NW * 32 * 64 + lay.small_padded_legacy() + F_NW * 1536) * sizeof(float);
     if (lds > 160 * 1024) return NF_ENOTSUP;
     static LdsOptIn opted = {};
     if (opt_in_lds(reinterpret_cast<const void *>(&rqs_fused_kernel<0, LU, 2>), lds, opted) != NF_OK) return NF_ENOTSUP;
@@ -1275,6 +1370,15 @@ extern "C" int nf_rqs_fused_final_row(int K, int g, int rb, int rho) {
     return K == 4 ? final_row_k<4>(g, rb, rho) : (K == 8 ? final_row_k<8>(g, rb, rho) : final_row_k<16>(g, rb, rho));
 }
 
+// Host-side view of the compact final section (8 bins): row of the (32 * 23, 128) weight held by MFMA row `rho` of compact
+// row-block `rb` (0..20), with NF_RQS_COMPACT_DIFF (bit 16) set where the row is stored MINUS logit 0 of its softmax (row
+// tf * 23 for a width row, tf * 23 + 8 for a height row); NF_ENOTSUP for any other bin count.
+extern "C" int nf_rqs_fused_compact_row(int K, int rb, int rho) {
+    if (K != 8) return NF_ENOTSUP;
+    if (rb < 0 || rb >= F_NCOMPACT || rho < 0 || rho > 31) return NF_EINVAL;
+    return compact_row(rb, rho);
+}
+
 extern "C" int64_t nf_rqs_fused_pack_size(int nI, int nT, int hidden, int num_blocks, int K) {
     if (nI != F_NI || nT != F_NI || hidden != F_H || !fused_bins_ok(K) || num_blocks < 0 || num_blocks > 16) return NF_ENOTSUP;
     FusedLayout lay;
@@ -1316,6 +1420,10 @@ extern "C" int nf_rqs_fused_pack(void *wpack, const void *w_init, const void *b_
     else if (K == 8) NF_PACK_FINAL(8);
     else NF_PACK_FINAL(16);
 #undef NF_PACK_FINAL
+    if (K == 8)     // + the compact final section (what the 8-bin inference kernels stream; the 24 stages above stay for the others)
+        hipLaunchKernelGGL(pack_compact_kernel, dim3(21 * 16), dim3(256), 0, st, (const float *)w_final, (const float *)b_final,
+                           stages + (size_t)lay.compact_stage(0) * F_STAGE, small + lay.off_bias_compact(),
+                           (float)(1.4426950408889634 / sqrt((double)hidden)));
     auto p = make_rqs_params<float>(K, NF_TAILS_LINEAR, tail_bound, 0, 1, 0, 1, min_bin_width, min_bin_height,
                                     min_derivative, 1.0);
     hipLaunchKernelGGL(pack_tables_kernel, dim3(1), dim3(64), 0, st, (const float *)uw, (const float *)uh,
@@ -1324,7 +1432,8 @@ extern "C" int nf_rqs_fused_pack(void *wpack, const void *w_init, const void *b_
     return NF_OK;
 }
 
-// Only what the training forward (nf_rqs_fused_train_fwd) reads: header, final-layer stages + bias, knot tables.
+// Only what the training forward (nf_rqs_fused_train_fwd) reads: header, the 24 final-layer stages + bias, knot tables (not the
+// compact final section of the inference kernels).
 extern "C" int nf_rqs_fused_pack_final(void *wpack, const void *w_final, const void *b_final, const void *uw, const void *uh,
                                        const void *ud, int hidden, int num_blocks, int K, double tail_bound,
                                        double min_bin_width, double min_bin_height, double min_derivative, nf_stream_t stream) {
@@ -1499,7 +1608,7 @@ extern "C" int nf_rqs_fused_train_fwd(const void *x, const void *h2, void *y, vo
     auto p = make_rqs_params<float>(K, NF_TAILS_LINEAR, tail_bound, 0, 1, 0, 1, min_bin_width, min_bin_height,
                                     min_derivative, sqrt((double)hidden));
     // + the waves' 6 KB transpose tiles for the row stores (they start in the unused second small buffer)
-    const size_t lds = (size_t)(2 * F_STAGE + F_NW * 32 * 64 + lay.small_padded() + F_NW * 1536) * sizeof(float);
+    const size_t lds = (size_t)(2 * F_STAGE + F_NW * 32 * 64 + lay.small_padded_legacy() + F_NW * 1536) * sizeof(float);
     if (lds > 160 * 1024) return NF_ENOTSUP;
     static LdsOptIn opted = {};
     if (opt_in_lds(reinterpret_cast<const void *>(&rqs_fused_kernel<0, false, true>), lds, opted) != NF_OK) return NF_ENOTSUP;
