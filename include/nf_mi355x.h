@@ -467,7 +467,8 @@ int64_t nf_linear_wgrad_scratch_floats(int64_t B, int M, int N);
 int nf_linear_wgrad(const void *dY, const void *X, void *dW, void *db, void *scratch, int64_t B, int M, int N,
                     int accumulate, nf_stream_t stream);
 /* Same with relu_x = 1: the second operand is relu(X), applied as the values are consumed (the caller keeps only the
- * pre-activation of the block, resnet.py:41-47). */
+ * pre-activation of the block, resnet.py:41-47).  The activation is fmaxf(x, 0) on every path: a NaN in X is consumed as 0
+ * under relu_x = 1 (torch.relu would keep it); an Inf stays an Inf. */
 /* Alignment: as nf_linear_wgrad. */
 int nf_linear_wgrad_act(const void *dY, const void *X, void *dW, void *db, void *scratch, int64_t B, int M, int N,
                         int accumulate, int relu_x, nf_stream_t stream);
