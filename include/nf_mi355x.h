@@ -835,6 +835,22 @@ int nf_made_forward_affine(const void *x, void *y, void *logdet, const void *blo
 /* Alignment: params 16 bytes, and x with D % 4 == 0 (NF_EINVAL otherwise). */
 int nf_made_forward(const void *x, void *params, const void *blob, const int32_t *table, int64_t B, int D, int hidden_padded,
                     int mult, nf_stream_t stream);
+/* A RealNVP coupling layer beyond the chain kernel's shapes (nf_realnvp_chain: d <= 16, widths <= 64) in ONE launch at inference, on
+ * the same tile engine in its plain-MLP mode.  Replaces normflows/flows/affine/coupling.py:209-229 (MaskedAffineFlow: s / t
+ * non-finite -> NaN, forward y = b z + (1 - b)(z exp(s) + t), ld = sum (1 - b) s; inverse y = b z + (1 - b)(z - t) exp(-s), ld = -sum;
+ * a missing net is the constant 0), :117-171 and :232-267 (AffineCoupling inside AffineCouplingBlock with the channel / channel_inv
+ * split: scale maps exp, sigmoid, sigmoid_inv and scale=False, the formulas of nf_affine_coupling) together with the conditioners,
+ * normflows/nets/mlp.py:5-58 (three Linear layers with bias, LeakyReLU(0.0) between them).  The conditioner reads only the
+ * features the layer leaves unchanged, so either direction is one conditioner pass.
+ *   blob, table : normflows_amd/flows/affine_wide_pack.pack(flow, d): hidden slots = [s-net units | t-net units] (a block: its one
+ *                 MLP), the hidden-to-hidden weight block-diagonal, final rows 2 f / 2 f + 1 = feature f's scale / shift parameter;
+ *                 table[13] = 1 (plain MLP), table[24] = the scale map (NF_SCALE_*; 4 = the masked flow's rule), and behind the
+ *                 items one word per 16 features, 2 bits each: 0 identity, 1 transformed, 2 transformed and fed to the net as 0.
+ *   z, y (B, D), 2 <= D <= 128 = table[0]; hidden_padded = table[3] (256 | 512, anything else NF_ENOTSUP); float32;
+ *   direction 0 = forward, 1 = inverse; logdet (B) combined according to `acc`.  Deterministic. */
+/* Alignment: with D % 4 == 0 z and y 16 bytes (the call is refused otherwise, before any launch); logdet element type. */
+int nf_affine_wide(const void *z, void *y, void *logdet, const void *blob, const int32_t *table, int64_t B, int D, int hidden_padded,
+                   int direction, int acc, nf_stream_t stream);
 /* The autoregressive rational-quadratic spline layer's density direction in one launch: replaces
  * normflows/flows/neural_spline/autoregressive.py:94-134 (MaskedPiecewiseRationalQuadraticAutoregressive._elementwise_forward over
  * Autoregressive.forward, flows/affine/autoregressive.py:24-27; what wrapper.py:241-245 AutoregressiveRationalQuadraticSpline.inverse

@@ -419,6 +419,29 @@ def set_realnvp_blocks(mode=True):
     realnvp_blocks = bool(mode)
 
 
+# MaskedAffineFlow(MLP s, MLP t) and AffineCouplingBlock(MLP) layers beyond the chain kernels' shapes (d > 16 or a width > 64; d <= 128,
+# <= 512 hidden slots, two hidden layers, LeakyReLU(0)) at inference as ONE launch (nf_affine_wide, csrc/affine_wide.hip); False = the
+# conditioners as library GEMMs + LeakyReLU launches with nf_masked_affine / nf_affine_coupling behind them (A/B runs, differential
+# tests).  Layers the chain kernels can take never come here, whatever realnvp_blocks says.
+affine_wide = True
+# While NormalizingFlow.use_graphs records a pass (its warm-up call and the capture alike, so both take one route) the launch is taken
+# from this many rows on.  Replayed from a graph the layer-wise kernels have no launch overhead left, and a small batch fills few of
+# the persistent workgroups: at 1 024 rows the one launch lasts 0.09-0.11 ms against 0.05-0.06 ms; replayed, it is no slower from
+# 8 192 rows on (d 64, two nets of 256) resp. 16 384 (d 128, one net of 512) (profiles/affine_wide_bench.json:
+# `graph_not_slower_from`, tools/affine_wide_bench.py); the gate is the larger of the two.  Eager calls, and a capture the caller makes with torch.cuda.graph directly,
+# take the launch at every size: such a caller warms up eagerly, and a gate on the capture alone would then record library GEMMs that
+# were never initialised outside it.  set_affine_wide(False) is the faster setting for those captures of small batches.
+affine_wide_graph_min_batch = 16384
+_graph_recording = 0          # > 0 inside core._GraphCache's warm-up + capture
+
+
+def set_affine_wide(mode=True, graph_min_batch=None):
+    global affine_wide, affine_wide_graph_min_batch
+    affine_wide = bool(mode)
+    if graph_min_batch is not None:
+        affine_wide_graph_min_batch = int(graph_min_batch)
+
+
 # Debug mode of the element-wise spline API (utils.splines): after every call a check launch (nf_rqs_spline_check)
 # sets device-side flags and the shim reads them back -- a host synchronisation per call, which is why it is off by default -- and
 # raises what the reference raises: AssertionError for a negative discriminant in the inverse direction (utils/splines.py:181),

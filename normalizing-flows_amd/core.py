@@ -455,15 +455,20 @@ class _GraphCache:
         entry = self.graphs.get(key)
         if entry is None:
             static_in = [t.clone() for t in inputs]
-            # warm-up on a side stream (also triggers lazy initialisations such as ActNorm's)
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                fn(*static_in)
-            torch.cuda.current_stream().wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                static_out = fn(*static_in)
+            # warm-up on a side stream (also triggers lazy initialisations such as ActNorm's); the warm-up and the capture run under
+            # one marker, so a route that is chosen differently for graph replay (config.affine_wide_graph_min_batch) is the same in both
+            _config._graph_recording += 1
+            try:
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    fn(*static_in)
+                torch.cuda.current_stream().wait_stream(s)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    static_out = fn(*static_in)
+            finally:
+                _config._graph_recording -= 1
             entry = (g, static_in, static_out, _packed_blobs(self.owner() if self.owner is not None else None))
             self.graphs[key] = entry
         g, static_in, static_out = entry[:3]

@@ -38,6 +38,7 @@ made_fwd_kernel(const float *__restrict__ x, float *__restrict__ y, float *__res
                 const int *__restrict__ table, int64_t B, int acc_mode, RqsParams<float> p, float *__restrict__ save,
                 unsigned *__restrict__ bits, int64_t Bp) {
     constexpr bool FT = false;
+    constexpr int direction = 0;             // (EPI 4 only: affine_wide.hip)
     float *const x_pad = nullptr;
 #include "made_fwd_body.hpp"
 }

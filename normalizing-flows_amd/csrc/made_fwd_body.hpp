@@ -2,7 +2,7 @@
 // (every epilogue; read its header comment first) and of made_fwd_train_ft.hip's made_fwd_train_ft_kernel (EPI 3 behind a gathered,
 // fed x tile).  A text fragment and not a function: inlined through a call the existing instantiations came out with other
 // registers (the 128-row tile spilled two more values), and a further template parameter would rename them.  The including kernel
-// provides: NSB, EPI, TR, FT (compile-time), x, y, logdet, blob, table, B, acc_mode, p, save, bits, Bp, x_pad.
+// provides: NSB, EPI, TR, FT (compile-time), x, y, logdet, blob, table, B, acc_mode, p, save, bits, Bp, x_pad, direction.
 //
 // FT (nf_made_forward_train_ft): the x tile of made_fwd_ft.hip in front of EPI 3 -- the MADE of the autoregressive spline layers with a
 // permuted mask and / or the periodic preprocessing of utils/nn.py:64-129 (nets/made.py:250-252) under autograd.  The tile is
@@ -24,6 +24,13 @@
 // EPI 3: EPI 1 under autograd (core.py:87-102 through a MADE): every layer's pre-activations are also written row-major to
 // save[l][Bp][Hp] (l = 0: the initial layer's h; 2 b + 1: block b's inner t; 2 b + 2: its output h) and the signs of what a ReLU
 // follows to bits[tile][2 b | 2 b + 1][item][512 lanes] -- the operands of made_bwd.hip.
+// EPI 4 (affine_wide.hip, nf_affine_wide): a RealNVP coupling layer -- MaskedAffineFlow (coupling.py:209-229) or AffineCouplingBlock
+// (:117-171, :232-267) -- on EPI 0's skeleton in plain-MLP mode: rows 2 f / 2 f + 1 = feature f's scale / shift parameter, the x tile is
+// the whole z row, `direction` (the including kernel's) picks forward / inverse and table[24] the scale map (NF_SCALE_*, or 4 = the
+// masked flow's exp with its non-finite -> NaN rule); affine.hip's formulas and signs.  A feature table follows the items (one word
+// per 16 features, 2 bits each): 0 = identity, 1 = transformed, 2 = transformed and FED AS ZERO (a block's z2 columns, which its
+// param_map never sees: a zero weight would turn an inf there into NaN for the whole row) -- the tile holds 0 for such a feature and
+// the epilogue reads its z from global memory again.  Its ReLU keeps NaN (torch's LeakyReLU(0): NaN stays NaN, fmaxf would drop it).
 
     static_assert(TR == 64 || (TR == 128 && NSB == 1 && EPI == 3), "128-row tiles: the 256-slot training forward only (mf_tr128)");
     static_assert(!FT || EPI == 3, "the gathered / fed x tile: the training forward only");
@@ -40,7 +47,11 @@
     const int MD = table[12] ? table[12] : table[6] * D;       // raw output row length: mult D for a MADE, out_features for a ResidualNet
     const int ldx = table[14] ? table[14] : D;                 // row stride of x (the conv path hands over 128-padded rows)
     const int plain = table[13];     // 1: a plain MLP  x -> W0 -> relu -> W1 -> relu -> Wf  (NB = 1 without the block's second linear and
-                                     // its residual; EPI 1 / 3 only): the 3x3 -> 1x1 -> 3x3 conv conditioner over pixel rows (conv_rows.hip)
+                                     // its residual; EPI 1 / 3: the 3x3 -> 1x1 -> 3x3 conv conditioner over pixel rows (conv_rows.hip);
+                                     // EPI 4: the stacked s / t nets or the param_map of a coupling layer; never EPI 0 / 2)
+    const int *mtab = table + MF_HDR + MF_NW * nitems * 2;    // EPI 4: the feature table (Dp / 16 words)
+    const int smap = table[24];                               // EPI 4: the scale map
+    const int nets = table[25];                               // EPI 4, a masked flow: bit 0 = it has an s-net, bit 1 = a t-net
     const int *items = table + MF_HDR + w * nitems * 2;       // [nitems][nkg, rb]
     const float *stream = blob + table[16 + w];
     const int rbs[2] = {w, HRB - 1 - w};                      // (the packer's wave_items: the hidden row-blocks of this wave)
@@ -99,6 +110,11 @@
 #pragma unroll
                         for (int i = 0; i < 4; ++i) if (4 * c + i < D) v[i] = xr[4 * c + i];
                 }
+                if constexpr (EPI == 4) {               // (c is wave-uniform: a scalar read)
+                    const unsigned mb = (unsigned)mtab[c >> 2] >> (8 * (c & 3));
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) if (((mb >> (2 * i)) & 3u) == 2u) v[i] = 0.0f;
+                }
                 *reinterpret_cast<f32x4 *>(xreg + ((size_t)c * TR + r) * 4) = v;
             }
         }
@@ -131,7 +147,7 @@
         for (int b = 0; b < NB; ++b) {
             MF_BARRIER();        // (b > 0: every wave has finished reading relu(t) of the previous block)
 #pragma unroll
-            for (int s = 0; s < 2; ++s) mf_publish<NS, true, TR>(acts, rbs[s], sb0s[s], hh, n, h[s]);
+            for (int s = 0; s < 2; ++s) mf_publish<NS, true, TR, EPI == 4>(acts, rbs[s], sb0s[s], hh, n, h[s]);
             if constexpr (EPI == 3)
 #pragma unroll
                 for (int s = 0; s < 2; ++s) btile[((size_t)(2 * b) * 2 + s) * 512] = mf_sign_bits<NS>(h[s]);
@@ -140,7 +156,7 @@
             for (int s = 0; s < 2; ++s) mf_item<NS, false, TR>(ring, items[2 * (2 + 4 * b + s)], acts + lane_b + 128 * sb0s[s], t[s]);
             MF_BARRIER();
 #pragma unroll
-            for (int s = 0; s < 2; ++s) mf_publish<NS, true, TR>(acts, rbs[s], sb0s[s], hh, n, t[s]);
+            for (int s = 0; s < 2; ++s) mf_publish<NS, true, TR, EPI == 4>(acts, rbs[s], sb0s[s], hh, n, t[s]);
             if constexpr (EPI == 3)
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
@@ -254,6 +270,51 @@
                                 }
                             }
                         }
+                    } else if constexpr (EPI == 4) {
+                        const unsigned mw = (unsigned)mtab[fb];       // the 16 features of this row-block
+                        const bool live = 32 * s + n < nrows;
+                        const float *zg = x + (row0 + 32 * s + n) * ldx;      // (read only for a live row)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const int f0 = 16 * fb + 4 * q + 2 * hh;
+                            float *xp = xreg + ((size_t)((2 * fb + (q >> 1)) * 2 + (q & 1)) * 64 + 32 * s + n) * 4 + 2 * hh;
+#pragma unroll
+                            for (int e = 0; e < 2; ++e) {
+                                const unsigned mode = (mw >> (2 * (4 * q + 2 * hh + e))) & 3u;
+                                if (f0 + e < D && (mode != 0u || smap == 4)) {
+                                    float sc = o[0][4 * q + 2 * e], sh = o[0][4 * q + 2 * e + 1];
+                                    float v = xp[e], yo;
+                                    if (mode == 2u) v = live ? zg[f0 + e] : 0.0f;
+                                    if (smap == 4) {             // masked_affine_kernel with b = 1 (identity) / 0
+                                        const float bi = mode == 0u ? 1.0f : 0.0f;
+                                        if (!(nets & 1)) sc = 0.0f;       // a missing net is the constant 0, whatever its zero rows
+                                        if (!(nets & 2)) sh = 0.0f;       // made of a non-finite hidden value (0 * inf)
+                                        if (!M<float>::finite(sc)) sc = M<float>::nan();
+                                        if (!M<float>::finite(sh)) sh = M<float>::nan();
+                                        const float zm = bi * v;
+                                        if (direction == 0) yo = zm + (1.0f - bi) * (v * M<float>::exp(sc) + sh);
+                                        else yo = zm + (1.0f - bi) * (v - sh) * M<float>::exp(-sc);
+                                        ldsum[s] += (1.0f - bi) * sc;
+                                    } else if (smap == NF_SCALE_NONE) {      // affine_coupling_kernel
+                                        yo = direction == 0 ? v + sh : v - sh;
+                                    } else if (smap == NF_SCALE_EXP) {
+                                        yo = direction == 0 ? v * M<float>::exp(sc) + sh : (v - sh) * M<float>::exp(-sc);
+                                        ldsum[s] += sc;
+                                    } else {
+                                        const float sg = sigmoid(sc + 2.0f);
+                                        const float lg = M<float>::log(sg);
+                                        if (smap == NF_SCALE_SIGMOID) {
+                                            yo = direction == 0 ? v / sg + sh : (v - sh) * sg;
+                                            ldsum[s] -= lg;
+                                        } else {
+                                            yo = direction == 0 ? v * sg + sh : (v - sh) / sg;
+                                            ldsum[s] += lg;
+                                        }
+                                    }
+                                    xp[e] = yo;
+                                }
+                            }
+                        }
                     } else {
 #pragma unroll
                         for (int ss = 0; ss < NSH; ++ss) {
@@ -277,12 +338,13 @@
                 }
             }
         }
-        MF_BARRIER();                          // every wave is done with the activations (and, EPI 0, has written its z values)
-        if constexpr (EPI == 0) {
+        MF_BARRIER();                          // every wave is done with the activations (and, EPI 0 / 4, has written its z values)
+        if constexpr (EPI == 0 || EPI == 4) {
             // per-sample log-det: the lane-halves' sums, then the 8 row-blocks' in a FIXED order (deterministic)
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                const float v = ldsum[s] + __shfl_xor(ldsum[s], 32);
+                float v = ldsum[s] + __shfl_xor(ldsum[s], 32);
+                if constexpr (EPI == 4) v = direction == 0 ? v : -v;       // (the inverse: the opposite sign, as affine.hip stores it)
                 const int fb = (s == 0 ? w : 7 - w);
                 if (hh == 0) acts[fb * 64 + 32 * s + n] = v;
             }

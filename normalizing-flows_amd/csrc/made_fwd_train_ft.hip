@@ -16,6 +16,7 @@ made_fwd_train_ft_kernel(const float *__restrict__ x, float *__restrict__ y, flo
     // y = params (B, mult D) in position order; logdet = x_pos (B, D): EPI 3 has no log-det, the body's FT tile load writes there
     constexpr int EPI = 3, TR = MF_ROWS;
     constexpr bool FT = true;
+    constexpr int direction = 0;             // (EPI 4 only: affine_wide.hip)
     const int acc_mode = NF_LD_WRITE;
     const RqsParams<float> p{};
 #include "made_fwd_body.hpp"

@@ -142,7 +142,8 @@ __device__ __forceinline__ void mf_item(MfRing &r, int nkg, const float *Bl, f32
 }
 
 // publish the row-block's values (ReLU'd or raw) as the next layer's B operand: act[(4 rb + q)][hh][32 sb + n][4]
-template <int NS, bool RELU, int TR = 64>
+// KEEPNAN: a ReLU that lets NaN through like torch's (made_fwd_body.hpp EPI 4); fmaxf returns the other operand
+template <int NS, bool RELU, int TR = 64, bool KEEPNAN = false>
 __device__ __forceinline__ void mf_publish(float *acts, int rb, int sb0, int hh, int n, const f32x16 (&v)[NS]) {
 #pragma unroll
     for (int s = 0; s < NS; ++s)
@@ -150,7 +151,10 @@ __device__ __forceinline__ void mf_publish(float *acts, int rb, int sb0, int hh,
         for (int q = 0; q < 4; ++q) {
             f32x4 o;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) o[i] = RELU ? fmaxf(v[s][4 * q + i], 0.0f) : v[s][4 * q + i];
+            for (int i = 0; i < 4; ++i) {
+                if constexpr (RELU && KEEPNAN) o[i] = v[s][4 * q + i] < 0.0f ? 0.0f : v[s][4 * q + i];
+                else o[i] = RELU ? fmaxf(v[s][4 * q + i], 0.0f) : v[s][4 * q + i];
+            }
             *reinterpret_cast<f32x4 *>(acts + ((size_t)((4 * rb + q) * 2 + hh) * TR + 32 * (sb0 + s) + n) * 4) = o;
         }
 }

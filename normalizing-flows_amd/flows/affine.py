@@ -9,6 +9,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from .. import _keys
 from .. import config as _config
 from .. import ops
 from ..autograd import ActNormFn, AffineCouplingFn, MaskedAffineFn, needs_grad
@@ -84,6 +85,33 @@ def conditioner_output(who, out, z, full_shape=None):
                              % (who, tuple(out.shape), tuple(full_shape)))
         out = out.expand(tuple(full_shape))
     return out
+
+
+def _affine_wide(flow, z, inverse, ld, acc):
+    """(y, log-det) of a MaskedAffineFlow / AffineCouplingBlock as ONE launch (nf_affine_wide: csrc/affine_wide.hip,
+    flows/affine_wide_pack.py), or None when the layer, the input or the switch declines it -- then the caller's layer-wise code runs.
+    The structure is looked at on every call (attribute reads: `.double()` may come after the first call); the pack, and the answer
+    of the checks that read values (a binary mask), are cached on the layer's parameters and buffers."""
+    if (not _config.affine_wide or z.dim() != 2 or not z.is_cuda or z.dtype != torch.float32 or needs_grad(z, flow)
+            or (ld is not None and ld.dtype != torch.float32)):
+        return None
+    if _config._graph_recording and z.shape[0] < _config.affine_wide_graph_min_batch:
+        return None         # (recorded for graph replay, a small batch is faster layer by layer: config.affine_wide_graph_min_batch)
+    from . import affine_wide_pack
+    d = z.shape[1]
+    if isinstance(affine_wide_pack.structure(flow, d), str):
+        return None
+
+    def build():
+        packed = affine_wide_pack.pack(flow, d)
+        if packed is None:
+            return None
+        return (torch.from_numpy(packed[0]).to(z.device), torch.from_numpy(packed[1]).to(z.device), int(packed[1][3]))
+
+    packed = _keys.pcached(flow, "_affine_wide_cache", list(flow.parameters()) + list(flow.buffers()), (str(z.device), d), build)
+    if packed is None:
+        return None
+    return ops.affine_wide(z, packed[0], packed[1], packed[2], 1 if inverse else 0, logdet=ld, acc=acc)
 
 
 class AffineConstFlow(Flow):
@@ -257,6 +285,10 @@ class MaskedAffineFlow(Flow):
 
     def _transform(self, z, inverse, ld=None, acc=None):
         need_net = self.s is not None or self.t is not None
+        if need_net:
+            out = _affine_wide(self, z, inverse, ld, acc)       # (wide MLP conditioners at inference: one launch)
+            if out is not None:
+                return out
         z_masked = self.b * z if need_net else None
         scale = conditioner_output("MaskedAffineFlow.s", self.s(z_masked), z, z.shape) if self.s is not None else None
         trans = conditioner_output("MaskedAffineFlow.t", self.t(z_masked), z, z.shape) if self.t is not None else None
@@ -333,6 +365,9 @@ class AffineCouplingBlock(Flow):
 
     def _go(self, z, inverse, ld, acc):
         if self.split_mode in ("channel", "channel_inv") and z.shape[1] >= 2:
+            out = _affine_wide(self, z, inverse, ld, acc)       # (a wide MLP param_map at inference: one launch)
+            if out is not None:
+                return out[0]
             y, _ = self._fused(z, inverse, ld, acc)
             return y
         return self._compose(z, inverse, ld, acc)

@@ -1228,6 +1228,20 @@ def made_forward_affine(x, blob, table, hidden_padded, logdet=None, acc=None):
     return y, logdet
 
 
+def affine_wide(z, blob, table, hidden_padded, direction, logdet=None, acc=None):
+    """A MaskedAffineFlow(MLP, MLP) / AffineCouplingBlock(MLP) beyond the chain kernel's shapes (coupling.py:117-171, :209-229,
+    :232-267 over nets/mlp.py:5-58) as one launch (nf_affine_wide); blob / table from flows/affine_wide_pack.pack."""
+    L.require_device(z, blob, table, logdet, dtype=torch.float32)
+    if z.dtype != torch.float32:
+        raise NotImplementedError("affine_wide: float32 only")
+    B, D = z.shape
+    z = _a16(z.contiguous(), D % 4 == 0)
+    y = torch.empty_like(z)
+    logdet, acc = _ld_buffer(logdet, acc, B, z)
+    L.call("nf_affine_wide", ptr(z), ptr(y), ptr(logdet), ptr(blob), ptr(table), B, D, hidden_padded, direction, acc, L.stream())
+    return y, logdet
+
+
 def made_forward_spline(x, blob, table, hidden_padded, tail_bound, min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3,
                         logdet=None, acc=None):
     """neural_spline/autoregressive.py:94-134 density direction (MADE + 8-bin spline with linear tails) as one launch
