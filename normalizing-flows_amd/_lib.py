@@ -166,7 +166,7 @@ def _declare_prototypes(handle):
 def lib():
     global _lib
     if _lib is None:
-        path = os.environ.get("NF_MI355X_LIB")   # ablation builds (tools/*_ablate.py): another build of the SAME sources
+        path = os.environ.get("NF_MI355X_LIB")   # another build of the SAME sources: the safe-waits library of the counted-wait differential test
         if not path:
             path = LIBPATH
             if not os.path.exists(LIBPATH):

@@ -184,7 +184,6 @@ extern "C" int nf_conv3x3_gather(const void *in, void *col, int64_t B, int C, in
     if (B < 0 || C < 1 || H < 1 || W < 1 || ld < 9 * C || (flip != 0 && flip != 1) || batch_stride < (int64_t)C * H * W) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!in || !col) return NF_EFAULT;
-#ifndef NF_CONV_ELEMENTWISE      // (-DNF_CONV_ELEMENTWISE: the one-thread-per-element kernels of rounds 4-5)
     if (B * H * W < (1ll << 30) && (int64_t)C * H * W < (1ll << 30)) {
         const int npx = (int)(B * H * W), K = 9 * C;
         int KP = 1;
@@ -206,7 +205,6 @@ extern "C" int nf_conv3x3_gather(const void *in, void *col, int64_t B, int C, in
         NF_CHECK_LAUNCH();
         return NF_OK;
     }
-#endif
     hipLaunchKernelGGL(nf::conv3x3_gather_kernel, dim3(nf::grid_for(B * H * W * 9 * C, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const float *)in, (float *)col, B, C, H, W, ld, flip, batch_stride);
     NF_CHECK_LAUNCH();
@@ -219,7 +217,6 @@ extern "C" int nf_conv3x3_gather_sum(const void *P, const void *bias, void *out,
     if (B < 0 || C < 1 || H < 1 || W < 1 || ld < 9 * C || (flip != 0 && flip != 1)) return NF_EINVAL;
     if (B == 0) return NF_OK;
     if (!P || !out) return NF_EFAULT;
-#ifndef NF_CONV_ELEMENTWISE
     if (B * H * W < (1ll << 30) && C <= 128) {
         const int npx = (int)(B * H * W);
         const int gpx = npx / 64 >= 2048 ? 64 : (npx / 32 >= 2048 ? 32 : 16);
@@ -238,7 +235,6 @@ extern "C" int nf_conv3x3_gather_sum(const void *P, const void *bias, void *out,
         NF_CHECK_LAUNCH();
         return NF_OK;
     }
-#endif
     hipLaunchKernelGGL(nf::conv3x3_gather_sum_kernel, dim3(nf::grid_for(B * C * H * W, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const float *)P, (const float *)bias, (float *)out, B, C, H, W, ld, flip);
     NF_CHECK_LAUNCH();

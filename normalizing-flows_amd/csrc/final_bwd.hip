@@ -9,7 +9,7 @@
 // Mapping (second version).  The first version mirrored the forward kernel -- 32 rows per wave on v_mfma_f32_32x32x2_f32, a lane
 // owning TWO spline elements per group -- and needed 400+ registers: one wave per SIMD, and with nobody to share the SIMD with
 // every LDS round trip, every vector-memory issue (~100-250 cycles each) and every dependent transcendental was exposed: the
-// phase trace (tools/final_bwd_probe.py --trace) showed the spline arithmetic at ~7 cycles per instruction and the MFMAs at 0.78
+// phase trace of that version showed the spline arithmetic at ~7 cycles per instruction and the MFMAs at 0.78
 // of their issue rate, 250-265 us per launch (ablations were additive to the microsecond: nothing overlapped).  This version is
 // built for TWO waves per SIMD:
 //   * a wave owns 16 rows and multiplies on v_mfma_f32_16x16x4_f32: lane l = (row n = l & 15, quarter hq = l >> 4); the MFMA's
@@ -38,17 +38,11 @@ namespace nf {
 typedef float f32x4a __attribute__((ext_vector_type(4)));
 #define FB_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-// Round 6: NF_FB_NW = 4 -> 64-row tiles, TWO workgroups per CU (the 8-wave workgroup spent a third of its time at the ring's stage
+// Round 6: FB_NW = 4 -> 64-row tiles, TWO workgroups per CU (the 8-wave workgroup spent a third of its time at the ring's stage
 // barriers with every wave of the CU in the same phase: two independent workgroups drift apart and fill each other's waits); the ring
-// then streams half stages (NF_FB_KS = 4 k-steps, 8 KB per slot) so that both workgroups' LDS fits: 2 x (16 + 4 x 14.9) KB.
-#ifndef NF_FB_NW
-#define NF_FB_NW 8
-#endif
-#ifndef NF_FB_KS
-#define NF_FB_KS 8
-#endif
-constexpr int FB_NW = NF_FB_NW;                   // waves per workgroup
-constexpr int FB_KS = NF_FB_KS;                   // k-steps of the final weight per ring stage (8: 16 KB stages; 4: 8 KB)
+// then streams half stages (FB_KS = 4 k-steps, 8 KB per slot) so that both workgroups' LDS fits: 2 x (16 + 4 x 14.9) KB.
+constexpr int FB_NW = 8;                          // waves per workgroup
+constexpr int FB_KS = 8;                          // k-steps of the final weight per ring stage (8: 16 KB stages; 4: 8 KB)
 constexpr int FB_STG = FB_KS * 512;               // floats per ring stage
 constexpr int FB_SPG = 24 / FB_KS;                // stages per group
 static_assert((FB_NW == 8 || FB_NW == 4) && (FB_KS == 8 || FB_KS == 4) && FB_STG % (256 * FB_NW) == 0, "ring geometry");
@@ -63,18 +57,7 @@ constexpr int FB_NST = 8 * FB_SPG;                // stages of the transposed fi
 constexpr int FB_PART = FBR_PART;                 // knot-space sums of a workgroup: [feature][7 w | 7 h | 7 d | 3 pad]
 constexpr int FB_NI = 7;                          // coalesced instructions per direction for the 32 runs of 192 bytes of a group
 
-#ifdef FB_TRACE      // phase trace (tools/final_bwd_probe.py --trace): shader-clock cycles per phase, summed over the tiles of workgroup 0 / wave 0
-static unsigned long long *g_fb_trace = nullptr;
-extern "C" void nf_final_bwd_debug_trace(void *buf) { g_fb_trace = (unsigned long long *)buf; }
-#define FB_T(i) do { const unsigned long long t1_ = clock64(); T_[i] += t1_ - t0_; t0_ = t1_; } while (0)
-#else
-#define FB_T(i) do {} while (0)
-#endif
-
 struct FinalBwdArgs {
-#ifdef FB_TRACE
-    unsigned long long *trace;
-#endif
     const float *x, *gy, *gld, *cond, *wt, *tables;
     float *gx, *gcond, *gh, *part;
     int64_t B;
@@ -84,7 +67,6 @@ struct FinalBwdArgs {
 
 __global__ void __launch_bounds__(FB_THREADS, FB_NW == 4 ? 2 : 1)
 final_bwd_kernel(FinalBwdArgs a) {
-    typedef __attribute__((address_space(3))) void *lds_ptr;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *ring = smem;                                    // 2 x FB_STG
     const int tid = threadIdx.x, lane = tid & 63, hq = lane >> 4, n = lane & 15;
@@ -109,12 +91,9 @@ final_bwd_kernel(FinalBwdArgs a) {
         constexpr int PW = FB_STG / FB_NW;     // floats of a stage per requesting wave
         const float *src = a.wt + (size_t)s * FB_STG + wid * PW + lane * 4;
         float *dst = ring + (gs & 1) * FB_STG + wid * PW;
+        // round 6: requests as inline asm (common.hpp NF_DMA16): the products' operand look-ahead survives compilation
 #pragma unroll
-#ifdef NF_BUILTIN_DMA
-        for (int i = 0; i < PW / 256; ++i) __builtin_amdgcn_global_load_lds(src + i * 256, (lds_ptr)(dst + i * 256), 16, 0, 0);
-#else       // round 6: requests as inline asm (common.hpp NF_DMA16): the products' operand look-ahead survives compilation
         for (int i = 0; i < PW / 256; ++i) NF_DMA16(src - lane * 4 + i * 256, lane * 16, dst + i * 256);
-#endif
     };
     // 2-slot ring: stage s has landed for every wave; stage s + 1 is requested into the slot stage s - 1 just left.  `after`:
     // vector-memory operations this wave issued AFTER the requests of stage s (they retire in order, so they may stay in flight)
@@ -125,9 +104,7 @@ final_bwd_kernel(FinalBwdArgs a) {
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         // the raw barrier: __syncthreads() is a fence, and with an LDS-DMA possibly pending the compiler implements it as
         // s_waitcnt vmcnt(0) -- the counted waits above never took effect before this was found (round 3, in the Glow kernels)
-#ifndef FB_ABL_NOBAR      // (timing-only ablation: how much of the launch is waves waiting for each other at the ring's stage barriers)
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
         if (stage + 1 < total_stages) issue(stage + 1);
         const float *buf = ring + (stage & 1) * FB_STG;
         ++stage;
@@ -154,16 +131,9 @@ final_bwd_kernel(FinalBwdArgs a) {
         const float *base = a.cond + group_off(g, row0_);
 #pragma unroll
         for (int i = 0; i < FB_NI; ++i)
-#ifdef NF_BUILTIN_DMA
-            if (piece_ok(i, row0_)) __builtin_amdgcn_global_load_lds(base + poff[i], (lds_ptr)(CS + 240 * i), 16, 0, 0);
-#else
             if (piece_ok(i, row0_)) NF_DMA16(base, poff[i] * 4u, CS + 240 * i);
-#endif
     };
 
-#ifdef FB_TRACE
-    unsigned long long T_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t0_ = clock64();
-#endif
     // the NEXT tile's x / grad_y rows (and its first group's parameter rows) are requested under the last group's MFMA stages of
     // the current one, where few registers are live: a tile used to start with every wave of the chip waiting ~10 us for 8 KB
     f32x4 nx[4], ng[4];
@@ -204,10 +174,8 @@ final_bwd_kernel(FinalBwdArgs a) {
         if (hq == 0) GL[n] = gl;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        FB_T(0);      // tile prologue: requests, x / grad_y rows into the stash
 
         // ---- identity half: lane = feature, the wave's 16 rows two at a time ----
-#ifndef FB_ABL_NOIDENT
         {
             float kw[F_K + 1], kh[F_K + 1], kd[F_K + 1];
 #pragma unroll
@@ -245,8 +213,6 @@ final_bwd_kernel(FinalBwdArgs a) {
                 }
             }
         }
-#endif
-        FB_T(1);      // identity half
 
         // ---- transform half + gh = g W_final, group by group ----
         f32x4a acc[8];
@@ -260,7 +226,6 @@ final_bwd_kernel(FinalBwdArgs a) {
             // the group's parameter rows have landed (requested at least two stages ago)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
-            FB_T(2);  // wait for the group's parameter rows
             float gq[24];
             {
                 float prm[24];
@@ -275,13 +240,7 @@ final_bwd_kernel(FinalBwdArgs a) {
                 }
                 const int so = n * FB_P + 2 * (8 * (g >> 1) + 4 * (hq >> 1) + 2 * (g & 1) + (hq & 1)) + par_t;
                 const float xt = X[so], gyt = G[so];
-#ifdef FB_ABL_NOSPLINE
-                G[so] = xt + gyt;
-#pragma unroll
-                for (int k = 0; k < 24; ++k) gq[k] = prm[k] * gyt;
-#else
                 G[so] = rqs_regs_bwd<false>(p, xt, prm, gyt, gl, gq, inv_div);
-#endif
             }
             // gradient row -> the lane's piece (over the parameters it has just read)
 #pragma unroll
@@ -289,16 +248,13 @@ final_bwd_kernel(FinalBwdArgs a) {
                 *reinterpret_cast<f32x4 *>(mine + 4 * q) = f32x4{gq[4 * q], gq[4 * q + 1], gq[4 * q + 2], gq[4 * q + 3]};
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            FB_T(3);  // the spline backward element + the piece write
             // Row traffic: one burst per group right behind stage 0's acquire (7 coalesced gradient-row stores, 7 requests of the
             // next group's parameter rows); they retire in order behind stage 1's requests, so they may stay in flight at its acquire.
             constexpr bool more = !LAST;
 #pragma unroll
             for (int rb = 0; rb < FB_SPG; ++rb) {
                 const float *buf = acquire((rb == 1 && full) ? (more ? 2 * FB_NI : (has_next ? 2 * FB_NI + 9 : FB_NI)) : 0);
-                FB_T(4);  // stage wait + barrier + next stage's requests
                 if (rb == 0) {
-#ifndef FB_ABL_NOROWS
                     float *gbase = a.gcond + group_off(g, row0);
 #pragma unroll
                     for (int i = 0; i < FB_NI; ++i) {
@@ -313,22 +269,8 @@ final_bwd_kernel(FinalBwdArgs a) {
                         request_rows(0, next_row0);
                         fetch_rows(next_row0);
                     }
-#endif
-                    FB_T(5);  // gradient-row stores + the next group's requests
                 }
-#ifndef FB_ABL_NOMFMA
                 // stage rb: k-steps v = KS rb .. KS rb + KS - 1 (B operand = the lane's gradient value v), 8 unit blocks each
-#ifdef NF_NO_PREFETCH
-#pragma unroll
-                for (int vv = 0; vv < FB_KS; ++vv) {
-#pragma unroll
-                    for (int uq = 0; uq < 2; ++uq) {
-                        const f32x4 w4 = *reinterpret_cast<const f32x4 *>(buf + ((vv * 2 + uq) * 64 + lane) * 4);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[4 * uq + j] = FB_MFMA(w4[j], gq[FB_KS * rb + vv], acc[4 * uq + j]);
-                    }
-                }
-#else
                 {   // the A operands two reads (8 MFMAs) ahead of their use -- real since the requests are inline asm (NF_DMA16)
                     f32x4 w0 = *reinterpret_cast<const f32x4 *>(buf + lane * 4), w1 = *reinterpret_cast<const f32x4 *>(buf + (64 + lane) * 4);
 #pragma unroll
@@ -342,14 +284,7 @@ final_bwd_kernel(FinalBwdArgs a) {
                         for (int j = 0; j < 4; ++j) acc[4 * uq + j] = FB_MFMA(w4[j], gq[FB_KS * rb + vv], acc[4 * uq + j]);
                     }
                 }
-#endif
-#else
-                (void)buf;
-#pragma unroll
-                for (int v = 0; v < FB_KS; ++v) acc[v][0] += gq[FB_KS * rb + v];
-#endif
                 asm volatile("" ::"v"(acc[0][0]), "v"(acc[7][0]));
-                FB_T(6);  // 16 A-operand reads + 64 MFMAs (issue time: the last MFMAs may still be executing)
             }
         };
 #pragma nounroll
@@ -383,14 +318,7 @@ final_bwd_kernel(FinalBwdArgs a) {
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        FB_T(7);      // gx / gh rows out
     }
-#ifdef FB_TRACE
-    if (a.trace && blockIdx.x == 0 && tid == 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) a.trace[i] = T_[i];
-    }
-#endif
 
     // ---- the workgroup's knot-space sums of the batch-shared parameters, fixed order ----
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -464,9 +392,6 @@ extern "C" int nf_final_bwd(const void *x, const void *grad_y, const void *grad_
     FusedLayout lay;
     lay.nblk = num_blocks;
     FinalBwdArgs a;
-#ifdef FB_TRACE
-    a.trace = g_fb_trace;
-#endif
     a.x = (const float *)x; a.gy = (const float *)grad_y; a.gld = (const float *)grad_logdet; a.cond = (const float *)cond24;
     a.wt = (const float *)w_t; a.tables = (const float *)wpack + F_HDR + lay.off_tables();
     a.gx = (float *)grad_x; a.gcond = (float *)grad_cond24; a.gh = (float *)grad_h; a.part = (float *)partials;

@@ -34,10 +34,7 @@ constexpr int GC_NW = 8;             // waves per workgroup
 constexpr int GC_PX = 32 * GC_NW;    // pixels per workgroup
 constexpr int GC_HDR = 64;
 constexpr int GC_STAGE = 4096;       // floats per stage (16 KB)
-#ifndef NF_GC_RING
-#define NF_GC_RING 3
-#endif
-constexpr int GC_RING = NF_GC_RING;  // weight-ring slots of the 256-pixel kernel
+constexpr int GC_RING = 3;           // weight-ring slots of the 256-pixel kernel
 constexpr int GC_OBP = 4;            // output row-blocks (x 3 channels) per sweep
 constexpr int GC_KG1MAX = 16;        // k-groups of GEMM 1 whose gathered operands are kept in registers (one stage)
 
@@ -140,16 +137,7 @@ __device__ __forceinline__ void gc_mm128(const float *buf, int lane, f32x16 &acc
     // Round 6: that measurement was void -- with the ring's requests issued through the builtin the compiler knew an LDS-DMA was
     // pending and answered EVERY later LDS read with s_waitcnt lgkmcnt(0) (the loop compiled to read -> full wait -> 4 MFMAs,
     // look-ahead or not).  With the requests as inline asm (gc_dma16) the look-ahead below is real: k-group s + 2's operand is
-    // requested before k-group s's MFMAs (-DNF_GC_NOPIPE: the plain loop).
-#ifdef NF_GC_NOPIPE
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-        const f32x4 a = *reinterpret_cast<const f32x4 *>(buf + s * 256 + lane * 4);
-        const f32x16 &bs = (s >> 2) == 0 ? b0 : ((s >> 2) == 1 ? b1 : ((s >> 2) == 2 ? b2 : b3));
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc = GC_MFMA(a[r], bs[4 * (s & 3) + r], acc);
-    }
-#else
+    // requested before k-group s's MFMAs.
     f32x4 a0 = *reinterpret_cast<const f32x4 *>(buf + lane * 4), a1 = *reinterpret_cast<const f32x4 *>(buf + 256 + lane * 4);
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
@@ -162,7 +150,6 @@ __device__ __forceinline__ void gc_mm128(const float *buf, int lane, f32x16 &acc
         for (int r = 0; r < 4; ++r) acc = GC_MFMA(a[r], bs[4 * (s & 3) + r], acc);
         __builtin_amdgcn_sched_barrier(0);
     }
-#endif
 }
 
 // One 16-byte-per-lane LDS-DMA request as inline asm (round 6, see gc_mm128): base = wave-uniform global pointer (SGPR pair),
@@ -218,17 +205,7 @@ struct GlowLevel {
     float *out0, *out1;           // level output: channels [0, cout0) -> out0, the rest -> out1; or, out_sq = 1, through
     int cout0, out_sq;            //   the Squeeze.forward view into out0 = (B, C / 4, 2H, 2W)
     float *logdet;                // (B)
-#ifdef NF_GL_TRACE
-    unsigned long long *trace;    // debug builds: phase timestamps of workgroup 0 (100 MHz wall clock), 8 per block
-#endif
 };
-#ifdef NF_GL_TRACE
-static unsigned long long *g_gl_trace = nullptr;
-extern "C" void nf_glow_debug_trace(void *buf) { g_gl_trace = (unsigned long long *)buf; }
-#define GL_T(b, idx) do { if (lv.trace && blockIdx.x == 0 && threadIdx.x == 0) lv.trace[(b) * 8 + (idx)] = wall_clock64(); } while (0)
-#else
-#define GL_T(b, idx) do {} while (0)
-#endif
 
 __host__ __device__ inline int gl_wmix_padded(int C) { return (C * C + C + 63) / 64 * 64; }
 __host__ __device__ inline int gb_lds_floats(const GlowLevel &lv, int Cout, int PXW) {
@@ -531,14 +508,8 @@ glow_convnet_kernel(const float *__restrict__ x, int64_t xs_img, float *__restri
                                ? stages + (size_t)(2 * s + (wid >> 2)) * GC_STAGE + ((wid & 3) * PPW) * 256
                                : stages + (size_t)phys(s) * GC_STAGE + (wid * PPW) * 256;
         float *dst = ring + (gs % GC_RING) * GC_STAGE + (wid * PPW) * 256;
-#ifdef NF_GC_BUILTIN_DMA
-#pragma unroll
-        for (int i = 0; i < PPW; ++i)
-            __builtin_amdgcn_global_load_lds(src + (tid0 & 63) * 4 + i * 256, (__attribute__((address_space(3))) void *)(dst + i * 256), 16, 0, 0);
-#else
 #pragma unroll
         for (int i = 0; i < PPW; ++i) gc_dma16(src, (uint32_t)(((tid0 & 63) * 4 + i * 256) * 4), dst + i * 256);
-#endif
     };
     // GC_RING-slot ring, DMA GC_RING - 1 stages ahead: the wait leaves the younger stages' pieces in flight (vector-memory
     // operations retire in order; anything else a wave has outstanding only makes the wait stricter).  With one stage ahead
@@ -571,7 +542,6 @@ glow_convnet_kernel(const float *__restrict__ x, int64_t xs_img, float *__restri
     }
 
     for (int b = 0; b < nb; ++b) {
-    GL_T(b, 0);
     if (b > 0) {        // (the stream has already run on into this block's first stages through blob_nxt)
         blob_cur = blob_nxt;
         cur_b = b;
@@ -642,7 +612,6 @@ glow_convnet_kernel(const float *__restrict__ x, int64_t xs_img, float *__restri
         gc_leaky(acc, mt.slope);
     };
     GL_BARRIER();   // the prologue's LDS writes
-    GL_T(b, 1);
 #pragma unroll
     for (int s = 0; s < GC_KG1MAX; ++s) {
 #pragma unroll
@@ -656,7 +625,6 @@ glow_convnet_kernel(const float *__restrict__ x, int64_t xs_img, float *__restri
     }
     if constexpr (pair1) { gemm1_pair(H0, H1); gemm1_pair(H2, H3); gemm1_pair(H4, H5); gemm1_pair(H6, H7); }
     else { gemm1(H0); gemm1(H1); gemm1(H2); gemm1(H3); gemm1(H4); gemm1(H5); gemm1(H6); gemm1(H7); }
-    GL_T(b, 2);
 
     // ---- sweeps over h2: GEMM 2 block by block, each block consumed at once by GEMM 3 ----
     for (int pass = 0; pass < mt.npass; ++pass) {
@@ -679,7 +647,6 @@ glow_convnet_kernel(const float *__restrict__ x, int64_t xs_img, float *__restri
             }
         }
         // ---- col2im: per output block, tap products -> LDS, 9-term neighbour gather, + bias, -> HBM ----
-        GL_T(b, 3);
 #pragma unroll
         for (int mm = 0; mm < GC_OBP; ++mm) {
             const int blk = GC_OBP * pass + mm;
@@ -693,12 +660,10 @@ glow_convnet_kernel(const float *__restrict__ x, int64_t xs_img, float *__restri
             }
         }
     }
-    GL_T(b, 4);
     if (fused) {
         gl_post<GC_PX, 64 * GC_NW>(lv, b, zin, zalt, wmix, pl.prm, pl.ldt, pl.ldacc, H, W, tid);
         float *t_ = zin; zin = zalt; zalt = t_;
     }
-    GL_T(b, 5);
     }  // blocks
     if (fused) gl_store<GC_PX, 64 * GC_NW>(lv, zin, pl.ldacc, H, W, img0, B, tid0);
 }
@@ -715,12 +680,9 @@ glow_convnet_kernel(const float *__restrict__ x, int64_t xs_img, float *__restri
 // which are latency-bound loops over the workgroup's threads.
 #define GC_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 constexpr int GS_NW = 4;
-#ifndef NF_GS_HW
-#define NF_GS_HW 4
-#endif
 // helper waves per instantiation (0: the MFMA waves do everything, as in round 2): with helpers the workgroup has two waves
 // per SIMD and 256 registers per lane, which the 16-block instantiation (64 output accumulators more) does not fit
-template <int OBT> struct GsHelpers { static constexpr int value = OBT <= 8 ? NF_GS_HW : 0; };
+template <int OBT> struct GsHelpers { static constexpr int value = OBT <= 8 ? 4 : 0; };
 constexpr int GS_PX = 16 * GS_NW;
 constexpr int GS_RING = 4;
 constexpr int GS_KB1MAX = 16;   // k-blocks of GEMM 1 whose gathered operands fit the register file (Cin <= 28)
@@ -778,7 +740,6 @@ glow_convnet_small_kernel(const float *__restrict__ x, int64_t xs_img, float *__
     }
 
     for (int b = 0; b < nb; ++b) {
-    GL_T(b, 0);
     const float *blob = fused ? lv.blob(b) : blob0;
     const float *stages = blob + gc_off_stages(mt);
     int stage = 0;   // per block: the ring is the col2im scratch at the end of a block, so the stream restarts
@@ -824,7 +785,6 @@ glow_convnet_small_kernel(const float *__restrict__ x, int64_t xs_img, float *__
         gc_fill_xin_global<GS_PX, GS_NT>(x, xs_img, xin, mt.Cin, H, W, img0, B, tid);
     }
     GL_BARRIER();
-    GL_T(b, 1);
 
     f32x4 O[2 * OBT];
     if (!mfma_wave) {
@@ -896,7 +856,6 @@ glow_convnet_small_kernel(const float *__restrict__ x, int64_t xs_img, float *__
         }
     }
 
-    GL_T(b, 2);
     // ---- one sweep: h2 block by block (GEMM 2), each consumed at once by GEMM 3 ----
 #pragma unroll
     for (int i = 0; i < 2 * OBT; ++i) O[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -951,7 +910,6 @@ glow_convnet_small_kernel(const float *__restrict__ x, int64_t xs_img, float *__
     }
 
     }  // MFMA waves
-    GL_T(b, 3);
     // ---- col2im: the weight ring is dead now; when all output blocks' tap products fit its 64 KB they go there at once
     // and ONE flat gather follows (two barriers in all), otherwise block by block through P ----
     if (mt.OB * 32 * GS_PX <= GS_RING * GC_STAGE) {
@@ -982,14 +940,12 @@ glow_convnet_small_kernel(const float *__restrict__ x, int64_t xs_img, float *__
             }
         }
     }
-    GL_T(b, 4);
     if (fused) {
         gl_post<GS_PX, GS_NT>(lv, b, zin, zalt, wmix, pl.prm, pl.ldt, pl.ldacc, H, W, tid);
         float *t_ = zin; zin = zalt; zalt = t_;
     } else {
         GL_BARRIER();
     }
-    GL_T(b, 5);
     }  // blocks
     if (fused) gl_store<GS_PX, GS_NT>(lv, zin, pl.ldacc, H, W, img0, B, tid);
 }
@@ -1007,10 +963,7 @@ glow_convnet_small_kernel(const float *__restrict__ x, int64_t xs_img, float *__
 // other's MFMAs); each workgroup streams all weights once (0.93 MB at the 4x4 level).  In a level chain the register
 // prefetch runs straight on into the next block's stream.
 constexpr int GT_PX = 16;
-#ifndef NF_GT_NW
-#define NF_GT_NW 8
-#endif
-constexpr int GT_NW = NF_GT_NW;
+constexpr int GT_NW = 8;
 constexpr int GT_BPW = 16 / GT_NW;   // 16-row blocks of h1 / h2 per wave
 constexpr int GT_PF = 16;          // units (16 rows x 16 k = [64 lanes][4] = 1 KB) a wave keeps in flight
 constexpr int GT_SLOT = 1024;      // floats of 4 units (blob granularity)
@@ -1162,7 +1115,6 @@ glow_convnet_tiny_kernel(const float *__restrict__ x, int64_t xs_img, float *__r
     };
 
     for (int b = 0; b < nb; ++b) {
-    GL_T(b, 0);
     const float *blob = fused ? lv.blob(b) : blob0;
     // where the prefetch continues when it runs off the end of THIS block's stream (it does so 16 units before the end)
     cross = (b + 1 < nb) ? stream_of(b + 1) : stream_of(b) + (size_t)(nunits - 1) * 256;
@@ -1186,7 +1138,6 @@ glow_convnet_tiny_kernel(const float *__restrict__ x, int64_t xs_img, float *__r
         cols[i] = xin[li * mt.Cin * PH * PW + py * PW + pxx + koff[16 * kb + 4 * gg + r]];
     }
     GL_BARRIER();
-    GL_T(b, 1);
 
     // ---- GEMM 1 -> h1s ----
     for (int bl = 0; bl < GT_BPW; ++bl) {
@@ -1197,7 +1148,6 @@ glow_convnet_tiny_kernel(const float *__restrict__ x, int64_t xs_img, float *__r
         *reinterpret_cast<f32x4 *>(h1s + ((b16 * 4 + g) * GT_PX + j16) * 4) = acc;
     }
     GL_BARRIER();
-    GL_T(b, 2);
     // ---- GEMM 2 -> h2s ----
     for (int bl = 0; bl < GT_BPW; ++bl) {
         const int b16 = GT_BPW * wid + bl;
@@ -1216,17 +1166,14 @@ glow_convnet_tiny_kernel(const float *__restrict__ x, int64_t xs_img, float *__r
         for (int r = 0; r < 4; ++r) P[(16 * o16 + 4 * g + r) * GT_PX + j16] = acc[r];
     }
     GL_BARRIER();
-    GL_T(b, 3);
     // ---- col2im over all output blocks in one flat loop ----
     gc_gather_block<GT_PX, 64 * GT_NW>(P, 0, mt, H, W, img0, B, small, out, fused ? pl.prm : nullptr, tid, mt.OB);
-    GL_T(b, 4);
     if (fused) {
         gl_post<GT_PX, 64 * GT_NW>(lv, b, zin, zalt, wmix, pl.prm, pl.ldt, pl.ldacc, H, W, tid);
         float *t_ = zin; zin = zalt; zalt = t_;
     } else {
         GL_BARRIER();
     }
-    GL_T(b, 5);
     }  // blocks
     if (fused) gl_store<GT_PX, 64 * GT_NW>(lv, zin, pl.ldacc, H, W, img0, B, tid);
 }
@@ -1404,9 +1351,6 @@ extern "C" int nf_glow_level(const void *in0, const void *in1, int cin0, int in_
     lv.in0 = (const float *)in0; lv.in1 = (const float *)in1; lv.cin0 = in_squeezed ? C : cin0; lv.in_sq = in_squeezed ? 1 : 0;
     lv.out0 = (float *)out0; lv.out1 = (float *)out1; lv.cout0 = out_squeezed ? C : cout0; lv.out_sq = out_squeezed ? 1 : 0;
     lv.logdet = (float *)logdet;
-#ifdef NF_GL_TRACE
-    lv.trace = g_gl_trace;
-#endif
     return gc_launch(in0, (int64_t)C * H * W, out0, nullptr, gc_meta(c1, Cout, leaky_slope), B, H, W, layout, lv,
                      (hipStream_t)stream);
 }

@@ -166,7 +166,6 @@ lu_tile_kernel(const T *__restrict__ x, T *__restrict__ y, T *__restrict__ logde
         // ---- stage rows: the 64 x D block is one contiguous span, read flat with unit stride (8 loads in flight per lane);
         //      density applies the permutation on the way in: t_j = x[perm[j]]  <=>  t[inv[c]] = x[c]
         const int span = ts * D;
-#ifndef NF_LU_ABL_NOSTAGE
         for (int base = 0; base < 64 * D; base += 64 * 8) {
             T v[8];
 #pragma unroll
@@ -184,7 +183,6 @@ lu_tile_kernel(const T *__restrict__ x, T *__restrict__ y, T *__restrict__ logde
                 }
             }
         }
-#endif
         // the tile is private to this wave: no workgroup barrier, wave-level ordering of LDS accesses suffices
         __builtin_amdgcn_wave_barrier();
         // Rows are processed four at a time (4 independent accumulators share every vector read of the sample row), which
@@ -219,7 +217,6 @@ lu_tile_kernel(const T *__restrict__ x, T *__restrict__ y, T *__restrict__ logde
                     for (int q = 0; q < V; ++q) a[r] += m[r].v[q] * t.v[q];
             }
         };
-#ifndef NF_LU_ABL_NOCOMPUTE
         const int Dg = Dp;
         if (direction == 0) {
             for (int i0 = 0; i0 < Dg; i0 += 4) {  // u_i = sum_{j >= i0} U_ij t_j   (U_ij = 0 for j < i)
@@ -265,12 +262,8 @@ lu_tile_kernel(const T *__restrict__ x, T *__restrict__ y, T *__restrict__ logde
                 for (int r = 0; r < 4; ++r) row[i0 + r] = t[r];
             }
         }
-#endif
         __builtin_amdgcn_wave_barrier();
         // ---- store rows flat (unit stride); the sample direction un-permutes on the way out: y[c] = t[inv[c]] ----
-#ifdef NF_LU_ABL_NOSTORE
-        if (lad == T(12345))
-#endif
         for (int e = lane; e < span; e += 64) {
             const int r = e / D, c = e - r * D;
             y[b0 * D + e] = direction == 0 ? tile[(size_t)r * P + c] : tile[(size_t)r * P + sinv[c]];

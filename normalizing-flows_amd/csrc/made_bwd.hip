@@ -547,12 +547,10 @@ extern "C" int nf_made_backward_t64(const void *g_params, const void *bits, void
 }
 
 static int made_wgrad_chunk_rows(int64_t Bp, int ntiles) {
-    // measured at config 5's layer (50 tiles, B = 65 536; ablation builds with -DNF_MW_SLOTS / -DNF_MW_TILE_MAJOR): 768 / 1024 / 1536 / 2048 / 3072 workgroups
+    // measured at config 5's layer (50 tiles, B = 65 536): 768 / 1024 / 1536 / 2048 / 3072 workgroups
     // = 1.19 / 1.12 / 0.98 / 1.07 / 0.99 ms for this launch + 18 / 24 / 33 / 40 / 55 us for the reduction: three rounds of 512
-#ifndef NF_MW_SLOTS
-#define NF_MW_SLOTS 1536
-#endif
-    int64_t want = (NF_MW_SLOTS + ntiles - 1) / ntiles;
+    constexpr int slots = 1536;
+    int64_t want = (slots + ntiles - 1) / ntiles;
     if (want < 1) want = 1;
     int64_t rows = (Bp + want - 1) / want;
     rows = (rows + 63) / 64 * 64;
@@ -585,14 +583,11 @@ extern "C" int nf_made_wgrad(const void *gp_pad, const void *x_pad, const void *
     const int64_t Bp = (B + 63) / 64 * 64;
     const int rows = made_wgrad_chunk_rows(Bp, ntiles);
     const int chunks = (int)((Bp + rows - 1) / rows);
-    // tile-major: the workgroups in flight together work on the same row chunk (its operands are shared through L2 / MALL)
-#ifndef NF_MW_TILE_MAJOR
-#define NF_MW_TILE_MAJOR 1
-#endif
-    const int tile_major = NF_MW_TILE_MAJOR;
-    const dim3 grid = tile_major ? dim3((unsigned)ntiles, (unsigned)chunks) : dim3((unsigned)chunks, (unsigned)ntiles);
+    // tile-major (the kernel's last argument): the workgroups in flight together work on the same row chunk (its operands are shared
+    // through L2 / MALL)
+    const dim3 grid((unsigned)ntiles, (unsigned)chunks);
     hipLaunchKernelGGL(nf::made_wgrad_kernel, grid, dim3(nf::MW_NT), 0, st, (const float *)gp_pad, (const float *)x_pad,
-                       (const float *)G, (const float *)save, (float *)part, (const int *)wtable, rows, Bp, tile_major);
+                       (const float *)G, (const float *)save, (float *)part, (const int *)wtable, rows, Bp, 1);
     NF_CHECK_LAUNCH();
     hipLaunchKernelGGL(nf::made_wgrad_reduce_kernel, dim3(64, (unsigned)ntiles), dim3(256), 0, st, (const float *)part, (float *)grads,
                        (const unsigned char *)mask, (const int *)wtable, (const int *)stable, chunks);
@@ -615,10 +610,9 @@ extern "C" int nf_made_wgrad_pos(const void *gp_pad, const void *x_pad, const vo
     hipStream_t st = (hipStream_t)stream;
     const int rows = made_wgrad_chunk_rows(B, ntiles);
     const int chunks = (int)((B + rows - 1) / rows);
-    const int tile_major = NF_MW_TILE_MAJOR;
-    const dim3 grid = tile_major ? dim3((unsigned)ntiles, (unsigned)chunks) : dim3((unsigned)chunks, (unsigned)ntiles);
+    const dim3 grid((unsigned)ntiles, (unsigned)chunks);      // tile-major, as nf_made_wgrad
     hipLaunchKernelGGL(nf::made_wgrad_pos_kernel, grid, dim3(nf::MW_NT), 0, st, (const float *)gp_pad, (const float *)x_pad,
-                       (const float *)gscratch, (const float *)fscratch, (float *)part, (const int *)wtable, rows, B, tile_major,
+                       (const float *)gscratch, (const float *)fscratch, (float *)part, (const int *)wtable, rows, B, 1,
                        num_layers, positions);
     NF_CHECK_LAUNCH();
     hipLaunchKernelGGL(nf::made_wgrad_reduce_kernel, dim3(64, (unsigned)ntiles), dim3(256), 0, st, (const float *)part, (float *)grads,

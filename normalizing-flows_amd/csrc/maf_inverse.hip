@@ -61,11 +61,7 @@ __device__ __forceinline__ void block_part_lds_x(const float *__restrict__ A, co
     const f32x4 *pa = reinterpret_cast<const f32x4 *>(A) + half * 32 + l31;
     const f32x4 *pa2 = reinterpret_cast<const f32x4 *>(PAIR ? A2 : A) + half * 32 + l31;
     const f32x4 *pb = reinterpret_cast<const f32x4 *>(Sl) + half * 64 + l31;
-#ifdef NF_MAF_ABL_NOBLOCK
-    const int nkb = 0;
-#else
     const int nkb = K >> 3;
-#endif
     if (nkb > 0) {
         // K is a multiple of 32 (host packer), i.e. nkb of 4: eight named operand stages, each refilled right after it is
         // consumed (prefetch distance = 8 k-blocks = 4096 MFMA cycles, no register rotation moves).
@@ -252,15 +248,9 @@ __device__ __forceinline__ void block_part(const float *__restrict__ A, const fl
 __device__ __forceinline__ void block_part_mode(int mode, const float *__restrict__ A, const float *__restrict__ A2,
                                                 const float *Sl, int K, float *ldsw, int lane, float *stash, float *ring,
                                                 f32x32 &out) {
-#ifdef NF_MAF_NO_RING
-    if (mode == 1) block_part_lds_x<true, false>(A, A2, Sl, K, ldsw, lane, stash);
-    else if (mode == 2) block_part_lds_x<false, true>(A, nullptr, Sl, K, ldsw, lane, stash);
-    else block_part_lds_x<false, false>(A, nullptr, Sl, K, ldsw, lane, nullptr);
-#else
     if (mode == 1) block_part_ring<true, false>(A, A2, Sl, K, ldsw, lane, stash, ring);
     else if (mode == 2) block_part_ring<false, true>(A, nullptr, Sl, K, ldsw, lane, stash, ring);
     else block_part_ring<false, false>(A, nullptr, Sl, K, ldsw, lane, nullptr, ring);
-#endif
 #pragma unroll
     for (int u = 0; u < MT; ++u) out[u] = ldsw[u * 64 + lane];
     __builtin_amdgcn_wave_barrier();
@@ -302,11 +292,7 @@ maf_inverse_kernel(const float *__restrict__ z, float *__restrict__ y, float *__
     const int D = table[0], Dp = table[1], Hp = table[3], T = table[4];
     const int64_t sample = wt * 64 + lane;
     const bool valid = sample < B;
-#ifdef NF_MAF_ABL_HOT   // every wave on the same scratch slab: L2-resident state, timing only
-    const int64_t wts = 0;
-#else
     const int64_t wts = active ? wt : 0;
-#endif
     const float *zr = z + (valid ? sample : B - 1) * D;
     float *Sw = S + wts * ((int64_t)5 * Hp * 64);   // [layer][Hp/8][2][64][4]
     float *Xw = Xs + wts * ((int64_t)Dp * 64);      // [Dp/8][2][64][4]
@@ -412,11 +398,7 @@ maf_inverse_kernel(const float *__restrict__ z, float *__restrict__ y, float *__
 
         // The sequential part indexes the register vectors with the (wave-uniform) unit number: one compact copy of each
         // layer's code instead of 32 predicated ones, and a scalar loop over the units of the current degree.
-#ifdef NF_MAF_ABL_NOSEQ
-        for (int s = 0; s < (B == 12345 ? ns : 0); ++s) {
-#else
         for (int s = 0; s < ns; ++s) {
-#endif
             const unsigned m = (unsigned)te[4 + s];
             int colf = dlo + s;
             float zf = 0.0f;
@@ -561,11 +543,7 @@ extern "C" int nf_maf_inverse(const void *z, void *y, void *logdet, const void *
     // the feature scratch is read with zero weights before it is written (K0 is padded to 32): it must hold finite values
     if (hipMemsetAsync(Xs, 0, (size_t)nwt * 64 * Dp * sizeof(float), st) != hipSuccess) return NF_EIO;
     const int grid = (int)((nwt + nf::MW - 1) / nf::MW);
-#ifdef NF_MAF_NO_PAIR
-    float *Ps = nullptr;
-#else
     float *Ps = Xs + nwt * 64 * Dp;
-#endif
     const size_t lds_ring = (size_t)nf::MW * nf::MRB * 512 * sizeof(float);
     static nf::LdsOptIn opted_aff;
     if (nf::opt_in_lds(reinterpret_cast<const void *>(&nf::maf_inverse_kernel<false>), lds_ring, opted_aff) != NF_OK)

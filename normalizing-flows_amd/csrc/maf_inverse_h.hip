@@ -25,18 +25,13 @@ namespace nf {
 
 constexpr int HT = 32;    // units per tile (flows/maf_pack.py TILE)
 constexpr int HS = 16;    // degrees per tile
-#ifndef NF_MAF_HNW
-#define NF_MAF_HNW 4
-#endif
-constexpr int HNW = NF_MAF_HNW;    // waves per workgroup (ablation, round 4, config 5 in one gpurun call: 4 -> 13.9 ms, 8 = one 8-wave
+constexpr int HNW = 4;             // waves per workgroup (measured in round 4 at config 5, one session: 4 -> 13.9 ms, 8 = one 8-wave
                                    // workgroup per CU -> 14.5 ms, 2 -> 24.5 ms); two workgroups per CU (their tile phases drift apart: one's sequential part overlaps the other's block part)
 constexpr int H_HDR = 8, H_ENT = 24;
 // floats of a tile record after the A operands, NL = 1 + 2 num_blocks hidden layers: bias[NL][32] | biasF | W0d[32][16] | Wd[NL-1] | WFd
 constexpr int h_seq(int NL) { return NL * HT + HT + HT * HS + (NL - 1) * HT * HT + HT * HT; }
-#ifndef NF_MAF_LB
-#define NF_MAF_LB 4     // round 5, same gpurun call: 8 activation slots 11.74 ms, 4 slots 11.14 ms (config 5; tools/maf_ablate5.py)
-#endif
-constexpr int h_lb(bool fast) { return fast ? NF_MAF_LB : 4; }     // activation slots of a wave's ring; + 4 + 4 weight slots of 1 KB
+constexpr int H_LB_FAST = 4;     // round 5, same session: 8 activation slots 11.74 ms, 4 slots 11.14 ms (config 5)
+constexpr int h_lb(bool fast) { return fast ? H_LB_FAST : 4; }     // activation slots of a wave's ring; + 4 + 4 weight slots of 1 KB
 
 #define HMFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
@@ -84,9 +79,6 @@ __device__ __forceinline__ void h_block(const float *__restrict__ A, const float
         // SGPR base + 32-bit lane offset (round 5): the three streams' bases are wave-uniform, so no 64-bit per-lane address is
         // computed or kept alive per stream (the VGPR-address form cost ~30 spilled registers once p stayed live across tiles)
         auto dma1 = [&](uint32_t dst, const float *base, uint32_t byte_off) {
-#ifdef NF_MAF_ABL_NO_DMA
-            return;
-#endif
             // (m0 is a reserved register: the compiler does not honour it as a clobber, so it is saved and restored here)
             uint32_t m0_;
             asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
@@ -128,15 +120,11 @@ __device__ __forceinline__ void h_block(const float *__restrict__ A, const float
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the slots' reads have returned: they may be requested again
             req_b(kb + LB);
             req_a(kb + 4, slot);
-#ifndef NF_MAF_ABL_NO_MFMA       // (ablation builds, tools/maf_ablate5.py: timing only, results are garbage)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 c0 = HMFMA(a[i], b[i], c0);
                 if constexpr (PAIR) c2 = HMFMA(a2[i], b[i], c2);
             }
-#else
-            c0[0] += a[0] * b[0] + a2[1];
-#endif
         };
         // prologue: the first LB - 4 activation blocks, then pseudo-steps -4 .. -1 in the steps' own order (nkb is a multiple of 4)
 #pragma unroll
@@ -160,13 +148,11 @@ __device__ __forceinline__ void h_block(const float *__restrict__ A, const float
                 f32x4 a2 = a;
                 if constexpr (PAIR) a2 = *reinterpret_cast<const f32x4 *>(ring + (LB + 4 + q) * 256 + lane * 4);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifndef NF_MAF_ABL_NO_MFMA
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     c0 = HMFMA(a[i], (*breg)[4 * q + i], c0);
                     if constexpr (PAIR) c2 = HMFMA(a2[i], (*breg)[4 * q + i], c2);
                 }
-#endif
             }
         }
     }
@@ -445,14 +431,9 @@ maf_inverse_h_kernel(const float *__restrict__ z, float *__restrict__ y, float *
         const float *A0 = rec;
         const float *Ah = A0 + K0 * HT;             // A1..A_{NL-1}, AF: Kh * 32 floats each
         // stage the sequential part's weights, one copy per workgroup
-#ifndef NF_MAF_ABL_NO_BARRIER
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS-only barrier: a fence would wait for the activation stores in flight
-#endif
         if constexpr (FAST) {       // regular tile: triangular record in reading order, copied as it is
             const f32x4 *src = reinterpret_cast<const f32x4 *>(Ah + (size_t)NL * Kh * HT);
-#ifdef NF_MAF_ABL_NO_STAGE
-            if (t == t_beg)
-#endif
             const int n4 = (te[20] == 2 ? hfx_seq(NL) : hf_seq(NL)) / 4;
             for (int i = threadIdx.x; i < n4; i += 64 * HNW) reinterpret_cast<f32x4 *>(seqw)[i] = src[i];
         } else {                    // the five 32 x 32 diagonal blocks with their columns in (half, register) order: source quad
@@ -468,9 +449,7 @@ maf_inverse_h_kernel(const float *__restrict__ z, float *__restrict__ y, float *
                 reinterpret_cast<f32x4 *>(seqw)[d] = src[i];
             }
         }
-#ifndef NF_MAF_ABL_NO_BARRIER
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS-only barrier: a fence would wait for the activation stores in flight
-#endif
         if (!active) continue;
         const float *bias = seqw;
         const float *biasF = bias + NL * HT;
@@ -482,11 +461,7 @@ maf_inverse_h_kernel(const float *__restrict__ z, float *__restrict__ y, float *
         {
             // tile pairing: even tile = its own products + the next tile's over the same operands (raw accumulators to the
             // stash); odd tile = the stash + the 32 units of its partner
-#ifdef NF_MAF_ABL_NO_PAIR
-            const int mode = 0;
-#else
             const int mode = !Pw ? 0 : ((t & 1) ? 2 : (t + 1 < T ? 1 : 0));
-#endif
             const float *Ah2 = Ah;
             int Kh2 = 0;
             if (mode == 1) {
@@ -542,7 +517,6 @@ maf_inverse_h_kernel(const float *__restrict__ z, float *__restrict__ y, float *
                                      l + 1 < NL ? p[l + 1 < NL ? l + 1 : 0] : pF);
             }
         }
-#ifndef NF_MAF_ABL_NO_BIAS
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int u = (r & 3) + 8 * (r >> 2) + 4 * hh;
@@ -550,7 +524,6 @@ maf_inverse_h_kernel(const float *__restrict__ z, float *__restrict__ y, float *
             for (int l = 0; l < NL; ++l) p[l][r] += bias[l * HT + u];
             pF[r] += biasF[u];
         }
-#endif
         f32x16 xg = {0};   // window features dlo-1 .. dlo+14 (0-based): xg[0] is the carry, xg[s+1] the output of step s
         xg[0] = xcarry;
 
@@ -563,12 +536,8 @@ maf_inverse_h_kernel(const float *__restrict__ z, float *__restrict__ y, float *
                 constexpr int G = decltype(G_)::value;
                 if (G < ns) {
                     float xn, pv = 0.0f;
-#ifndef NF_MAF_ABL_NO_SEQ
                     if (G < HX_STEPS && xtile) hf_step<NB, (G < HX_STEPS ? G : 0), true>(p, pF, xg, wh, zin[G], ld, xn, pv, wx, mx, hh);
                     else hf_step<NB, G>(p, pF, xg, wh, zin[G], ld, xn, pv);
-#else
-                    xn = zin[G] + p[0][G] + pF[G] + wh[G][0];
-#endif
                     xcarry = xn;
                     const int f = dlo + G;
                     if constexpr (TRAIN) {      // wave-uniform base + 32-bit lane offset: no 64-bit per-lane address kept across the steps
@@ -681,17 +650,9 @@ maf_inverse_h_kernel(const float *__restrict__ z, float *__restrict__ y, float *
         // ---- publish the tile: the register quads ARE the B-operand entries (k-block 4 t + q, half hh) ----
         // Not the tiles nobody streams back: the layer's last tile, and on the fast path (tile t + 1 contracts tile t from the
         // registers) the one before it when this launch runs through the end of the layer (a later LAUNCH would reload it).
-#ifdef NF_MAF_ABL_PUBLISH_ALL
-        const bool pub = true;
-#else
         const bool pub = bits != nullptr || (FAST ? (t + 2 < T || (t + 1 < T && t_stop < T)) : t + 1 < T);   // (bits: the training
         // forward -- nf_maf_scratch_rows reads the whole scratch back as the weight-gradient launch's activations)
-#endif
-#ifdef NF_MAF_ABL_NO_PUBLISH
-        if (p[0][0] == 1.2345f)
-#else
         if (pub)
-#endif
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const size_t o = ((size_t)((4 * t + q) * 2 + hh) * 32 + n) * 4;

@@ -52,49 +52,28 @@ __device__ __forceinline__ void mf_ring_start(MfRing &r, const float *stream, in
 }
 
 // four k-groups: ring entries HALF .. HALF + 3 = stream entries e0 .. e0 + 3 of the item; acc[sb] += W[32 x 32] . act[32 x 32 samples].
-// MF_SCHED (ablation switch, tools/build_variant.py; measured in ONE gpurun call at config 5's layer, B = 65 536):
-//   0 = the compiler's own schedule (default, 0.721 ms): hipcc sinks the eight re-requests of a loop iteration to its end and waits
-//       for the first of them at the top of the next one -- which turns the two waves of a SIMD into a ping-pong: one issues its 64
-//       MFMAs (4096 cycles) while the other's eight requests (one L2 round trip) are in flight;
-//   1 = every entry's re-request pinned right behind the MFMAs that consumed it (__builtin_amdgcn_sched_barrier): 0.772 ms -- the
-//       scheduling barriers also pin each k-group's LDS reads right in front of its MFMAs;
-//   2 = 1 + the B operand software-pipelined one k-group ahead (b = this k-group's values on entry, the next group's on exit;
-//       bp = the NEXT k-group's address, clamped to `blast`): 0.745 ms.
-#ifndef MF_SCHED
-#define MF_SCHED 0
-#endif
+// The schedule is the compiler's own (measured in one session at config 5's layer, B = 65 536: 0.721 ms): hipcc sinks the eight
+// re-requests of a loop iteration to its end and waits for the first of them at the top of the next one -- which turns the two waves
+// of a SIMD into a ping-pong: one issues its 64 MFMAs (4096 cycles) while the other's eight requests (one L2 round trip) are in
+// flight.  Two hand-pinned schedules were slower and were removed: every entry's re-request pinned right behind the MFMAs that
+// consumed it (__builtin_amdgcn_sched_barrier, which also pins each k-group's LDS reads right in front of its MFMAs): 0.772 ms; that
+// plus the B operand software-pipelined one k-group ahead: 0.745 ms.
 // TR = rows per tile (64; 128 for the narrow NSF networks whose activations leave room for it): a k-group of activations is
 // [2 hh][TR rows][4] = 8 TR floats.
 template <int NS, int HALF, int TR = 64>
-__device__ __forceinline__ void mf_group(MfRing &r, int e0, const float *&bp, const float *blast, f32x4 (&b)[2], f32x16 (&acc)[NS]) {
+__device__ __forceinline__ void mf_group(MfRing &r, int e0, const float *&bp, f32x4 (&b)[2], f32x16 (&acc)[NS]) {
     constexpr int KGS = 8 * TR;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        f32x4 bn[2];
-        bn[0] = *reinterpret_cast<const f32x4 *>(bp);
-        if constexpr (NS == 2) bn[1] = *reinterpret_cast<const f32x4 *>(bp + 128);
-        if constexpr (MF_SCHED == 2) {
-            bp = bp + KGS < blast ? bp + KGS : blast;
-            __builtin_amdgcn_sched_barrier(0);       // (the reads go out IN FRONT of this k-group's MFMAs, not behind them)
-        } else {
-            bp += KGS;
-            b[0] = bn[0];
-            if constexpr (NS == 2) b[1] = bn[1];
-        }
+        b[0] = *reinterpret_cast<const f32x4 *>(bp);
+        if constexpr (NS == 2) b[1] = *reinterpret_cast<const f32x4 *>(bp + 128);
+        bp += KGS;
         const f32x4 av = r.a[HALF + j];
-        if constexpr (MF_SCHED == 0) r.a[HALF + j] = *reinterpret_cast<const f32x4 *>(r.ap + (size_t)(e0 + j + 8) * 256);
+        r.a[HALF + j] = *reinterpret_cast<const f32x4 *>(r.ap + (size_t)(e0 + j + 8) * 256);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             acc[0] = MF_MFMA(av[i], b[0][i], acc[0]);
             if constexpr (NS == 2) acc[1] = MF_MFMA(av[i], b[1][i], acc[1]);
-        }
-        if constexpr (MF_SCHED != 0) {
-            r.a[HALF + j] = *reinterpret_cast<const f32x4 *>(r.ap + (size_t)(e0 + j + 8) * 256);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if constexpr (MF_SCHED == 2) {
-            b[0] = bn[0];
-            if constexpr (NS == 2) b[1] = bn[1];
         }
     }
 }
@@ -103,15 +82,8 @@ __device__ __forceinline__ void mf_group(MfRing &r, int e0, const float *&bp, co
 // offset 4 (64 hh + n [+ 32 sb]).  nkg is a multiple of 4 (packer).
 template <int NS, bool ADD, int TR = 64>
 __device__ __forceinline__ void mf_item(MfRing &r, int nkg, const float *Bl, f32x16 (&acc)[NS]) {
-    constexpr int KGS = 8 * TR;
     f32x4 b[2];
-    const float *blast = Bl + (size_t)(nkg > 0 ? nkg - 1 : 0) * KGS;
     const float *bp = Bl;
-    if constexpr (MF_SCHED == 2) {
-        b[0] = *reinterpret_cast<const f32x4 *>(Bl);
-        if constexpr (NS == 2) b[1] = *reinterpret_cast<const f32x4 *>(Bl + 128);
-        bp = nkg > 1 ? Bl + KGS : Bl;
-    }
     // bias group = ring entries 0..3: entry q holds bias[8 q + 4 hh + 0..3] = accumulator registers 4 q + i
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -122,14 +94,13 @@ __device__ __forceinline__ void mf_item(MfRing &r, int nkg, const float *Bl, f32
 #pragma unroll
             for (int i = 0; i < 4; ++i) acc[s][4 * q + i] = ADD ? acc[s][4 * q + i] + bq[i] : bq[i];
     }
-    if constexpr (MF_SCHED != 0) __builtin_amdgcn_sched_barrier(0);
     int kg = 0;
     for (; kg + 8 <= nkg; kg += 8) {
-        mf_group<NS, 4, TR>(r, 4 + kg, bp, blast, b, acc);
-        mf_group<NS, 0, TR>(r, 8 + kg, bp, blast, b, acc);
+        mf_group<NS, 4, TR>(r, 4 + kg, bp, b, acc);
+        mf_group<NS, 0, TR>(r, 8 + kg, bp, b, acc);
     }
     if (kg < nkg) {          // an odd number of A groups: bias + A groups is even, the next item starts in ring half 0
-        mf_group<NS, 4, TR>(r, 4 + kg, bp, blast, b, acc);
+        mf_group<NS, 4, TR>(r, 4 + kg, bp, b, acc);
     } else {                 // the next item's first entries sit in ring half 1: swap the halves
 #pragma unroll
         for (int j = 0; j < 4; ++j) {

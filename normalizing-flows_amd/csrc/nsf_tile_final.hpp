@@ -32,10 +32,6 @@ for (int j = 0; j < nfi; ++j) {                       // (rolled: one copy of th
 #ifdef NSF_TILE_FT      // list tails: bound and type of the feature from the table; 0 / log-det 0 outside (utils/splines.py:48-57)
             nsf_regs_ft<DIR == 1, KB>(p, ftl[FT_BOUND * NSF_FT_STRIDE + PI + (valid ? tf : 0)],
                                       __float_as_int(ftl[FT_TAILS * NSF_FT_STRIDE + PI + (valid ? tf : 0)]), *xp, prm, yv, lad);
-#elif defined(NF_EPI_SCALAR)
-            rqs_regs<DIR == 1, KB>(p, *xp, prm, yv, lad);
-#elif defined(NF_EPI_FULL_KNOTS)
-            rqs_regs_t<DIR == 1, KB>(p, *xp, prm, yv, lad);
 #else           // round 6: first descent level before the knots exist (fused_common.hpp rqs_regs_h): half the live arrays
             rqs_regs_h<DIR == 1, KB>(p, *xp, prm, yv, lad);
 #endif

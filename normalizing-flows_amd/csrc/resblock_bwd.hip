@@ -41,18 +41,7 @@ constexpr int BB_R = 64, BB_P = 132, BB_TILE = BB_R * BB_P, BB_H = 128, BB_D = 6
 constexpr int BB_SLOTS = BB_R * (BB_P / 4);          // 16-byte slots of a tile = 2112 = 33 DMA instructions of 64 lanes
 constexpr int BB_NI = BB_SLOTS / 64;                 // 33
 
-#ifdef NF_BB_TRACE
-static unsigned long long *g_bb_trace = nullptr;
-extern "C" void nf_resblock_bwd_debug_trace(void *buf) { g_bb_trace = (unsigned long long *)buf; }
-#define BB_T(i) do { if (a.trace && blockIdx.x == 0 && threadIdx.x == 0) a.trace[tcount * 12 + (i)] = wall_clock64(); } while (0)
-#else
-#define BB_T(i) do {} while (0)
-#endif
-
 struct BlockBwdArgs {
-#ifdef NF_BB_TRACE
-    unsigned long long *trace;
-#endif
     const float *gh, *t, *hin, *W1, *W2;
     float *gh_in;          // (B, 128); not written by the INIT variant
     float *part;           // [2][grid][128 * 128 + 128]: (dW2, db2) then (dW1, db1)
@@ -144,13 +133,7 @@ resblock_bwd_kernel(BlockBwdArgs a) {
 #pragma unroll
     for (int ib = 0; ib < 4; ++ib) acc0[ib] = f32x4b{0.f, 0.f, 0.f, 0.f};
     float bs2[2] = {0.f, 0.f}, bs1[2] = {0.f, 0.f}, bs0 = 0.f;
-    int tcount = 0;
-    BB_T(7);
-#ifdef NF_BB_TRACE
-    if (a.trace && blockIdx.x == 0 && threadIdx.x == 0) a.trace[6] = clock64();
-#endif
     BB_BARRIER_ALL();
-    tcount = 1;
 
     // out[row][16 wid + c] = sum_k A[row][k] W[k][16 wid + c] for the 64 rows of an LDS tile: C[mb][r] = row 16 mb + 4 q4 + r.
     // Round 6: software-pipelined by hand.  hipcc emitted "4 ds_read_b128 -> s_waitcnt lgkmcnt(0) -> 16 MFMAs" per Q: every one of
@@ -158,7 +141,6 @@ resblock_bwd_kernel(BlockBwdArgs a) {
     // MFMAs.  Here a step is HALF a Q (two 16-row blocks: 2 reads, 8 MFMAs alternating between two accumulators, so no MFMA waits
     // for its predecessor's 40-cycle latency) and step p + 1's operands are requested before step p's MFMAs are issued: the same 16
     // operand registers as before, now double-buffered; the scheduling barriers keep the compiler from undoing the order.
-#ifndef NF_BB_NOPIPE
     auto product = [&](const float *At, const float (&Wr)[32], f32x4b (&C)[4], int c, int q4, auto &&between) {
 #pragma unroll
         for (int mb = 0; mb < 4; ++mb) C[mb] = f32x4b{0.f, 0.f, 0.f, 0.f};
@@ -218,45 +200,9 @@ resblock_bwd_kernel(BlockBwdArgs a) {
             for (int ib = 0; ib < 4; ++ib) bv[ib] = bn[ib];
         }
     };
-#else
-    auto product = [&](const float *At, const float (&Wr)[32], f32x4b (&C)[4], int c, int q4, auto &&between) {
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) C[mb] = f32x4b{0.f, 0.f, 0.f, 0.f};
-        const float *ap = At + c * BB_P + 4 * q4;
-#pragma unroll
-        for (int Q = 0; Q < 8; ++Q) {
-            f32x4 av[4];
-#pragma unroll
-            for (int mb = 0; mb < 4; ++mb) av[mb] = *reinterpret_cast<const f32x4 *>(ap + 16 * mb * BB_P + 16 * Q);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int mb = 0; mb < 4; ++mb) C[mb] = MFMA16(av[mb][j], Wr[4 * Q + j], C[mb]);
-            between(Q);
-        }
-    };
-    auto wgrad = [&](const float *At, const float *Bt, f32x4b (&acc)[2][4], float (&bs)[2], int c, int q4) {
-        const float *ap = At + q4 * BB_P + 32 * om + c, *bp = Bt + q4 * BB_P + 64 * in_ + c;
-#pragma unroll 4
-        for (int kb = 0; kb < BB_R / 4; ++kb) {
-            float av[2], bv[4];
-#pragma unroll
-            for (int ob = 0; ob < 2; ++ob) av[ob] = ap[kb * 4 * BB_P + 16 * ob];
-#pragma unroll
-            for (int ib = 0; ib < 4; ++ib) bv[ib] = fmaxf(bp[kb * 4 * BB_P + 16 * ib], 0.0f);
-            bs[0] += av[0];
-            bs[1] += av[1];
-#pragma unroll
-            for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-                for (int ib = 0; ib < 4; ++ib) acc[ob][ib] = MFMA16(av[ob], bv[ib], acc[ob][ib]);
-        }
-    };
-#endif
 
-    for (; tile < ntiles; tile += grid, ++tcount) {
+    for (; tile < ntiles; tile += grid) {
         const bool more = tile + grid < ntiles, first = tile == (int64_t)blockIdx.x;     // the first tile's h_in: requested above
-        BB_T(0);
         // per-tile lane index (loop-invariant LDS / global addresses hoisted out of the tile loop cost registers)
         int l_ = lane;
         asm volatile("" : "+v"(l_));
@@ -273,12 +219,9 @@ resblock_bwd_kernel(BlockBwdArgs a) {
                 Dt[idx] = Tt[idx] > 0.0f ? C[mb][r] : 0.0f;
                 outv[4 * mb + r] = Gt[idx];
             }
-        BB_T(1);
         // ---- dW2 += gh^T relu(t), db2 += colsum(gh) ----
         wgrad(Gt, Tt, acc2, bs2, c, q4);
-        BB_T(2);
         BB_BARRIER_ALL();          // Dt complete, h_in (and x) landed; every wave is done with Gt and Tt
-        BB_T(3);
         // ---- gh_in = gh + (gt W1) [h_in > 0]; behind the MFMAs the next tile's gh / t requests (Gt, Tt: free) ----
         product(Dt, W1r, C, c, q4, [&](int Q) {
             if (more) {
@@ -295,20 +238,15 @@ resblock_bwd_kernel(BlockBwdArgs a) {
                 const int idx = (16 * mb + 4 * q4 + r) * BB_P + 16 * wid + c;
                 outv[4 * mb + r] += Ht[idx] > 0.0f ? C[mb][r] : 0.0f;
             }
-        BB_T(4);
         // ---- dW1 += gt^T relu(h_in), db1 += colsum(gt) ----
         wgrad(Dt, Ht, acc1, bs1, c, q4);
-        BB_T(5);
         BB_BARRIER_ALL();          // next tile's gh / t landed; every wave is done with Ht and Dt
-        BB_T(6);
         // gh_in -> Dt: written back as whole rows (full 128-byte lines), or (INIT) the A operand of the initial layer's products
 #pragma unroll
         for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
             for (int r = 0; r < 4; ++r) Dt[(16 * mb + 4 * q4 + r) * BB_P + 16 * wid + c] = outv[4 * mb + r];
-        BB_T(8);
         BB_BARRIER_LDS();
-        BB_T(9);
         if (!INIT) {
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
@@ -348,7 +286,6 @@ resblock_bwd_kernel(BlockBwdArgs a) {
                     for (int ib = 0; ib < 4; ++ib) acc0[ib] = MFMA16(av, bv[ib], acc0[ib]);
                 }
             }
-            BB_T(10);
             {
                 f32x4b C3[2] = {f32x4b{0.f, 0.f, 0.f, 0.f}, f32x4b{0.f, 0.f, 0.f, 0.f}};
                 const float *ap = Dt + (16 * mb0 + c) * BB_P + 4 * q4;
@@ -366,16 +303,11 @@ resblock_bwd_kernel(BlockBwdArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) gp[(16 * m + r) * BB_D] = old[4 * m + r] + C3[m][r];
             }
-            BB_T(11);
             BB_BARRIER_LDS();      // every wave is done with Dt and Xt
             if (more) issue_x(a.x + (tile + grid) * (BB_R * BB_D));
         }
     }
 
-    BB_T(0);
-#ifdef NF_BB_TRACE
-    if (a.trace && blockIdx.x == 0 && threadIdx.x == 0) { a.trace[5] = clock64(); a.trace[4] = wall_clock64(); }
-#endif
     // ---- partial tiles: [problem][workgroup][128 * 128 + 128] ----
     constexpr int64_t nW = BB_H * BB_H, stride = nW + BB_H;
     float *o2 = a.part + (int64_t)blockIdx.x * stride, *o1 = a.part + ((int64_t)grid + blockIdx.x) * stride;
@@ -460,9 +392,6 @@ extern "C" int nf_resblock_bwd_partials(const void *gh, const void *t, const voi
     const int64_t stride = (int64_t)BB_H * BB_H + BB_H;
     a.part0 = (float *)scratch + 2 * grid * stride;
     a.B = B;
-#ifdef NF_BB_TRACE
-    a.trace = g_bb_trace;
-#endif
     const size_t lds = (size_t)(4 * BB_TILE + (init ? BB_R * BB_D : 0)) * sizeof(float);
     static LdsOptIn opt0 = {}, opt1 = {};
     if (init) {

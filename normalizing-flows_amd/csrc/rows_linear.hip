@@ -22,18 +22,7 @@ namespace nf {
 // rqs_fused.hip).  Per row: one read of `in`, the mask sources, one write of out1 and out2.
 constexpr int RB_NW = 8;
 
-#ifdef NF_RB_TRACE
-static unsigned long long *g_rb_trace = nullptr;
-extern "C" void nf_rows_block_debug_trace(void *buf) { g_rb_trace = (unsigned long long *)buf; }
-#define RB_T(i) do { if (a.trace && blockIdx.x == 0 && threadIdx.x == 0) a.trace[i] = wall_clock64(); } while (0)
-#else
-#define RB_T(i) do {} while (0)
-#endif
-
 struct RowsBlockArgs {
-#ifdef NF_RB_TRACE
-    unsigned long long *trace;
-#endif
     const float *in; int64_t ldi;
     const float *M1; int64_t ldw1; int trans1;
     const float *c1;
@@ -100,7 +89,6 @@ rows_block_kernel(RowsBlockArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem_rb[];
     float *W1l = smem_rb, *W2l = smem_rb + 4 * 16 * 64 * 4;
     const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5;
-    RB_T(0);
     // Both panels -> LDS, each thread's 16 loads in flight before its first LDS write.  (Deferring the second panel's
     // commit behind the first product was measured: the 32 registers it pins cost what the shorter prologue gains.)
     {
@@ -111,32 +99,20 @@ rows_block_kernel(RowsBlockArgs a) {
         rb_commit_panel<true, 64 * RB_NW>(p2r, a.trans2, W2l, tid);
     }
     __syncthreads();
-    RB_T(1);
     const int nmb = (a.H + 31) >> 5;
     const int64_t ntiles = (a.B + 32 * RB_NW - 1) / (32 * RB_NW);
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t row = (tile * RB_NW + (tid >> 6)) * 32 + (lane & 31);
         const bool rv = row < a.B;
         const int64_t rc = rv ? row : a.B - 1;
-#ifdef NF_RB_ABL_COALESCED   // ablation (wrong results): every global access of the tile as consecutive 16-byte pieces per lane
-        const int64_t row0 = (tile * RB_NW + (tid >> 6)) * 32;
-#define RB_ADDR(base, ld, c0, idx) ((base) + row0 * (ld) + ((idx) * 64 + lane) * 4)
-#else
-#define RB_ADDR(base, ld, c0, idx) ((base) + rc * (ld) + (c0))
-#endif
         float xv[64];
         {
-            const float *src = RB_ADDR(a.in, a.ldi, 64 * hh, 0);
-#ifdef NF_RB_ABL_COALESCED
-#define RB_XOFF(q) ((q) * 256)
-#else
-#define RB_XOFF(q) (4 * (q))
-#endif
+            const float *src = a.in + rc * a.ldi + 64 * hh;
             const int kleft = a.H - 64 * hh;
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (4 * q + 3 < kleft) v = *reinterpret_cast<const f32x4 *>(src + RB_XOFF(q));
+                if (4 * q + 3 < kleft) v = *reinterpret_cast<const f32x4 *>(src + 4 * q);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) xv[4 * q + r] = a.relu1 ? fmaxf(v[r], 0.0f) : v[r];
             }
@@ -154,7 +130,7 @@ rows_block_kernel(RowsBlockArgs a) {
                 for (int q = 0; q < 4; ++q) {
                     const int c0 = 32 * m + 8 * q + 4 * hh;
                     mk[q] = f32x4{1.f, 1.f, 1.f, 1.f};
-                    if (a.m1 && c0 < a.H) mk[q] = *reinterpret_cast<const f32x4 *>(RB_ADDR(a.m1, a.ldm1, c0, m * 4 + q));
+                    if (a.m1 && c0 < a.H) mk[q] = *reinterpret_cast<const f32x4 *>(a.m1 + rc * a.ldm1 + c0);
                 }
                 const float *wl = W1l + (size_t)m * 16 * 256 + lane * 4;
 #pragma unroll
@@ -171,7 +147,7 @@ rows_block_kernel(RowsBlockArgs a) {
                         if (a.c1) v += *reinterpret_cast<const f32x4 *>(a.c1 + c0);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] = mk[q][r] > 0.0f ? v[r] : 0.0f;
-                        if (rv) *reinterpret_cast<f32x4 *>(RB_ADDR(a.out1, a.ldo1, c0, m * 4 + q)) = v;
+                        if (rv) *reinterpret_cast<f32x4 *>(a.out1 + rc * a.ldo1 + c0) = v;
                     } else {
                         v = f32x4{0.f, 0.f, 0.f, 0.f};
                     }
@@ -180,7 +156,6 @@ rows_block_kernel(RowsBlockArgs a) {
                 }
             }
         }
-        RB_T(3);
         // ---- second product + residual ----
         for (int mo = 0; mo < nmb; ++mo) {
             f32x4 mk[4], rs[4];
@@ -190,8 +165,8 @@ rows_block_kernel(RowsBlockArgs a) {
                 mk[q] = f32x4{1.f, 1.f, 1.f, 1.f};
                 rs[q] = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (c0 < a.H) {
-                    if (a.m2) mk[q] = *reinterpret_cast<const f32x4 *>(RB_ADDR(a.m2, a.ldm2, c0, mo * 4 + q));
-                    rs[q] = *reinterpret_cast<const f32x4 *>(RB_ADDR(a.in, a.ldi, c0, mo * 4 + q));      // the residual: `in` itself (cache-hot)
+                    if (a.m2) mk[q] = *reinterpret_cast<const f32x4 *>(a.m2 + rc * a.ldm2 + c0);
+                    rs[q] = *reinterpret_cast<const f32x4 *>(a.in + rc * a.ldi + c0);      // the residual: `in` itself (cache-hot)
                 }
             }
             f32x16 o = {0};
@@ -212,10 +187,9 @@ rows_block_kernel(RowsBlockArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = mk[q][r] > 0.0f ? v[r] : 0.0f;
                 v += rs[q];
-                *reinterpret_cast<f32x4 *>(RB_ADDR(a.out2, a.ldo2, c0, mo * 4 + q)) = v;
+                *reinterpret_cast<f32x4 *>(a.out2 + rc * a.ldo2 + c0) = v;
             }
         }
-        RB_T(4);
     }
 }
 
@@ -241,9 +215,6 @@ extern "C" int nf_rows_block(const void *in, int64_t ldi, const void *M1, int64_
     a.M2 = (const float *)M2; a.ldw2 = ldw2; a.trans2 = trans2 ? 1 : 0;
     a.c2 = (const float *)c2; a.m2 = (const float *)mask2; a.ldm2 = ldm2; a.out2 = (float *)out2; a.ldo2 = ldo2;
     a.B = B; a.H = H; a.relu1 = relu1 ? 1 : 0; a.relu2 = relu2 ? 1 : 0;
-#ifdef NF_RB_TRACE
-    a.trace = g_rb_trace;
-#endif
     const size_t lds = (size_t)2 * 4 * 16 * 64 * 4 * sizeof(float);   // two 64 KB panels
     static LdsOptIn opted = {};
     if (opt_in_lds(reinterpret_cast<const void *>(&rows_block_kernel), lds, opted) != NF_OK) return NF_ENOTSUP;

@@ -184,7 +184,6 @@ rqs_coupling_bwd_kernel(const T *__restrict__ x, const T *__restrict__ gy, const
         }
         // transform elements and identity elements in two separate passes: within a pass every lane runs the same code
         // (one mixed pass made each wave execute both heavy branches)
-#ifndef NF_BWD_ABL_NOT
         if (do_t) {
             const T div = p.wh_div;
             for (int el = threadIdx.x; el < ts * nT; el += blockDim.x) {
@@ -218,8 +217,6 @@ rqs_coupling_bwd_kernel(const T *__restrict__ x, const T *__restrict__ gy, const
                 }
             }
         }
-#endif
-#ifndef NF_BWD_ABL_NOI
         if (do_i) {
             for (int el = threadIdx.x; el < ts * nI; el += blockDim.x) {
                 const int bl = el / nI, j = el - bl * nI;
@@ -247,7 +244,6 @@ rqs_coupling_bwd_kernel(const T *__restrict__ x, const T *__restrict__ gy, const
                                                          aw, ah, ad, []() {});
             }
         }
-#endif
         if (stage) {
             __syncthreads();
             T *dst = gcond + bt * nT * (int64_t)M;
@@ -277,12 +273,8 @@ rqs_coupling_bwd_kernel(const T *__restrict__ x, const T *__restrict__ gy, const
 // Wave-private tiles (as rqs_coupling_wave_kernel): SPW samples per pass; conditioner rows in, gradient rows out through
 // the wave's own LDS region with unit-stride global accesses, x / grad_y rows staged, gx rows written whole.  The shared
 // (identity-half) parameters accumulate in workgroup LDS by atomics as in the tiled kernel.  float32, 8 bins, linear tails.
-#ifndef NF_BWD_WAVE_OCC
-#define NF_BWD_WAVE_OCC 2   // waves per SIMD the register allocation aims at (3: 168 VGPRs + spills, measured slower)
-#endif
-#ifndef NF_BWD_WAVE_WAVES
-#define NF_BWD_WAVE_WAVES 8  // waves per workgroup: one workgroup per CU = fewest rounds of end-of-kernel global atomics
-#endif
+constexpr int NF_BWD_WAVE_OCC = 2;     // waves per SIMD the register allocation aims at (3: 168 VGPRs + spills, measured slower)
+constexpr int NF_BWD_WAVE_WAVES = 8;   // waves per workgroup: one workgroup per CU = fewest rounds of end-of-kernel global atomics
 // CP: floats per (sample, transform feature) row of cond / grad_cond: 23 = the reference's layout (B, nT * 23); 24 = the
 // padded rows the training variant of the fused kernel writes (rqs_fused.hip, 16-byte aligned: read and written as f32x4)
 template <int CP>
@@ -353,7 +345,6 @@ rqs_coupling_bwd_wave_kernel(const float *__restrict__ x, const float *__restric
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-#ifndef NF_BWD_ABL_NOT
         if (do_t) {
             for (int e = lane; e < ns * nT; e += 64) {
                 const int s_ = e / nT, j = e - s_ * nT, col = s_tidx[j];
@@ -388,8 +379,6 @@ rqs_coupling_bwd_wave_kernel(const float *__restrict__ x, const float *__restric
                 w_gx[s_ * D + col] = gxv;
             }
         }
-#endif
-#ifndef NF_BWD_ABL_NOI
         if (do_i) {
             for (int e = lane; e < ns * nI; e += 64) {
                 const int s_ = e / nI, j = e - s_ * nI, col = s_iidx[j];
@@ -424,7 +413,6 @@ rqs_coupling_bwd_wave_kernel(const float *__restrict__ x, const float *__restric
                                                                []() {});
             }
         }
-#endif
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         if (do_t) {
@@ -560,13 +548,7 @@ rqs_coupling_bwd_pipe_kernel(const float *__restrict__ x, const float *__restric
             }
             prm[M] = 0.0f;
             const float xv = bufc[XOFF + s_ * D + col_t], gyv = bufc[XOFF + SPW * D + s_ * D + col_t];
-#ifdef NF_BWD_ABL_NOMATH      // ablation (wrong results): the pass without the spline arithmetic = staging + traffic only
-            float gxv = gyv + gl + xv;
-#pragma unroll
-            for (int k = 0; k < 24; ++k) g[k] = prm[k] * gyv;
-#else
             const float gxv = rqs_regs_bwd<false>(p, xv, prm, gyv, gl, g, inv_div);
-#endif
             if constexpr (CP == 24) {
                 g[M] = 0.0f;
 #pragma unroll
@@ -587,13 +569,7 @@ rqs_coupling_bwd_pipe_kernel(const float *__restrict__ x, const float *__restric
 #pragma unroll
             for (int k = 0; k < 24; ++k) prm[k] = pr[k];
             const float xv = bufc[XOFF + s_ * D + col_i], gyv = bufc[XOFF + SPW * D + s_ * D + col_i];
-#if defined(NF_BWD_ABL_NOMATH) || defined(NF_BWD_ABL_NOIDENT)     // ablation: without the identity half's arithmetic
-            w_gx[s_ * D + col_i] = gyv + xv;
-#pragma unroll
-            for (int k = 0; k < 24; ++k) g[k] = prm[k] * gyv;
-#else
             w_gx[s_ * D + col_i] = rqs_regs_bwd<false>(p, xv, prm, gyv, gl, g, 1.0f);
-#endif
 #pragma unroll
             for (int k = 0; k < M; ++k) racc[k] += g[k];      // a lane keeps its feature for the whole launch: register sums
         }
@@ -668,7 +644,6 @@ static int launch_bwd_wave(const void *x, const void *grad_y, const void *grad_l
                            int nT, int64_t B, int D, const nf::RqsParams<float> &p, int mode, void *grad_x, void *grad_cond,
                            void *grad_uw, void *grad_uh, void *grad_ud, hipStream_t st) {
     using namespace nf;
-#ifndef NF_BWD_NO_PIPE
     if (nI == 32 && nT == 32 && D == 64 && mode == NF_RQS_DENSITY && uw && (B & 1) == 0 && B >= 2 &&
         ((((uintptr_t)x | (uintptr_t)grad_y | (uintptr_t)cond | (uintptr_t)grad_cond | (uintptr_t)grad_x) & 15) == 0) &&
         (((uintptr_t)grad_logdet & 3) == 0)) {
@@ -686,7 +661,6 @@ static int launch_bwd_wave(const void *x, const void *grad_y, const void *grad_l
             return NF_OK;
         }
     }
-#endif
     const int nmax = nT > nI ? nT : nI;
     int SPW = nmax > 0 ? 64 / nmax : 1;
     if (SPW < 1) SPW = 1;

@@ -15,9 +15,7 @@
 #include "common.hpp"
 #include "rqs_bwd_common.hpp"
 
-#ifndef NF_BWD_FT_WAVES
-#define NF_BWD_FT_WAVES 8    // waves per workgroup: one workgroup per CU (rqs_bwd.hip NF_BWD_WAVE_WAVES)
-#endif
+constexpr int NF_BWD_FT_WAVES = 8;    // waves per workgroup: one workgroup per CU (rqs_bwd.hip NF_BWD_WAVE_WAVES)
 
 namespace nf {
 

@@ -38,12 +38,8 @@
 #include <type_traits>
 
 // Rows the training variants write for the backward (386 MB per launch) are not read again by this launch: non-temporal stores
-// (measured 29.7-29.8 vs 29.9-30.0 ms per training step, three alternating runs; -DNF_TRAIN_TEMPORAL_STORES: ordinary stores).
-#ifndef NF_TRAIN_TEMPORAL_STORES
+// (measured 29.7-29.8 vs 29.9-30.0 ms per training step, three alternating runs, against ordinary stores).
 #define NF_TRAIN_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#else
-#define NF_TRAIN_STORE(ptr, val) (*(ptr) = (val))
-#endif
 
 // This file is compiled twice: as it stands (8 waves = 256 rows per workgroup, every entry point) and through rqs_fused_nw4.hip
 // (-DNF_FUSED_SECONDARY: 4 waves = 128 rows per workgroup, only the inference kernel under another name and its chain dispatch) for
@@ -342,24 +338,6 @@ pack_lu_train_multi_kernel(const void *const *__restrict__ table, float eps, int
 // ---- the fused layer kernel -----------------------------------------------------------------------------------
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
-// Ask the scheduler to lay a region out as 64 x { 1 MFMA, NF_PIPE_VALU VALU/transcendental instructions }: the
-// default (bottom-up) list scheduler clusters the epilogue at ~15 VALU per MFMA behind the last third of the region's
-// MFMAs, which overflows the 64-cycle MFMA shadow when both waves of a SIMD are in that phase.
-#ifndef NF_PIPE_VALU
-#define NF_PIPE_VALU 5
-#endif
-#ifndef NF_USE_SCHED_PIPE  /* measured: no gain over the default schedule (tools/fused_ablate.py) */
-#define NF_SCHED_PIPE() do {} while (0)
-#else
-#define NF_SCHED_PIPE()                                                         \
-    do {                                                                        \
-        _Pragma("unroll") for (int i_ = 0; i_ < 64; ++i_) {                     \
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                  \
-            __builtin_amdgcn_sched_group_barrier(0x402, NF_PIPE_VALU, 0);       \
-        }                                                                       \
-    } while (0)
-#endif
-
 // acc += Wblock(32 x 128) * B, where the B operand for (k-group s, r) is `bsrc[s >> 2][4 (s & 3) + r]`
 // (optionally through ReLU): 16 ds_read_b128 + 64 MFMA.
 // HB: hidden row-blocks in use (4 = 128 units; 2 / 1 = layers of <= 64 / <= 32 hidden units packed into the same 128-unit
@@ -367,10 +345,6 @@ pack_lu_train_multi_kernel(const void *const *__restrict__ table, float eps, int
 template <bool RELU, int HB = 4, int LA = 2>
 __device__ __forceinline__ void mm128(const float *buf, int lane, f32x16 &acc, const f32x16 &b0, const f32x16 &b1,
                                       const f32x16 &b2, const f32x16 &b3) {
-#ifdef NF_EXP_SETPRIO
-    __builtin_amdgcn_s_setprio(1);
-#endif
-#ifndef NF_NO_PREFETCH
     // A operands two k-groups ahead of their use (real since round 6: see NF_DMA16)
     // LA = 1: one k-group ahead (the instantiations that sit at the 256-register limit: 8 registers fewer)
     f32x4 a0 = *reinterpret_cast<const f32x4 *>(buf + lane * 4), a1 = a0;
@@ -385,24 +359,14 @@ __device__ __forceinline__ void mm128(const float *buf, int lane, f32x16 &acc, c
             a0 = *reinterpret_cast<const f32x4 *>(buf + (s + 1) * 256 + lane * 4);
         }
         __builtin_amdgcn_sched_barrier(0);   // keeps the request in FRONT of the k-group's MFMAs (without it: +0.5 % lost again)
-#else
-#pragma unroll
-    for (int s = 0; s < 4 * HB; ++s) {
-        const f32x4 a = *reinterpret_cast<const f32x4 *>(buf + s * 256 + lane * 4);
-#endif
         const f32x16 &bs = (s >> 2) == 0 ? b0 : ((s >> 2) == 1 ? b1 : ((s >> 2) == 2 ? b2 : b3));
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             float bv = bs[4 * (s & 3) + r];
-#ifndef NF_ABL_NORELU
             if (RELU) bv = fmaxf(bv, 0.0f);
-#endif
             acc = MFMA(a[r], bv, acc);
         }
     }
-#ifdef NF_EXP_SETPRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 // 2 row-blocks x 8 k-groups of the composed 64 x 64 LU matrix: out[slot 16 m + reg] = bias + sum_k W[.][k] xin[k-slot]
@@ -425,10 +389,7 @@ __device__ __forceinline__ void lu_mm(const float *buf, int lane, const float (&
 #define NF_FUSED_WAVES 8
 #endif
 constexpr int F_NW = NF_FUSED_WAVES;
-#ifndef NF_DMA_WAVES
-#define NF_DMA_WAVES 4
-#endif
-constexpr int F_DMA_WAVES = NF_DMA_WAVES < F_NW ? NF_DMA_WAVES : F_NW;   // waves that issue the weight ring's LDS-DMAs
+constexpr int F_DMA_WAVES = 4 < F_NW ? 4 : F_NW;   // waves that issue the weight ring's LDS-DMAs
 constexpr int F_THREADS = 64 * F_NW;
 constexpr int F_ROWS = 32 * F_NW;
 
@@ -522,26 +483,14 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
         const int layer = gs / nstages, s = gs - layer * nstages;
         const float *src = fa.blob[layer] + lay.off_stages() + (size_t)phys(s) * F_STAGE + (wid * PPW) * 256 + lane * 4;
         float *dst = ring + (gs & 1) * F_STAGE + (wid * PPW) * 256;
-#ifdef NF_BUILTIN_DMA
-#pragma unroll
-        for (int i = 0; i < PPW; ++i)
-            __builtin_amdgcn_global_load_lds(src + i * 256, (__attribute__((address_space(3))) void *)(dst + i * 256), 16, 0, 0);
-#else
         // round 6: requests as inline asm (common.hpp NF_DMA16) so that the products' operand look-ahead survives compilation
 #pragma unroll
         for (int i = 0; i < PPW; ++i) NF_DMA16(src - lane * 4 + i * 256, lane * 16, dst + i * 256);
-#endif
     };
     auto issue_small = [&](int layer) {  // small section of `layer` -> LDS buffer layer & 1 (1 KB pieces round-robin)
         const float *src = fa.blob[layer] + F_HDR;
         float *dst = small2 + (layer & 1) * small_pitch;
-#ifdef NF_BUILTIN_DMA
-        for (int piece = wid; piece * 256 < small_pitch; piece += F_NW)
-            __builtin_amdgcn_global_load_lds(src + piece * 256 + lane * 4,
-                                             (__attribute__((address_space(3))) void *)(dst + piece * 256), 16, 0, 0);
-#else
         for (int piece = wid; piece * 256 < small_pitch; piece += F_NW) NF_DMA16(src + piece * 256, lane * 16, dst + piece * 256);
-#endif
     };
     // `after`: vector-memory operations (training stores) this wave issued AFTER the requests of the stage it now waits for;
     // they retire in order, so they may stay in flight.  Only trusted for full tiles (every store instruction of the wave
@@ -551,12 +500,8 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
     auto acquire = [&](int after = 0) -> const float * {
         if (TRAIN && after == 14 && full_tile) NF_WAIT_VMCNT(14);
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifndef NF_ABL_NOBAR
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-#ifndef NF_ABL_NODMA
         if (stage + 1 < total_stages) issue(stage + 1);
-#endif
         const float *buf = ring + (stage & 1) * F_STAGE;
         ++stage;
         return buf;
@@ -650,9 +595,6 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
     // enough), written back as 128-byte row pieces: 8 lanes per row, 8 rows per instruction
     auto store_act = [&](int t, const f32x16 &V0, const f32x16 &V1, const f32x16 &V2, const f32x16 &V3) {
         if constexpr (TRAIN == 2) {
-#ifdef NF_ABL_NOACT
-            return;
-#endif
             int l_ = lane;      // per-lane addresses derived afresh at every call: hoisted out of the kernel they cost ~30 VGPRs
             asm volatile("" : "+v"(l_));
             float *tw = small2 + small_pitch + wid * 1536;
@@ -661,21 +603,6 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
             const float *tww = tw + rl * 36 + 4 * cl;
             const int64_t row0 = (int64_t)blockIdx.x * F_ROWS + wid * 32 + rl;
             float *dst = act_out + ((size_t)t * (size_t)B + row0) * F_H + 4 * cl;
-#ifdef NF_TRAIN_ACT_DIRECT      // ablation: 16-byte pieces straight from the C-layout registers (32 bytes per row and instruction)
-            {
-                const int64_t rowd = (int64_t)blockIdx.x * F_ROWS + wid * 32 + (l_ & 31);
-                float *dd = act_out + ((size_t)t * (size_t)B + rowd) * F_H + 4 * (l_ >> 5);
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    const f32x16 &V = m == 0 ? V0 : (m == 1 ? V1 : (m == 2 ? V2 : V3));
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if (rowd < B)
-                            NF_TRAIN_STORE(reinterpret_cast<f32x4 *>(dd + 32 * m + 8 * q), (f32x4{V[4 * q], V[4 * q + 1], V[4 * q + 2], V[4 * q + 3]}));
-                }
-                return;
-            }
-#endif
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 const f32x16 &V = m == 0 ? V0 : (m == 1 ? V1 : (m == 2 ? V2 : V3));
@@ -773,15 +700,6 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
             H2 += load_bias16(bsrc + 64);
             H3 += load_bias16(bsrc + 96);
         }
-#ifdef NF_EXP_RELU_PER_USE
-        store_act(1 + 2 * blk, T0, T1, T2, T3);
-        mm128<true, HB, LA>(acquire(), lane, H0, T0, T1, T2, T3);
-        if constexpr (HB >= 2) mm128<true, HB, LA>(acquire(), lane, H1, T0, T1, T2, T3);
-        if constexpr (HB == 4) {
-            mm128<true, HB, LA>(acquire(), lane, H2, T0, T1, T2, T3);
-            mm128<true, HB, LA>(acquire(), lane, H3, T0, T1, T2, T3);
-        }
-#else
         const float *buf2 = acquire();
         store_act(1 + 2 * blk, T0, T1, T2, T3);      // the pre-activation (the backward's ReLU mask and weight-gradient operand)
         // T is dead after this linear: ReLU it once in place (64 v_max) instead of once per use (256)
@@ -798,18 +716,11 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
             mm128<false, HB, LA>(acquire(), lane, H2, T0, T1, T2, T3);
             mm128<false, HB, LA>(acquire(), lane, H3, T0, T1, T2, T3);
         }
-#endif
-#ifdef NF_EXP_RELU_PER_USE
-        store_act(2 + 2 * blk, H0, H1, H2, H3);
-#endif
     }
     }  // TRAIN != 1
 
     // ---- final layer in 8 groups of 3 row-blocks; each group yields the parameters of 2 spline elements ----
-    // Software pipeline: the spline evaluations of group g-1 (pure VALU work on registers) are placed in the same
-    // scheduling regions as the 3 x 64 MFMAs of group g, so that they issue in the shadow of the 64-cycle MFMAs
-    // instead of leaving the matrix pipe idle (ablation: epilogue + unconditional splines exposed = 22 % of the
-    // kernel).  Region 1: element 0, region 2: element 1, region 3: two unconditional-spline elements (density).
+    // (measured with the epilogue and the unconditional splines taken out: they are 22 % of the kernel)
     float prm[FPL][MP];
     auto extract = [&](const f32x16 &A0, const f32x16 &A1, const f32x16 &A2) {
         // lane's parameter list v = 16 rb + reg: feature f = v / MP, parameter v % MP
@@ -817,29 +728,15 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
         for (int v = 0; v < 48; ++v) prm[v / MP][v % MP] = v < 16 ? A0[v] : (v < 32 ? A1[v - 16] : A2[v - 32]);
     };
     auto element = [&](int g, int f) {
-#ifdef NF_ABL_NOEPI
-#pragma unroll
-        for (int v = 0; v < MP; ++v) asm volatile("" ::"v"(prm[f][v]));
-        return;
-#endif
         const int slot = 8 * (g / GQ) + 2 * ((g % GQ) * FPL + f) + par_t;
         const float xt = st[slot * 64];
         float yt, l;
-#ifdef NF_EPI_SCALAR
-        rqs_regs<DIR == 1, KB>(p, xt, prm[f], yt, l);
-#else
         rqs_regs_t<DIR == 1, KB>(p, xt, prm[f], yt, l);      // (round 5: binary bin descent; K = 4 / 16 and the training forward come here)
-#endif
         st[slot * 64] = yt;
         ld += l;
     };
-    // both elements of a group at once on packed arithmetic + the binary bin descent (fused_common.hpp rqs_regs2, round 5);
-    // -DNF_EPI_SCALAR = the element-by-element evaluation of rounds 1-4 (ablation)
+    // both elements of a group at once on packed arithmetic + the binary bin descent (fused_common.hpp rqs_regs2, round 5)
     auto element_pair = [&](int g) {
-#if defined(NF_ABL_NOEPI) || defined(NF_EPI_SCALAR)
-        element(g, 0);
-        element(g, 1);
-#else
         if constexpr (FPL == 2) {
             const int s0 = 8 * (g / GQ) + 2 * ((g % GQ) * FPL) + par_t, s1 = s0 + 2;
             float y0, y1, l0, l1;
@@ -849,12 +746,8 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
             ld += l0;
             ld += l1;
         }
-#endif
     };
     auto uncond_group = [&](int g) {  // density only: the FPL identity slots of chunk Q = g / GQ that go with this group
-#ifdef NF_ABL_NOUNCOND
-        return;
-#endif
         const float *tabs = small + lay.off_tables();
 #pragma unroll
         for (int e = 0; e < FPL; ++e) {
@@ -867,47 +760,10 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
             ld += l;
         }
     };
-#ifdef NF_F32_SWPIPE
-    static_assert(!COMPACT, "the software-pipelined order streams the 24 legacy stages");
-    static_assert(KB == F_K && HB == 4, "the software-pipelined order is written for 8 bins, 128 hidden units");
-    {   // group 0: MFMAs only
-        const float *bsrc = small + lay.off_bias_final() + hh * 16;
-        f32x16 A0 = load_bias16(bsrc), A1 = load_bias16(bsrc + 32), A2 = load_bias16(bsrc + 64);
-        mm128<false, 4, LA>(acquire(), lane, A0, H0, H1, H2, H3);
-        mm128<false, 4, LA>(acquire(), lane, A1, H0, H1, H2, H3);
-        mm128<false, 4, LA>(acquire(), lane, A2, H0, H1, H2, H3);
-        extract(A0, A1, A2);
-    }
-    for (int g = 1; g < 8; ++g) {
-        const float *bsrc = small + lay.off_bias_final() + (g * 3) * 32 + hh * 16;
-        f32x16 A0 = load_bias16(bsrc), A1 = load_bias16(bsrc + 32), A2 = load_bias16(bsrc + 64);
-        {
-            const float *buf = acquire();
-            mm128<false, 4, LA>(buf, lane, A0, H0, H1, H2, H3);
-            element(g - 1, 0);
-            NF_SCHED_PIPE();
-        }
-        {
-            const float *buf = acquire();
-            mm128<false, 4, LA>(buf, lane, A1, H0, H1, H2, H3);
-            element(g - 1, 1);
-            NF_SCHED_PIPE();
-        }
-        {
-            const float *buf = acquire();
-            mm128<false, 4, LA>(buf, lane, A2, H0, H1, H2, H3);
-            if (DIR == 0) uncond_group(g - 1);
-            NF_SCHED_PIPE();
-        }
-        extract(A0, A1, A2);
-    }
-    element(7, 0);
-    element(7, 1);
-    if (DIR == 0) uncond_group(7);
-#else
     // The exact-fp32 MFMA shares the vector ALU (tools/ubench/overlap.py): there is nothing to hide the epilogue
     // behind, so each group's spline elements are evaluated straight from its accumulators (no parameter copies, lower
-    // register pressure); the software-pipelined order (NF_F32_SWPIPE) only pays on the bf16 matrix pipe.
+    // register pressure).  A software-pipelined order (group g - 1's splines inside group g's MFMA regions) only pays on the bf16
+    // matrix pipe and was removed.
     if constexpr (COMPACT) {
         // 21 row-blocks, no padding: the lane's accumulator slots v = 16 rb + reg list 21 values per feature, pair j (= group j of
         // the legacy order: same features, same stash slots) owns slots [42 j, 42 j + 42) and is complete after row-block
@@ -942,10 +798,6 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
                 p1[v] = zero ? 0.0f : val(S0 + 21 + c);
             }
             C = NNEW == 3 ? A2 : A1;
-#ifdef NF_ABL_NOEPI
-#pragma unroll
-            for (int v = 0; v < MP; ++v) asm volatile("" ::"v"(p0[v]), "v"(p1[v]));
-#else
             const int s0 = 8 * (J / 2) + 4 * (J % 2) + par_t, s1 = s0 + 2;
             float y0, y1, l0, l1;
             rqs_regs2<DIR == 1, KB, true>(p, st[s0 * 64], st[s1 * 64], p0, p1, y0, y1, l0, l1);
@@ -953,7 +805,6 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
             st[s1 * 64] = y1;
             ld += l0;
             ld += l1;
-#endif
             if (DIR == 0) uncond_group(J);
         };
         pair(std::integral_constant<int, 0>{});
@@ -971,35 +822,16 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
         {
             // behind group g - 1's 14 parameter stores (training); group 0: the last residual block's output goes out here
             const float *buf = acquire(g > 0 ? 14 : 0);
-#ifndef NF_EXP_RELU_PER_USE
             if (g == 0) {
                 if (nblk == 0) store_xlu();
                 store_act(2 * nblk, H0, H1, H2, H3);
             }
-#endif
             mm128<false, HB, LA>(buf, lane, A0, H0, H1, H2, H3);
         }
         mm128<false, HB, LA>(acquire(), lane, A1, H0, H1, H2, H3);
         mm128<false, HB, LA>(acquire(), lane, A2, H0, H1, H2, H3);
         extract(A0, A1, A2);
-#ifdef NF_ABL_NOCOND
-        if constexpr (false) {
-#else
         if constexpr (TRAIN) {
-#endif
-#ifdef NF_TRAIN_DIRECT_STORES
-            if (valid) {   // the two features' parameter sets, raw scale, for the backward kernel (pitch 24 floats per feature)
-                float *dst = cond_out + row * (F_NI * 24) + (8 * (g >> 1) + 4 * hh + 2 * (g & 1)) * 24;
-#pragma unroll
-                for (int q = 0; q < 6; ++q) {
-                    const float u_ = q < 4 ? unscale : 1.0f;
-                    *reinterpret_cast<f32x4 *>(dst + 4 * q) =
-                        f32x4{prm[0][4 * q] * u_, prm[0][4 * q + 1] * u_, prm[0][4 * q + 2] * u_, prm[0][4 * q + 3] * u_};
-                    *reinterpret_cast<f32x4 *>(dst + 24 + 4 * q) =
-                        f32x4{prm[1][4 * q] * u_, prm[1][4 * q + 1] * u_, prm[1][4 * q + 2] * u_, prm[1][4 * q + 3] * u_};
-                }
-            }
-#else
             // The two features' parameter sets (raw scale, pitch 24 floats per feature) for the backward kernel, through a 6 KB
             // transpose tile per wave: a lane holds ITS row's 192 contiguous bytes (rows 3 KB apart), so direct 16-byte stores
             // touch 64 partial lines per instruction (280 MB of fabric writes for 218 MB of rows, 40 us of the launch);
@@ -1034,7 +866,6 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
                 }
                 __builtin_amdgcn_wave_barrier();
             }
-#endif
         }
         if constexpr (FPL == 2 && TRAIN != 2) {      // (the training forward's row stores leave no registers for the pair: 4 spills)
             element_pair(g);
@@ -1044,7 +875,6 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
         }
         if (DIR == 0) uncond_group(g);
     }
-#endif
 
     if (LU && DIR == 1) {
         // LULinearPermute.forward (mixing.py:555-558): triangular solves + inverse permutation as one dense product
@@ -1238,9 +1068,7 @@ extern "C" int nf_rqs_fused_train_fwd_nw4_(int lu, const void *x, void *xlu_out,
                                            const void *fa, int64_t B, int hidden, int num_blocks, const void *p, int acc,
                                            nf_stream_t stream);
 // Batches of at most NF_FUSED_SMALL_ROWS rows run on 128-row workgroups (rqs_fused_nw4.hip; the note at nf_rqs_fused_chain).
-#ifndef NF_FUSED_SMALL_ROWS
-#define NF_FUSED_SMALL_ROWS 32768
-#endif
+constexpr int NF_FUSED_SMALL_ROWS = 32768;
 static int g_small_batch = 1;
 
 // One-launch pack of a whole layer (8 bins, no LU) for the training forward nf_rqs_fused_train_full_fwd.

@@ -27,11 +27,7 @@ typedef unsigned int u32;
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 
 constexpr int X3_SLOT_BYTES = 12288;          // ring slot = largest stage
-#ifdef NF_X3_WIDE_FINAL
-constexpr int X3_FINAL_BYTES = 12288;
-#else
 constexpr int X3_FINAL_BYTES = 9216;          // final-layer stage: 3 row-blocks x 3 splits x 1 KB
-#endif
 constexpr int X3_SLOT_FLOATS = X3_SLOT_BYTES / 4;
 // The kernel consumes the blob's K-step stages in PAIRS ("super-stages": 24 KB, or 18 KB in the final layer): 8 waves
 // x 3 LDS-DMA instructions each per super-stage, one barrier per 2 K steps.
@@ -165,23 +161,12 @@ struct A3 {
 __device__ __forceinline__ A3 load_a3(const unsigned short *abuf, int lane) {
     A3 a;
     a.hi = *reinterpret_cast<const bf16x8 *>(abuf + lane * 8);
-#ifdef NF_X3_ABL_LDS13      // timing ablation (wrong results): one LDS read per row-block instead of three
-    a.mid = a.hi;
-    a.lo = a.hi;
-#else
     a.mid = *reinterpret_cast<const bf16x8 *>(abuf + 64 * 8 + lane * 8);
     a.lo = *reinterpret_cast<const bf16x8 *>(abuf + 2 * 64 * 8 + lane * 8);
-#endif
     return a;
 }
 __device__ __forceinline__ void mm_x3_4(const unsigned short *buf, int lane, const Split3 &b, f32x16 &c0, f32x16 &c1,
                                         f32x16 &c2, f32x16 &c3) {
-#ifdef NF_X3_NO_INTERLEAVE
-    mm_x3(buf + 0 * 3 * 512, lane, b, c0);
-    mm_x3(buf + 1 * 3 * 512, lane, b, c1);
-    mm_x3(buf + 2 * 3 * 512, lane, b, c2);
-    mm_x3(buf + 3 * 3 * 512, lane, b, c3);
-#else
     const A3 a0 = load_a3(buf, lane), a1 = load_a3(buf + 3 * 512, lane), a2 = load_a3(buf + 6 * 512, lane),
              a3 = load_a3(buf + 9 * 512, lane);
     c0 = MFMA16(a0.lo, b.hi, c0); c1 = MFMA16(a1.lo, b.hi, c1); c2 = MFMA16(a2.lo, b.hi, c2); c3 = MFMA16(a3.lo, b.hi, c3);
@@ -190,15 +175,9 @@ __device__ __forceinline__ void mm_x3_4(const unsigned short *buf, int lane, con
     c0 = MFMA16(a0.mid, b.hi, c0); c1 = MFMA16(a1.mid, b.hi, c1); c2 = MFMA16(a2.mid, b.hi, c2); c3 = MFMA16(a3.mid, b.hi, c3);
     c0 = MFMA16(a0.hi, b.mid, c0); c1 = MFMA16(a1.hi, b.mid, c1); c2 = MFMA16(a2.hi, b.mid, c2); c3 = MFMA16(a3.hi, b.mid, c3);
     c0 = MFMA16(a0.hi, b.hi, c0); c1 = MFMA16(a1.hi, b.hi, c1); c2 = MFMA16(a2.hi, b.hi, c2); c3 = MFMA16(a3.hi, b.hi, c3);
-#endif
 }
 __device__ __forceinline__ void mm_x3_3(const unsigned short *buf, int lane, const Split3 &b, f32x16 &c0, f32x16 &c1,
                                         f32x16 &c2) {
-#ifdef NF_X3_NO_INTERLEAVE
-    mm_x3(buf + 0 * 3 * 512, lane, b, c0);
-    mm_x3(buf + 1 * 3 * 512, lane, b, c1);
-    mm_x3(buf + 2 * 3 * 512, lane, b, c2);
-#else
     const A3 a0 = load_a3(buf, lane), a1 = load_a3(buf + 3 * 512, lane), a2 = load_a3(buf + 6 * 512, lane);
     c0 = MFMA16(a0.lo, b.hi, c0); c1 = MFMA16(a1.lo, b.hi, c1); c2 = MFMA16(a2.lo, b.hi, c2);
     c0 = MFMA16(a0.hi, b.lo, c0); c1 = MFMA16(a1.hi, b.lo, c1); c2 = MFMA16(a2.hi, b.lo, c2);
@@ -206,7 +185,6 @@ __device__ __forceinline__ void mm_x3_3(const unsigned short *buf, int lane, con
     c0 = MFMA16(a0.mid, b.hi, c0); c1 = MFMA16(a1.mid, b.hi, c1); c2 = MFMA16(a2.mid, b.hi, c2);
     c0 = MFMA16(a0.hi, b.mid, c0); c1 = MFMA16(a1.hi, b.mid, c1); c2 = MFMA16(a2.hi, b.mid, c2);
     c0 = MFMA16(a0.hi, b.hi, c0); c1 = MFMA16(a1.hi, b.hi, c1); c2 = MFMA16(a2.hi, b.hi, c2);
-#endif
 }
 
 template <bool RELU>
@@ -259,11 +237,7 @@ rqs_fused_x3_kernel(const float *__restrict__ x, float *__restrict__ y, float *_
             wide = true;
             return lay.off_lu(1);          // LU && DIR == 1: the layer's last acquire
         }
-#ifdef NF_X3_WIDE_FINAL
-        wide = true;
-#else
         wide = b < lay.n_init() + lay.n_hidden();
-#endif
         return lay.base_off(b);
     };
     // the DMA stream is issued in acquire order across the layers: (is_layer, is_local) = the next pair to request; past the
@@ -303,16 +277,10 @@ rqs_fused_x3_kernel(const float *__restrict__ x, float *__restrict__ y, float *_
     int stage = 0;
     auto acquire = [&]() -> const unsigned short * {
         // this wave's 3 pieces of `stage` have landed once at most the 3 pieces of stage+1 are outstanding
-#ifndef NF_ABL_NOWAIT
         NF_WAIT_VMCNT(3);
-#endif
-#ifndef NF_ABL_NOBAR
         __builtin_amdgcn_s_barrier();
-#endif
         asm volatile("" ::: "memory");
-#ifndef NF_ABL_NODMA
         issue(stage + 2);
-#endif
         const unsigned short *buf = reinterpret_cast<const unsigned short *>(ring + (stage % 3) * X3_RING_FLOATS);
         ++stage;
         return buf;
@@ -492,11 +460,6 @@ rqs_fused_x3_kernel(const float *__restrict__ x, float *__restrict__ y, float *_
         }
     };
     auto element = [&](int g, int f, const float (&prm)[24]) {
-#ifdef NF_ABL_NOEPI
-#pragma unroll
-        for (int v = 0; v < 24; ++v) asm volatile("" ::"v"(prm[v]));
-        return;
-#endif
         const int slot = 8 * (g >> 1) + 4 * (g & 1) + par_t + 2 * f;
         const float xt = st[slot * 64];
         float yt, l;
@@ -505,9 +468,6 @@ rqs_fused_x3_kernel(const float *__restrict__ x, float *__restrict__ y, float *_
         ld += l;
     };
     auto uncond_pair = [&](int g) {
-#ifdef NF_ABL_NOUNCOND
-        return;
-#endif
         const float *tabs = small + fl.off_tables();
 #pragma unroll
         for (int e = 0; e < 2; ++e) {

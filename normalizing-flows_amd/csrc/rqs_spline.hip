@@ -569,9 +569,7 @@ rqs_coupling_pipe_kernel(const float *__restrict__ x, float *__restrict__ y, flo
     }
 }
 
-#ifndef NF_FWD_TS_ELEMS
-#define NF_FWD_TS_ELEMS 256   // elements per tile and pass: ~one per lane
-#endif
+constexpr int NF_FWD_TS_ELEMS = 256;   // elements per tile and pass: ~one per lane
 
 template <typename T>
 static int launch_rqs_coupling(const void *x, void *y, void *logdet, const void *cond, const void *uw, const void *uh,
@@ -593,7 +591,6 @@ static int launch_rqs_coupling(const void *x, void *y, void *logdet, const void 
             return NF_OK;
         }
     }
-#ifndef NF_FWD_NO_PIPE
     if constexpr (std::is_same<T, float>::value) {
         // the default NSF layer shape (D = 64 or 128, alternating halves) on the software-pipelined kernel
         if (K == F_K && p.tails == NF_TAILS_LINEAR && !p.dfull && !tails_t && !bound_t && !tails_i && !bound_i && nI == nT &&
@@ -624,8 +621,6 @@ static int launch_rqs_coupling(const void *x, void *y, void *logdet, const void 
 #undef NF_FWD_PIPE_LAUNCH
         }
     }
-#endif
-#ifndef NF_FWD_NO_WAVE_KERNEL
     {   // wave-private tiles when four waves' regions fit 64 KB of LDS
         int SPW = nmax > 0 ? 64 / nmax : 1;
         if (SPW < 1) SPW = 1;
@@ -643,7 +638,6 @@ static int launch_rqs_coupling(const void *x, void *y, void *logdet, const void 
             return NF_OK;
         }
     }
-#endif
     int TS = NF_FWD_TS_ELEMS / (nmax > 0 ? nmax : 1);
     if (TS < 1) TS = 1;
     if (TS > 64) TS = 64;

@@ -246,9 +246,6 @@ static_assert(sizeof(PairTail) <= 2048, "NF_PAIR_TAIL_BYTES");
 
 static int pair_tail_launch(const nf::PairTail &T, nf_stream_t stream) {
     using namespace nf;
-#ifdef NF_ABL_NO_REDUCE       // timing-only ablation: what the step costs without the two launches that only produce parameter gradients
-    return NF_OK;
-#endif
     hipLaunchKernelGGL(layer_reduce_kernel, dim3(T.J.nblocks + F_NI + 1), dim3(64 * RL), 0, (hipStream_t)stream, T.J);
     NF_CHECK_LAUNCH();
     // (gld = the one-element sum, B = 1: the parameter kernel's own summation loop degenerates to a single load)

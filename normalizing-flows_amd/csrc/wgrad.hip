@@ -49,9 +49,6 @@ wgrad_partial_vec_kernel(const float *__restrict__ dY, const float *__restrict__
     // the two-trip prefetch collapses.  Rows past the chunk end are zeroed when consumed instead.
     struct Trip { f32x2 a[4]; f32x4 x[4]; };
     auto load = [&](int64_t b, Trip &tr) {
-#ifdef NF_WG_ABL_NOLOAD
-        if (B != 12345) return;
-#endif
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             int64_t r = b + 2 * j + h;
@@ -62,10 +59,6 @@ wgrad_partial_vec_kernel(const float *__restrict__ dY, const float *__restrict__
         }
     };
     auto mma = [&](int64_t b, const Trip &tr) {
-#ifdef NF_WG_ABL_NOMMA
-        bs0 += tr.a[0][0] + tr.x[0][0] + tr.a[1][0] + tr.x[1][0] + tr.a[2][0] + tr.x[2][0] + tr.a[3][0] + tr.x[3][0];
-        if (B != 12345) return;
-#endif
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const bool live = b + 2 * j + h < b1;
@@ -312,17 +305,11 @@ wgrad_tile_kernel(const float *__restrict__ dY, const float *__restrict__ X, flo
 // (Round 3, measured and dropped: all M / 128 tiles of a row chunk on ONE XCD, so that the chunk of X comes from HBM once instead
 // of once per tile -- 147 -> 152 us at 768 x 128: the kernel is bound by its MFMA issue (busy 0.62), not by the 390 MB it reads;
 // 768 instead of 512 workgroups: 143 us.)
-#ifndef NF_W3_NR
-#define NF_W3_NR 3      // measured 4 / 3 / 2 slots: 145 / 139 / 143 us at 768 x 128
-#endif
-#ifndef NF_W3_OCC
-#define NF_W3_OCC 3
-#endif
-#ifndef NF_W3_HW
-#define NF_W3_HW 4      // helper waves: they issue the ring's requests (a vector-memory instruction costs its wave 100-250 issue cycles:
-#endif                  // 4 per step against the step's 32 MFMAs = 2048 cycles when the MFMA waves issued them)
-constexpr int W3_KS = 16, W3_NR = NF_W3_NR, W3_HW = NF_W3_HW, W3_NT = 64 * (4 + W3_HW);
-__global__ void __launch_bounds__(W3_NT, W3_HW ? 4 : NF_W3_OCC)      // second argument = waves per SIMD: two 8-wave workgroups per CU
+constexpr int W3_NR = 3;      // measured 4 / 3 / 2 slots: 145 / 139 / 143 us at 768 x 128
+constexpr int W3_HW = 4;      // helper waves: they issue the ring's requests (a vector-memory instruction costs its wave 100-250 issue cycles:
+                              // 4 per step against the step's 32 MFMAs = 2048 cycles when the MFMA waves issued them)
+constexpr int W3_KS = 16, W3_NT = 64 * (4 + W3_HW);
+__global__ void __launch_bounds__(W3_NT, 4)      // second argument = waves per SIMD: two 8-wave workgroups per CU
 wgrad_ring_kernel(const float *__restrict__ dY, const float *__restrict__ X, float *__restrict__ part, int64_t B, int M,
                   int chunk_rows, int want_bias, int x_relu, int64_t zdY, int64_t zX, int64_t zpart) {
     typedef __attribute__((address_space(3))) void *lds_ptr;
@@ -419,10 +406,7 @@ wgrad_ring_kernel(const float *__restrict__ dY, const float *__restrict__ X, flo
 
 static int wgrad_tile_chunk_rows(int64_t B, int M) {
     const int mt = (M + W2_T - 1) / W2_T;
-#ifndef NF_W2_SLOTS
-#define NF_W2_SLOTS 512
-#endif
-    int64_t want = NF_W2_SLOTS / mt;               // at most 512 workgroups (two per CU): one more would cost a second round
+    int64_t want = 512 / mt;               // at most 512 workgroups (two per CU): one more would cost a second round
     if (want < 1) want = 1;
     int64_t rows = (B + want - 1) / want;
     rows = (rows + W2_KS - 1) / W2_KS * W2_KS;
@@ -471,24 +455,12 @@ static int wgrad_chunk_rows(int64_t B, int M, bool vec) {
 }  // namespace nf
 
 static inline bool wgrad_use_ring(int64_t B, int M, int N) {
-#ifdef NF_WGRAD_NO_RING
-    return false;
-#else
-#ifdef NF_WGRAD_RING_M128
-    const int mmin = 128;
-#else
     const int mmin = 256;
-#endif
     return N == 128 && M % 128 == 0 && M >= mmin && B % 16 == 0;
-#endif
 }
 
 static inline bool wgrad_use_tile(int M, int N) {
-#ifdef NF_WGRAD_NO_TILE
-    return false;
-#else
     return N >= 96 && N <= 128 && N % 4 == 0 && M % 4 == 0 && M >= 256;   // M = 128: 39 us vs 35 us wave-private (measured)
-#endif
 }
 
 extern "C" int64_t nf_linear_wgrad_scratch_floats(int64_t B, int M, int N) {

@@ -1335,6 +1335,32 @@ def test_no_fence_barrier_behind_counted_vmcnt_waits():
     assert not bad, bad
 
 
+def test_no_build_switches_in_kernel_sources():
+    """Source lint for DESIGN 3.2 ("Build switches"): the only macros a preprocessor conditional of csrc/ may test are include guards
+    and the five names a shipped build or translation unit defines -- NF_SAFE_WAITS (_lib.build_safe_waits), NF_FUSED_SECONDARY and
+    NF_FUSED_WAVES (rqs_fused_nw4.hip), NSF_TILE_CONTEXT (nsf_ctx.hip), NSF_TILE_FT (nsf_circ.hip).  Anything else is a path that
+    no build compiles and no test runs."""
+    import glob
+    import re
+    include_guards = set()          # (every header uses `#pragma once`)
+    kept = {"NF_SAFE_WAITS", "NF_FUSED_SECONDARY", "NF_FUSED_WAVES", "NSF_TILE_CONTEXT", "NSF_TILE_FT"}
+    csrc = os.path.join(ROOT, "normalizing-flows_amd", "csrc")
+    tested = {}
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.hpp"))):
+        text = re.sub(r"\\\n", " ", open(path).read())              # a directive continued over several lines is one directive
+        for line in text.split("\n"):
+            m = re.match(r"\s*#\s*(ifdef|ifndef|if|elif)\b(.*)", line)
+            if m:
+                expr = re.sub(r"//.*|/\*.*?\*/", "", m.group(2))
+                for name in set(re.findall(r"[A-Za-z_]\w*", expr)) - {"defined"}:
+                    tested.setdefault(name, os.path.basename(path))
+    assert set(tested) == include_guards | kept, (
+        "csrc/ tests macros in preprocessor conditionals other than its include guards and %s: %s (and no longer tests: %s).  A product "
+        "path is selected at run time from what the code can observe, not by a build flag: a branch no build selects is deleted "
+        "together with its switch." % (sorted(kept), {k: v for k, v in sorted(tested.items()) if k not in include_guards | kept},
+                                       sorted((include_guards | kept) - set(tested))))
+
+
 def test_streaming_kernels_have_no_flat_loads(nfa):
     """Disassembly lint for DESIGN 3.5 item 3: a FLAT load counts on lgkmcnt as well as vmcnt, so every wait for an LDS read
     also waits for it -- the 16-pixel Glow kernel's register weight stream was FLAT loads (its base comes out of a pointer

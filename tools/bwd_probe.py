@@ -1,5 +1,4 @@
-"""Time of nf_rqs_coupling_bwd_p24 (software-pipelined spline backward) at the benchmark shape; with NF_MI355X_LIB pointing at an
-ablation build (tools/build_variant.py ... -DNF_BWD_ABL_NOMATH / -DNF_BWD_ABL_NOIDENT) the same launch without the arithmetic."""
+"""Time of nf_rqs_coupling_bwd_p24 (software-pipelined spline backward) at the benchmark shape."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,4 +22,4 @@ s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True
 s.record()
 for _ in range(30): f()
 e.record(); torch.cuda.synchronize()
-print("%s: %.1f us per launch" % (os.environ.get("NF_MI355X_LIB", "product build").split("/")[-1], s.elapsed_time(e) / 30 * 1e3))
+print("%.1f us per launch" % (s.elapsed_time(e) / 30 * 1e3))

@@ -3,9 +3,8 @@
 imported from /root/reference, PyTorch CPU, on the benchmark of record -- BASELINE configs[1], the same seeded model and the
 same rows bench.py runs on the GPU (bench.build_c2_model(lib=normflows), bench.c2_inputs).
 
-The reference tree exists only in the build container (the GPU box has no /root/reference).  Rounds 2-4 ran this script THERE
-(8 cores); round 5 stages the package for one `gpurun` call (tools/stage_reference.py -> .refstage/, git-ignored) and runs it ON
-THE GPU BOX's host cores with `--ref .refstage --where "gpu box"`.  The JSON output is committed under profiles/; bench.py reads
+The reference tree exists only in the build container, so this script runs there (`--ref DIR` names another location of the
+package, `--where TEXT` is recorded with the result).  The JSON output is committed under profiles/; bench.py reads
 the newest one and reports it as the `kind: "reference"` entry of `cpu_baseline` (with where it was measured and the core count)
 next to the `kind: "port"` entry it times live.
 

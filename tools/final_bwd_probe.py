@@ -1,6 +1,4 @@
-"""Time of nf_final_bwd (+ reduce) at the benchmark shape on random saved tensors; NF_MI355X_LIB selects an ablation build
-(tools/build_variant.py fbX "-DFB_ABL_NOIDENT | -DFB_ABL_NOSPLINE | -DFB_ABL_NOROWS | -DFB_ABL_NOMFMA" final_bwd.hip: wrong results,
-timing only)."""
+"""Time of nf_final_bwd (+ reduce) at the benchmark shape on random saved tensors."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -25,25 +23,10 @@ ops.rqs_fused_pack_all(blob, d(net.initial_layer.weight), d(net.initial_layer.bi
                        d(u.unnormalized_derivatives), wfull=wfull_t, wpad=wpad, identity_idx=c.identity_features)
 f = lambda: ops.final_bwd(x, gy, gld, cond24, wpad, blob, d(u.unnormalized_widths), d(u.unnormalized_heights),
                           d(u.unnormalized_derivatives), c._fused_parity, len(net.blocks))
-if "--trace" in sys.argv:      # build: tools/build_variant.py fb_TRACE "-DFB_TRACE" final_bwd.hip
-    import ctypes
-    tr = torch.zeros(16, dtype=torch.int64, device=dev)
-    nfa._lib.lib().nf_final_bwd_debug_trace(ctypes.c_void_p(tr.data_ptr()))
-    for _ in range(3): f()
-    torch.cuda.synchronize()
-    t = tr.cpu().tolist()
-    names = ["tile prologue", "identity half", "wait parameter rows", "spline x2 + piece write", "stage wait + barrier", "row stores + requests",
-             "A reads + MFMA issue", "epilogue"]
-    tot = sum(t[:8])
-    for n, v in zip(names, t):
-        print("  %-26s %9d cycles  %5.1f %%" % (n, v, 100.0 * v / max(tot, 1)))
-    print("  total %d cycles (workgroup 0, wave 0, all its tiles)" % tot)
-    sys.exit(0)
 for _ in range(5): f()
 torch.cuda.synchronize()
 s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 s.record()
 for _ in range(30): f()
 e.record(); torch.cuda.synchronize()
-print("%s: %.1f us per call (nf_final_bwd + nf_final_bwd_reduce + allocations), B = %d" % (
-    os.environ.get("NF_MI355X_LIB", "product build").split("/")[-1], s.elapsed_time(e) / 30 * 1e3, B))
+print("%.1f us per call (nf_final_bwd + nf_final_bwd_reduce + allocations), B = %d" % (s.elapsed_time(e) / 30 * 1e3, B))

@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""Times nf_rqs_fused_train_full_fwd (whole-layer training forward) alone on the benchmark layer shape; NF_MI355X_LIB selects a
-build variant (tools/build_variant.py, e.g. -DNF_ABL_NOACT / -DNF_ABL_NOCOND: without the activation / parameter-row stores)."""
+"""Times nf_rqs_fused_train_full_fwd (whole-layer training forward) alone on the benchmark layer shape."""
 import os
 import sys
 
@@ -37,4 +36,4 @@ for _ in range(5):
     torch.cuda.synchronize()
     ts.append(s.elapsed_time(e) / 10 * 1e3)
 ts.sort()
-print("nf_rqs_fused_train_full_fwd B=%d: median %.1f us  min %.1f us  [%s]" % (B, ts[len(ts) // 2], ts[0], os.environ.get("NF_MI355X_LIB", "default")))
+print("nf_rqs_fused_train_full_fwd B=%d: median %.1f us  min %.1f us" % (B, ts[len(ts) // 2], ts[0]))

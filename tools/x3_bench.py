@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""Times one log_prob pass of the benchmark model on the split-bf16 path (persistent chain, no graph).  NF_MI355X_LIB selects
-a build variant (tools/build_variant.py; ablations give wrong results, timing only)."""
+"""Times one log_prob pass of the benchmark model on the split-bf16 path (persistent chain, no graph)."""
 import os
 import sys
 
@@ -40,9 +39,8 @@ for mode in (os.environ.get("NF_GEMM", "bf16x3"),) + (("f32",) if len(batches) >
         frac = (Bn * FLOP_ROW / (med * 1e-3)) / 2.5166e15 if mode == "bf16x3" else (Bn * FLOP_ROW / 6 / (med * 1e-3)) / 157.3e12
         out.append(dict(mode=mode, rows=Bn, ms_median=round(med, 4), ms_min=round(ts[0], 4), mrows_per_s=round(Bn / med / 1e3, 3),
                         frac_of_peak=round(frac, 4)))
-        print("log_prob %s rows %d: median %.3f ms  min %.3f ms  (%.2f M rows/s, %.3f of the %s MFMA peak)  [%s]"
-              % (mode, Bn, med, ts[0], Bn / med / 1e3, frac, "bf16" if mode == "bf16x3" else "fp32",
-                 os.environ.get("NF_MI355X_LIB", "default")))
+        print("log_prob %s rows %d: median %.3f ms  min %.3f ms  (%.2f M rows/s, %.3f of the %s MFMA peak)"
+              % (mode, Bn, med, ts[0], Bn / med / 1e3, frac, "bf16" if mode == "bf16x3" else "fp32"))
         del x
 nfa.config.set_fused_gemm("f32")
 if "--json" in sys.argv:
