@@ -851,6 +851,29 @@ int nf_made_forward(const void *x, void *params, const void *blob, const int32_t
 /* Alignment: with D % 4 == 0 z and y 16 bytes (the call is refused otherwise, before any launch); logdet element type. */
 int nf_affine_wide(const void *z, void *y, void *logdet, const void *blob, const int32_t *table, int64_t B, int D, int hidden_padded,
                    int direction, int acc, nf_stream_t stream);
+/* The same layers UNDER AUTOGRAD: the conditioner runs on nf_made_forward_train / nf_made_backward / nf_made_wgrad in plain-MLP mode
+ * (the training structure of normflows_amd/flows/affine_wide_pack.train_structure), and these two are the element-wise coupling map
+ * around it.  P is the raw conditioner output in the pack's own layout: row stride ldp (>= 2 D, even), entry 2 f = feature f's scale
+ * parameter, 2 f + 1 = its shift parameter, for all D features.  modes: one word per 16 features, 2 bits each (0 identity, 1 / 2
+ * transformed: affine_wide_pack.mode_words); smap: NF_SCALE_* or 4 = the masked flow's rule; nets: bit 0 = a masked flow has s, bit 1
+ * = it has t (a missing net's parameter is the constant 0); direction 0 = forward, 1 = inverse.  float32; 2 <= D <= 128.
+ *
+ * nf_affine_wide_apply replaces what the reference computes on the conditioners' outputs, normflows/flows/affine/coupling.py:209-229
+ * (MaskedAffineFlow.forward / .inverse: s / t non-finite -> NaN, y = b z + (1 - b)(z exp(s) + t), ld = sum (1 - b) s; the inverse
+ * y = b z + (1 - b)(z - t) exp(-s), ld = -sum) and :117-171 with the channel split / merge of :232-267 (AffineCoupling: exp, sigmoid,
+ * sigmoid_inv, scale=False -- the formulas of nf_affine_coupling): y (B, D) and logdet (B) are WRITTEN, not accumulated; the per-row
+ * log-det sum runs in a fixed order (deterministic).
+ *
+ * nf_affine_wide_apply_bwd replaces PyTorch autograd through those same lines (the closed forms of nf_masked_affine_bwd /
+ * nf_affine_coupling_bwd): from the cotangents gy (B, D) and gld (B) -- either may be NULL = zeros -- it writes gz (B, D), the
+ * derivative through the element-wise map only (the conditioner's share comes from nf_made_backward), and gP, the conditioner
+ * output's gradient, as the (Bp, ldg) buffer nf_made_backward / nf_made_wgrad take as g_params: Bp >= B rows of ldg >= 2 D floats (ldg
+ * a multiple of 4), zeros in the rows of identity features (a block) and of a missing net, beyond 2 D and beyond B. */
+/* Alignment: P 8 bytes, gP 16 bytes; with D % 4 == 0 z, y, gy and gz 16 bytes (the call is refused otherwise, before any launch). */
+int nf_affine_wide_apply(const void *z, const void *P, const int32_t *modes, void *y, void *logdet, int64_t B, int D, int ldp, int smap,
+                         int nets, int direction, nf_stream_t stream);
+int nf_affine_wide_apply_bwd(const void *z, const void *P, const void *gy, const void *gld, const int32_t *modes, void *gz, void *gP,
+                             int64_t B, int64_t Bp, int D, int ldp, int ldg, int smap, int nets, int direction, nf_stream_t stream);
 /* The autoregressive rational-quadratic spline layer's density direction in one launch: replaces
  * normflows/flows/neural_spline/autoregressive.py:94-134 (MaskedPiecewiseRationalQuadraticAutoregressive._elementwise_forward over
  * Autoregressive.forward, flows/affine/autoregressive.py:24-27; what wrapper.py:241-245 AutoregressiveRationalQuadraticSpline.inverse

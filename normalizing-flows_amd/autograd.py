@@ -1146,6 +1146,51 @@ class ConvNetFn(torch.autograd.Function):
         return None, None, gx, gw1, flat[c0:c0 + n0], gw2, flat[c1:c1 + n1], gw3, gb3
 
 
+class AffineWideFn(torch.autograd.Function):
+    """A wide RealNVP coupling layer under autograd -- MaskedAffineFlow(MLP s, MLP t) (affine/coupling.py:174-229) or
+    AffineCouplingBlock(MLP) (:99-171, :232-267) over nets/mlp.py:5-58, the layers nf_affine_wide runs at inference -- on the MADE
+    training kernels in plain-MLP mode with the coupling map around them (flows/affine_wide_pack.train_structure,
+    csrc/affine_wide_train.hip): forward = nf_pack_gather (the streams from the parameters as they are NOW) + nf_made_forward_train
+    (the stacked conditioner: P (B, 2 d), row 2 f / 2 f + 1 = feature f's scale / shift parameter) + nf_affine_wide_apply -> (y, ld);
+    backward = nf_affine_wide_apply_bwd (gz through the element-wise map, gP in g_params' padded shape) + nf_made_backward (the
+    conditioner's input gradient) + nf_made_wgrad (unless the conditioner is frozen), carved into the parameters' own shapes.
+    fwd = (gather indices [forward | backward], table, hidden_padded, forward stream length), bwd = the structure's backward dict,
+    modes = the mode words on the device, cfg = (scale map, nets bits, direction, carve recipes); params = weight, bias of every
+    Linear in affine_wide_pack.linears order."""
+
+    @staticmethod
+    def forward(ctx, fwd, bwd, modes, cfg, z, *params):
+        src, table, hp, nfwd = fwd
+        smap, nets, direction, _ = cfg
+        ctx.set_materialize_grads(False)
+        both = ops.pack_gather([p_.detach() for p_ in params], src)
+        z = z.contiguous()
+        P, save, bits = ops.made_forward_train(z, both[:nfwd], table, hp, 2 * z.shape[1], 1)
+        y, ld = ops.affine_wide_apply(z, P, modes, smap, nets, direction)
+        ctx.save_for_backward(z, P, save, bits, both)
+        ctx.bwd, ctx.modes, ctx.cfg, ctx.nfwd = bwd, modes, cfg, nfwd
+        return y, ld
+
+    @staticmethod
+    @once_differentiable          # (the backward is a set of kernels, not a differentiable graph: double backward raises)
+    def backward(ctx, gy, gld):
+        z, P, save, bits, both = ctx.saved_tensors
+        bwd = ctx.bwd
+        smap, nets, direction, recipes = ctx.cfg
+        B, d = z.shape
+        need_w = any(ctx.needs_input_grad[5:])
+        # (a missing cotangent goes to the kernel as NULL: no zero tensor is built)
+        gz, gP = ops.affine_wide_apply_bwd(z, P, gy, gld, ctx.modes, smap, nets, direction, save.shape[1], bwd["Mp"])
+        gx, G = ops.made_backward(gP, bits, both[ctx.nfwd:], bwd["table"], d, bwd["Hp"], 1, rows=B, out_features=2 * d, want_G=need_w)
+        grads = [None] * (len(ctx.needs_input_grad) - 5)
+        if need_w:                # (frozen conditioner: no weight-gradient launch)
+            flat = ops.made_wgrad(gP, z, G, save, bwd["wtable"], bwd["stable"], bwd["mask"], bwd["ntiles"], bwd["nflat"], bwd["Mp"],
+                                  bwd["Dx"], rows=B)
+            from .flows import affine_wide_pack
+            grads = affine_wide_pack.carve(flat, bwd["offsets"], recipes)
+        return (None, None, None, None, gz.add_(gx) if ctx.needs_input_grad[4] else None) + tuple(grads)
+
+
 class MafInverseFn(torch.autograd.Function):
     """MaskedAffineAutoregressive.inverse (affine/autoregressive.py:29-38 + :114-128: the DENSITY direction of the reference's MAF, D
     sequential MADE passes) under autograd WITHOUT differentiating through the D passes.  x = T^-1(z) satisfies T(x; theta) = z with

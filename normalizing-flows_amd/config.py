@@ -442,6 +442,28 @@ def set_affine_wide(mode=True, graph_min_batch=None):
         affine_wide_graph_min_batch = int(graph_min_batch)
 
 
+# The same layers UNDER AUTOGRAD on HIP kernels (autograd.AffineWideFn: nf_pack_gather, nf_made_forward_train in plain-MLP mode on the
+# stacked [s | t] conditioner, nf_affine_wide_apply; backward nf_affine_wide_apply_bwd, nf_made_backward, nf_made_wgrad) instead of
+# b * z, one library GEMM per Linear, one LeakyReLU launch per activation and MaskedAffineFn / AffineCouplingFn on top.  OPT-IN,
+# default False: with the switch off these layers' gradients are bit for bit what the layer-wise route gives (the MFMA kernels sum
+# in another order than the library GEMMs), which tests/test_gpu_affine_wide.py pins for the default configuration.  The route also
+# follows made_train and made_fused, so inside higher_order_gradients() the torch modules run and double backward keeps working.
+affine_wide_train = False
+# While a stream is being CAPTURED (NormalizingFlow.use_graphs' recording, or a caller's own torch.cuda.graph) the route is taken from
+# this many rows on: replayed from a graph the layer-wise route has no launch overhead left, and at 1 024 rows its step lasts 0.18 ms
+# against 0.30 ms (d 128, one net of 512).  Replayed, the route is not slower from 2 048 rows on (d 64, two nets of 256) resp. 8 192
+# (d 128, one net of 512) (profiles/affine_wide_train_bench.json: `capture_not_slower_from`, tools/affine_wide_train_bench.py); the
+# gate is the larger of the two.  Eager steps take the route at every size (1.3x - 2.2x faster over the swept sizes).
+affine_wide_train_capture_min_batch = 8192
+
+
+def set_affine_wide_train(mode=True, capture_min_batch=None):
+    global affine_wide_train, affine_wide_train_capture_min_batch
+    affine_wide_train = bool(mode)
+    if capture_min_batch is not None:
+        affine_wide_train_capture_min_batch = int(capture_min_batch)
+
+
 # Debug mode of the element-wise spline API (utils.splines): after every call a check launch (nf_rqs_spline_check)
 # sets device-side flags and the shim reads them back -- a host synchronisation per call, which is why it is off by default -- and
 # raises what the reference raises: AssertionError for a negative discriminant in the inverse direction (utils/splines.py:181),

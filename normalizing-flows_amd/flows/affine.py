@@ -114,6 +114,51 @@ def _affine_wide(flow, z, inverse, ld, acc):
     return ops.affine_wide(z, packed[0], packed[1], packed[2], 1 if inverse else 0, logdet=ld, acc=acc)
 
 
+def _affine_wide_train(flow, z, inverse):
+    """(y, per-sample log-det) of a MaskedAffineFlow / AffineCouplingBlock UNDER AUTOGRAD on the MADE training kernels
+    (autograd.AffineWideFn, flows/affine_wide_pack.train_structure), or None when the switch (config.affine_wide_train: opt-in), the
+    layer or the input declines it -- then the caller's layer-wise code runs.  Eligibility that can be read from attributes is looked
+    at on every call; the value-independent structure is built once per layer and device; the streams are gathered from the live
+    parameters in every forward, so an optimizer step needs no invalidation."""
+    if not (_config.affine_wide_train and _config.made_train and _config.made_fused) or _config.torch_elementwise:
+        return None
+    if z.dim() != 2 or not z.is_cuda or z.dtype != torch.float32 or not needs_grad(z, flow):
+        return None
+    if z.shape[0] < _config.affine_wide_train_capture_min_batch and (_config._graph_recording or torch.cuda.is_current_stream_capturing()):
+        return None         # (replayed from a graph, a small batch is faster layer by layer)
+    from .. import nets
+    from ..autograd import AffineWideFn
+    from . import affine_wide_pack
+    d = z.shape[1]
+    st = affine_wide_pack.structure(flow, d)
+    if isinstance(st, str):
+        return None
+    lins = affine_wide_pack.linears(st)
+    plist = [t for l in lins for t in (l.weight, l.bias)]
+    if not all(p.is_cuda and p.device == z.device and p.is_contiguous() for p in plist):
+        return None
+    if st["kind"] == "masked":
+        if flow.b.device != z.device:
+            return None
+        skey = (flow.b.data_ptr(), flow.b._version, st["s"] is not None, st["t"] is not None)
+    else:
+        skey = (st["c1"], bool(st["flip"]), int(st["smap"]))
+
+    def build():
+        ts = affine_wide_pack.train_structure(flow, d)
+        return None if isinstance(ts, str) else ts
+
+    struct = nets._train_struct_for(flow, build, z.device, ("affine_wide", st["kind"], d, tuple(tuple(l.weight.shape) for l in lins)) + skey)
+    if struct is None:
+        return None
+    modes = struct.get("modes_dev")
+    if modes is None:
+        modes = struct["modes_dev"] = torch.from_numpy(struct["modes"]).to(z.device)
+    fwd = (struct["src"], struct["table"], struct["hp"], struct["nfwd"])
+    cfg = (struct["smap"], struct["nets"], 1 if inverse else 0, struct["carve"])
+    return AffineWideFn.apply(fwd, struct["bwd"], modes, cfg, z, *plist)
+
+
 class AffineConstFlow(Flow):
     """Per-dimension learned scale and shift (coupling.py:9-54); base class of ActNorm."""
 
@@ -286,6 +331,10 @@ class MaskedAffineFlow(Flow):
     def _transform(self, z, inverse, ld=None, acc=None):
         need_net = self.s is not None or self.t is not None
         if need_net:
+            if _config.affine_wide_train and (ld is None or ld.dtype == torch.float32):
+                out = _affine_wide_train(self, z, inverse)      # (wide MLP conditioners under autograd, opt-in: the MADE training kernels)
+                if out is not None:
+                    return out[0], _fold_ld(ld, acc, out[1])
             out = _affine_wide(self, z, inverse, ld, acc)       # (wide MLP conditioners at inference: one launch)
             if out is not None:
                 return out
@@ -365,6 +414,11 @@ class AffineCouplingBlock(Flow):
 
     def _go(self, z, inverse, ld, acc):
         if self.split_mode in ("channel", "channel_inv") and z.shape[1] >= 2:
+            if _config.affine_wide_train and (ld is None or ld.dtype == torch.float32):
+                out = _affine_wide_train(self, z, inverse)      # (a wide MLP param_map under autograd, opt-in: the MADE training kernels)
+                if out is not None:
+                    _fold_ld(ld, acc, out[1])
+                    return out[0]
             out = _affine_wide(self, z, inverse, ld, acc)       # (a wide MLP param_map at inference: one launch)
             if out is not None:
                 return out[0]

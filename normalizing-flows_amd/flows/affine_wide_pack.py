@@ -25,7 +25,9 @@ module only rearranges weights.  ONE formulation serves both layer types:
 Non-finite values.  An inf / NaN in z, and a non-finite s / t / param_map output, land where the layer-wise route puts them.  One
 difference remains: the zero blocks of the stacked weights are multiplied like any other, so a non-finite HIDDEN activation of one
 net (finite inputs and weights do not produce one) reaches the other net's outputs as NaN (0 * inf), where the layer-wise route
-keeps that other net finite.
+keeps that other net finite.  Under autograd (train_structure, autograd.AffineWideFn; config.affine_wide_train) there is a second one
+for a block: the MADE training forward has no zero-fed tile, so the z2 columns meet the ZERO WEIGHTS of the initial layer, and a
+non-finite z2 entry turns the whole row into NaN (0 * inf) where the layer-wise route keeps it finite.  Finite inputs are unaffected.
 """
 import numpy as np
 import torch
@@ -197,6 +199,107 @@ def slot_layers(flow, d, wb=None):
     return dict(D=d, H=st["slots"], NB=1, Hp=Hp, NSB=Hp // 256, Dp=Dp, NFB=NFB, MD=2 * d, mult=2, order=np.arange(st["slots"]),
                 slot_of=np.arange(st["slots"]), layers=layers, plain=True, modes=modes.astype(np.int64), smap=int(st["smap"]),
                 offs=st["offs"])
+
+
+# ---- under autograd: the MADE training kernels in plain-MLP mode around nf_affine_wide_apply / _bwd (autograd.AffineWideFn) ------------
+def linears(st):
+    """The Linears of structure()'s dict in parameter order: s's three, then t's (a block: the param_map's)."""
+    return [l for k in ("s", "t", "net") if st.get(k) is not None for l in st[k]]
+
+
+def _train_key(flow, st):
+    import hashlib
+    shapes = tuple(tuple(l.weight.shape) for l in linears(st))
+    if st["kind"] == "masked":
+        b = flow.b.detach().reshape(-1).cpu().numpy().astype(np.float32)
+        return ("affine_wide", "masked", st["d"], shapes, st["s"] is not None, st["t"] is not None, hashlib.sha1(b.tobytes()).hexdigest())
+    return ("affine_wide", "block", st["d"], shapes, st["c1"], bool(st["flip"]), int(st["smap"]))
+
+
+def _train_masks(sl, kind):
+    """The weight problems' masks over the STACKED parameter layout ((slots, d), (slots, slots), (2 d, slots)): where nf_made_wgrad
+    writes.  Everything else stays the exact 0 the reference's autograd gives: the zero blocks of the stacked weights, and for a masked
+    flow the first-layer columns f with b_f = 0 (the reference feeds b * z) and the final rows of features with b_f = 1 (multiplied by
+    1 - b).  A block's param_map has no columns for z2 and no rows for z1 to begin with."""
+    H, d = sl["H"], sl["D"]
+    (_, M0, _), (_, M1, _), _, (_, Mf, _) = sl["layers"]
+    m0, m1, mf = M0[:H, :d].copy(), M1[:H, :H].copy(), Mf[:2 * d, :H].copy()
+    if kind == "masked":
+        ident = sl["modes"] == IDENTITY
+        m0[:, ~ident] = False
+        mf[np.repeat(ident, 2), :] = False
+    return [m0, m1, mf]
+
+
+def _carve_recipes(st, sl):
+    """Per parameter (weight, bias of every Linear in linears() order) where its gradient sits in the stacked flat result: (problem,
+    "w" | "b", row slice, column slice, swap) -- views of the stacked problems; swap: a block's final rows come in (scale, shift) pairs
+    and leave as the param_map's (shift, scale) rows."""
+    d, out = st["d"], []
+    for k in ("s", "t", "net"):
+        if st.get(k) is None:
+            continue
+        o = st["offs"][k]
+        l0, l1, _ = st[k]
+        h1, h2 = l0.out_features, l1.out_features
+        if st["kind"] == "masked":
+            cols, rows, swap = slice(0, d), slice(0 if k == "s" else 1, 2 * d, 2), False
+        else:
+            c1, c2 = st["c1"], d - st["c1"]
+            z1_0, z2_0 = (c2 if st["flip"] else 0), (0 if st["flip"] else c1)
+            cols = slice(z1_0, z1_0 + c1)
+            scale = st["smap"] != 3
+            rows, swap = (slice(2 * z2_0, 2 * z2_0 + 2 * c2), True) if scale else (slice(2 * z2_0 + 1, 2 * z2_0 + 2 * c2, 2), False)
+        out += [(0, "w", slice(o, o + h1), cols, False), (0, "b", slice(o, o + h1), None, False),
+                (1, "w", slice(o, o + h2), slice(o, o + h1), False), (1, "b", slice(o, o + h2), None, False),
+                (2, "w", rows, slice(o, o + h2), swap), (2, "b", rows, None, swap)]
+    return out
+
+
+def train_structure(flow, d):
+    """The value-independent part of the layer's training packs (made_pack.train_structure over slot_layers with values and with the
+    positions of made_pack.index_arrays), shared between layers of one structure (made_pack._shared), or the reason (str) the layer
+    is declined -- exactly structure() + the binary-mask check, the layers nf_affine_wide takes.  The dict of
+    made_pack.train_structure (the forward / backward streams are gathered from the live parameters in every forward: flat = [0, the
+    weight and bias of every Linear in linears() order]) with
+      bwd["table"][14] = bwd["Mp"]   g_params arrives in the padded shape nf_affine_wide_apply_bwd writes (no pad copy)
+      modes, smap, nets              the operands of nf_affine_wide_apply / _bwd
+      carve                          _carve_recipes: every parameter's gradient as a view of nf_made_wgrad's stacked flat result.
+
+    Non-finite values under autograd.  As at inference, with one more difference for a block: its z2 columns meet ZERO WEIGHTS here
+    instead of a zeroed tile, so a non-finite z2 entry turns the whole row into NaN (0 * inf) where the layer-wise route keeps it
+    finite.  Finite inputs are unaffected."""
+    st = structure(flow, d)
+    if isinstance(st, str):
+        return st
+
+    def build():
+        sl_v = slot_layers(flow, d)
+        if isinstance(sl_v, str):
+            return sl_v
+        lins = linears(st)
+        idx = made_pack.index_arrays([tuple(l.weight.shape) for l in lins])
+        sl_i = slot_layers(flow, d, wb={id(l): wb for l, wb in zip(lins, idx)})
+        sl_v["masks"] = sl_i["masks"] = _train_masks(sl_v, st["kind"])
+        ts = made_pack.train_structure(sl_v, sl_i)
+        ts["bwd"]["table"][14] = ts["bwd"]["Mp"]
+        ts.update(modes=mode_words(sl_v["modes"], sl_v["Dp"]), smap=int(sl_v["smap"]), d=d,
+                  nets=(1 if "s" in sl_v["offs"] else 0) | (2 if "t" in sl_v["offs"] else 0), carve=_carve_recipes(st, sl_v))
+        return ts
+    return made_pack._shared(_train_key(flow, st), build)
+
+
+def carve(flat, offsets, recipes):
+    """Every parameter's gradient in its own shape out of nf_made_wgrad's flat result (torch or numpy)."""
+    out = []
+    for prob, what, rows, cols, swap in recipes:
+        woff, shape, boff, n = offsets[prob]
+        g = flat[woff:woff + shape[0] * shape[1]].reshape(shape)[rows, cols] if what == "w" else flat[boff:boff + n][rows]
+        if swap:          # (scale, shift) pairs -> the param_map's (shift, scale) rows: the one copy of this carve
+            g = g.reshape((g.shape[0] // 2, 2) + tuple(g.shape[1:]))
+            g = (g.flip(1) if hasattr(g, "flip") else g[:, ::-1]).reshape((-1,) + tuple(g.shape[2:]))
+        out.append(g)
+    return out
 
 
 def mode_words(modes, Dp):

@@ -1242,6 +1242,43 @@ def affine_wide(z, blob, table, hidden_padded, direction, logdet=None, acc=None)
     return y, logdet
 
 
+def affine_wide_apply(z, P, modes, smap, nets, direction):
+    """The coupling map of a wide RealNVP layer on the raw conditioner output P (B, >= 2 D: 2 f / 2 f + 1 = feature f's scale / shift
+    parameter; coupling.py:209-229, :117-171) -- nf_affine_wide_apply: (y (B, D), log-det (B)), written.  modes: the int32 words of
+    flows/affine_wide_pack.mode_words; smap: _lib.SCALE code or 4 (masked); nets: bit 0 = s, bit 1 = t."""
+    L.require_device(z, P, modes, dtype=torch.float32)
+    B, D = z.shape
+    if P.dim() != 2 or P.shape[0] < B or P.shape[1] < 2 * D or modes.dtype != torch.int32 or modes.numel() < (D + 15) // 16:
+        raise ValueError("affine_wide_apply: P is (>= B, >= 2 D), modes one int32 word per 16 features")
+    z = _a16(z.contiguous(), D % 4 == 0)
+    P = P.contiguous()
+    y = torch.empty_like(z)
+    ld = torch.empty(B, dtype=z.dtype, device=z.device)
+    L.call("nf_affine_wide_apply", ptr(z), ptr(P), ptr(modes), ptr(y), ptr(ld), B, D, P.shape[1], smap, nets, direction, L.stream())
+    return y, ld
+
+
+def affine_wide_apply_bwd(z, P, gy, gld, modes, smap, nets, direction, rows_padded, ld_out):
+    """The backward of affine_wide_apply (nf_affine_wide_apply_bwd): (gz (B, D) through the element-wise map only, gP (rows_padded,
+    ld_out): the conditioner output's gradient in the padded shape made_backward / made_wgrad take as g_params, zeros in the padding).
+    gy / gld may be None (zeros; no tensor is built)."""
+    L.require_device(z, P, gy, gld, modes, dtype=torch.float32)
+    B, D = z.shape
+    if P.dim() != 2 or P.shape[0] < B or P.shape[1] < 2 * D or modes.dtype != torch.int32 or modes.numel() < (D + 15) // 16:
+        raise ValueError("affine_wide_apply_bwd: P is (>= B, >= 2 D), modes one int32 word per 16 features")
+    L.check_count("affine_wide_apply_bwd", "gy", gy, B * D, "B D")
+    L.check_count("affine_wide_apply_bwd", "gld", gld, B, "B")
+    z = _a16(z.contiguous(), D % 4 == 0)
+    P = P.contiguous()
+    gy = None if gy is None else _a16(gy.contiguous(), D % 4 == 0)
+    gld = None if gld is None else gld.contiguous()
+    gz = torch.empty_like(z)
+    gP = torch.empty(rows_padded, ld_out, dtype=z.dtype, device=z.device)
+    L.call("nf_affine_wide_apply_bwd", ptr(z), ptr(P), ptr(gy), ptr(gld), ptr(modes), ptr(gz), ptr(gP), B, rows_padded, D, P.shape[1],
+           ld_out, smap, nets, direction, L.stream())
+    return gz, gP
+
+
 def made_forward_spline(x, blob, table, hidden_padded, tail_bound, min_bin_width=1e-3, min_bin_height=1e-3, min_derivative=1e-3,
                         logdet=None, acc=None):
     """neural_spline/autoregressive.py:94-134 density direction (MADE + 8-bin spline with linear tails) as one launch
