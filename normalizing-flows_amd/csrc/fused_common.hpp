@@ -130,8 +130,16 @@ __device__ __forceinline__ float frcp(float x) { return __builtin_amdgcn_rcpf(x)
 __device__ __forceinline__ float fsqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 // softplus = log1p(exp(x)) (threshold 20 like torch); log1p(t) = log(1+t) * t / ((1+t) - 1) keeps full relative
 // accuracy for tiny t (Kahan), selected against the t itself when 1+t rounds to 1.
+// RAW: x comes (through selects) from MFMA accumulators; the clamp is then the bare instruction (fmin_raw below: no canonicalising
+// v_max x, x in front of it).  Same value for every input: a NaN loses against 20 either way.
+__device__ __forceinline__ float fmin_raw(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+template <bool RAW = false>
 __device__ __forceinline__ float fsoftplus(float x) {
-    const float t = fexp(fminf(x, 20.0f));
+    const float t = fexp(RAW ? fmin_raw(x, 20.0f) : fminf(x, 20.0f));
     const float u = 1.0f + t;
     const float w = u - 1.0f;
     const float l1p = (w == 0.0f) ? t : flog(u) * (t * frcp(w));
@@ -319,6 +327,19 @@ __device__ __forceinline__ float fmax_raw(float a, float b) {
     asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+// ReLU of an accumulator value as ONE instruction: v_med3_f32 x, 0, +inf = x clamped to [0, +inf].  fmaxf(x, 0.0f) makes the compiler
+// canonicalise an operand that comes from an MFMA first (v_max x, x: a second instruction per value); the median does not need it.
+// Same value as fmaxf(x, 0.0f) for every input: with a NaN among its operands the instruction returns the minimum of the other two,
+// 0, as fmaxf(NaN, 0.0f) does.  The +inf goes through an empty asm (a scalar register, no instruction) so that the compiler does not
+// see the constant and turn the median back into the canonicalising maximum.
+// The instruction itself is a builtin, NOT inline assembly like the maxima above: those sit behind the descent's selects, this one
+// reads registers an MFMA has just written and writes registers the next MFMA reads, and only an instruction the compiler knows
+// gets the wait states such neighbours need (as `asm("v_max_f32 %0, 0, %1")` the sample-direction kernels returned wrong rows).
+__device__ __forceinline__ float relu_raw(float x) {
+    float top = __builtin_inff();
+    asm("" : "+s"(top));
+    return __builtin_amdgcn_fmed3f(x, 0.0f, top);
+}
 
 // elements (x0, prm0) and (x1, prm1); prm as in rqs_regs.  KB a power of two.
 // Z0 (the compact final section of the 8-bin inference kernels): prm[0] and prm[KB], logit 0 of the two softmaxes, are the constant 0
@@ -372,8 +393,9 @@ __device__ __forceinline__ void rqs_regs2(const RqsParams<float> &p, float x0, f
         rqs_descend2<KB>(x, kw, kh, dp, slo, shi, olo, ohi, dl0, dl1);
     else
         rqs_descend2<KB>(x, kh, kw, dp, slo, shi, olo, ohi, dl0, dl1);
-    const f32x2e d0 = p.min_d + f32x2e{fsoftplus(dl0[0]), fsoftplus(dl0[1])};
-    const f32x2e d1 = p.min_d + f32x2e{fsoftplus(dl1[0]), fsoftplus(dl1[1])};
+    // (Z0: the logits are accumulator values picked by the descent's selects)
+    const f32x2e d0 = p.min_d + f32x2e{fsoftplus<Z0>(dl0[0]), fsoftplus<Z0>(dl0[1])};
+    const f32x2e d1 = p.min_d + f32x2e{fsoftplus<Z0>(dl1[0]), fsoftplus<Z0>(dl1[1])};
     f32x2e yy, ll;
     if (!INVERSE)
         rqs_eval_bin_fast2<false, Z0>(x, slo, shi - slo, olo, ohi - olo, d0, d1, yy, ll);
@@ -534,6 +556,30 @@ __device__ __forceinline__ void rqs_table_fast(const RqsParams<float> &p, float 
     rqs_eval_bin_fast<INVERSE>(x, cw0, cw1 - cw0, ch0, ch1 - ch0, d0, d1, yy, ll);
     y = inside ? yy : x;
     lad = inside ? ll : 0.0f;
+}
+
+// TWO batch-shared elements (x0 from tab0, x1 from tab1): bin search and table reads per element as in rqs_table_fast, then ONE bin
+// evaluation on packed arithmetic (rqs_eval_bin_fast2, plain reciprocals: the same formulas as rqs_eval_bin_fast).
+template <bool INVERSE, int KB = F_K>
+__device__ __forceinline__ void rqs_table_fast2(const RqsParams<float> &p, float x0, float x1, const float *tab0, const float *tab1,
+                                                float &y0, float &y1, float &lad0, float &lad1) {
+    const f32x2e x = {x0, x1};
+    const i32x2e inside = (x >= p.left) & (x <= p.right);
+    const float *srch0 = INVERSE ? tab0 + (KB + 1) : tab0, *srch1 = INVERSE ? tab1 + (KB + 1) : tab1;
+    int b0 = 0, b1 = 0;
+#pragma unroll
+    for (int k = 1; k < KB; ++k) {
+        b0 = (x0 >= srch0[k]) ? k : b0;
+        b1 = (x1 >= srch1[k]) ? k : b1;
+    }
+    const f32x2e cw0 = {tab0[b0], tab1[b1]}, cw1 = {tab0[b0 + 1], tab1[b1 + 1]};
+    const f32x2e ch0 = {tab0[KB + 1 + b0], tab1[KB + 1 + b1]}, ch1 = {tab0[KB + 2 + b0], tab1[KB + 2 + b1]};
+    const f32x2e d0 = {tab0[2 * (KB + 1) + b0], tab1[2 * (KB + 1) + b1]}, d1 = {tab0[2 * (KB + 1) + b0 + 1], tab1[2 * (KB + 1) + b1 + 1]};
+    f32x2e yy, ll;
+    rqs_eval_bin_fast2<INVERSE, false>(x, cw0, cw1 - cw0, ch0, ch1 - ch0, d0, d1, yy, ll);
+    const f32x2e yr = inside ? yy : x;
+    const f32x2e lr = inside ? ll : pk_bc(0.0f);
+    y0 = yr[0]; y1 = yr[1]; lad0 = lr[0]; lad1 = lr[1];
 }
 
 __device__ __forceinline__ f32x16 load_bias16(const float *src) {

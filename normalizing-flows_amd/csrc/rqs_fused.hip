@@ -339,7 +339,7 @@ pack_lu_train_multi_kernel(const void *const *__restrict__ table, float eps, int
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 // acc += Wblock(32 x 128) * B, where the B operand for (k-group s, r) is `bsrc[s >> 2][4 (s & 3) + r]`
-// (optionally through ReLU): 16 ds_read_b128 + 64 MFMA.
+// (optionally through ReLU -- only where the caller cannot do it once per activation with relu_raw): 16 ds_read_b128 + 64 MFMA.
 // HB: hidden row-blocks in use (4 = 128 units; 2 / 1 = layers of <= 64 / <= 32 hidden units packed into the same 128-unit
 // blob: the units beyond are zero rows / columns, so their k-groups and row-blocks are skipped -- exactly, not approximately).
 template <bool RELU, int HB = 4, int LA = 2>
@@ -435,6 +435,13 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
     // 8 bins, inference: the final layer streams the blob's COMPACT section (21 rows per feature, logit 0 of each softmax == 0:
     // fused_common.hpp) -- 21 row-blocks instead of 24
     constexpr bool COMPACT = KB == 8 && TRAIN == 0;
+    // ReLU on the raw accumulators (relu_raw: no canonicalising v_max x, x in front).  Not in the 16-bin density kernel with the fused
+    // LU at 128 hidden units: 2 spilled registers with it; that one keeps fmaxf, per use inside the products, as before
+    constexpr bool RAW_RELU = !(KB == 16 && DIR == 0 && LU && HB == 4);
+    auto relu_acc = [](float v) __attribute__((always_inline)) { return RAW_RELU ? relu_raw(v) : fmaxf(v, 0.0f); };
+    // the identity half's splines two at a time on packed arithmetic (uncond_group): inference only -- the whole-layer training forward
+    // with the fused LU on 128-row workgroups spills 3 registers with it and keeps the element-by-element form
+    constexpr bool PAIR_TAB = TRAIN == 0;
     constexpr int MP = 3 * KB, FPL = 16 / KB, GQ = KB / 4, TABW = 3 * (KB + 1);   // slots per feature, features per lane-half and
                                                                                  // group, groups per 16-column chunk, table row
     FusedLayout lay;
@@ -567,18 +574,22 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
 #pragma unroll
         for (int Q = 0; Q < 4; ++Q) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
+            for (int r = 0; r < 4; r += 2) {      // two elements per step: one packed bin evaluation for both (rqs_table_fast2)
                 const int c = 8 * Q + 2 * r + par_i;
                 const int f = 8 * Q + 4 * hh + r;  // identity feature index
-                const float xi = st[c * 64];
+                const float xi0 = st[c * 64], xi1 = st[(c + 2) * 64];
                 if (DIR == 1) {
-                    float yi, l;
-                    rqs_table_fast<true, KB>(p, xi, tabs + f * TABW, yi, l);
-                    st[c * 64] = yi;
-                    ld += l;
-                    bx[4 * Q + r] = yi;
+                    float y0, y1, l0, l1;
+                    rqs_table_fast2<true, KB>(p, xi0, xi1, tabs + f * TABW, tabs + (f + 1) * TABW, y0, y1, l0, l1);
+                    st[c * 64] = y0;
+                    st[(c + 2) * 64] = y1;
+                    ld += l0;
+                    ld += l1;
+                    bx[4 * Q + r] = y0;
+                    bx[4 * Q + r + 1] = y1;
                 } else {
-                    bx[4 * Q + r] = xi;
+                    bx[4 * Q + r] = xi0;
+                    bx[4 * Q + r + 1] = xi1;
                 }
             }
         }
@@ -674,7 +685,7 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
     // acquire's wait for the DMA also waited for the write acknowledgements of 16 KB per wave (vector-memory operations retire in order)
     // ---- residual blocks: H += W2 relu(W1 relu(H) + b1) + b2 (resnet.py:37-50) ----
     for (int blk = 0; blk < nblk; ++blk) {
-        f32x16 T0, T1, T2, T3;
+        f32x16 T0, T1, T2, T3, R0, R1, R2, R3;
         {
             const float *bsrc = small + lay.off_bias_hidden(2 * blk) + hh * 16;
             T0 = load_bias16(bsrc);
@@ -686,10 +697,28 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
             const float *buf = acquire();
             if (blk == 0) store_xlu();
             store_act(2 * blk, H0, H1, H2, H3);         // the block's input (blk = 0: the initial layer's output)
-            mm128<true, HB, LA>(buf, lane, T0, H0, H1, H2, H3);
+            // relu(H) once per block, explicitly (one instruction per value on the raw accumulators), shared by the four products
+            if constexpr (RAW_RELU) {
+#pragma unroll
+                for (int c = 0; c < 16; ++c) {
+                    R0[c] = relu_raw(H0[c]);
+                    R1[c] = relu_raw(H1[c]);
+                    R2[c] = relu_raw(H2[c]);
+                    R3[c] = relu_raw(H3[c]);
+                }
+                mm128<false, HB, LA>(buf, lane, T0, R0, R1, R2, R3);
+            } else {
+                mm128<true, HB, LA>(buf, lane, T0, H0, H1, H2, H3);
+            }
         }
-        if constexpr (HB >= 2) mm128<true, HB, LA>(acquire(), lane, T1, H0, H1, H2, H3);
-        if constexpr (HB == 4) {
+        if constexpr (RAW_RELU) {
+            if constexpr (HB >= 2) mm128<false, HB, LA>(acquire(), lane, T1, R0, R1, R2, R3);
+            if constexpr (HB == 4) {
+                mm128<false, HB, LA>(acquire(), lane, T2, R0, R1, R2, R3);
+                mm128<false, HB, LA>(acquire(), lane, T3, R0, R1, R2, R3);
+            }
+        } else {
+            mm128<true, HB, LA>(acquire(), lane, T1, H0, H1, H2, H3);
             mm128<true, HB, LA>(acquire(), lane, T2, H0, H1, H2, H3);
             mm128<true, HB, LA>(acquire(), lane, T3, H0, H1, H2, H3);
         }
@@ -705,10 +734,10 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
         // T is dead after this linear: ReLU it once in place (64 v_max) instead of once per use (256)
 #pragma unroll
         for (int c = 0; c < 16; ++c) {
-            T0[c] = fmaxf(T0[c], 0.0f);
-            T1[c] = fmaxf(T1[c], 0.0f);
-            T2[c] = fmaxf(T2[c], 0.0f);
-            T3[c] = fmaxf(T3[c], 0.0f);
+            T0[c] = relu_acc(T0[c]);
+            T1[c] = relu_acc(T1[c]);
+            T2[c] = relu_acc(T2[c]);
+            T3[c] = relu_acc(T3[c]);
         }
         mm128<false, HB, LA>(buf2, lane, H0, T0, T1, T2, T3);
         if constexpr (HB >= 2) mm128<false, HB, LA>(acquire(), lane, H1, T0, T1, T2, T3);
@@ -749,15 +778,30 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
     };
     auto uncond_group = [&](int g) {  // density only: the FPL identity slots of chunk Q = g / GQ that go with this group
         const float *tabs = small + lay.off_tables();
+        if constexpr (FPL >= 2 && PAIR_TAB) {      // 8 / 4 bins: the slots two at a time, one packed bin evaluation per pair (rqs_table_fast2)
 #pragma unroll
-        for (int e = 0; e < FPL; ++e) {
-            const int r = FPL * (g % GQ) + e;
-            const int c = 8 * (g / GQ) + 2 * r + par_i;
-            const int f = 8 * (g / GQ) + 4 * hh + r;
-            float yi, l;
-            rqs_table_fast<false, KB>(p, st[c * 64], tabs + f * TABW, yi, l);
-            st[c * 64] = yi;
-            ld += l;
+            for (int e = 0; e < FPL; e += 2) {
+                const int r = FPL * (g % GQ) + e;
+                const int c = 8 * (g / GQ) + 2 * r + par_i;
+                const int f = 8 * (g / GQ) + 4 * hh + r;
+                float y0, y1, l0, l1;
+                rqs_table_fast2<false, KB>(p, st[c * 64], st[(c + 2) * 64], tabs + f * TABW, tabs + (f + 1) * TABW, y0, y1, l0, l1);
+                st[c * 64] = y0;
+                st[(c + 2) * 64] = y1;
+                ld += l0;
+                ld += l1;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < FPL; ++e) {
+                const int r = FPL * (g % GQ) + e;
+                const int c = 8 * (g / GQ) + 2 * r + par_i;
+                const int f = 8 * (g / GQ) + 4 * hh + r;
+                float yi, l;
+                rqs_table_fast<false, KB>(p, st[c * 64], tabs + f * TABW, yi, l);
+                st[c * 64] = yi;
+                ld += l;
+            }
         }
     };
     // The exact-fp32 MFMA shares the vector ALU (tools/ubench/overlap.py): there is nothing to hide the epilogue
@@ -770,13 +814,19 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
         // (42 (j + 1) + 15) / 16 - 1: 3, 6, 8, 11, 14, 16, 19, 21 row-blocks.  The start offsets 42 j mod 16 all differ, so the eight
         // bodies are distinct (static unroll); a pair's last row-block holds up to 14 values of the NEXT pair and is carried
         // along.  Narrow layers leave after their ngrp pairs (wave-uniform).
+        // The carry is a matter of NAMES, not of a copy: four accumulator sets take the roles (carried, new 0, new 1, new 2) in
+        // rotation -- the set a body fills last is the one the next body is handed as its carried set (a copy was 8 v_mov_b64 per
+        // body).
         const float *bfin = small + lay.off_bias_compact() + hh * 16;
-        f32x16 C = {};      // a pair's last row-block: its tail belongs to the next pair
-        auto pair = [&](auto jc) __attribute__((always_inline)) {      // (not inlined, its captures go through memory)
+        f32x16 E0, E1, E2, E3;
+        // C: the previous pair's last row-block (its tail belongs to this pair; pair 0 reads none of it); A2: filled by the pairs
+        // with three new row-blocks only
+        auto pair = [&](auto jc, const f32x16 &C, f32x16 &A0, f32x16 &A1, f32x16 &A2) __attribute__((always_inline)) {      // (not inlined, its captures go through memory)
             constexpr int J = decltype(jc)::value;
             constexpr int S0 = 42 * J, RN = (S0 + 15) / 16, RE = (S0 + 42 + 15) / 16, NNEW = RE - RN;   // new row-blocks [RN, RE)
             static_assert(NNEW == 2 || NNEW == 3, "row-blocks per pair");
-            f32x16 A0 = load_bias16(bfin + RN * 32), A1 = load_bias16(bfin + (RN + 1) * 32), A2 = A1;
+            A0 = load_bias16(bfin + RN * 32);
+            A1 = load_bias16(bfin + (RN + 1) * 32);
             mm128<false, HB, LA>(acquire(), lane, A0, H0, H1, H2, H3);
             mm128<false, HB, LA>(acquire(), lane, A1, H0, H1, H2, H3);
             if constexpr (NNEW == 3) {
@@ -797,7 +847,6 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
                 p0[v] = zero ? 0.0f : val(S0 + c);
                 p1[v] = zero ? 0.0f : val(S0 + 21 + c);
             }
-            C = NNEW == 3 ? A2 : A1;
             const int s0 = 8 * (J / 2) + 4 * (J % 2) + par_t, s1 = s0 + 2;
             float y0, y1, l0, l1;
             rqs_regs2<DIR == 1, KB, true>(p, st[s0 * 64], st[s1 * 64], p0, p1, y0, y1, l0, l1);
@@ -807,14 +856,29 @@ rqs_fused_kernel(const float *__restrict__ x, float *__restrict__ y, float *__re
             ld += l1;
             if (DIR == 0) uncond_group(J);
         };
-        pair(std::integral_constant<int, 0>{});
-        if (ngrp > 1) pair(std::integral_constant<int, 1>{});
-        if (ngrp > 2) pair(std::integral_constant<int, 2>{});
-        if (ngrp > 3) pair(std::integral_constant<int, 3>{});
-        if (ngrp > 4) pair(std::integral_constant<int, 4>{});
-        if (ngrp > 5) pair(std::integral_constant<int, 5>{});
-        if (ngrp > 6) pair(std::integral_constant<int, 6>{});
-        if (ngrp > 7) pair(std::integral_constant<int, 7>{});
+        // new row-blocks per pair: 3 3 2 3 3 2 3 2; the carried set of each call is the last set the call before it filled
+        pair(std::integral_constant<int, 0>{}, E0, E1, E2, E3);
+        // (the early exits are NESTED: a pair runs only behind the one before it, so no set has two possible sources at a join --
+        // as a flat sequence of ifs the joins cost 11 spilled registers in the benchmark's instantiation)
+        if (ngrp > 1) {
+            pair(std::integral_constant<int, 1>{}, E3, E0, E1, E2);
+            if (ngrp > 2) {
+                pair(std::integral_constant<int, 2>{}, E2, E3, E0, E1);
+                if (ngrp > 3) {
+                    pair(std::integral_constant<int, 3>{}, E0, E1, E2, E3);
+                    if (ngrp > 4) {
+                        pair(std::integral_constant<int, 4>{}, E3, E0, E1, E2);
+                        if (ngrp > 5) {
+                            pair(std::integral_constant<int, 5>{}, E2, E3, E0, E1);
+                            if (ngrp > 6) {
+                                pair(std::integral_constant<int, 6>{}, E0, E1, E2, E3);
+                                if (ngrp > 7) pair(std::integral_constant<int, 7>{}, E3, E0, E1, E2);
+                            }
+                        }
+                    }
+                }
+            }
+        }
     } else
     for (int g = 0; g < ngrp; ++g) {   // (up to) KB groups of 3 row-blocks
         const float *bsrc = small + lay.off_bias_final() + (g * 3) * 32 + hh * 16;
