@@ -1289,6 +1289,50 @@ int nf_rows_block(const void *in, int64_t ldi, const void *M1, int64_t ldw1, int
 int nf_squeeze(const void *z, void *y, int64_t B, int C, int H, int W, int direction, int dtype,
                nf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Runs of Planar / Radial flows as one launch (csrc/rank1_chain.hip), float32.
+ * Replaces normflows/flows/planar.py:51-64 (Planar.forward), :66-81 (Planar.inverse, leaky_relu) and
+ * normflows/flows/radial.py:37-46 (Radial.forward) for K consecutive layers on z (B, d), d = prod(shape) <= 128, K <= 64.
+ *
+ * P (K, 2 d + 4): one record per layer, [kind, s0, s1, s2, vecA[d], vecB[d]].  The constraints (planar.py:55-56, radial.py:38)
+ * are applied by the caller; the kernels read effective parameters only:
+ *
+ *   field   Planar                      Radial
+ *   kind    0 (tanh) or 1 (leaky)       2
+ *   s0      b                           a = |alpha|
+ *   s1      w . u_hat                   beta' = log(1 + exp(beta)) - |alpha|
+ *   s2      slope (0.2)                 d - 1
+ *   vecA    w                           z_0
+ *   vecB    u_hat                       unused, zero
+ *
+ * direction 0: records 0 .. K - 1 forward.  direction 1: records K - 1 .. 0 inverted; only kind 1 has an inverse.  P lives in
+ * device memory, so the kinds cannot be checked here without a synchronising copy: the caller checks them (ops.rank1_chain
+ * raises ValueError before any launch); a kind 0 record met in direction 1 yields NaN rows, never a fault.
+ *
+ * nf_rank1_rows(d): rows per 256-lane workgroup: 256 for d <= 16 (lane = row), 16 for 16 < d <= 128 (16 lanes per row);
+ *   NF_ENOTSUP for d outside 1..128.  The grid is min(row tiles, nf_persistent_workgroups()).
+ * nf_rank1_chain: y (B, d); logdet (B) combined according to acc (NF_LD_WRITE / _ADD / _SUB) as in nf_realnvp_chain.
+ * nf_rank1_chain_train_fwd: logdet WRITTEN; save (K, B): save[q, r] = Planar's lin / Radial's r of the q-th EXECUTED record.
+ * nf_rank1_chain_bwd: walks the records backwards from the OUTPUT y, rebuilding every record's input from its output and the
+ *   saved scalar.  gy (B, d) / gld (B): cotangents (NULL = zeros); gz (B, d) or NULL (not wanted).  need_gP != 0: gP (K, 2 d + 4)
+ *   = the gradient of P (kind, s2 and a Radial record's vecB: 0), through slabs (nf_rank1_train_scratch_floats floats: one slab per
+ *   wave, written by that wave alone) and a second launch that sums them in a fixed order.  No atomics: bit-identical from run to
+ *   run.  need_gP == 0: one launch, slabs and gP may be NULL.
+ * Returns NF_ENOTSUP for d outside 1..128, NF_ERANGE for K > 64, NF_EINVAL for K < 1, B < 0, a direction other than 0 / 1 or an
+ * unknown acc, NF_EFAULT for a NULL required pointer when B > 0.  B == 0 returns NF_OK without reading any pointer.
+ */
+int nf_rank1_rows(int d);
+int64_t nf_rank1_train_scratch_floats(int64_t B, int d, int K);
+/* Alignment: element type (every access is a 4-byte one). */
+int nf_rank1_chain(const void *z, void *y, void *logdet, const void *P, int64_t B, int d, int K, int direction, int acc,
+                   nf_stream_t stream);
+/* Alignment: element type. */
+int nf_rank1_chain_train_fwd(const void *z, void *y, void *logdet, void *save, const void *P, int64_t B, int d, int K,
+                             int direction, nf_stream_t stream);
+/* Alignment: element type. */
+int nf_rank1_chain_bwd(const void *y, const void *save, const void *gy, const void *gld, void *gz, const void *P, void *slabs,
+                       void *gP, int64_t B, int d, int K, int direction, int need_gP, nf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1482,3 +1482,25 @@ class RealNVPChainFn(torch.autograd.Function):
                                           ctx.needs_input_grad[0])
         return (gz, None, None) + tuple(realnvp_pack.carve(st, grads, k) if need and st["sides"][k][1] is not None else None
                                         for k, need in enumerate(needs))
+
+
+class Rank1ChainFn(torch.autograd.Function):
+    """A run of Planar / Radial layers (planar.py:51-81, radial.py:37-46) as one forward and one backward launch
+    (csrc/rank1_chain.hip).  `P` = flows/rank1_pack.pack of the run, built from the live parameters by differentiable torch
+    operations: the backward returns gP and torch's autograd carries it on to the leaves.  Saved: the OUTPUT y and one scalar per
+    record and row; the backward rebuilds every record's input from them.  Returns (y, per-row log-det)."""
+
+    @staticmethod
+    def forward(ctx, z, P, kinds, direction):
+        y, ld, save = ops.rank1_chain_train_fwd(z, P.detach(), kinds, direction)
+        ctx.save_for_backward(y, save, P)
+        ctx.kinds, ctx.direction = kinds, direction
+        ctx.set_materialize_grads(False)
+        return y, ld
+
+    @staticmethod
+    @once_differentiable          # (the backward is a set of kernels, not a differentiable graph: double backward raises)
+    def backward(ctx, gy, gld):
+        y, save, P = ctx.saved_tensors
+        gz, gP = ops.rank1_chain_bwd(y, save, gy, gld, P, ctx.kinds, ctx.direction, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
+        return gz, gP, None, None

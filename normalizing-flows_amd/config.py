@@ -464,6 +464,22 @@ def set_affine_wide_train(mode=True, capture_min_batch=None):
         affine_wide_train_capture_min_batch = int(capture_min_batch)
 
 
+# Runs of Planar / Radial layers (exact types, float32 CUDA inputs of <= 128 elements per row, <= 64 layers per launch) on the rank-1
+# chain kernels (csrc/rank1_chain.hip): ONE launch at inference (nf_rank1_chain), one forward and one backward launch under
+# autograd (autograd.Rank1ChainFn), the u- and beta-constraints computed on the stacked parameters in front of them
+# (flows/rank1_pack.py); False = every layer's torch formulas, the reference's arithmetic (A/B runs, differential tests).  The
+# Function is once-differentiable: inside higher_order_gradients() the torch formulas run.
+# Default on: eager, the kernels' median lies below the formulas' minimum for every measured model, leg and batch size; replayed from
+# a captured graph they are not slower at any swept size either (1 024 .. 65 536 rows), so there is no batch-size gate for recorded
+# passes (profiles/rank1_bench.json: `default_on_criterion`, `graph_not_slower_from`; tools/rank1_bench.py).
+rank1_chain = True
+
+
+def set_rank1_chain(mode=True):
+    global rank1_chain
+    rank1_chain = bool(mode)
+
+
 # Debug mode of the element-wise spline API (utils.splines): after every call a check launch (nf_rqs_spline_check)
 # sets device-side flags and the shim reads them back -- a host synchronisation per call, which is why it is off by default -- and
 # raises what the reference raises: AssertionError for a negative discriminant in the inverse direction (utils/splines.py:181),

@@ -41,6 +41,8 @@ def invalidate_caches(module):
         if hasattr(m, "refresh_graphs"):
             m.refresh_graphs()
     _realnvp_cache.clear()
+    from .flows import rank1_pack
+    rank1_pack._rank1_cache.clear()
 
 
 def _pair_signature(crqs):
@@ -313,10 +315,24 @@ def _row_wise(f):
     from .flows.affine import AffineConstFlow
     from .flows.mixing import Permute
     from .flows.normalization import ActNorm
+    from .flows.planar import Planar
+    from .flows.radial import Radial
     t = type(f)
-    if t in (CoupledRationalQuadraticSpline, LULinearPermute, Permute, AffineConstFlow):
+    if t in (CoupledRationalQuadraticSpline, LULinearPermute, Permute, AffineConstFlow, Planar, Radial):
         return True
     return t is ActNorm and f.initialised()
+
+
+def _rank1_run_end(flows, order, k):
+    """The position behind the run of Planar / Radial layers (exact types: a subclass goes layer by layer) that starts at position k
+    of the processing order, cut after rank1_pack.MAX_RECORDS layers (k itself: no such layer there)."""
+    from .flows import rank1_pack
+    from .flows.planar import Planar
+    from .flows.radial import Radial
+    k2 = k
+    while k2 < len(order) and k2 - k < rank1_pack.MAX_RECORDS and type(flows[order[k2]]) in (Planar, Radial):
+        k2 += 1
+    return k2
 
 
 def run_chain(flows, z, inverse, ld, acc):
@@ -376,6 +392,18 @@ def _run_chain_impl(flows, z, inverse, ld, acc):
             z = _run_realnvp([flows[q] for q in idx], z, inverse, ld, acc)
             k = k2
             continue
+        k2 = _rank1_run_end(flows, order, k)
+        if k2 > k:        # a run of Planar / Radial layers (one already counts): one launch (csrc/rank1_chain.hip)
+            from .flows import rank1_pack
+            run = [flows[q] for q in sorted(order[k:k2])]
+            if rank1_pack.eligible(run, z, False):
+                if inverse and not rank1_pack.eligible(run, z, True):
+                    # a tanh Planar or a Radial layer in the run: the reference's error, before anything is launched
+                    raise NotImplementedError("This flow has no algebraic inverse.")
+                z = flush(z)
+                z = rank1_pack.run(run, z, inverse, ld, acc)
+                k = k2
+                continue
         pair = None
         if k + 1 < n:
             j = order[k + 1]
@@ -423,6 +451,8 @@ def _packed_blobs(owner):
                 if k.endswith("_cache"):
                     _cached_tensors(v, out)
     _cached_tensors(list(_realnvp_cache.values()), out)
+    from .flows import rank1_pack
+    _cached_tensors(list(rank1_pack._rank1_cache.values()), out)
     return out
 
 

@@ -10,3 +10,5 @@ from .autoregressive import (Autoregressive, MaskedAffineAutoregressive,
                              MaskedPiecewiseRationalQuadraticAutoregressive, AutoregressiveRationalQuadraticSpline,
                              CircularAutoregressiveRationalQuadraticSpline)
 from .periodic import PeriodicWrap, PeriodicShift
+from .planar import Planar
+from .radial import Radial

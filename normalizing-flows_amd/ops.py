@@ -1938,3 +1938,69 @@ def realnvp_chain_bwd(save, gy, gld, blob, d, hmax, act, direction, wmask, want_
     L.call("nf_realnvp_chain_bwd", ptr(save), _cptr(gy), _cptr(gld), ptr(gz), ptr(blob), ptr(slabs), ptr(grads), B, d, hmax, act,
            nblob, direction, wmask, L.stream())
     return gz, grads
+
+
+def rank1_rows(d):
+    """Rows per workgroup of the rank-1 chain kernels (nf_rank1_rows): 256 for d <= 16, 16 up to d = 128; 0 = d is not taken."""
+    rows = L.query("nf_rank1_rows", int(d))
+    if rows == L.ENOTSUP:
+        return 0
+    if rows < 0:
+        L.check(rows, "nf_rank1_rows")
+    return rows
+
+
+def _rank1_shape(entry, z, P, kinds, direction):
+    """(B, d, K) of a rank-1 chain call after its operand checks: z (B, d) contiguous, P (K, 2 d + 4) (flows/rank1_pack.py), `kinds`
+    = the record kinds, known on the host; in direction 1 every record must be leaky Planar (kind 1): ValueError before any launch."""
+    if z.dim() != 2 or P.dim() != 2 or not z.is_contiguous() or not P.is_contiguous():
+        raise ValueError("%s: z (B, d) and P (K, 2 d + 4) must be contiguous matrices" % entry)
+    B, d = z.shape
+    K = P.shape[0]
+    L.check_count(entry, "P", P, K * (2 * d + 4), "K (2 d + 4)")
+    if len(kinds) != K or any(k not in (0, 1, 2) for k in kinds):
+        raise ValueError("%s: %d record kinds %r for K = %d records" % (entry, len(kinds), tuple(kinds), K))
+    if direction not in (0, 1):
+        raise ValueError("%s: direction must be 0 or 1" % entry)
+    if direction == 1 and any(k != 1 for k in kinds):
+        raise ValueError("%s: direction 1 takes leaky Planar records (kind 1) only, got kinds %r" % (entry, tuple(kinds)))
+    return B, d, K
+
+
+def rank1_chain(z, P, kinds, direction, logdet=None, acc=None):
+    """A run of Planar / Radial layers in one launch (nf_rank1_chain): (y, logdet); logdet combined by `acc` when given."""
+    L.require_device(z, P, logdet, dtype=torch.float32)
+    B, d, K = _rank1_shape("rank1_chain", z, P, kinds, direction)
+    y = torch.empty_like(z)
+    logdet, acc = _ld_buffer(logdet, acc, B, z)
+    L.check_count("rank1_chain", "logdet", logdet, B, "B")
+    L.call("nf_rank1_chain", ptr(z), ptr(y), ptr(logdet), ptr(P), B, d, K, direction, acc, L.stream())
+    return y, logdet
+
+
+def rank1_chain_train_fwd(z, P, kinds, direction):
+    """nf_rank1_chain_train_fwd: (y, per-row log-det, save (K, B) = every executed record's lin / r)."""
+    L.require_device(z, P, dtype=torch.float32)
+    B, d, K = _rank1_shape("rank1_chain_train_fwd", z, P, kinds, direction)
+    y = torch.empty_like(z)
+    logdet = torch.empty(B, dtype=z.dtype, device=z.device)
+    save = torch.empty(K, B, dtype=z.dtype, device=z.device)
+    L.call("nf_rank1_chain_train_fwd", ptr(z), ptr(y), ptr(logdet), ptr(save), ptr(P), B, d, K, direction, L.stream())
+    return y, logdet, save
+
+
+def rank1_chain_bwd(y, save, gy, gld, P, kinds, direction, need_gP, want_gz):
+    """nf_rank1_chain_bwd: (gz or None, gP (K, 2 d + 4) or None when not need_gP).  gy / gld may be None (zeros)."""
+    L.require_device(y, save, gy, gld, P, dtype=torch.float32)
+    B, d, K = _rank1_shape("rank1_chain_bwd", y, P, kinds, direction)
+    L.check_count("rank1_chain_bwd", "save", save, K * B, "K B")
+    L.check_count("rank1_chain_bwd", "gy", gy, B * d, "B d")
+    L.check_count("rank1_chain_bwd", "gld", gld, B, "B")
+    gz = torch.empty_like(y) if want_gz else None
+    slabs = gP = None
+    if need_gP:
+        slabs = torch.empty(L.size("nf_rank1_train_scratch_floats", B, d, K), dtype=y.dtype, device=y.device)
+        gP = torch.empty_like(P)
+    L.call("nf_rank1_chain_bwd", ptr(y), ptr(save.contiguous()), _cptr(gy), _cptr(gld), ptr(gz), ptr(P), ptr(slabs), ptr(gP), B, d, K,
+           direction, 1 if need_gP else 0, L.stream())
+    return gz, gP
