@@ -1333,6 +1333,45 @@ int nf_rank1_chain_train_fwd(const void *z, void *y, void *logdet, void *save, c
 int nf_rank1_chain_bwd(const void *y, const void *save, const void *gy, const void *gld, void *gz, const void *P, void *slabs,
                        void *gP, int64_t B, int d, int K, int direction, int need_gP, nf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Residual flows x + g(x) on 2-D rows, g a LipschitzMLP (csrc/lipmlp.hip), float32.
+ * Replaces normflows/flows/residual.py:118-124 (iResBlock.forward), :133-142 (one step of _inverse_fixed_point and its stop test)
+ * and :148-161 (the brute-force branch of _logdetgrad: g(x), the 2 x 2 Jacobian of g by three autograd passes, log|det(I + J)|) with
+ * normflows/nets/lipschitz.py:66-67 (LipschitzMLP.forward), :272-274 (InducedNormLinear.forward) and :647-648 (Swish.forward), and,
+ * between Residual layers, normflows/flows/affine/coupling.py:38-54 (AffineConstFlow / ActNorm), for K consecutive layers on z (B, 2).
+ *
+ * blob (flows/lipmlp_pack.py): K headers of 16 floats in the order the layers are executed, then one weight block per Residual record,
+ * nf_lipmlp_blob_floats(K, nres, hp) floats in all, hp = nf_lipmlp_width(widest hidden layer) in {32, 64, 128}; widths are zero-padded.
+ *
+ *   header   [0] kind: 0 Residual, 1 affine forward y = z e + t, 2 affine inverse y = (z - t) e
+ *            [1] number of hidden (hp x hp) products, 0 .. 2 (a network with 1 .. 3 hidden layers)
+ *            [2 .. 5] softplus(beta) of the Swish in front of linear layer 0 .. 3
+ *            [6, 7] e = exp(s) (kind 1) or exp(-s) (kind 2)   [8, 9] t   [10] the affine record's log-det, +-sum(s)
+ *            [11] index of the record's weight block          [12 .. 15] zero
+ *   block    W_0^T (2, hp) | b_0 (hp) | 2 x [W_m^T (hp in, hp out) | b_m (hp)] | W_last (2, hp) | b_last (2) | 2 zeros
+ *            = 2 hp^2 + 7 hp + 4 floats; every W is the EFFECTIVE weight W / max(1, (u . W v) / coeff) (lipschitz.py:264-270).
+ *
+ * nf_lipmlp_rows(hp): rows per 256-lane workgroup, 4096 / hp; the grid is min(row tiles, nf_persistent_workgroups()).
+ * nf_lipmlp_chain: every Residual record in its density direction x -> x + g(x); y (B, 2); logdet (B) = the sum of the records'
+ *   log-dets (Residual: log|(1 + J00)(1 + J11) - J01 J10|) combined according to acc (NF_LD_WRITE / _ADD / _SUB).
+ * nf_lipmlp_apply: ONE network (K = 1, a Residual header): mode 0: out = x + g(x); mode 1: out = yin - g(x), and *count (int32,
+ *   device) is increased by the number of elements with !((out - x)^2 / (atol + |yin| rtol) < 1): the caller zeroes it, reads it
+ *   back and stops at 0 (residual.py:137).  An ordinary vector atomic per wave that has something to add.
+ * Returns NF_ENOTSUP for hp outside {32, 64, 128}, NF_ERANGE for K > 32, NF_EINVAL for K < 1, B < 0, nres outside 1 .. K, nblob other
+ * than nf_lipmlp_blob_floats(K, nres, hp), an unknown acc / mode or negative or all-zero tolerances,
+ * NF_EFAULT for a NULL required pointer when B > 0.  B == 0 returns NF_OK without reading any pointer.  The header's kinds and indices
+ * live in device memory: an index outside 0 .. nres - 1 is clamped, never followed.
+ */
+int nf_lipmlp_width(int hmax);
+int nf_lipmlp_rows(int hp);
+int64_t nf_lipmlp_blob_floats(int K, int nres, int hp);
+/* Alignment: element type; a blob off a 16-byte boundary is read by 4-byte loads instead of 16-byte ones (same arithmetic). */
+int nf_lipmlp_chain(const void *z, void *y, void *logdet, const void *blob, int64_t nblob, int64_t B, int hp, int K, int nres, int acc,
+                    nf_stream_t stream);
+/* Alignment: element type; a blob off a 16-byte boundary is read by 4-byte loads instead of 16-byte ones (same arithmetic). */
+int nf_lipmlp_apply(const void *x, const void *yin, void *out, void *count, const void *blob, int64_t nblob, int64_t B, int hp, int mode,
+                    double atol, double rtol, nf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,9 @@ _TABLE = {
     "nets.mlp": ("nets", ["MLP"]),
     "nets.cnn": ("nets", ["ConvNet2d"]),
     "nets.made": ("nets", ["MaskedLinear", "MaskedFeedforwardBlock", "MaskedResidualBlock", "MADE"]),
+    "nets.lipschitz": ("nets", ["LipschitzMLP", "InducedNormLinear", "Swish"]),
+    "flows.residual": ("flows.residual", ["Residual", "iResBlock"]),
+    "utils.optim": ("utils.optim", ["set_requires_grad", "clear_grad", "update_lipschitz"]),
     "distributions.base": ("distributions", ["BaseDistribution", "DiagGaussian", "ConditionalDiagGaussian", "ClassCondDiagGaussian", "GlowBase", "UniformGaussian"]),
 }
 

@@ -480,6 +480,24 @@ def set_rank1_chain(mode=True):
     rank1_chain = bool(mode)
 
 
+# Residual flows on 2-D rows (exact type, a LipschitzMLP of 1 .. 3 hidden layers of width <= 128, `brute_force or not training`, CUDA
+# float32, no gradient needed) on the kernels of csrc/lipmlp.hip: the density direction of a maximal run of [Residual | initialised
+# ActNorm | AffineConstFlow] layers with at least one Residual as ONE launch (nf_lipmlp_chain; value, exact 2 x 2 Jacobian by
+# forward-mode tangents and log|det| per Residual record), the fixed-point direction as one launch and one read-back per iteration
+# (nf_lipmlp_apply) and one Jacobian launch at the point found; effective weights packed in front of them with torch
+# (flows/lipmlp_pack.py).  False = the torch formulas, the reference's arithmetic (A/B runs, differential tests).
+# Default on: eager, the kernels' median lies below the formulas' minimum in every measured case (`log_prob` of the 16-layer example model
+# at 1 024 and 65 536 rows, `sample` at 1 024 rows); replayed from a captured graph they are not slower at any swept size either
+# (1 024 .. 65 536 rows), so there is no batch-size gate for recorded passes (profiles/residual_bench.json: `default_on_criterion`,
+# `graph_not_slower_from`; tools/residual_bench.py).
+residual_chain = True
+
+
+def set_residual_chain(mode=True):
+    global residual_chain
+    residual_chain = bool(mode)
+
+
 # Debug mode of the element-wise spline API (utils.splines): after every call a check launch (nf_rqs_spline_check)
 # sets device-side flags and the shim reads them back -- a host synchronisation per call, which is why it is off by default -- and
 # raises what the reference raises: AssertionError for a negative discriminant in the inverse direction (utils/splines.py:181),

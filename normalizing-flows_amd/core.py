@@ -43,6 +43,8 @@ def invalidate_caches(module):
     _realnvp_cache.clear()
     from .flows import rank1_pack
     rank1_pack._rank1_cache.clear()
+    from .flows import lipmlp_pack
+    lipmlp_pack._lipmlp_cache.clear()
 
 
 def _pair_signature(crqs):
@@ -317,8 +319,9 @@ def _row_wise(f):
     from .flows.normalization import ActNorm
     from .flows.planar import Planar
     from .flows.radial import Radial
+    from .flows.residual import Residual
     t = type(f)
-    if t in (CoupledRationalQuadraticSpline, LULinearPermute, Permute, AffineConstFlow, Planar, Radial):
+    if t in (CoupledRationalQuadraticSpline, LULinearPermute, Permute, AffineConstFlow, Planar, Radial, Residual):
         return True
     return t is ActNorm and f.initialised()
 
@@ -332,6 +335,26 @@ def _rank1_run_end(flows, order, k):
     k2 = k
     while k2 < len(order) and k2 - k < rank1_pack.MAX_RECORDS and type(flows[order[k2]]) in (Planar, Radial):
         k2 += 1
+    return k2
+
+
+def _residual_run_end(flows, order, k, z, inverse):
+    """The position behind the run of [Residual | initialised ActNorm | AffineConstFlow] layers (flows/lipmlp_pack.member) that
+    starts at position k of the processing order and that the residual-flow kernels take as one launch: it holds at least one
+    Residual, this pass is the density direction of all of them (inverse for reverse=True), and it is cut after
+    lipmlp_pack.MAX_RECORDS layers (k itself: no such run there)."""
+    from .flows import lipmlp_pack
+    k2 = k
+    found = False
+    while k2 < len(order) and k2 - k < lipmlp_pack.MAX_RECORDS and lipmlp_pack.member(flows[order[k2]]):
+        f = flows[order[k2]]
+        if lipmlp_pack.residual_ok(f):
+            if bool(f.reverse) != bool(inverse):
+                break
+            found = True
+        k2 += 1
+    if not found or not lipmlp_pack.eligible([flows[q] for q in order[k:k2]], z):
+        return k
     return k2
 
 
@@ -371,6 +394,7 @@ def _run_chain_impl(flows, z, inverse, ld, acc):
         rn_train = all(f_.initialised() for f_ in flows if isinstance(f_, ActNorm))
     if rn_train and z.shape[0] < _config.realnvp_train_capture_min_batch:
         rn_train = not torch.cuda.is_current_stream_capturing()      # (replayed, small batches are faster layer by layer)
+    res_ok = _config.residual_chain and z.dim() == 2 and z.shape[1] == 2 and z.is_cuda and z.dtype == torch.float32
     while k < n:
         i = order[k]
         f = flows[i]
@@ -404,6 +428,13 @@ def _run_chain_impl(flows, z, inverse, ld, acc):
                 z = rank1_pack.run(run, z, inverse, ld, acc)
                 k = k2
                 continue
+        k2 = _residual_run_end(flows, order, k, z, inverse) if res_ok else k
+        if k2 > k:        # a run with a Residual layer in its density direction: one launch (csrc/lipmlp.hip)
+            from .flows import lipmlp_pack
+            z = flush(z)
+            z = lipmlp_pack.run_density([flows[q] for q in order[k:k2]], z, ld, acc, inverse)
+            k = k2
+            continue
         pair = None
         if k + 1 < n:
             j = order[k + 1]
@@ -453,6 +484,8 @@ def _packed_blobs(owner):
     _cached_tensors(list(_realnvp_cache.values()), out)
     from .flows import rank1_pack
     _cached_tensors(list(rank1_pack._rank1_cache.values()), out)
+    from .flows import lipmlp_pack
+    _cached_tensors(list(lipmlp_pack._lipmlp_cache.values()), out)
     return out
 
 

@@ -12,3 +12,4 @@ from .autoregressive import (Autoregressive, MaskedAffineAutoregressive,
 from .periodic import PeriodicWrap, PeriodicShift
 from .planar import Planar
 from .radial import Radial
+from .residual import Residual

@@ -6,6 +6,8 @@ state_dict keys.  These modules are the MFMA-shaped part of the path.  `forward`
 GEMMs / convolutions through torch (rocBLAS / hipBLASLt / MIOpen); the NSF coupling layer bypasses
 ResidualNet.forward and feeds the same weights to the hand-written fused MFMA kernel when the shape allows.
 """
+import math
+
 import torch
 from . import _keys
 from torch import nn
@@ -751,3 +753,129 @@ class MADE(nn.Module):
         for block in self.blocks:
             outputs = block(outputs, context)
         return self.final_layer(outputs)
+
+
+# ---- Lipschitz-bounded networks of the residual flows (normflows/nets/lipschitz.py:14-67, :132-292, :642-648) ------------------------
+class Swish(nn.Module):
+    """x sigmoid(softplus(beta) x) / 1.1 with a learnable beta (0.5): the 1.1 keeps the activation's own slope below 1."""
+
+    def __init__(self):
+        super().__init__()
+        self.beta = nn.Parameter(torch.tensor([0.5]))
+
+    def forward(self, x):
+        return x * torch.sigmoid(x * F.softplus(self.beta)) / 1.1
+
+
+def _unit(x, out=None):
+    """x / max(|x|_2, 1e-12), into `out` when given (the power iteration updates the buffers u, v in place)."""
+    return F.normalize(x, p=2, dim=0, out=out)
+
+
+class InducedNormLinear(nn.Module):
+    """Linear layer whose weight is divided by max(1, sigma / coeff), sigma = u . W v the spectral-norm estimate of a power iteration
+    kept in the buffers u (out), v (in): Lipschitz constant <= coeff once u, v have converged.  Only the 2 -> 2 induced norm
+    (domain = codomain = 2, what LipschitzMLP builds) exists here; parameter / buffer names, shapes and registration order, and the
+    order of the seeded draws (weight, bias, u, v, then 200 iterations) are the reference's."""
+
+    def __init__(self, in_features, out_features, bias=True, coeff=0.97, domain=2, codomain=2, n_iterations=None, atol=None,
+                 rtol=None, zero_init=False, **unused_kwargs):
+        super().__init__()
+        if torch.is_tensor(domain) or torch.is_tensor(codomain) or domain != 2 or codomain != 2:
+            raise NotImplementedError("InducedNormLinear: only the induced 2 -> 2 norm (domain = codomain = 2) is implemented, "
+                                      "got domain = %r, codomain = %r" % (domain, codomain))
+        self.in_features, self.out_features = in_features, out_features
+        self.coeff, self.n_iterations, self.atol, self.rtol = coeff, n_iterations, atol, rtol
+        self.domain, self.codomain = domain, codomain
+        self.weight = nn.Parameter(torch.empty(out_features, in_features))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(out_features))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters(zero_init)
+        self.register_buffer("scale", torch.tensor(0.0))
+        self.register_buffer("u", _unit(torch.empty(out_features).normal_(0, 1)))
+        self.register_buffer("v", _unit(torch.empty(in_features).normal_(0, 1)))
+        with torch.no_grad():
+            self.compute_weight(True, n_iterations=200, atol=None, rtol=None)
+
+    def reset_parameters(self, zero_init=False):
+        init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        if zero_init:
+            self.weight.data.div_(1000)         # (an exactly zero weight cannot be normalised)
+        if self.bias is not None:
+            bound = 1 / math.sqrt(self.in_features)
+            init.uniform_(self.bias, -bound, bound)
+
+    def compute_domain_codomain(self):
+        return self.domain, self.codomain
+
+    def compute_one_iter(self):
+        """sigma after one more power iteration; the buffers stay as they are."""
+        weight = self.weight.detach()
+        u = _unit(torch.mv(weight, self.v.detach()))
+        v = _unit(torch.mv(weight.t(), u))
+        return torch.dot(u, torch.mv(weight, v))
+
+    def compute_weight(self, update=True, n_iterations=None, atol=None, rtol=None):
+        """The normalised weight.  update=True first runs the power iteration on the buffers: n_iterations steps, or -- with
+        n_iterations None -- up to 200 steps until u and v move by less than atol + rtol max(.) in the root-mean-square.  `scale`
+        (= sigma) is written on every call."""
+        u, v, weight = self.u, self.v, self.weight
+        if update:
+            n_iterations = self.n_iterations if n_iterations is None else n_iterations
+            atol = self.atol if atol is None else atol
+            rtol = self.rtol if rtol is None else atol      # (the reference's rule: a given rtol is replaced by atol)
+            if n_iterations is None and (atol is None or rtol is None):
+                raise ValueError("Need one of n_iteration or (atol, rtol).")
+            by_tolerance = n_iterations is None
+            with torch.no_grad():
+                for _ in range(200 if by_tolerance else n_iterations):
+                    if by_tolerance:
+                        u0, v0 = u.clone(), v.clone()
+                    u = _unit(torch.mv(weight, v), out=u)
+                    v = _unit(torch.mv(weight.t(), u), out=v)
+                    if by_tolerance:
+                        du = torch.norm(u - u0) / u.nelement() ** 0.5
+                        dv = torch.norm(v - v0) / v.nelement() ** 0.5
+                        if du < atol + rtol * torch.max(u) and dv < atol + rtol * torch.max(v):
+                            break
+                self.v.copy_(v)
+                self.u.copy_(u)
+                u, v = u.clone(), v.clone()
+        sigma = torch.dot(u, torch.mv(weight, v))
+        with torch.no_grad():
+            self.scale.copy_(sigma)
+        return weight / torch.max(torch.ones(1, device=weight.device), sigma / self.coeff)
+
+    def forward(self, input):
+        return F.linear(input, self.compute_weight(update=False), self.bias)
+
+    def extra_repr(self):
+        return ("in_features={}, out_features={}, bias={}, coeff={}, domain={:.2f}, codomain={:.2f}, n_iters={}, atol={}, rtol={}, "
+                "learnable_ord={}".format(self.in_features, self.out_features, self.bias is not None, self.coeff, self.domain,
+                                          self.codomain, self.n_iterations, self.atol, self.rtol, False))
+
+
+class LipschitzMLP(nn.Module):
+    """Sequential(Swish, InducedNormLinear, Swish, InducedNormLinear, ...) over `channels` -- the activation comes FIRST -- with
+    every layer's Lipschitz constant held at lipschitz_const: the g of a residual flow x + g(x)."""
+
+    def __init__(self, channels, lipschitz_const=0.97, max_lipschitz_iter=5, lipschitz_tolerance=None, init_zeros=True):
+        super().__init__()
+        self.n_layers = len(channels) - 1
+        self.channels = channels
+        self.lipschitz_const = lipschitz_const
+        self.max_lipschitz_iter = max_lipschitz_iter
+        self.lipschitz_tolerance = lipschitz_tolerance
+        self.init_zeros = init_zeros
+        layers = []
+        for i in range(self.n_layers):
+            layers.append(Swish())
+            layers.append(InducedNormLinear(channels[i], channels[i + 1], coeff=lipschitz_const, domain=2, codomain=2,
+                                            n_iterations=max_lipschitz_iter, atol=lipschitz_tolerance, rtol=lipschitz_tolerance,
+                                            zero_init=init_zeros and i == self.n_layers - 1))
+        self.net = nn.Sequential(*layers)
+
+    def forward(self, x):
+        return self.net(x)

@@ -2004,3 +2004,53 @@ def rank1_chain_bwd(y, save, gy, gld, P, kinds, direction, need_gP, want_gz):
     L.call("nf_rank1_chain_bwd", ptr(y), ptr(save.contiguous()), _cptr(gy), _cptr(gld), ptr(gz), ptr(P), ptr(slabs), ptr(gP), B, d, K,
            direction, 1 if need_gP else 0, L.stream())
     return gz, gP
+
+
+def lipmlp_width(hmax):
+    """The padded hidden width of the residual-flow kernels for a widest hidden layer `hmax` (nf_lipmlp_width): 32, 64 or 128; 0 =
+    not taken."""
+    hp = L.query("nf_lipmlp_width", int(hmax))
+    if hp == L.ENOTSUP:
+        return 0
+    if hp < 0:
+        L.check(hp, "nf_lipmlp_width")
+    return hp
+
+
+def _lipmlp_rows(entry, blob, K, nres, hp, *rows):
+    """B of a residual-flow call after its operand checks: every row operand a contiguous (B, 2) matrix of one shape, blob a
+    contiguous vector of nf_lipmlp_blob_floats(K, nres, hp) floats (flows/lipmlp_pack.py)."""
+    z = rows[0]
+    if any(t.dim() != 2 or t.shape[1] != 2 or t.shape != z.shape or not t.is_contiguous() for t in rows):
+        raise ValueError("%s: the row operands must be contiguous (B, 2) matrices of one shape" % entry)
+    if blob.dim() != 1 or not blob.is_contiguous():
+        raise ValueError("%s: blob must be a contiguous vector" % entry)
+    L.check_count(entry, "blob", blob, L.size("nf_lipmlp_blob_floats", int(K), int(nres), int(hp)), "K 16 + nres (2 hp^2 + 7 hp + 4)")
+    return z.shape[0]
+
+
+def lipmlp_chain(z, blob, K, nres, hp, logdet=None, acc=None):
+    """A run of [Residual | ActNorm | AffineConstFlow] layers in the Residuals' density direction as one launch (nf_lipmlp_chain):
+    (y, logdet); logdet combined by `acc` when given."""
+    L.require_device(z, blob, logdet, dtype=torch.float32)
+    B = _lipmlp_rows("lipmlp_chain", blob, K, nres, hp, z)
+    y = torch.empty_like(z)
+    logdet, acc = _ld_buffer(logdet, acc, B, z)
+    L.check_count("lipmlp_chain", "logdet", logdet, B, "B")
+    L.call("nf_lipmlp_chain", ptr(z), ptr(y), ptr(logdet), ptr(blob), blob.numel(), B, int(hp), int(K), int(nres), acc, L.stream())
+    return y, logdet
+
+
+def lipmlp_apply(x, y, blob, hp, mode, count=None, atol=1e-5, rtol=1e-5):
+    """One LipschitzMLP g in one launch (nf_lipmlp_apply).  mode 0: x + g(x).  mode 1: the fixed-point step y - g(x); `count` (one
+    int32 on the device, zeroed by the caller) receives the number of elements whose squared step is not below atol + |y| rtol."""
+    L.require_device(x, y, blob, count, dtype=torch.float32)
+    if mode not in (0, 1):
+        raise ValueError("lipmlp_apply: mode must be 0 or 1")
+    B = _lipmlp_rows("lipmlp_apply", blob, 1, 1, hp, *((x,) if mode == 0 else (x, y)))
+    if mode == 1 and (count is None or count.dtype != torch.int32 or count.numel() != 1):
+        raise ValueError("lipmlp_apply: mode 1 needs `count`, one int32 on the device")
+    out = torch.empty_like(x)
+    L.call("nf_lipmlp_apply", ptr(x), ptr(y if mode == 1 else None), ptr(out), ptr(count if mode == 1 else None), ptr(blob),
+           blob.numel(), B, int(hp), mode, float(atol), float(rtol), L.stream())
+    return out

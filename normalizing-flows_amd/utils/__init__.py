@@ -3,3 +3,5 @@ from .eval import bitsPerDim, bitsPerDimDataset
 from .preprocessing import Logit, Jitter, Scale
 from .nn import sum_except_batch, tile
 from . import splines
+from . import optim
+from .optim import clear_grad, set_requires_grad, update_lipschitz
