@@ -1372,6 +1372,60 @@ int nf_lipmlp_chain(const void *z, void *y, void *logdet, const void *blob, int6
 int nf_lipmlp_apply(const void *x, const void *yin, void *out, void *count, const void *blob, int64_t nblob, int64_t B, int hp, int mode,
                     double atol, double rtol, nf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Closed-form 2-D target and prior densities (csrc/density2d.hip), float32: lp (B) = log p(z) of z (B, 2) in one launch and, when
+ * gz (B, 2) is not NULL, d lp / d z in the same launch.
+ * Replaces normflows/distributions/target.py:123-129 (TwoMoons.log_prob), :150-160 (CircularGaussianMixture.log_prob), :189-195
+ * (RingMixture.log_prob) and normflows/distributions/prior.py:140-149 (TwoModes.log_prob), :183-194 (Sinusoidal.log_prob), :226-245
+ * (Sinusoidal_gap.log_prob), :277-296 (Sinusoidal_split.log_prob), :317-327 (Smiley.log_prob), and what PyTorch autograd derives
+ * from them: abs has derivative 0 at 0, the 2-norm and the 4-norm have derivative 0 at the origin.
+ *
+ * rec_host: nrec <= 8 floats in HOST memory, read during the call and passed to the kernel by value; n: the number of modes.
+ *
+ *   kind                         n         rec
+ *   0 TwoModes / TwoMoons        -         loc, 1 / (2 scale), |loc|, 1 / (3 scale), 2 / (3 scale)^2
+ *   1 Sinusoidal                 -         2 pi / period, 1 / scale, (20 scale)^-4
+ *   2 Sinusoidal_gap             -         as kind 1, then 2 / scale^2, w2_amp, w2_mu, w2_scale
+ *   3 Sinusoidal_split           -         as kind 1, then 2 / scale^2, w3_amp, w3_mu, w3_scale
+ *   4 Smiley                     -         loc, 1 / (2 scale), 0.8, 1.2
+ *   5 RingMixture                n_rings   2 / n_rings, 1 / (2 scale^2)
+ *   6 CircularGaussianMixture    n_modes   2 pi / n_modes, 2 pi; dscale: the module's `scale` buffer (one float in DEVICE memory)
+ *
+ * Kinds 5 and 6 sum their modes as a streaming log-sum-exp in registers; kind 6 keeps the mode centres in LDS (n <= 256).
+ * nf_density2d_grid(B): workgroups of 256 rows the launch uses (the rows beyond grid x 256 are reached by the grid-stride loop).
+ * Returns NF_ENOTSUP for an unknown kind, NF_ERANGE for n < 1 or above the kind's limit (256 modes, 65 536 rings), NF_EINVAL for
+ * B < 0 or nrec outside 0..8, NF_EFAULT for a NULL z / lp (or dscale of kind 6) when B > 0.  B == 0 returns NF_OK.
+ */
+int nf_density2d_grid(int64_t B);
+/* Alignment: element type (every access is a 4-byte one). */
+int nf_density2d(const void *z, void *lp, void *gz, int kind, int n, const float *rec_host, int nrec, const void *dscale, int64_t B,
+                 nf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Diagonal Gaussian mixture: log-density and its backward (csrc/gmm.hip), float32.
+ * Replaces normflows/distributions/base.py:645-659 (GaussianMixture.log_prob; :634-641 in forward) and its autograd backward.
+ *
+ * R: one vector of 2 M d + M floats, [loc (M, d) | log_scale (M, d) | logw (M)], logw = log_softmax(weight_scores).
+ *   lp_b = logsumexp_m( -d/2 log 2 pi + logw_m - 1/2 sum_j ((z_bj - loc_mj) e^{-ls_mj})^2 - sum_j ls_mj )
+ * nf_gmm_log_prob: out (B) combined with lp according to acc (NF_LD_WRITE / _ADD / _SUB).
+ * nf_gmm_log_prob_bwd: lp (B) as nf_gmm_log_prob WROTE it, g (B) its cotangent; the responsibilities r_bm = exp(lp_bm - lp_b) are
+ *   recomputed.  gz (B, d) or NULL (not wanted).  want: bit 0 gloc, bit 1 glog_scale, bit 2 glogw; want != 0: gR (2 M d + M) = the
+ *   gradient of R (zero in the sections that are not wanted), through slabs (nf_gmm_scratch_floats floats: one slab per wave,
+ *   written by that wave alone) and a second launch that sums them in a fixed order.  No atomics: bit-identical from run to run.
+ *   want == 0: one launch, slabs and gR may be NULL.
+ * nf_gmm_rows(d): rows per 256-lane workgroup: 256 for d <= 16 (lane = row), 16 for 16 < d <= 128 (16 lanes per row).  The grid is
+ *   min(row tiles, nf_persistent_workgroups()).
+ * Returns NF_ENOTSUP for d outside 1..128, M outside 1..64 or M d > 4096 (R's loc and inverse scales fill 32 KB of LDS), NF_EINVAL for
+ * B < 0, an unknown acc or want outside 0..7, NF_EFAULT for a NULL required pointer when B > 0.  B == 0 returns NF_OK.
+ */
+int nf_gmm_rows(int d);
+int64_t nf_gmm_scratch_floats(int64_t B, int M, int d);
+/* Alignment: element type. */
+int nf_gmm_log_prob(const void *z, const void *R, void *out, int64_t B, int M, int d, int acc, nf_stream_t stream);
+/* Alignment: element type. */
+int nf_gmm_log_prob_bwd(const void *z, const void *R, const void *lp, const void *g, void *gz, void *slabs, void *gR, int64_t B,
+                        int M, int d, int want, nf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

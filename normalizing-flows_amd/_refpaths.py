@@ -9,7 +9,9 @@ they hold no code."""
 import sys
 import types
 
-# reference path (below the package) -> (module of this package that holds the names, names the reference defines there)
+# reference path (below the package) -> (module of this package that holds the names, names the reference defines there); a name
+# written "module:Name" is held by that other module of this package (base.Uniform: `distributions.Uniform` is the encoder's
+# Uniform in the reference, so the base distribution of that name is not an attribute of `distributions` here either)
 _TABLE = {
     "flows.affine.coupling": ("flows.affine", ["AffineConstFlow", "CCAffineConst", "AffineCoupling", "MaskedAffineFlow", "AffineCouplingBlock"]),
     "flows.affine.glow": ("flows.glow", ["GlowBlock"]),
@@ -25,7 +27,10 @@ _TABLE = {
     "nets.lipschitz": ("nets", ["LipschitzMLP", "InducedNormLinear", "Swish"]),
     "flows.residual": ("flows.residual", ["Residual", "iResBlock"]),
     "utils.optim": ("utils.optim", ["set_requires_grad", "clear_grad", "update_lipschitz"]),
-    "distributions.base": ("distributions", ["BaseDistribution", "DiagGaussian", "ConditionalDiagGaussian", "ClassCondDiagGaussian", "GlowBase", "UniformGaussian"]),
+    "distributions.base": ("distributions", ["BaseDistribution", "DiagGaussian", "ConditionalDiagGaussian", "ClassCondDiagGaussian", "GlowBase", "UniformGaussian",
+                                             "GaussianMixture", "dist_mixture:Uniform"]),
+    "distributions.target": ("dist_target", ["Target", "TwoIndependent", "TwoMoons", "CircularGaussianMixture", "RingMixture", "ConditionalDiagGaussian"]),
+    "distributions.prior": ("dist_prior", ["PriorDistribution", "ImagePrior", "TwoModes", "Sinusoidal", "Sinusoidal_gap", "Sinusoidal_split", "Smiley"]),
 }
 
 
@@ -42,8 +47,12 @@ def install(pkg):
         alias = types.ModuleType(full, "alias of the reference's module path normflows.%s (see _refpaths.py)" % path)
         exported = []
         for n in names:
-            if hasattr(holder, n):
-                setattr(alias, n, getattr(holder, n))
+            h = holder
+            if ":" in n:
+                mod, n = n.split(":")
+                h = getattr(pkg, mod)
+            if hasattr(h, n):
+                setattr(alias, n, getattr(h, n))
                 exported.append(n)
         alias.__all__ = exported
         sys.modules[full] = alias

@@ -1504,3 +1504,48 @@ class Rank1ChainFn(torch.autograd.Function):
         y, save, P = ctx.saved_tensors
         gz, gP = ops.rank1_chain_bwd(y, save, gy, gld, P, ctx.kinds, ctx.direction, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
         return gz, gP, None, None
+
+
+class Density2dFn(torch.autograd.Function):
+    """log p(z) of a closed-form 2-D target or prior (csrc/density2d.hip) with its input gradient from the SAME launch: the forward
+    saves d lp / d z (B, 2), the backward is one broadcast multiply with the cotangent.  kind / n / rec / dscale: ops.density2d."""
+
+    @staticmethod
+    def forward(ctx, z, kind, n, rec, dscale):
+        lp, gz = ops.density2d(z, kind, n, rec, dscale, want_grad=True)
+        ctx.save_for_backward(gz)
+        ctx.set_materialize_grads(False)
+        return lp
+
+    @staticmethod
+    @once_differentiable          # (the saved derivative is a kernel's output, not a differentiable graph: double backward raises)
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None, None
+        (gz,) = ctx.saved_tensors
+        return g.unsqueeze(1) * gz, None, None, None, None
+
+
+class GmmLogProbFn(torch.autograd.Function):
+    """GaussianMixture.log_prob (distributions/base.py:645-659) as one forward launch and one backward launch plus a fixed-order slab
+    reduction (csrc/gmm.hip).  `R` = dist_mixture.record of the module, built from the live parameters by differentiable torch
+    operations: the backward returns gR and torch's autograd carries it on to the leaves (the softmax's backward included).  `want`:
+    which sections of gR anybody needs (bit 0 loc, 1 log_scale, 2 weight_scores); 0 = no slab work.  Saved: z, R and lp."""
+
+    @staticmethod
+    def forward(ctx, z, R, M, want):
+        lp = ops.gmm_log_prob(z, R.detach(), M)
+        ctx.save_for_backward(z, R, lp)
+        ctx.M, ctx.want = M, want
+        ctx.set_materialize_grads(False)
+        return lp
+
+    @staticmethod
+    @once_differentiable          # (the backward is a set of kernels, not a differentiable graph: double backward raises)
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None
+        z, R, lp = ctx.saved_tensors
+        want = ctx.want if ctx.needs_input_grad[1] else 0
+        gz, gR = ops.gmm_log_prob_bwd(z, R, ctx.M, lp, g, ctx.needs_input_grad[0], want)
+        return gz, gR, None, None

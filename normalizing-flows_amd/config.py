@@ -480,6 +480,26 @@ def set_rank1_chain(mode=True):
     rank1_chain = bool(mode)
 
 
+# The densities a model is trained against or starts from: the closed-form 2-D targets and priors (TwoMoons, CircularGaussianMixture,
+# RingMixture, TwoModes, Sinusoidal, Sinusoidal_gap, Sinusoidal_split, Smiley: exact types, contiguous float32 CUDA (B, 2) input) as ONE
+# launch that writes log p and, under autograd, d log p / d z (nf_density2d, autograd.Density2dFn), and GaussianMixture.log_prob
+# (exact type, float32 parameters, contiguous float32 CUDA (B, d) input, d <= 128, M <= 64, M d <= 4096) as one forward launch and one
+# backward launch plus a fixed-order slab reduction (nf_gmm_log_prob / _bwd, autograd.GmmLogProbFn; the record is built by torch in
+# dist_mixture.record).  False = the torch formulas, the reference's arithmetic op for op (A/B runs, differential tests).  Both
+# Functions are once-differentiable: inside higher_order_gradients() the torch formulas run.
+# Default OFF.  Measured (tools/target_bench.py, profiles/target_bench.json): eager, the kernels' median lies below the formulas'
+# minimum in 29 of the 30 cases (every density, leg and batch size: 2.0x - 20x; the reverse-KL step of 32 Planar layers at 65 536
+# rows), but not for that step at 1 024 rows, which is host-bound (off 2.78 ms median, 2.11 minimum; on 2.48) -- and the project's
+# rule is default on only when it holds in every case (`default_on_criterion`).  Replayed from a captured graph the step is faster
+# on the kernels at every swept size, 1 024 .. 65 536 rows (`graph_not_slower_from`): no batch-size gate.
+target_density = False
+
+
+def set_target_density(mode=True):
+    global target_density
+    target_density = bool(mode)
+
+
 # Residual flows on 2-D rows (exact type, a LipschitzMLP of 1 .. 3 hidden layers of width <= 128, `brute_force or not training`, CUDA
 # float32, no gradient needed) on the kernels of csrc/lipmlp.hip: the density direction of a maximal run of [Residual | initialised
 # ActNorm | AffineConstFlow] layers with at least one Residual as ONE launch (nf_lipmlp_chain; value, exact 2 x 2 Jacobian by

@@ -327,3 +327,12 @@ class ConditionalDiagGaussian(BaseDistribution):
         B = z.shape[0]
         return ops.diag_gaussian_log_prob_rows(z, mean.expand(B, *mean.shape[1:]).contiguous(),
                                                log_scale.expand(B, *log_scale.shape[1:]).contiguous(), None, 0.0)
+
+
+# The names of the reference's distributions/__init__.py that live in sibling files: the targets (dist_target.py), the priors
+# (dist_prior.py) and the mixture base (dist_mixture.py).  The target-side ConditionalDiagGaussian and base.Uniform are NOT exported
+# here, as there: distributions.target.ConditionalDiagGaussian and distributions.base.Uniform reach them (_refpaths.py).
+from .dist_target import Target, TwoMoons, CircularGaussianMixture, RingMixture, TwoIndependent  # noqa: E402
+from .dist_prior import (PriorDistribution, ImagePrior, TwoModes, Sinusoidal, Sinusoidal_split, Sinusoidal_gap,  # noqa: E402
+                         Smiley)
+from .dist_mixture import GaussianMixture  # noqa: E402

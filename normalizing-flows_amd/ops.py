@@ -2006,6 +2006,71 @@ def rank1_chain_bwd(y, save, gy, gld, P, kinds, direction, need_gP, want_gz):
     return gz, gP
 
 
+def density2d_grid(B):
+    """Workgroups (of 256 rows) of an nf_density2d launch on B rows; rows beyond grid x 256 are reached by its grid-stride loop."""
+    return L.query("nf_density2d_grid", int(B))
+
+
+def density2d(z, kind, n, rec, dscale=None, want_grad=False):
+    """nf_density2d: (lp (B), d lp / d z (B, 2) or None) of a closed-form 2-D density on z (B, 2) in one launch.  kind / n / rec: the
+    table of include/nf_mi355x.h (rec: up to 8 Python floats); dscale: CircularGaussianMixture's `scale` buffer (device)."""
+    L.require_device(z, dscale, dtype=torch.float32)
+    if z.dim() != 2 or z.shape[1] != 2 or not z.is_contiguous():
+        raise ValueError("density2d: z must be a contiguous (B, 2) matrix, got %s" % (tuple(z.shape),))
+    L.check_count("density2d", "dscale", dscale, 1, "one float")
+    B = z.shape[0]
+    lp = torch.empty(B, dtype=z.dtype, device=z.device)
+    gz = torch.empty_like(z) if want_grad else None
+    rec_host = (C.c_float * len(rec))(*rec)
+    L.call("nf_density2d", ptr(z), ptr(lp), ptr(gz), int(kind), int(n), rec_host, len(rec), ptr(dscale), B, L.stream())
+    return lp, gz
+
+
+def gmm_rows(d):
+    """Rows per workgroup of the mixture kernels (nf_gmm_rows): 256 for d <= 16, 16 up to d = 128; 0 = d is not taken."""
+    rows = L.query("nf_gmm_rows", int(d))
+    if rows == L.ENOTSUP:
+        return 0
+    if rows < 0:
+        L.check(rows, "nf_gmm_rows")
+    return rows
+
+
+def _gmm_shape(entry, z, R, M):
+    """(B, d) of a mixture call after its operand checks: z (B, d) contiguous, R a contiguous vector of 2 M d + M floats."""
+    if z.dim() != 2 or R.dim() != 1 or not z.is_contiguous() or not R.is_contiguous():
+        raise ValueError("%s: z (B, d) and R (2 M d + M) must be contiguous" % entry)
+    B, d = z.shape
+    L.check_count(entry, "R", R, 2 * M * d + M, "2 M d + M")
+    return B, d
+
+
+def gmm_log_prob(z, R, M, out=None, acc=None):
+    """nf_gmm_log_prob: log-density (B) of the diagonal mixture with record R; combined into `out` by `acc` when given."""
+    L.require_device(z, R, out, dtype=torch.float32)
+    B, d = _gmm_shape("gmm_log_prob", z, R, M)
+    out, acc = _ld_buffer(out, acc, B, z)
+    L.check_count("gmm_log_prob", "out", out, B, "B")
+    L.call("nf_gmm_log_prob", ptr(z), ptr(R), ptr(out), B, M, d, acc, L.stream())
+    return out
+
+
+def gmm_log_prob_bwd(z, R, M, lp, g, want_gz, want):
+    """nf_gmm_log_prob_bwd: (gz or None, gR (2 M d + M) or None when want == 0).  want: bit 0 loc, 1 log_scale, 2 logw."""
+    L.require_device(z, R, lp, g, dtype=torch.float32)
+    B, d = _gmm_shape("gmm_log_prob_bwd", z, R, M)
+    L.check_count("gmm_log_prob_bwd", "lp", lp, B, "B")
+    L.check_count("gmm_log_prob_bwd", "g", g, B, "B")
+    gz = torch.empty_like(z) if want_gz else None
+    slabs = gR = None
+    if want:
+        slabs = torch.empty(L.size("nf_gmm_scratch_floats", B, M, d), dtype=z.dtype, device=z.device)
+        gR = torch.empty_like(R)
+    L.call("nf_gmm_log_prob_bwd", ptr(z), ptr(R), ptr(lp.contiguous()), ptr(g.contiguous()), ptr(gz), ptr(slabs), ptr(gR), B, M, d,
+           int(want), L.stream())
+    return gz, gR
+
+
 def lipmlp_width(hmax):
     """The padded hidden width of the residual-flow kernels for a widest hidden layer `hmax` (nf_lipmlp_width): 32, 64 or 128; 0 =
     not taken."""
