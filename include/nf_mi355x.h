@@ -1426,6 +1426,52 @@ int nf_gmm_log_prob(const void *z, const void *R, void *out, int64_t B, int M, i
 int nf_gmm_log_prob_bwd(const void *z, const void *R, const void *lp, const void *g, void *gz, void *slabs, void *gR, int64_t B,
                         int M, int d, int want, nf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Stochastic flow layers on (B, 2) batches (csrc/hmc2d.hip), float32: one launch per HamiltonianMonteCarlo transition, one launch
+ * for the `steps` random-walk steps of MetropolisHastings with a DiagGaussianProposal.
+ * Replaces normflows/flows/stochastic.py:27-47 (MetropolisHastings.forward) and :73-108 (HamiltonianMonteCarlo.forward, gradlogP)
+ * with everything they call.  The random numbers are the caller's.
+ *
+ * The target of a launch is w_0 log p_0(z) + w_1 log p_1(z), nterms = 1 or 2 (normflows/distributions/linear_interpolation.py).
+ *   tkind (host, nterms x 2 ints): kind, n of each term -- kinds 0..6 of nf_density2d, or 7: a diagonal Gaussian in 2-D.
+ *   trec (host, nterms x 9 floats): the weight w, then the 8 floats of nf_density2d's record (zero-padded; unused for kind 7).
+ *   a00, a01 / a10, a11: device pointers of term 0 / 1 -- kind 6: aX0 = the `scale` buffer (1 float); kind 7: aX0 = loc (2 floats),
+ *   aX1 = log_scale (2 floats); NULL otherwise.  At most one term of kind 6 per launch (its centres live in LDS).
+ *
+ * nf_hmc2d: z, eps (B, 2) standard-normal noise, u (B) uniforms, log_step_size (2) and log_mass (2) in device memory, steps >= 0
+ *   leapfrog steps, max_abs_grad (0 = no clipping; the clipped gradient drives the dynamics, the Metropolis test and the log-det use
+ *   the densities).  Writes z_out (B, 2), log_det (B) and accept (B floats: 1 accepted, 0 rejected); on a rejected row z_out is z's
+ *   bits and log_det is 0.  Accepts on u < probability (a NaN probability rejects).  side != NULL (training): (B, 8) floats per row,
+ *   d z_new / d log_step_size (2) | d z_new / d log_mass (2) | grad log p at z (2) | grad log p at z_out (2), the last two unclipped;
+ *   the force is a constant to autograd (gradlogP detaches), so the tangents are running scalars per dimension.
+ * nf_hmc2d_bwd: gz_out (B, 2) and gld (B) the cotangents (either may be NULL = zero).  gz (B, 2) or NULL:
+ *   gz = gz_out + gld (grad log p(z) - grad log p(z_out)).  want: bit 0 log_step_size, bit 1 log_mass; want != 0:
+ *   gpar (4) = [g log_step_size | g log_mass] = sum over rows of accept (gz_out - gld grad log p(z_out)) * tangent (zero in the pair
+ *   that is not wanted), through slabs (nf_hmc2d_bwd_scratch_floats floats, one slab per wave) and a second launch that sums them in
+ *   a fixed order.  No atomics: bit-identical from run to run.  want == 0: one launch (none when gz is NULL as well).
+ * nf_mh2d: eps (steps, B, 2), u (steps, B), scale (nscale = 1 or 2 floats in device memory).  Accepts on
+ *   u <= min(exp(log p(z') - log p(z)), 1) with a NaN rejecting.  gside != NULL: (B, 4) floats per row, grad log p at z | at z_out.
+ * nf_*_grid(B): workgroups of 256 rows of the launch (rows beyond grid x 256 are reached by the grid-stride loop).
+ * Returns NF_ENOTSUP for an unknown kind or two terms of kind 6, NF_ERANGE for n outside the kind's limits, NF_EINVAL for B < 0,
+ * steps < 0, nterms outside 1..2, nscale outside 1..2, a negative max_abs_grad or want outside 0..3, NF_EFAULT for a NULL required
+ * pointer when B > 0.  B == 0 returns NF_OK.
+ */
+int nf_hmc2d_grid(int64_t B);
+int nf_mh2d_grid(int64_t B);
+int nf_hmc2d_bwd_grid(int64_t B);
+int64_t nf_hmc2d_bwd_scratch_floats(int64_t B);
+/* Alignment: element type (every access is a 4-byte one). */
+int nf_hmc2d(const void *z, const void *eps, const void *u, const void *log_step_size, const void *log_mass, const int *tkind,
+             const float *trec, const void *a00, const void *a01, const void *a10, const void *a11, int nterms, int steps,
+             double max_abs_grad, void *z_out, void *log_det, void *accept, void *side, int64_t B, nf_stream_t stream);
+/* Alignment: element type. */
+int nf_hmc2d_bwd(const void *gz_out, const void *gld, const void *accept, const void *side, void *gz, void *slabs, void *gpar, int want,
+                 int64_t B, nf_stream_t stream);
+/* Alignment: element type. */
+int nf_mh2d(const void *z, const void *eps, const void *u, const void *scale, int nscale, const int *tkind, const float *trec,
+            const void *a00, const void *a01, const void *a10, const void *a11, int nterms, int steps, void *z_out, void *log_det,
+            void *gside, int64_t B, nf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,8 @@ The on-disk package directory is `normalizing-flows_amd/`; import it as `normflo
 at the repository root).
 """
 from . import _lib, config, ops, nets, flows, distributions, transforms, utils, dp
+from . import sampling
+from .sampling import HAIS
 from .core import NormalizingFlow, ConditionalNormalizingFlow, MultiscaleFlow, invalidate_caches
 from .distributions import DiagGaussian, ConditionalDiagGaussian, ClassCondDiagGaussian, GlowBase, UniformGaussian
 

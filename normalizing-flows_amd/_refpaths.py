@@ -30,6 +30,8 @@ _TABLE = {
     "distributions.base": ("distributions", ["BaseDistribution", "DiagGaussian", "ConditionalDiagGaussian", "ClassCondDiagGaussian", "GlowBase", "UniformGaussian",
                                              "GaussianMixture", "dist_mixture:Uniform"]),
     "distributions.target": ("dist_target", ["Target", "TwoIndependent", "TwoMoons", "CircularGaussianMixture", "RingMixture", "ConditionalDiagGaussian"]),
+    "distributions.mh_proposal": ("dist_mh", ["MHProposal", "DiagGaussianProposal"]),
+    "distributions.linear_interpolation": ("dist_mh", ["LinearInterpolation"]),
     "distributions.prior": ("dist_prior", ["PriorDistribution", "ImagePrior", "TwoModes", "Sinusoidal", "Sinusoidal_gap", "Sinusoidal_split", "Smiley"]),
 }
 

@@ -1549,3 +1549,57 @@ class GmmLogProbFn(torch.autograd.Function):
         want = ctx.want if ctx.needs_input_grad[1] else 0
         gz, gR = ops.gmm_log_prob_bwd(z, R, ctx.M, lp, g, ctx.needs_input_grad[0], want)
         return gz, gR, None, None
+
+
+class Hmc2dFn(torch.autograd.Function):
+    """One HamiltonianMonteCarlo transition on explicit noise (csrc/hmc2d.hip): the forward launch also writes, per row, the
+    tangents of z_new to log_step_size and log_mass (gradlogP detaches: the force is a constant) and grad log p at z and at z_out.
+    The backward is one launch, gz = gz_out + gld (grad_lp(z) - grad_lp(z_out)), plus the fixed-order slab reduction of
+    accept (gz_out - gld grad_lp(z_out)) * tangent when a parameter wants its gradient (a frozen pair costs no slab work).
+    terms / steps / clip: ops.hmc2d.  Returns (z_out, log_det)."""
+
+    @staticmethod
+    def forward(ctx, z, log_step_size, log_mass, eps, u, terms, steps, clip):
+        z_out, log_det, accept, side = ops.hmc2d(z, eps, u, log_step_size.detach(), log_mass.detach(), terms, steps, clip, want_side=True)
+        ctx.save_for_backward(accept, side)
+        ctx.shapes = (log_step_size.shape, log_mass.shape)
+        ctx.set_materialize_grads(False)
+        return z_out, log_det
+
+    @staticmethod
+    @once_differentiable          # (the backward is a set of kernels, not a differentiable graph: double backward raises)
+    def backward(ctx, gz_out, gld):
+        none = (None,) * 8
+        if gz_out is None and gld is None:
+            return none
+        accept, side = ctx.saved_tensors
+        want = (1 if ctx.needs_input_grad[1] else 0) | (2 if ctx.needs_input_grad[2] else 0)
+        gz, gpar = ops.hmc2d_bwd(gz_out, gld, accept, side, ctx.needs_input_grad[0], want)
+        gs = gpar[:2].reshape(ctx.shapes[0]) if want & 1 else None
+        gm = gpar[2:].reshape(ctx.shapes[1]) if want & 2 else None
+        return (gz, gs, gm) + none[3:]
+
+
+class Mh2dFn(torch.autograd.Function):
+    """The `steps` steps of MetropolisHastings with a DiagGaussianProposal on explicit noise (csrc/hmc2d.hip): the forward launch
+    also writes grad log p at z and at z_out.  z_out is z plus a constant and the log-det telescopes to log p(z) - log p(z_out), so
+    the backward is one broadcast expression.  Returns (z_out, log_det)."""
+
+    @staticmethod
+    def forward(ctx, z, scale, eps, u, terms, steps):
+        z_out, log_det, gside = ops.mh2d(z, eps, u, scale, terms, steps, want_side=True)
+        ctx.save_for_backward(gside)
+        ctx.set_materialize_grads(False)
+        return z_out, log_det
+
+    @staticmethod
+    @once_differentiable          # (the saved derivatives are a kernel's output, not a differentiable graph: double backward raises)
+    def backward(ctx, gz_out, gld):
+        none = (None,) * 6
+        if gz_out is None and gld is None:
+            return none
+        (gside,) = ctx.saved_tensors
+        if gld is None:
+            return (gz_out,) + none[1:]
+        gz = gld.unsqueeze(1) * (gside[:, :2] - gside[:, 2:])
+        return ((gz if gz_out is None else gz_out + gz),) + none[1:]

@@ -500,6 +500,27 @@ def set_target_density(mode=True):
     target_density = bool(mode)
 
 
+# The stochastic flow layers: flows.HamiltonianMonteCarlo (exact type) and flows.MetropolisHastings (exact type, with an exact-type
+# DiagGaussianProposal of shape (2,)) on contiguous float32 CUDA (B, 2) inputs against one of the eight closed-form 2-D densities, a
+# 2-D DiagGaussian (float32, no temperature, no gradient wanted) or a LinearInterpolation of two of them with a host-side alpha: ONE
+# launch per layer call (nf_hmc2d / nf_mh2d, csrc/hmc2d.hip; stochastic_route.py) with the random numbers drawn by torch in front of
+# it in the reference's order, and under autograd autograd.Hmc2dFn / Mh2dFn (one backward launch plus a fixed-order slab reduction
+# for log_step_size / log_mass).  False = the torch formulas, the reference's arithmetic op for op (A/B runs, differential tests).
+# The route evaluates the densities itself: it does not depend on target_density.  Both Functions are once-differentiable: inside
+# higher_order_gradients() the torch formulas run.
+# Default on: eager, the kernels' median lies below the formulas' minimum in every measured case (HMC with 5 leapfrog steps against
+# TwoModes and CircularGaussianMixture(8), MH with 10 steps, a 10-layer HAIS chain; forward, and forward + backward to log_step_size /
+# log_mass; 1 024 and 65 536 rows: 11x - 256x); replayed from a captured graph the explicit-noise transitions are faster at every swept
+# size (1 024 .. 65 536 rows), so there is no batch-size gate for recorded passes (profiles/stochastic_bench.json:
+# `default_on_criterion`, `graph_not_slower_from`; tools/stochastic_bench.py).
+stochastic_kernels = True
+
+
+def set_stochastic_kernels(mode=True):
+    global stochastic_kernels
+    stochastic_kernels = bool(mode)
+
+
 # Residual flows on 2-D rows (exact type, a LipschitzMLP of 1 .. 3 hidden layers of width <= 128, `brute_force or not training`, CUDA
 # float32, no gradient needed) on the kernels of csrc/lipmlp.hip: the density direction of a maximal run of [Residual | initialised
 # ActNorm | AffineConstFlow] layers with at least one Residual as ONE launch (nf_lipmlp_chain; value, exact 2 x 2 Jacobian by

@@ -336,3 +336,4 @@ from .dist_target import Target, TwoMoons, CircularGaussianMixture, RingMixture,
 from .dist_prior import (PriorDistribution, ImagePrior, TwoModes, Sinusoidal, Sinusoidal_split, Sinusoidal_gap,  # noqa: E402
                          Smiley)
 from .dist_mixture import GaussianMixture  # noqa: E402
+from .dist_mh import MHProposal, DiagGaussianProposal, LinearInterpolation  # noqa: E402

@@ -13,3 +13,4 @@ from .periodic import PeriodicWrap, PeriodicShift
 from .planar import Planar
 from .radial import Radial
 from .residual import Residual
+from .stochastic import MetropolisHastings, HamiltonianMonteCarlo

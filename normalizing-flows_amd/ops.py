@@ -2071,6 +2071,101 @@ def gmm_log_prob_bwd(z, R, M, lp, g, want_gz, want):
     return gz, gR
 
 
+def hmc2d_grid(B):
+    """Workgroups (of 256 rows) of an nf_hmc2d launch on B rows; rows beyond grid x 256 are reached by its grid-stride loop."""
+    return L.query("nf_hmc2d_grid", int(B))
+
+
+def mh2d_grid(B):
+    """Workgroups (of 256 rows) of an nf_mh2d launch on B rows."""
+    return L.query("nf_mh2d_grid", int(B))
+
+
+def hmc2d_bwd_grid(B):
+    """Workgroups (of 256 rows) of an nf_hmc2d_bwd launch on B rows."""
+    return L.query("nf_hmc2d_bwd_grid", int(B))
+
+
+def _h2_target(entry, terms):
+    """The host tables and device pointers of a launch's target from stochastic_route.target_terms' list: (tkind, trec, aux tensors)."""
+    if not 1 <= len(terms) <= 2:
+        raise ValueError("%s: a target has one or two terms, got %d" % (entry, len(terms)))
+    tkind, trec, aux = [], [], []
+    for w, kind, n, rec, a0, a1 in terms:
+        if len(rec) > 8:
+            raise ValueError("%s: a record holds at most 8 floats" % entry)
+        tkind += [int(kind), int(n)]
+        trec += [float(w)] + [float(x) for x in rec] + [0.0] * (8 - len(rec))
+        L.check_count(entry, "a0", a0, 1 if kind == 6 else 2, "kind 6: scale; kind 7: loc")
+        L.check_count(entry, "a1", a1, 2, "kind 7: log_scale")
+        aux += [a0, a1]
+    aux += [None] * (4 - len(aux))
+    return (C.c_int * len(tkind))(*tkind), (C.c_float * len(trec))(*trec), aux
+
+
+def _h2_rows(entry, z, **rows):
+    if z.dim() != 2 or z.shape[1] != 2 or not z.is_contiguous():
+        raise ValueError("%s: z must be a contiguous (B, 2) matrix, got %s" % (entry, tuple(z.shape)))
+    for name, (t, n) in rows.items():
+        L.check_count(entry, name, t, n, "per row of z %s" % (tuple(z.shape),))
+        if t is not None and not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous" % (entry, name))
+    return z.shape[0]
+
+
+def hmc2d(z, eps, u, log_step_size, log_mass, terms, steps, max_abs_grad=0.0, want_side=False):
+    """nf_hmc2d: one HamiltonianMonteCarlo transition on z (B, 2) in one launch for given noise eps (B, 2) and uniforms u (B):
+    (z_out, log_det, accept (B floats), side (B, 8) or None).  terms: stochastic_route.target_terms; log_step_size / log_mass: two
+    floats each in device memory; max_abs_grad 0 = no clipping.  side (training): the tangents of z_new to log_step_size and
+    log_mass, and grad log p at z and at z_out."""
+    tkind, trec, aux = _h2_target("hmc2d", terms)
+    L.require_device(z, eps, u, log_step_size, log_mass, *aux, dtype=torch.float32)
+    B = _h2_rows("hmc2d", z, eps=(eps, 2 * z.shape[0]), u=(u, z.shape[0]), log_step_size=(log_step_size, 2), log_mass=(log_mass, 2))
+    z_out = torch.empty_like(z)
+    log_det = torch.empty(B, dtype=z.dtype, device=z.device)
+    accept = torch.empty(B, dtype=z.dtype, device=z.device)
+    side = torch.empty((B, 8), dtype=z.dtype, device=z.device) if want_side else None
+    L.call("nf_hmc2d", ptr(z), ptr(eps), ptr(u), ptr(log_step_size), ptr(log_mass), tkind, trec, _cptr(aux[0]), _cptr(aux[1]),
+           _cptr(aux[2]), _cptr(aux[3]), len(terms), int(steps), float(max_abs_grad), ptr(z_out), ptr(log_det), ptr(accept), ptr(side), B,
+           L.stream())
+    return z_out, log_det, accept, side
+
+
+def hmc2d_bwd(gz_out, gld, accept, side, want_gz, want):
+    """nf_hmc2d_bwd: (gz (B, 2) or None, gpar (4) = [g log_step_size | g log_mass] or None when want == 0).  gz_out / gld: the
+    cotangents, either may be None; want: bit 0 log_step_size, bit 1 log_mass.  want == 0: no slab work, one launch."""
+    L.require_device(gz_out, gld, accept, side, dtype=torch.float32)
+    B = accept.numel()
+    L.check_count("hmc2d_bwd", "side", side, 8 * B, "8 B")
+    L.check_count("hmc2d_bwd", "gz_out", gz_out, 2 * B, "2 B")
+    L.check_count("hmc2d_bwd", "gld", gld, B, "B")
+    gz = torch.empty((B, 2), dtype=side.dtype, device=side.device) if want_gz else None
+    slabs = gpar = None
+    if want:
+        slabs = torch.empty(L.size("nf_hmc2d_bwd_scratch_floats", B), dtype=side.dtype, device=side.device)
+        gpar = torch.zeros(4, dtype=side.dtype, device=side.device) if B == 0 else torch.empty(4, dtype=side.dtype, device=side.device)
+    L.call("nf_hmc2d_bwd", _cptr(gz_out), _cptr(gld), ptr(accept), ptr(side), ptr(gz), ptr(slabs), ptr(gpar), int(want), B, L.stream())
+    return gz, gpar
+
+
+def mh2d(z, eps, u, scale, terms, steps, want_side=False):
+    """nf_mh2d: `steps` random-walk Metropolis-Hastings steps on z (B, 2) in one launch for given noise eps (steps, B, 2) and
+    uniforms u (steps, B); scale: the proposal's buffer (one or two floats, device).  (z_out, log_det, gside (B, 4) or None):
+    gside = grad log p at z | at z_out."""
+    tkind, trec, aux = _h2_target("mh2d", terms)
+    L.require_device(z, eps, u, scale, *aux, dtype=torch.float32)
+    steps = int(steps)
+    B = _h2_rows("mh2d", z, eps=(eps, steps * 2 * z.shape[0]), u=(u, steps * z.shape[0]))
+    if scale.numel() not in (1, 2) or not scale.is_contiguous():
+        raise ValueError("mh2d: scale holds one or two contiguous floats, got shape %s" % (tuple(scale.shape),))
+    z_out = torch.empty_like(z)
+    log_det = torch.empty(B, dtype=z.dtype, device=z.device)
+    gside = torch.empty((B, 4), dtype=z.dtype, device=z.device) if want_side else None
+    L.call("nf_mh2d", ptr(z), ptr(eps), ptr(u), ptr(scale), scale.numel(), tkind, trec, _cptr(aux[0]), _cptr(aux[1]), _cptr(aux[2]),
+           _cptr(aux[3]), len(terms), steps, ptr(z_out), ptr(log_det), ptr(gside), B, L.stream())
+    return z_out, log_det, gside
+
+
 def lipmlp_width(hmax):
     """The padded hidden width of the residual-flow kernels for a widest hidden layer `hmax` (nf_lipmlp_width): 32, 64 or 128; 0 =
     not taken."""
