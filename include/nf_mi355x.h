@@ -1373,6 +1373,44 @@ int nf_lipmlp_apply(const void *x, const void *yin, void *out, void *count, cons
                     double atol, double rtol, nf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Training of ONE Residual layer y = x + g(x) on 2-D rows (csrc/lipmlp_train.hip), float32: one forward launch, one backward launch
+ * and, when the blob needs a gradient, one fixed-order reduction launch.
+ * Replaces normflows/flows/residual.py:143-268 under autograd (iResBlock._logdetgrad with basic_logdet_estimator,
+ * neumann_logdet_estimator, the exact trace, the brute-force determinant, and MemoryEfficientLogDetEstimator) together with the
+ * network's own backward.  On 2-D rows every estimator is a closed-form function of the exact 2 x 2 Jacobian J_ij = d g_i / d x_j.
+ *
+ * blob: ONE Residual record of the layout above (K = 1, nres = 1): nblob = 16 + 2 hp^2 + 7 hp + 4 floats.
+ *
+ * nf_lipmlp_train_fwd: x (B, 2) -> y (B, 2) = x + g(x), ld (B) and jhat (B, 4) = d ld / d J, row-major [J00, J01, J10, J11].
+ *   kind   0 brute force      ld = log|det(I + J)|                                   jhat = (I + J)^(-T)
+ *          1 Hutchinson       ld = sum_k a_k v^T J^k v                               jhat = sum_k a_k sum_{m<k} (v^T J^m)^T (J^(k-1-m) v)^T
+ *          2 Neumann          ld = n^T J v, n = v + sum_k (-1)^k coef(k) v^T J^k     jhat = n v^T  (n held constant)
+ *          3 exact trace      ld = sum_k a_k tr(J^k)                                 jhat = sum_k a_k k (J^(k-1))^T
+ *   with a_k = (-1)^(k+1) coef(k) / k, k = 1 .. nterms <= 32, v = the row of vareps (B, 2) (kinds 1, 2; may be NULL otherwise).
+ *   coef: nterms floats in HOST memory, coef[k - 1] = coef(k); they travel by value in the launch arguments (no copy to the device,
+ *   nothing to keep alive).  kind 0 reads neither nterms nor coef.  The sign is the series' own: the caller negates for a flow whose
+ *   log-det convention asks for it.  Saved for the backward: x, jhat and the blob.
+ * nf_lipmlp_train_bwd: gx (B, 2) = gy + the cotangent of x through g and J, for gy (B, 2) the cotangent of y and w (B) the
+ *   cotangent of ld; gy NULL or w NULL: zeros.  gx NULL: not written.  want = 1: gblob (nblob) = the gradient of the whole blob
+ *   (effective weights, biases, header [2 .. 5] = the Swish slopes; every other entry 0), through slabs of
+ *   nf_lipmlp_train_scratch_floats(B, hp) floats (one blob per workgroup, accumulated over the tiles the workgroup walks) and a
+ *   fixed-order reduction launch; want = 0: no slab work, no reduction, slabs / gblob not read.  The tile's forward is recomputed.
+ * nf_lipmlp_train_rows(hp): rows per 256-lane workgroup of the BACKWARD, 2048 / hp (the forward's are nf_lipmlp_rows(hp)); both grids
+ *   are min(row tiles, nf_persistent_workgroups()).  No atomics: results are bit-identical from run to run.
+ * Returns NF_ENOTSUP for hp outside {32, 64, 128}, NF_ERANGE for nterms > 32, NF_EINVAL for B < 0, another nblob, an unknown kind /
+ * want, nterms < 1 with kind != 0, or a jhat off a 16-byte boundary, NF_EFAULT for a NULL required pointer when B > 0.  B == 0 returns
+ * NF_OK before any launch.
+ */
+int nf_lipmlp_train_rows(int hp);
+int64_t nf_lipmlp_train_scratch_floats(int64_t B, int hp);
+/* Alignment: element type; jhat 16 bytes; a blob off a 16-byte boundary is read by 4-byte loads (same arithmetic). */
+int nf_lipmlp_train_fwd(const void *x, const void *vareps, void *y, void *ld, void *jhat, const void *blob, int64_t nblob, int64_t B,
+                        int hp, int kind, int nterms, const float *coef_host, nf_stream_t stream);
+/* Alignment: element type; jhat 16 bytes; a blob off a 16-byte boundary is read by 4-byte loads (same arithmetic). */
+int nf_lipmlp_train_bwd(const void *x, const void *gy, const void *jhat, const void *w, void *gx, const void *blob, void *slabs,
+                        void *gblob, int64_t nblob, int64_t B, int hp, int want, nf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Closed-form 2-D target and prior densities (csrc/density2d.hip), float32: lp (B) = log p(z) of z (B, 2) in one launch and, when
  * gz (B, 2) is not NULL, d lp / d z in the same launch.
  * Replaces normflows/distributions/target.py:123-129 (TwoMoons.log_prob), :150-160 (CircularGaussianMixture.log_prob), :189-195

@@ -1506,6 +1506,34 @@ class Rank1ChainFn(torch.autograd.Function):
         return gz, gP, None, None
 
 
+class LipMlpTrainFn(torch.autograd.Function):
+    """One Residual layer y = x + g(x) on 2-D rows with its log-det estimate, as one forward and one backward launch
+    (csrc/lipmlp_train.hip).  `blob` = flows/lipmlp_pack.pack_train of the layer, built from the live parameters by differentiable
+    torch operations: the backward returns the blob's gradient and torch's autograd carries it on to the leaves (the division by
+    max(1, sigma / coeff) and softplus(beta) included).  Saved: x, the blob and jhat = d ld / d J (B, 4).  first_row: the log-det
+    cotangent handed to the kernel is gld[0] for every row (MemoryEfficientLogDetEstimator.backward, residual.py:247-268), read on
+    the device.  Returns (y, ld)."""
+
+    @staticmethod
+    def forward(ctx, x, blob, hp, kind, coef, vareps, first_row):
+        y, ld, jhat = ops.lipmlp_train_fwd(x, blob.detach(), hp, kind, coef, vareps)
+        ctx.save_for_backward(x, blob, jhat)
+        ctx.hp, ctx.first_row = hp, first_row
+        ctx.set_materialize_grads(False)
+        return y, ld
+
+    @staticmethod
+    @once_differentiable          # (the backward is a set of kernels, not a differentiable graph: double backward raises)
+    def backward(ctx, gy, gld):
+        x, blob, jhat = ctx.saved_tensors
+        if gy is None and gld is None:
+            return None, None, None, None, None, None, None
+        if gld is not None and ctx.first_row:
+            gld = gld[0:1].expand(gld.shape[0])
+        gx, gblob = ops.lipmlp_train_bwd(x, gy, jhat, gld, blob.detach(), ctx.hp, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
+        return gx, gblob, None, None, None, None, None
+
+
 class Density2dFn(torch.autograd.Function):
     """log p(z) of a closed-form 2-D target or prior (csrc/density2d.hip) with its input gradient from the SAME launch: the forward
     saves d lp / d z (B, 2), the backward is one broadcast multiply with the cotangent.  kind / n / rec / dscale: ops.density2d."""

@@ -539,6 +539,22 @@ def set_residual_chain(mode=True):
     residual_chain = bool(mode)
 
 
+# Training of 2-D Residual layers on the kernels of csrc/lipmlp_train.hip: a density-direction pass that needs a gradient, or a
+# training-mode pass on a stochastic log-det estimator, runs as one forward launch (value, estimate and the estimate's cotangent of
+# the exact 2 x 2 Jacobian) and one backward launch plus a fixed-order reduction (autograd.LipMlpTrainFn, flows/lipmlp_pack.py:
+# train_eligible has the conditions; residual_chain must be on as well); False = the torch formulas, the reference's arithmetic.  The
+# random draws come in the reference's order in front of the launch, so one seed gives both routes the same numbers.  The Function is
+# once-differentiable: inside higher_order_gradients() the torch formulas run.
+# Default OFF whatever tools/residual_train_bench.py says (profiles/residual_train_bench.json: `default_on_criterion`); turning it on
+# is a change of its own.
+residual_train = False
+
+
+def set_residual_train(mode=True):
+    global residual_train
+    residual_train = bool(mode)
+
+
 # Debug mode of the element-wise spline API (utils.splines): after every call a check launch (nf_rqs_spline_check)
 # sets device-side flags and the shim reads them back -- a host synchronisation per call, which is why it is off by default -- and
 # raises what the reference raises: AssertionError for a negative discriminant in the inverse direction (utils/splines.py:181),

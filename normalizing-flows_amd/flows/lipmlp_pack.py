@@ -13,7 +13,12 @@ Every W is the EFFECTIVE weight W / max(1, (u . W v) / coeff) (lipschitz.py:264-
 on the run's linear layers stacked by shape -- one batched product per shape whatever the number of layers -- and, as on the torch
 route, every layer's `scale` buffer receives its sigma.  The blob is cached against the versions of the parameters AND of the
 buffers u, v (_keys.pcached): update_lipschitz rewrites those in place and changes the effective weight without touching a
-parameter."""
+parameter.
+
+Training (csrc/lipmlp_train.hip, config.residual_train): ONE Residual layer per call; pack_train builds the same record from the
+LIVE parameters with differentiable torch operations, so the kernel's blob gradient reaches weight, bias and beta -- through the
+division by max(1, sigma / coeff) and through softplus -- by torch's autograd; train_eligible has the conditions, run_train the
+order of the random draws."""
 import torch
 from torch.nn import functional as F
 
@@ -25,6 +30,7 @@ HMAX = 128              # widest hidden layer
 HDR = 16
 ATOL = RTOL = 1e-5      # the fixed-point stop rule (residual.py:133)
 MAX_ITER = 1000
+MAX_TERMS = 32          # series terms of one training forward (nf_lipmlp_train_fwd)
 
 _lipmlp_cache = {}      # (id of the run's first layer, K) -> (version key, (blob, hp, nres))
 last_iterations = None  # further fixed-point steps of the last run_sampling call (residual.py:135-141's i)
@@ -215,3 +221,104 @@ def run_sampling(layer, z):
     last_iterations = i
     _, log_det = ops.lipmlp_chain(x, blob, 1, 1, hp)
     return x, -log_det
+
+
+def pack_train(layer, hp=None):
+    """The blob of ONE Residual record (the layout at the head of this file, K = 1) as a differentiable function of the layer's live
+    parameters: effective weights W / max(1, (u . W v) / coeff) with the gradient through sigma and the maximum left to torch,
+    softplus(beta), biases, zero padding.  Every layer's `scale` buffer receives its sigma, as on the torch route."""
+    pairs = linears(layer.iresblock.nnet)
+    hp = width([layer]) if hp is None else hp
+    n = len(pairs)
+    dev = pairs[0][1].weight.device
+    weff = []
+    for _, lin in pairs:
+        sigma = torch.dot(lin.u, torch.mv(lin.weight, lin.v))
+        with torch.no_grad():
+            lin.scale.copy_(sigma)
+        weff.append(lin.weight / torch.max(torch.ones(1, device=dev), sigma / lin.coeff))       # (lipschitz.py:270, as written)
+
+    def zeros(k):
+        return torch.zeros(k, dtype=torch.float32, device=dev)
+
+    parts = [zeros(1), torch.full((1,), float(n - 2), dtype=torch.float32, device=dev),
+             F.softplus(torch.cat([sw.beta for sw, _ in pairs])), zeros(HDR - 2 - n)]
+    h1 = pairs[0][1].out_features
+    parts += [F.pad(weff[0].t(), (0, hp - h1)).reshape(-1), F.pad(pairs[0][1].bias, (0, hp - h1))]
+    for m in range(2):
+        if m < n - 2:
+            lin = pairs[1 + m][1]
+            parts += [F.pad(weff[1 + m].t(), (0, hp - lin.out_features, 0, hp - lin.in_features)).reshape(-1),
+                      F.pad(lin.bias, (0, hp - lin.out_features))]
+        else:
+            parts.append(zeros(hp * hp + hp))
+    last = pairs[-1][1]
+    parts += [F.pad(weff[-1], (0, hp - last.in_features)).reshape(-1), last.bias, zeros(2)]
+    return torch.cat(parts)
+
+
+def _on_device(z):
+    """The kernels' input: a CUDA float32 contiguous (B, 2) tensor with B > 0."""
+    return bool(torch.is_tensor(z) and z.is_cuda and z.dtype == torch.float32 and z.dim() == 2 and z.shape[1] == 2
+                and z.shape[0] > 0 and z.is_contiguous())
+
+
+def _stochastic(ires):
+    """True when the layer's log-det on 2-D rows is one of the series estimators (training mode without brute_force)."""
+    return bool(ires.training and not ires.brute_force)
+
+
+def train_eligible(layer, z, density=True):
+    """True when the training kernels take `layer` on z: both switches on, exact type Residual with a net linears() accepts, the
+    density direction, a CUDA float32 contiguous (B, 2) tensor with B > 0, float32 tensors on z's device, not inside
+    config.higher_order_gradients(), and EITHER a gradient is needed (grad enabled, and z or a parameter of the layer requires one)
+    OR the layer is in training mode on a stochastic estimator (which the inference kernels do not compute).  While a stream is
+    being captured only deterministic truncations are taken (brute force, evaluation mode, or n_power_series set): the host draw
+    of a random truncation cannot be recorded."""
+    if not (_config.residual_train and _config.residual_chain and not _config.torch_elementwise and density
+            and _is_residual(layer) and _on_device(z)):
+        return False
+    ires = layer.iresblock
+    if linears(ires.nnet) is None:
+        return False
+    needs_grad = torch.is_grad_enabled() and (z.requires_grad or any(p.requires_grad for p in layer.parameters()))
+    if not (needs_grad or _stochastic(ires)):
+        return False
+    if any(t.dtype != torch.float32 or t.device != z.device for t in tensors([layer])):
+        return False
+    if _stochastic(ires) and ires.n_power_series is None and torch.cuda.is_current_stream_capturing():
+        return False
+    if _stochastic(ires) and ires.n_power_series is not None and not 1 <= ires.n_power_series <= MAX_TERMS:
+        return False
+    return True
+
+
+def run_train(layer, z):
+    """((y, log_det), None) of `layer` (train_eligible(layer, z) holds) in its density direction on the training kernels, or
+    (None, truncation) when the drawn truncation has more than MAX_TERMS terms (or none): the caller runs the torch formulas
+    with that draw.  The random draws come in the reference's order in front of the launch (residual.py:163-190): the NumPy
+    truncation draw, then ONE torch.randn_like(z)."""
+    from ..autograd import LipMlpTrainFn
+    ires = layer.iresblock
+    kind, coef, vareps, first_row, drawn = 0, (), None, False, None
+    if _stochastic(ires):
+        trunc = ires._truncation()
+        n_terms, coeff, drawn = trunc
+        if not 1 <= n_terms <= MAX_TERMS:
+            return None, trunc
+        coef = [float(coeff(k)) for k in range(1, n_terms + 1)]
+        if ires.exact_trace:
+            kind, coef[0] = 3, 1.0      # (the reference takes the first term's trace unweighted)
+        else:
+            vareps = torch.randn_like(z)
+            kind = 2 if ires.neumann_grad else 1
+            first_row = bool(ires.grad_in_forward)
+    hp = width([layer])
+    y, ld = LipMlpTrainFn.apply(z, pack_train(layer, hp), hp, kind, tuple(coef), vareps, first_row)
+    if _stochastic(ires) and ires.n_power_series is None:
+        with torch.no_grad():
+            est = ld.detach()
+            ires.last_n_samples.copy_(torch.tensor(drawn).to(ires.last_n_samples))
+            ires.last_firmom.copy_(torch.mean(est).to(ires.last_firmom))
+            ires.last_secmom.copy_(torch.mean(est ** 2).to(ires.last_secmom))
+    return (y, ld), None

@@ -7,7 +7,9 @@ reference's numbers.
 The deterministic part -- 2-D inputs with `brute_force or not training`: the exact 2 x 2 Jacobian determinant -- runs on the HIP
 kernels of csrc/lipmlp.hip for a CUDA float32 input when no gradient is needed (flows/lipmlp_pack.py has the conditions): the density
 direction as one launch per layer, or per run of layers inside core.run_chain; the fixed-point direction as one launch and one
-read-back per iteration.  Everything else takes the torch formulas below.
+read-back per iteration.  With config.residual_train on, a density-direction pass of such a layer that DOES need a gradient, or a
+training-mode pass on a stochastic estimator, runs on the training kernels of csrc/lipmlp_train.hip (one forward and one backward
+launch; lipmlp_pack.train_eligible).  Everything else takes the torch formulas below.
 
 One deliberate difference from the reference: under torch.no_grad() the outputs are detached and the caller's tensor is left alone
 (the reference leaks a graph out of its enable_grad block and flips requires_grad on the caller's input)."""
@@ -33,13 +35,19 @@ class Residual(Flow):
                                    grad_in_forward=reduce_memory, exact_trace=exact_trace, geom_p=geom_p, lamb=lamb,
                                    n_power_series=n_power_series, brute_force=brute_force, n_dist=n_dist)
 
-    def _torch_pass(self, z, density):
-        """(z', log_det) by the torch formulas: density=True is x + g(x), False the fixed-point iteration."""
-        z, log_det = self.iresblock.forward(z, 0) if density else self.iresblock.inverse(z, 0)
+    def _torch_pass(self, z, density, truncation=None):
+        """(z', log_det) by the torch formulas: density=True is x + g(x), False the fixed-point iteration.  truncation: what
+        iResBlock._truncation() returned when a route has drawn it already and then declined the call."""
+        z, log_det = self.iresblock.forward(z, 0, truncation) if density else self.iresblock.inverse(z, 0)
         return z, -log_det.view(-1)
 
     def _pass(self, z, density):
         from . import lipmlp_pack
+        if lipmlp_pack.train_eligible(self, z, density):
+            out, drawn = lipmlp_pack.run_train(self, z)
+            if out is not None:
+                return out
+            return self._torch_pass(z, density, drawn)      # more than 32 series terms drawn: the formulas, with that draw
         if type(self) is Residual and lipmlp_pack.eligible([self], z, sampling=not density):
             if density:
                 return lipmlp_pack.run_density([self], z, None, None)
@@ -78,10 +86,10 @@ class iResBlock(nn.Module):
         self.register_buffer("last_firmom", torch.zeros(1))
         self.register_buffer("last_secmom", torch.zeros(1))
 
-    def forward(self, x, logpx=None):
+    def forward(self, x, logpx=None, truncation=None):
         if logpx is None:
             return x + self.nnet(x)
-        g, logdetgrad = self._logdetgrad(x)
+        g, logdetgrad = self._logdetgrad(x, truncation)
         return x + g, logpx - logdetgrad
 
     def inverse(self, y, logpy=None):
@@ -123,16 +131,16 @@ class iResBlock(nn.Module):
 
         return max(n) + exact, coeff, n
 
-    def _logdetgrad(self, x):
-        """(g(x), log|det d(x + g(x)) / dx|) as a (B, 1) column."""
+    def _logdetgrad(self, x, truncation=None):
+        """(g(x), log|det d(x + g(x)) / dx|) as a (B, 1) column.  truncation: a _truncation() result drawn by the caller."""
         keep_graph = torch.is_grad_enabled()
         with torch.enable_grad():
-            g, logdetgrad = self._logdetgrad_impl(x if keep_graph else x.detach())
+            g, logdetgrad = self._logdetgrad_impl(x if keep_graph else x.detach(), truncation)
         if not keep_graph:
             g, logdetgrad = g.detach(), logdetgrad.detach()
         return g, logdetgrad
 
-    def _logdetgrad_impl(self, x):
+    def _logdetgrad_impl(self, x, truncation=None):
         if (self.brute_force or not self.training) and x.ndimension() == 2 and x.shape[1] == 2:
             x = _differentiable(x)
             g = self.nnet(x)
@@ -140,7 +148,7 @@ class iResBlock(nn.Module):
             det = (jac[:, 0, 0] + 1) * (jac[:, 1, 1] + 1) - jac[:, 0, 1] * jac[:, 1, 0]
             return g, torch.log(torch.abs(det)).view(-1, 1)
 
-        n_terms, coeff, drawn = self._truncation()
+        n_terms, coeff, drawn = self._truncation() if truncation is None else truncation
         if not self.exact_trace:
             vareps = torch.randn_like(x)
             estimator = neumann_logdet_estimator if self.training and self.neumann_grad else basic_logdet_estimator

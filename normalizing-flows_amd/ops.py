@@ -2214,3 +2214,58 @@ def lipmlp_apply(x, y, blob, hp, mode, count=None, atol=1e-5, rtol=1e-5):
     L.call("nf_lipmlp_apply", ptr(x), ptr(y if mode == 1 else None), ptr(out), ptr(count if mode == 1 else None), ptr(blob),
            blob.numel(), B, int(hp), mode, float(atol), float(rtol), L.stream())
     return out
+
+
+def lipmlp_train_rows(hp):
+    """Rows per workgroup of the residual-flow BACKWARD kernel (nf_lipmlp_train_rows): 2048 / hp."""
+    rows = L.query("nf_lipmlp_train_rows", int(hp))
+    if rows < 0:
+        L.check(rows, "nf_lipmlp_train_rows")
+    return rows
+
+
+LIPMLP_TRAIN_MAX_TERMS = 32     # series terms of one nf_lipmlp_train_fwd call (they travel in the launch arguments)
+
+
+def lipmlp_train_fwd(x, blob, hp, kind, coef=(), vareps=None):
+    """nf_lipmlp_train_fwd on ONE Residual record: (y (B, 2), ld (B), jhat (B, 4) = d ld / d J).  kind: 0 brute force, 1 Hutchinson,
+    2 Neumann, 3 exact trace; coef: Python floats, coef[k - 1] = the weight of series term k (kinds 1 - 3, at most 32); vareps (B, 2):
+    the probe vectors of kinds 1 and 2."""
+    L.require_device(x, blob, vareps, dtype=torch.float32)
+    if kind not in (0, 1, 2, 3):
+        raise ValueError("lipmlp_train_fwd: kind must be 0 .. 3")
+    if kind in (1, 2) and vareps is None:
+        raise ValueError("lipmlp_train_fwd: kinds 1 and 2 need vareps (B, 2)")
+    B = _lipmlp_rows("lipmlp_train_fwd", blob, 1, 1, hp, *((x,) if vareps is None else (x, vareps)))
+    y = torch.empty_like(x)
+    ld = torch.empty(B, dtype=x.dtype, device=x.device)
+    jhat = torch.empty(B, 4, dtype=x.dtype, device=x.device)
+    coef = [float(c) for c in coef] if kind else []
+    coef_host = (C.c_float * max(len(coef), 1))(*coef)
+    L.call("nf_lipmlp_train_fwd", ptr(x), ptr(vareps), ptr(y), ptr(ld), ptr(jhat), ptr(blob), blob.numel(), B, int(hp), int(kind),
+           len(coef), coef_host, L.stream())
+    return y, ld, jhat
+
+
+def lipmlp_train_bwd(x, gy, jhat, w, blob, hp, want_gblob, want_gx=True):
+    """nf_lipmlp_train_bwd: (gx (B, 2) or None, gblob or None when not want_gblob -- then no slab is allocated and no reduction is
+    launched).  gy (B, 2) / w (B): the cotangents of y and of ld, of any strides (a non-contiguous one is copied); None = zeros."""
+    L.require_device(x, gy, jhat, w, blob, dtype=torch.float32)
+    B = _lipmlp_rows("lipmlp_train_bwd", blob, 1, 1, hp, x)
+    if gy is not None and gy.shape != x.shape:      # (autograd hands over expanded / strided cotangents: _cptr copies those)
+        raise ValueError("lipmlp_train_bwd: gy has shape %s, x %s" % (tuple(gy.shape), tuple(x.shape)))
+    L.check_count("lipmlp_train_bwd", "jhat", jhat, 4 * B, "4 B")
+    L.check_count("lipmlp_train_bwd", "w", w, B, "B")
+    gx = torch.empty_like(x) if want_gx else None
+    slabs = gblob = None
+    if want_gblob and B:
+        slabs = torch.empty(L.size("nf_lipmlp_train_scratch_floats", B, int(hp)), dtype=x.dtype, device=x.device)
+        gblob = torch.empty_like(blob)
+    elif want_gblob:
+        gblob = torch.zeros_like(blob)
+    # contiguous copies of strided cotangents stay referenced until the launch is enqueued: a copy dropped inside the argument list
+    # hands its block back to the allocator, and the next copy in the same list can land on it
+    gy, jhat, w = (None if t is None else t.contiguous() for t in (gy, jhat, w))
+    L.call("nf_lipmlp_train_bwd", ptr(x), ptr(gy), ptr(jhat), ptr(w), ptr(gx), ptr(blob), ptr(slabs), ptr(gblob), blob.numel(), B,
+           int(hp), 1 if slabs is not None else 0, L.stream())
+    return gx, gblob
