@@ -1373,6 +1373,49 @@ int nf_lipmlp_apply(const void *x, const void *yin, void *out, void *count, cons
                     double atol, double rtol, nf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Residual flows x + g(x) on d-dimensional rows, 3 <= d <= 64, at inference (csrc/lipmlp_nd.hip), float32.
+ * Replaces normflows/flows/residual.py:118-124 (iResBlock.forward), :133-142 (one step of _inverse_fixed_point and its stop test),
+ * :188-228 (the power-series branch of _logdetgrad without exact_trace, in evaluation mode) and :355-365 (basic_logdet_estimator: one
+ * vector-Jacobian product through the network per series term) with normflows/nets/lipschitz.py:66-67, :272-274, :647-648, and,
+ * between Residual layers, normflows/flows/affine/coupling.py:38-54 (AffineConstFlow / ActNorm), for K consecutive layers on z (B, d).
+ *
+ * Per Residual record and row: y = x + g(x), ld = sum_{k = 1 .. n} a_k v^T J^k v with J the Jacobian of g at x, v the row of vareps
+ * and a_k = (-1)^(k+1) coef(k) / k, by forward-mode tangents w_k = J w_{k-1}, w_0 = v (the same scalar as the reference's v^T J^k).
+ *
+ * blob (flows/lipmlp_nd_pack.py), dp = d rounded up to a multiple of 4, hp = nf_lipmlp_width(widest hidden layer):
+ *   K headers of 16 floats in execution order   [0] kind: 0 Residual, 1 affine forward y = z e + t, 2 affine inverse y = (z - t) e
+ *            [1] number of hidden (hp x hp) products, 0 .. 2   [2 .. 5] softplus(beta) of the Swish in front of linear layer 0 .. 3
+ *            [10] the affine record's log-det, +-sum(s)   [11] index of the Residual record's weight block, which is also its index
+ *            into vareps, nterms and coef   [6 .. 9], [12 .. 15] zero
+ *   K affine slots of 2 dp floats               e = exp(+-s) (dp) | t (dp); zeros for a Residual record
+ *   nres weight blocks                          W_0^T (dp, hp) | b_0 (hp) | 2 x [W_m^T (hp in, hp out) | b_m (hp)] | W_last^T (hp, dp) |
+ *            b_last (dp) = 2 hp^2 + 2 dp hp + 3 hp + dp floats; every W is the EFFECTIVE weight W / max(1, (u . W v) / coeff).
+ *   = nf_lipmlp_nd_blob_floats(K, nres, hp, d) floats; widths are zero-padded.
+ *
+ * nf_lipmlp_nd_rows(hp, d): rows per 256-lane workgroup: 4096 / hp, halved until four (hp + 4)-wide planes (activations and three
+ *   Swish-derivative planes) and four (dp + 4)-wide arrays (x, v, w, the input Swish's derivative) per row fit 160 KiB of LDS; the
+ *   grid is min(row tiles, nf_persistent_workgroups()).
+ * nf_lipmlp_nd_chain: every Residual record in its density direction; y (B, d); logdet (B) = the sum of the records' log-dets combined
+ *   according to acc (NF_LD_WRITE / _ADD / _SUB).  vareps (nres, B, d) on the device.  nterms: nres ints and coef: nres x 48 floats
+ *   (coef[48 r + k - 1] = coef(k) of Residual record r) in HOST memory; they travel by value in the launch arguments (no copy to the
+ *   device, nothing to keep alive, and a recorded launch replays its own draw).  At most 8 Residual records and 48 terms per record.
+ * nf_lipmlp_nd_apply: ONE network (K = 1, nres = 1): mode 0: out = x + g(x); mode 1: out = yin - g(x), and *count (int32, device) is
+ *   increased by the number of elements with !((out - x)^2 / (atol + |yin| rtol) < 1), by an ordinary vector atomic per wave.
+ * Returns NF_ENOTSUP for hp outside {32, 64, 128} or d outside 3 .. 64, NF_ERANGE for K > 32, nres > 8 or a term count > 48,
+ * NF_EINVAL for K < 1, nres outside 1 .. K, a term count < 1, B < 0, another nblob, an unknown acc / mode or negative or all-zero
+ * tolerances, NF_EFAULT for a NULL required pointer when B > 0 (nterms / coef: always required).  B == 0 returns NF_OK before any
+ * launch.  The header's kinds and indices live in device memory: an index outside 0 .. nres - 1 is clamped, never followed.
+ */
+int nf_lipmlp_nd_rows(int hp, int d);
+int64_t nf_lipmlp_nd_blob_floats(int K, int nres, int hp, int d);
+/* Alignment: element type; a blob off a 16-byte boundary is read by 4-byte loads instead of 16-byte ones (same arithmetic). */
+int nf_lipmlp_nd_chain(const void *z, const void *vareps, void *y, void *logdet, const void *blob, int64_t nblob, int64_t B, int d,
+                       int hp, int K, int nres, const int *nterms_host, const float *coef_host, int acc, nf_stream_t stream);
+/* Alignment: element type; a blob off a 16-byte boundary is read by 4-byte loads instead of 16-byte ones (same arithmetic). */
+int nf_lipmlp_nd_apply(const void *x, const void *yin, void *out, void *count, const void *blob, int64_t nblob, int64_t B, int d,
+                       int hp, int mode, double atol, double rtol, nf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training of ONE Residual layer y = x + g(x) on 2-D rows (csrc/lipmlp_train.hip), float32: one forward launch, one backward launch
  * and, when the blob needs a gradient, one fixed-order reduction launch.
  * Replaces normflows/flows/residual.py:143-268 under autograd (iResBlock._logdetgrad with basic_logdet_estimator,

@@ -555,6 +555,24 @@ def set_residual_train(mode=True):
     residual_train = bool(mode)
 
 
+# Residual layers on (B, d) rows with 3 <= d <= 64 at inference (evaluation mode, exact_trace=False, CUDA float32, no gradient needed)
+# on the kernels of csrc/lipmlp_nd.hip: the density direction of a maximal run of [Residual | initialised ActNorm | AffineConstFlow]
+# layers as ONE launch (nf_lipmlp_nd_chain: value pass, then one forward-mode tangent pass per term of Hutchinson's power series),
+# the fixed-point direction as one launch and one read-back per iteration (nf_lipmlp_nd_apply) and one series launch at the point
+# found (flows/lipmlp_nd_pack.py: eligible has the conditions; residual_chain must be on as well).  Every layer's truncation and
+# noise are drawn in the reference's order, from the same generators, in front of the launch.  False = the torch formulas, the
+# reference's arithmetic: one autograd pass through the network per series term.
+# Default OFF whatever tools/residual_nd_bench.py says: the route changes which float32 rounding a seeded evaluation gets (forward-
+# mode tangents against the reference's vector-Jacobian products), the d > 2 workloads have no soak run behind them yet, and
+# training at d > 2 still takes the formulas; turning it on is a change of its own (profiles/residual_nd_bench.json).
+residual_nd = False
+
+
+def set_residual_nd(mode=True):
+    global residual_nd
+    residual_nd = bool(mode)
+
+
 # Debug mode of the element-wise spline API (utils.splines): after every call a check launch (nf_rqs_spline_check)
 # sets device-side flags and the shim reads them back -- a host synchronisation per call, which is why it is off by default -- and
 # raises what the reference raises: AssertionError for a negative discriminant in the inverse direction (utils/splines.py:181),

@@ -45,6 +45,8 @@ def invalidate_caches(module):
     rank1_pack._rank1_cache.clear()
     from .flows import lipmlp_pack
     lipmlp_pack._lipmlp_cache.clear()
+    from .flows import lipmlp_nd_pack
+    lipmlp_nd_pack._lipmlp_nd_cache.clear()
 
 
 def _pair_signature(crqs):
@@ -358,6 +360,40 @@ def _residual_run_end(flows, order, k, z, inverse):
     return k2
 
 
+def _residual_nd_run_end(flows, order, k, z, inverse, state=None):
+    """_residual_run_end for (B, d) rows with 3 <= d <= 64: the run is cut after lipmlp_nd_pack.MAX_RECORDS layers and in front of a
+    Residual layer beyond lipmlp_nd_pack.MAX_RES of them.  Every layer is classified once per call (lipmlp_nd_pack.classify: one
+    walk of its net) and the verdicts are handed on to eligible().  state: a dict of the caller's that remembers how far a scan
+    found members but no Residual, so that a stretch of affine layers is walked once, not once per position."""
+    from .flows import lipmlp_nd_pack
+    if state is not None and k < state.get("skip", 0):
+        return k
+    d = z.shape[1]
+    k2 = k
+    nres = 0
+    kinds = []
+    stopped_at_residual = False
+    while k2 < len(order) and k2 - k < lipmlp_nd_pack.MAX_RECORDS:
+        f = flows[order[k2]]
+        c = lipmlp_nd_pack.classify(f)
+        if abs(c) != d:
+            break
+        if c > 0:
+            if bool(f.reverse) != bool(inverse) or nres == lipmlp_nd_pack.MAX_RES:
+                stopped_at_residual = True
+                break
+            nres += 1
+        kinds.append(c)
+        k2 += 1
+    if not nres:
+        if state is not None and not stopped_at_residual and k2 - k < lipmlp_nd_pack.MAX_RECORDS:
+            state["skip"] = k2      # members without a Residual up to a non-member: no run starts in between
+        return k
+    if not lipmlp_nd_pack.eligible([flows[q] for q in order[k:k2]], z, kinds=kinds):
+        return k
+    return k2
+
+
 def run_chain(flows, z, inverse, ld, acc):
     """_run_chain_impl behind the training step's one-launch weight packing (_prepack.py): a differentiable density pass first
     packs every eligible layer's weights / LU factors with one launch per kind; the layers then skip their own pack launches."""
@@ -395,6 +431,11 @@ def _run_chain_impl(flows, z, inverse, ld, acc):
     if rn_train and z.shape[0] < _config.realnvp_train_capture_min_batch:
         rn_train = not torch.cuda.is_current_stream_capturing()      # (replayed, small batches are faster layer by layer)
     res_ok = _config.residual_chain and z.dim() == 2 and z.shape[1] == 2 and z.is_cuda and z.dtype == torch.float32
+    res_nd_ok = False
+    if _config.residual_nd and _config.residual_chain:
+        from .flows import lipmlp_nd_pack
+        res_nd_ok = lipmlp_nd_pack.on_device(z)
+    nd_state = {}
     while k < n:
         i = order[k]
         f = flows[i]
@@ -433,6 +474,13 @@ def _run_chain_impl(flows, z, inverse, ld, acc):
             from .flows import lipmlp_pack
             z = flush(z)
             z = lipmlp_pack.run_density([flows[q] for q in order[k:k2]], z, ld, acc, inverse)
+            k = k2
+            continue
+        k2 = _residual_nd_run_end(flows, order, k, z, inverse, nd_state) if res_nd_ok else k
+        if k2 > k:        # the same on (B, d) rows, 3 <= d <= 64, at inference: one launch (csrc/lipmlp_nd.hip)
+            from .flows import lipmlp_nd_pack
+            z = flush(z)
+            z = lipmlp_nd_pack.run_density([flows[q] for q in order[k:k2]], z, ld, acc, inverse)
             k = k2
             continue
         pair = None
@@ -486,6 +534,8 @@ def _packed_blobs(owner):
     _cached_tensors(list(rank1_pack._rank1_cache.values()), out)
     from .flows import lipmlp_pack
     _cached_tensors(list(lipmlp_pack._lipmlp_cache.values()), out)
+    from .flows import lipmlp_nd_pack
+    _cached_tensors(list(lipmlp_nd_pack._lipmlp_nd_cache.values()), out)
     return out
 
 

@@ -9,7 +9,9 @@ kernels of csrc/lipmlp.hip for a CUDA float32 input when no gradient is needed (
 direction as one launch per layer, or per run of layers inside core.run_chain; the fixed-point direction as one launch and one
 read-back per iteration.  With config.residual_train on, a density-direction pass of such a layer that DOES need a gradient, or a
 training-mode pass on a stochastic estimator, runs on the training kernels of csrc/lipmlp_train.hip (one forward and one backward
-launch; lipmlp_pack.train_eligible).  Everything else takes the torch formulas below.
+launch; lipmlp_pack.train_eligible).  With config.residual_nd on, an evaluation-mode layer with exact_trace off on (B, d) rows,
+3 <= d <= 64, runs Hutchinson's power series on the kernels of csrc/lipmlp_nd.hip (flows/lipmlp_nd_pack.py has the conditions and
+the order of the draws).  Everything else takes the torch formulas below: training at d > 2, exact_trace, d > 64.
 
 One deliberate difference from the reference: under torch.no_grad() the outputs are detached and the caller's tensor is left alone
 (the reference leaks a graph out of its enable_grad block and flips requires_grad on the caller's input)."""
@@ -19,6 +21,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from .. import config as _config
 from .base import Flow
 
 
@@ -52,7 +55,22 @@ class Residual(Flow):
             if density:
                 return lipmlp_pack.run_density([self], z, None, None)
             return lipmlp_pack.run_sampling(self, z)
+        if _config.residual_nd:         # (B, d) rows, 3 <= d <= 64, at inference: csrc/lipmlp_nd.hip
+            from . import lipmlp_nd_pack
+            if lipmlp_nd_pack.eligible([self], z, sampling=not density):
+                if density:
+                    return lipmlp_nd_pack.run_density([self], z, None, None)
+                return lipmlp_nd_pack.run_sampling(self, z)
         return self._torch_pass(z, density)
+
+    def _density_nd(self, z, vareps, terms, coefs):
+        """The density direction on the d-dimensional kernels with the noise and the truncation handed in (nothing is drawn):
+        vareps (B, d), terms series terms with the weights coefs[k - 1] = coef(k).  For tests and fixtures: one seed gives CPU and
+        GPU generators different numbers.  Raises where flows/lipmlp_nd_pack.eligible declines."""
+        from . import lipmlp_nd_pack
+        if not lipmlp_nd_pack.eligible([self], z):
+            raise NotImplementedError("Residual._density_nd: config.residual_nd is off or the d-dimensional kernels do not take this call")
+        return lipmlp_nd_pack.run_density_noise([self], z, vareps.reshape((1,) + tuple(z.shape)), [terms], [coefs])
 
     def forward(self, z):
         return self._pass(z, not self.reverse)

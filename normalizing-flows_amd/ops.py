@@ -2269,3 +2269,68 @@ def lipmlp_train_bwd(x, gy, jhat, w, blob, hp, want_gblob, want_gx=True):
     L.call("nf_lipmlp_train_bwd", ptr(x), ptr(gy), ptr(jhat), ptr(w), ptr(gx), ptr(blob), ptr(slabs), ptr(gblob), blob.numel(), B,
            int(hp), 1 if slabs is not None else 0, L.stream())
     return gx, gblob
+
+
+LIPMLP_ND_MAX_RES = 8           # Residual records of one nf_lipmlp_nd_chain call
+LIPMLP_ND_MAX_TERMS = 48        # series terms per record (they travel in the launch arguments)
+
+
+def lipmlp_nd_rows(hp, d):
+    """Rows per workgroup of the d-dimensional residual-flow kernels (nf_lipmlp_nd_rows)."""
+    rows = L.query("nf_lipmlp_nd_rows", int(hp), int(d))
+    if rows < 0:
+        L.check(rows, "nf_lipmlp_nd_rows")
+    return rows
+
+
+def _lipmlp_nd_rows(entry, blob, K, nres, hp, *rows):
+    """(B, d) of a d-dimensional residual-flow call after its operand checks: every row operand a contiguous (B, d) matrix of one
+    shape, blob a contiguous vector of nf_lipmlp_nd_blob_floats(K, nres, hp, d) floats (flows/lipmlp_nd_pack.py)."""
+    z = rows[0]
+    if any(t.dim() != 2 or t.shape != z.shape or not t.is_contiguous() for t in rows):
+        raise ValueError("%s: the row operands must be contiguous (B, d) matrices of one shape" % entry)
+    if blob.dim() != 1 or not blob.is_contiguous():
+        raise ValueError("%s: blob must be a contiguous vector" % entry)
+    L.check_count(entry, "blob", blob, L.size("nf_lipmlp_nd_blob_floats", int(K), int(nres), int(hp), int(z.shape[1])),
+                  "K (16 + 2 dp) + nres (2 hp^2 + 2 dp hp + 3 hp + dp)")
+    return z.shape
+
+
+def lipmlp_nd_chain(z, vareps, blob, K, nres, hp, terms, coefs, logdet=None, acc=None):
+    """A run of [Residual | ActNorm | AffineConstFlow] layers on (B, d) rows, 3 <= d <= 64, in the Residuals' density direction as
+    one launch (nf_lipmlp_nd_chain): (y, logdet); logdet combined by `acc` when given.  vareps (nres, B, d): the probe vectors;
+    terms: nres term counts (1 .. 48); coefs: per Residual record the Python floats coef(1) .. coef(terms)."""
+    L.require_device(z, vareps, blob, logdet, dtype=torch.float32)
+    B, d = _lipmlp_nd_rows("lipmlp_nd_chain", blob, K, nres, hp, z)
+    if vareps.shape != (nres, B, d) or not vareps.is_contiguous():
+        raise ValueError("lipmlp_nd_chain: vareps must be a contiguous (nres, B, d) tensor, got %s" % (tuple(vareps.shape),))
+    terms = [int(t) for t in terms]
+    if len(terms) != nres or len(coefs) != nres or any(len(c) != t for c, t in zip(coefs, terms)):
+        raise ValueError("lipmlp_nd_chain: one term count and one list of that many coefficients per Residual record")
+    y = torch.empty_like(z)
+    logdet, acc = _ld_buffer(logdet, acc, B, z)
+    L.check_count("lipmlp_nd_chain", "logdet", logdet, B, "B")
+    nterms_host = (C.c_int * max(nres, 1))(*terms)
+    coef_host = (C.c_float * (max(nres, 1) * LIPMLP_ND_MAX_TERMS))()
+    for r, c in enumerate(coefs):
+        for k, v in enumerate(c[:LIPMLP_ND_MAX_TERMS]):
+            coef_host[r * LIPMLP_ND_MAX_TERMS + k] = float(v)
+    L.call("nf_lipmlp_nd_chain", ptr(z), ptr(vareps), ptr(y), ptr(logdet), ptr(blob), blob.numel(), B, d, int(hp), int(K), int(nres),
+           nterms_host, coef_host, acc, L.stream())
+    return y, logdet
+
+
+def lipmlp_nd_apply(x, y, blob, hp, mode, count=None, atol=1e-5, rtol=1e-5):
+    """One LipschitzMLP g on (B, d) rows in one launch (nf_lipmlp_nd_apply).  mode 0: x + g(x).  mode 1: the fixed-point step
+    y - g(x); `count` (one int32 on the device, zeroed by the caller) receives the number of elements whose squared step is not below
+    atol + |y| rtol."""
+    L.require_device(x, y, blob, count, dtype=torch.float32)
+    if mode not in (0, 1):
+        raise ValueError("lipmlp_nd_apply: mode must be 0 or 1")
+    B, d = _lipmlp_nd_rows("lipmlp_nd_apply", blob, 1, 1, hp, *((x,) if mode == 0 else (x, y)))
+    if mode == 1 and (count is None or count.dtype != torch.int32 or count.numel() != 1):
+        raise ValueError("lipmlp_nd_apply: mode 1 needs `count`, one int32 on the device")
+    out = torch.empty_like(x)
+    L.call("nf_lipmlp_nd_apply", ptr(x), ptr(y if mode == 1 else None), ptr(out), ptr(count if mode == 1 else None), ptr(blob),
+           blob.numel(), B, d, int(hp), mode, float(atol), float(rtol), L.stream())
+    return out
